@@ -60,6 +60,8 @@ def build_library(force: bool = False, verbose: bool = False, probe: bool = Fals
         os.makedirs(VARIANTS, exist_ok=True)
         lib = os.path.join(VARIANTS, f"libbts_{tag}.so")
         obj_dir = OBJ + "_" + tag
+    if os.path.isdir(obj_dir) and not os.access(obj_dir, os.W_OK | os.X_OK):
+        obj_dir += f"_uid{os.getuid()}"      # another user's build left the shared directory behind: a clean checkout still builds
     stamp = os.path.join(obj_dir, "digest.txt")
     dig = _digest() + hashlib.sha256(" ".join(flags).encode()).hexdigest()
     if not force and os.path.exists(lib) and os.path.exists(stamp) and open(stamp).read().strip() == dig:

@@ -2,7 +2,7 @@
 KITTI eval_depth forward pass, bs=1, 192x640 frames, 64 samples/ray, both stereo views' rays rendered from the single
 encoder view (245 760 rays, 15.7 M field queries per step), fp32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = what the reference's evaluator does per frame after the CNN (models/bts/evaluator.py:60-79): hand the feature
@@ -11,7 +11,10 @@ rays (`renderer(all_rays, want_weights=True, want_alphas=True)`), `reconstruct`,
 resident in HBM before the timed region.  N > 1: every rank renders its own frame (frames are independent -> weak scaling,
 no collective on the data path); value = total rays of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  Next to the headline it carries `others` (N = 1: BASELINE configs[2], [3], [4], [4] at K = 128 and the
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up (SETTLE_FRAMES + W steps), times exactly K steps and prints the headline: `metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (= the timed region / K) and the workload's config.  `--dump-outputs DIR`
+also writes what the last timed step computed (dump_outputs).  Everything below is measured with `--full` only.
+With `--full`, next to the headline the line carries `others` (N = 1: BASELINE configs[2], [3], [4], [4] at K = 128 and the
 occupancy profile, each = `bench.py --workload X --steps CHILD_STEPS --warmup CHILD_WARMUP` in a child process) and, under torch.distributed.run, `ddp_train`
 (KITTI-Raw shapes with the Monodepth2 encoder through DistributedDataParallel: the path's one collective, with `allreduce_ms`);
 `--no-others` skips both.  `roofline` is for the dominant kernel (bts::render_kernel_p = bts_render_fwd) TOGETHER WITH bts::project_kernel
@@ -49,6 +52,9 @@ H, W, K, C, HD, V = 192, 640, 64, 64, 64, 2
 # 40 warm-up steps: the device needs ~25 ms of continuous work to reach its steady state (profiles/r06q), and ten 0.65 ms steps of
 # exp_kitti_raw.yaml's shapes are a quarter of that
 CHILD_STEPS, CHILD_WARMUP = 40, 40
+# untimed frames a plain eval run renders in front of its W warm-up frames: the ~25 ms of continuous work the device needs to reach its
+# steady state (profiles/r06q); with --full the entry-by-entry split in front of the warm-up does this
+SETTLE_FRAMES = 30
 
 
 def parse():
@@ -103,6 +109,14 @@ def parse():
     ap.add_argument("--no-gpu-eager-baseline", action="store_true",
                     help="skip ref_gpu_baseline: the oracle's torch ops eagerly on the GPU (the reference's own code path on this device, the "
                          "denominator of north_star's >= 10x target); on by default at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures besides the headline: roofline / per-entry-point event times, the entry-by-entry "
+                         "split of the eval frame, the collector-on loop, cpu_baseline / ref_gpu_baseline, `others` and `ddp_train`, "
+                         "the training lines' other_layout and allreduce.  Off: set up, warm up, time the steps, print the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; an "
+                         "array beyond its share of the 60 MB budget is a fixed, seeded sample of its elements).  The inputs and the "
+                         "jitter draws depend on the arguments only, so two builds can be compared output for output")
     ap.add_argument("--cpu-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-rows", type=int, default=24, help="image rows of view 0 rendered by the CPU oracle sample")
     return ap.parse_args()
@@ -123,6 +137,37 @@ def park_gc():
 def gc_parked():
     """what the JSON line records as `gc_parked`: was the cyclic collector off during the timed loops of this process?"""
     return os.environ.get("BTS_BENCH_KEEP_GC") != "1"
+
+
+DUMP_BUDGET = 15_000_000      # --dump-outputs: float32 elements over all arrays of one step (60 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy as float32.  Arrays that fit their share of DUMP_BUDGET (the budget split evenly,
+    what a small array leaves over going to the larger ones) are written whole; a larger one as the elements at fixed, seeded positions
+    (torch.randint from seed 0 over its flattened length, sorted) -- the same positions on every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sizes = {k: t.numel() for k, t in arrays.items()}
+    caps, left = {}, DUMP_BUDGET
+    for k in sorted(sizes, key=sizes.get):
+        caps[k] = min(sizes[k], left // (len(sizes) - len(caps)))
+        left -= caps[k]
+    for k, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if caps[k] < sizes[k]:
+            idx = torch.randint(0, sizes[k], (caps[k],), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, f"{k}.npy"), flat.float().cpu().numpy().reshape(t.shape if caps[k] == sizes[k] else (-1,)))
+
+
+def eval_arrays(res):
+    """what a caller of the eval step receives: the frame's per-ray outputs (depth = z-depth after distance_to_z) and its rays"""
+    part = res["coarse"][0]
+    out = {k: part[k] for k in ("depth", "rgb", "weights", "alphas", "invalid") if torch.is_tensor(part.get(k))}
+    if torch.is_tensor(res.get("rays")):
+        out["rays"] = res["rays"]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -233,9 +278,11 @@ def glue_workload(args, world, rank, dev):
     def step():
         time.sleep(1e-3 * (rank + 1))
         return (x @ x).sum()
-    elapsed, _ = timed_region(step, args.steps, dev, warmup=args.warmup)
+    elapsed, last = timed_region(step, args.steps, dev, warmup=args.warmup)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"sum": last.reshape(1)})
     return {"metric": "launch glue stand-in (not a measurement)", "value": world * args.steps / elapsed, "unit": "steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic", "gc_parked": gc_parked(),
@@ -517,7 +564,9 @@ def train_workload(args, world, rank, dev):
 
     def step():   # base_trainer.py:287-297
         net.zero_grad(set_to_none=True)
-        model(images, projs, poses).backward()
+        loss = model(images, projs, poses)
+        loss.backward()
+        return loss
 
     native.SPARSE_PROJ_GRAD = not args.dense_proj_grad
     if args.tile_stats or args.ops_profile:      # (the diagnostics below want a warmed-up process; the timed path warms up inside timed_region)
@@ -567,9 +616,37 @@ def train_workload(args, world, rank, dev):
         for (name, where), (cnt, us) in sorted(by.items(), key=lambda kv: -kv[1][1]):
             print(f"{name:28s} {cnt / 3:6.1f} {us / 3:9.1f}  {where}", file=sys.stderr)
         return
-    timer = KernelTimer()
-    timer.install()
-    elapsed, _ = timed_region(step, args.steps, dev, before=torch.cuda.reset_peak_memory_stats, timer=timer, warmup=args.warmup)
+    timer = KernelTimer() if args.full else None
+    if timer is not None:
+        timer.install()
+    elapsed, loss = timed_region(step, args.steps, dev, before=torch.cuda.reset_peak_memory_stats, timer=timer, warmup=args.warmup)
+    if args.dump_outputs and rank == 0:       # the step's loss and every gradient it left on the parameters
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1),
+                                         **{f"grad.{k}": p.grad for k, p in net.named_parameters() if p.grad is not None}})
+    del loss
+    n_rays = n * cfg["rays"]
+
+    def headline():
+        what = (f"{cfg['yaml']} shapes: bs={n}/GPU, {Vt} frames ({len(ids_loss)} loss + {len(ids_render)} render views), {Hh}x{Ww}, {cfg['rays']} patch "
+                f"rays (8x8) per sample, {Kt} samples/ray, C={Cc}, d_hidden={Hd}, {Nb} ResnetBlockFC, code {cfg['code_mode']}, "
+                + (f"{n_scales} renders per step (multiscale, trainer.py:220-242), " if n_scales > 1 else "")
+                + ("everything after the CNN (feature-map encoder stand-in): " if args.encoder == "feature_map" else
+                   f"whole step incl. the shipped Monodepth2 (ResNet-{cfg['resnet']}, random weights), "
+                   + "hand-over F -> bts_project_features: ")
+                + "sample, render, photometric loss, backward; "
+                + ("every per-sample output of the reference trainer's dict materialised (--full-outputs)" if args.full_outputs else
+                   "lean_training_outputs: the loss' invalid-ray mask reads per-ray reductions from the render epilogue (SURVEY 8f.1)"))
+        return {
+            "metric": f"training-step rays/sec ({cfg['yaml']} shapes): render forward + loss + backward" + (" + CNN" if args.encoder != "feature_map" else ""),
+            "value": world * n_rays * args.steps / elapsed,
+            "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "gc_parked": gc_parked(),
+            "config": {"workload": what, "rays_per_step_per_gpu": n_rays, "samples_per_ray": Kt, "renders_per_step": n_scales,
+                       "parallelism": parallelism("batch", world), "peak_hbm_bytes": torch.cuda.max_memory_allocated(),
+                       "feat_layout": "nhwc (channels_last: Monodepth2's hand-over)" if args.encoder != "feature_map" else args.feat_layout}}
+
+    if not args.full:           # the plain run: the headline and nothing else
+        return headline() if rank == 0 else None
     n_event_steps = len(timed_region.sampled)
     timer.remove()
     # for the byte model of `traffic_ratio`: the 64-texel tiles of every scale's map the LAST step's samples touched (the forward's flags stay
@@ -598,7 +675,6 @@ def train_workload(args, world, rank, dev):
                          bucket_bytes=grad_bytes, world=world, backend=torch.distributed.get_backend(),
                          note="device time of the RCCL kernels per step (torch.profiler, two steps after the timed region); at world 1 the "
                               "collective is a local copy -- the number says the path ran, not what xGMI costs")
-    n_rays = n * cfg["rays"]
     # per STEP and entry point: the four scales of re10k are four calls each on the entry-by-entry path
     ms = timer.ms_per_step(n_event_steps)
     if rank == 0:
@@ -645,23 +721,8 @@ def train_workload(args, world, rank, dev):
                             for k, v in tj.items()}
                 counters["source"] = (f"profiles/{prof[-1]}/{tname}: rocprofv3 --pmc passes of tools/train_probe.py (same shapes); `traffic` = "
                                       "fetch + write bytes of " + ", ".join(render) + " per launch; FETCH_SIZE doubled per MI355X_MICROARCH.md")
-        what = (f"{cfg['yaml']} shapes: bs={n}/GPU, {Vt} frames ({len(ids_loss)} loss + {len(ids_render)} render views), {Hh}x{Ww}, {cfg['rays']} patch "
-                f"rays (8x8) per sample, {Kt} samples/ray, C={Cc}, d_hidden={Hd}, {Nb} ResnetBlockFC, code {cfg['code_mode']}, "
-                + (f"{n_scales} renders per step (multiscale, trainer.py:220-242), " if n_scales > 1 else "")
-                + ("everything after the CNN (feature-map encoder stand-in): " if args.encoder == "feature_map" else
-                   f"whole step incl. the shipped Monodepth2 (ResNet-{cfg['resnet']}, random weights), "
-                   + "hand-over F -> bts_project_features: ")
-                + "sample, render, photometric loss, backward; "
-                + ("every per-sample output of the reference trainer's dict materialised (--full-outputs)" if args.full_outputs else
-                   "lean_training_outputs: the loss' invalid-ray mask reads per-ray reductions from the render epilogue (SURVEY 8f.1)"))
         out = {
-            "metric": f"training-step rays/sec ({cfg['yaml']} shapes): render forward + loss + backward" + (" + CNN" if args.encoder != "feature_map" else ""),
-            "value": world * n_rays * args.steps / elapsed,
-            "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "gc_parked": gc_parked(),
-            "config": {"workload": what, "rays_per_step_per_gpu": n_rays, "samples_per_ray": Kt, "renders_per_step": n_scales,
-                       "parallelism": parallelism("batch", world), "peak_hbm_bytes": torch.cuda.max_memory_allocated(),
-                       "feat_layout": "nhwc (channels_last: Monodepth2's hand-over)" if args.encoder != "feature_map" else args.feat_layout},
+            **headline(),
             "roofline": {"bound": "valu", "achieved": achieved, "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / PEAK_FP32_MATRIX_TFLOPS, "traffic": traffic, "event_steps": n_event_steps,
                          **({"algorithmic_bytes": byte_model["algorithmic_bytes"], "state_bytes": byte_model["state_bytes"], "traffic_ratio": traffic_ratio,
@@ -689,6 +750,7 @@ def train_workload(args, world, rank, dev):
             import copy
             a2 = copy.copy(args)
             a2.feat_layout, a2.steps, a2.warmup, a2.no_cpu_baseline, a2.no_other_layout = ("nchw" if args.feat_layout == "nhwc" else "nhwc"), 20, 5, True, True
+            a2.dump_outputs = None
             torch.cuda.empty_cache()
             try:
                 o2 = train_workload(a2, world, rank, dev)
@@ -735,10 +797,24 @@ def profile_workload(args, world, rank, dev):
         a = sigmas.reshape(Y, Z, X)
         return (torch.cumsum(a, 0) <= 8).float().sum(0) / Y
 
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
     elapsed, prof = timed_region(step, args.steps, dev, events=ev, warmup=args.warmup)
-    kernel_ms = sum(ev[i][0].elapsed_time(ev[i][1]) for i in timed_region.sampled) / len(timed_region.sampled)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"occupancy": prof})
     n_pts = Y * Z * X
+
+    def headline():
+        return {
+            "metric": "density-field queries/sec (64x256x256 occupancy profile, scripts/inference_setup.py)", "value": world * n_pts * args.steps / elapsed,
+            "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "gc_parked": gc_parked(),
+            "config": {"workload": "occupancy profile of one KITTI-360 frame: 64 x 256 x 256 = 4 194 304 query points (get_pts defaults), nv = 2 "
+                                   "views flag invalid points, learn_empty=True, one fused pass (bts_occupancy_profile)", "points_per_step_per_gpu": n_pts,
+                       "parallelism": parallelism("frames", world)}}
+
+    if not args.full:           # the plain run: the headline and nothing else
+        return headline() if rank == 0 else None
+    kernel_ms = sum(ev[i][0].elapsed_time(ev[i][1]) for i in timed_region.sampled) / len(timed_region.sampled)
     if rank == 0:
         ref_ms, agree = None, None
         if world == 1:
@@ -753,14 +829,9 @@ def profile_workload(args, world, rank, dev):
         flop = n_pts * FLOP_PER_POINT                 # algorithmic
         exec_flop = n_pts * EXEC_FLOP_PER_POINT       # what the query kernel executes (the projected map is built by encode, outside the step)
         achieved = exec_flop / (kernel_ms * 1e-3) / 1e12
-        out = {
-            "metric": "density-field queries/sec (64x256x256 occupancy profile, scripts/inference_setup.py)", "value": world * n_pts * args.steps / elapsed,
-            "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "gc_parked": gc_parked(),
-            "config": {"workload": "occupancy profile of one KITTI-360 frame: 64 x 256 x 256 = 4 194 304 query points (get_pts defaults), nv = 2 "
-                                   "views flag invalid points, learn_empty=True, one fused pass (bts_occupancy_profile)", "points_per_step_per_gpu": n_pts,
-                       "parallelism": parallelism("frames", world),
-                       "reference_flow_on_hip_queries_ms": ref_ms, "columns_equal_to_reference_flow": agree},
+        out = headline()
+        out["config"].update(reference_flow_on_hip_queries_ms=ref_ms, columns_equal_to_reference_flow=agree)
+        out.update({
             "roofline": {"bound": "valu", "achieved": achieved, "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_MATRIX_TFLOPS,
                          "traffic": None, "kernel": "bts::query_kernel_p<64,64,0,2> (profile mode)", "kernel_ms": kernel_ms,
                          "executed_flop_per_launch": exec_flop, "algorithmic_flop_per_launch": flop,
@@ -768,7 +839,7 @@ def profile_workload(args, world, rank, dev):
                          "note": "`achieved` / `frac` = the 5 760 FLOP / query the kernel EXECUTES (the projected-feature form, DESIGN.md section 3, like "
                                  "the render kernel) against the fp32 vector = fp32-input-MFMA peak; `frac_algorithmic` prices SURVEY 8d's 13 312 FLOP / "
                                  "query and exceeds 1 by construction"},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             from oracle import bts_oracle as O
             threads = min(16, os.cpu_count() or 8)
@@ -848,7 +919,7 @@ def main():
         # evaluator.py:60-79 after the CNN.  Default: behindthescenes_amd.FusedEvalFrame = ONE library call (bts_eval_frame: hand-over, rays of
         # every pixel, render with sample_coarse inside, distance_to_z); --entries / --shard rays: the same kernels entry by entry
         if frame.fused:
-            return frame(images, projs, poses, ids_encoder=[0], ids_render=[0])["coarse"][0]["depth"]
+            return frame(images, projs, poses, ids_encoder=[0], ids_render=[0])
         with torch.no_grad():
             net.encode(images, projs, poses, ids_encoder=[0], ids_render=[0])
             all_rays, all_rgb_gt = sampler.sample(images * .5 + .5, poses, projs)
@@ -860,7 +931,7 @@ def main():
             rd["rgb_gt"] = all_rgb_gt
             rd = sampler.reconstruct(rd)
             depth_z = bts.distance_to_z(rd["coarse"]["depth"], projs)
-        return depth_z
+        return dict(coarse=[dict(rd["coarse"], depth=depth_z)], rays=rd.get("rays"))
 
     # Everything ELSE this workload measures on the GPU runs first, the warm-up and the timed region last: the device takes ~25 ms of
     # continuous work to reach its steady state after the idle seconds of the set-up, and the driver's W = 5 warm-up frames are 5 ms
@@ -871,7 +942,7 @@ def main():
     # region measures the steady state; profiles/r06q: 1.05 -> 0.99 ms per step at the driver's --steps 20 --warmup 5.
     split_ms = None
     unpark_gc = park_gc()     # (the collector pass -- ~30 ms of host time with the GPU idle -- in front of ALL of it)
-    if frame.fused:
+    if args.full and frame.fused:
         frame.fused = False
         for _ in range(20):
             step()
@@ -883,8 +954,40 @@ def main():
         t2.remove()
         split_ms = t2.ms_per_step(10)
         frame.fused = True
-    timer.install()
-    elapsed, _ = timed_region(step, args.steps, dev, timer=timer, warmup=args.warmup, unpark_gc=unpark_gc)
+    elif frame.fused:
+        # without --full the split does not run, but its ~30 ms of continuous device work are what the headline needs: the same
+        # steady state in front of the W warm-up frames (without them: 1.05 instead of 0.98 ms per step at --steps 20 --warmup 5)
+        for _ in range(SETTLE_FRAMES):
+            step()
+    torch.manual_seed(4242)    # the warm-up and timed steps draw the same jitter with and without --full's work in front of them
+    if args.full:
+        timer.install()
+    elapsed, last = timed_region(step, args.steps, dev, timer=timer if args.full else None, warmup=args.warmup, unpark_gc=unpark_gc)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eval_arrays(last))
+    del last
+    step_ms = elapsed * 1e3 / args.steps
+    value = (1 if shard_rays else world) * n_rays * args.steps / elapsed
+    rays_launch = n_rays // world if shard_rays else n_rays            # rays one launch of the render kernel processes on this rank
+
+    def headline():
+        return {
+            "metric": "rendered rays/sec (192x640x64 samples)", "value": value, "unit": "rays/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_ms, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "gc_parked": gc_parked(),
+            "config": {"workload": "KITTI eval_depth.yaml forward, bs=1/GPU, 192x640, 2 views x 122880 rays, 64 samples/ray, nv=1, "
+                                   "learn_empty=True (the yaml's effective default), want_weights+alphas, renderer only (feature-map "
+                                   "encoder stand-in)" + (": ONE frame, its rays sharded over the ranks + all-gather of the per-ray outputs" if shard_rays else ""),
+                       "rays_per_step_per_gpu": rays_launch, "samples_per_ray": K, "parallelism": parallelism("rays" if shard_rays else "frames", world),
+                       **({"all_gather_bytes_per_step": n_rays * (3 + 1 + 3 * K) * 4,
+                           "all_gather": "rgb, depth, weights, alphas, invalid of all rays on every rank (what the un-sharded call returns)"} if shard_rays else {})}}
+
+    if not args.full:           # the plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline()))
+        if launched:
+            torch.distributed.destroy_process_group()
+        return
     n_event_steps = len(timed_region.sampled)
     timer.remove()
     # the same loop once more with Python's cyclic collector ON (what an evaluation loop that does not park it sees), outside the timed
@@ -919,10 +1022,7 @@ def main():
         counters["source"] = (f"profiles/{prof[-1]}/traffic.json: rocprofv3 --pmc passes of tools/kernel_probe.py (same kernel, same workload); FETCH_SIZE "
                               "doubled per MI355X_MICROARCH.md; valu_busy = SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES, wait_frac = SQ_WAIT_ANY / SQ_WAVE_CYCLES, "
                               "mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x kernel cycles)")
-    step_ms = elapsed * 1e3 / args.steps
-    value = (1 if shard_rays else world) * n_rays * args.steps / elapsed
     if rank == 0:
-        rays_launch = n_rays // world if shard_rays else n_rays            # rays one launch of the render kernel processes on this rank
         flop_per_launch = rays_launch * K * FLOP_PER_POINT                  # algorithmic
         exec_flop = rays_launch * K * EXEC_FLOP_PER_POINT + H * W * PROJECT_FLOP_PER_TEXEL      # what render_kernel_p + project_kernel execute
         exec_ms = kernel_ms + project_ms
@@ -936,15 +1036,7 @@ def main():
             per_simd = counters["valu_insts_per_ray"] * rays_launch / 1024
             valu_issue = {k: per_simd * ns * 1e-6 / render_ms for k, ns in VALU_NS_PER_INST_2WAVES.items()}
         out = {
-            "metric": "rendered rays/sec (192x640x64 samples)", "value": value, "unit": "rays/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_ms, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "gc_parked": gc_parked(), "ms_per_step_gc_on": gc_on_ms,
-            "config": {"workload": "KITTI eval_depth.yaml forward, bs=1/GPU, 192x640, 2 views x 122880 rays, 64 samples/ray, nv=1, "
-                                   "learn_empty=True (the yaml's effective default), want_weights+alphas, renderer only (feature-map "
-                                   "encoder stand-in)" + (": ONE frame, its rays sharded over the ranks + all-gather of the per-ray outputs" if shard_rays else ""),
-                       "rays_per_step_per_gpu": rays_launch, "samples_per_ray": K, "parallelism": parallelism("rays" if shard_rays else "frames", world),
-                       **({"all_gather_bytes_per_step": n_rays * (3 + 1 + 3 * K) * 4,
-                           "all_gather": "rgb, depth, weights, alphas, invalid of all rays on every rank (what the un-sharded call returns)"} if shard_rays else {})},
+            **headline(), "ms_per_step_gc_on": gc_on_ms,
             "roofline": {"bound": "valu", "achieved": achieved, "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / PEAK_FP32_MATRIX_TFLOPS, "traffic": traffic,
                          "kernel": "bts::render_kernel_p<64,64,0,1,true,true> + bts::project_kernel<64,64>" + (" inside bts_eval_frame (one call: + cameras, "
@@ -1028,6 +1120,7 @@ def sub_records(args, world, rank, dev, launched):
     def run(workload, steps=10, warmup=3, **kw):
         a = copy.copy(args)
         a.workload, a.steps, a.warmup, a.no_cpu_baseline, a.samples, a.encoder = workload, steps, warmup, True, 0, "feature_map"
+        a.dump_outputs = None
         for k, v in kw.items():
             setattr(a, k, v)
         try:
@@ -1045,7 +1138,8 @@ def sub_records(args, world, rank, dev, launched):
         the extra steps are ~0.1 s of a child process that spends seconds importing torch."""
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK",
                                                                   "LOCAL_WORLD_SIZE", "ROLE_RANK", "TORCHELASTIC_RUN_ID")}
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", str(CHILD_STEPS), "--warmup", str(CHILD_WARMUP), "--no-cpu-baseline", "--no-others"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", str(CHILD_STEPS), "--warmup", str(CHILD_WARMUP), "--no-cpu-baseline", "--no-others",
+               "--full"]
         if samples:
             cmd += ["--samples", str(samples)]
         try:

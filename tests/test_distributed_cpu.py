@@ -139,3 +139,25 @@ def test_bench_launch_glue_under_torch_distributed_run_world_2():
     assert bench.launch_context(dict(RANK="3", LOCAL_RANK="1", WORLD_SIZE="8", MASTER_PORT="1")) == (8, 3, 1, True)
     assert bench.launch_context(dict(RANK="0", WORLD_SIZE="1")) == (1, 0, 0, False)        # no rendezvous port: not a distributed launch
     assert [bench.parallelism(k, 8) for k in ("frames", "rays", "batch")] == ["frames x8", "rays x8 of one frame", "batch x8"]
+
+
+def test_bench_dump_outputs_budget_and_fixed_positions(tmp_path):
+    """bench.py --dump-outputs: small arrays are written whole, large ones as a sample at fixed positions (the same on every call),
+    all float32, the whole dump within the 64 MB budget."""
+    import numpy as np
+    import bench
+    big = torch.arange(8_000_000, dtype=torch.float64)               # float32 holds these integers exactly: each value names its position
+    arrays = {"small": torch.arange(12.0).reshape(3, 4), "a": big, "b": big.reshape(4000, 2000), "c": big + 1}
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    total = sum(f.stat().st_size for f in (tmp_path / "one").iterdir())
+    assert total <= 64e6 and sum(np.load(f).size for f in (tmp_path / "one").iterdir()) <= bench.DUMP_BUDGET
+    one = {f.stem: np.load(f) for f in (tmp_path / "one").iterdir()}
+    assert set(one) == set(arrays) and all(a.dtype == np.float32 for a in one.values())
+    np.testing.assert_array_equal(one["small"], arrays["small"].numpy())
+    for k in ("a", "b", "c"):
+        assert one[k].ndim == 1 and 1_000_000 < one[k].size < 8_000_000
+        np.testing.assert_array_equal(one[k], np.load(tmp_path / "two" / f"{k}.npy"))
+        assert (np.diff(one[k]) >= 0).all()
+    np.testing.assert_array_equal(one["a"], one["b"])                # the positions depend on the length only
+    np.testing.assert_array_equal(one["c"], one["a"] + 1)

@@ -18,8 +18,8 @@ def test_bench_runs_under_torch_distributed_run(workload):
     initialises the process group whenever it is launched that way (backend nccl = RCCL, device_id), so its barrier / MAX all-reduce
     / DDP path executes here exactly as it will on a node; prints ONE JSON line with the contract's keys.  The training workloads wrap a
     REAL DistributedDataParallel at world size 1 (wrap_ddp(force=True)): reducer, bucket views and the RCCL all-reduce run through
-    RenderFunction / ProjectFunction; `train_monodepth2` puts the shipped encoder's ~140 MB gradient bucket on it.  `eval` (the default
-    line) carries `others` (every other BASELINE config + the occupancy profile) and `ddp_train` (KITTI-Raw shapes + Monodepth2)."""
+    RenderFunction / ProjectFunction; `train_monodepth2` puts the shipped encoder's ~140 MB gradient bucket on it.  With --full, `eval`
+    carries `others` (every other BASELINE config + the occupancy profile) and `ddp_train` (KITTI-Raw shapes + Monodepth2)."""
     import json
     import bench          # the child-run step counts are bench.py's constants, never a literal here (round-5 verdict, weak 1)
     with socket.socket() as s:
@@ -29,7 +29,7 @@ def test_bench_runs_under_torch_distributed_run(workload):
     if workload == "eval_shard_rays":       # SURVEY 8e's second axis: ONE frame, its rays over the ranks, all-gather inside the timed region
         extra = ["--workload", "eval", "--shard", "rays", "--no-others"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port",
-           str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra
+           str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -57,3 +57,30 @@ def test_bench_runs_under_torch_distributed_run(workload):
     assert ar["backend"] == "nccl" and ar["allreduce_ms"] >= 0 and ar["world"] == 1, ar
     if workload != "train":
         assert ar["bucket_bytes"] > 50e6, ar       # Monodepth2 (ResNet-50 encoder + decoder) + the MLP: the real gradient bucket
+
+
+def test_plain_bench_line_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` as later measurements run it: the headline keys and nothing that
+    --full measures, exactly K timed steps, and the last step's outputs as float32 .npy files within the 64 MB budget."""
+    import json
+    import numpy as np
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in out, k
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["unit"] == "rays/s" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 245760 / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    for k in ("roofline", "others", "cpu_baseline", "ref_gpu_baseline", "ms_per_step_gc_on"):
+        assert k not in out, k
+    files = {f.name: np.load(f) for f in out_dir.iterdir()}
+    assert {"depth.npy", "rgb.npy", "weights.npy", "alphas.npy", "invalid.npy", "rays.npy"} <= set(files), sorted(files)
+    assert sum(f.stat().st_size for f in out_dir.iterdir()) <= 64e6
+    assert files["depth.npy"].shape == (1, 2, 192, 640) and files["rgb.npy"].shape == (1, 2, 192, 640, 1, 3)
+    for name, a in files.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+    assert (files["depth.npy"] > 0).all() and (files["depth.npy"] <= 80.0 + 1e-3).all()     # z-depth: distance along the ray x cos

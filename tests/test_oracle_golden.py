@@ -1,5 +1,5 @@
 """CPU: pins the oracle (oracle/bts_oracle.py) against fixtures produced by the REAL reference
-(tests/golden/gen_golden.py) and, when the reference tree is present, against the live reference."""
+(tests/golden/gen_golden.py, tests/golden/gen_golden_fullres.py)."""
 import numpy as np
 import pytest
 import torch
@@ -77,32 +77,27 @@ def test_gen_rays_and_distance_to_z_golden():
     torch.testing.assert_close(dz, torch.from_numpy(z["dist_to_z"]), rtol=1e-6, atol=0)
 
 
-@pytest.mark.needs_reference
 def test_oracle_against_live_reference_fullres_slice():
-    """Build-container only: a fresh (not committed) comparison against the live reference at the real
-    192x640 resolution on a slice of rays, so that the oracle is not just fitted to the small fixtures."""
-    from oracle.ref_shim import load_reference
-    from tests.golden.gen_golden import ref_conf, load_mlp_into
-    ref = load_reference()
+    """The oracle against the reference at the real 192x640 resolution on a slice of rays (tests/golden/fullres_slice.npz, written
+    from the live reference by tests/golden/gen_golden_fullres.py), so that the oracle is not just fitted to the small fixtures."""
+    f = np.load(f"{GOLDEN}/fullres_slice.npz")
+    shape = tuple(int(n) for n in f["invalid_shape"])
+    ref_out = dict(rgb=torch.from_numpy(f["rgb"]), depth=torch.from_numpy(f["depth"]), z_every64=torch.from_numpy(f["z_every64"]),
+                   invalid=torch.from_numpy(np.unpackbits(f["invalid_bits"], count=int(np.prod(shape))).reshape(shape).astype(np.float32)))
     cfg = O.FieldConfig()
     scene = O.synthetic_scene(1, 2, 192, 640, 64, seed=9, intrinsics=O.K_KITTIRAW)
     g = torch.Generator().manual_seed(5)
     mlp = O.init_mlp(103, 64, 0, gen=g)
-    net = ref.make_net(ref_conf(cfg, 0, 64), [scene["feat"]])
-    load_mlp_into(net, mlp)
-    renderer = ref.NeRFRenderer(n_coarse=64, lindisp=True, hard_alpha_cap=True).eval()
-    net.eval()
-    net.encode(scene["images"], scene["projs"], scene["poses"], ids_encoder=[0], ids_render=[0])
     rays = O.image_rays(scene["poses"], scene["projs"], 192, 640, 3.0, 80.0)[:, ::97].contiguous()
     u = torch.rand(rays.shape[1], 64, generator=g)
     z = O.sample_coarse(rays.reshape(-1, 8), 64, True, u)
+    torch.testing.assert_close(z[::64], ref_out["z_every64"], rtol=1e-6, atol=0)        # the inputs are the ones the reference saw
     with torch.no_grad():
-        ref_out = renderer.composite(net, rays.reshape(-1, 8), z, coarse=True, sb=1)
         st = O.make_state(scene, [0], cfg)
         our = O.composite(rays.reshape(-1, 8), z, 1, st, mlp, cfg, hard_alpha_cap=True)
-    torch.testing.assert_close(our[2], ref_out[2], rtol=2e-6, atol=0)
-    torch.testing.assert_close(our[1], ref_out[1], rtol=0, atol=2e-6)
-    assert torch.equal(our[4], ref_out[4])
+    torch.testing.assert_close(our[2], ref_out["depth"], rtol=2e-6, atol=0)
+    torch.testing.assert_close(our[1], ref_out["rgb"], rtol=0, atol=2e-6)
+    assert torch.equal(our[4], ref_out["invalid"])
 
 
 def _train_step_case():

@@ -5,7 +5,8 @@
 # Steps:
 #   pytest[:<-k expr>]      the GPU suite (or the tests matching the expression)
 #   smoke                   __graft_entry__.smoke()
-#   bench[:<args>]          bench.py <args> -> bench[_<args>].json (+ .err)      (args with , for spaces, e.g. bench:--workload,train)
+#   bench[:<args>]          bench.py --full <args> -> bench[_<args>].json (+ .err)      (args with , for spaces, e.g. bench:--workload,train)
+#   torchrun[:<args>]       bench.py --full <args> under torch.distributed.run at N = 1 -> bench_torchrun_n1.json (+ .err)
 #   trace:<name>:<args>     rocprofv3 --kernel-trace --stats of bench.py <args> -> <name>_kernel_stats.csv (+ the bts:: lines on stdout)
 #   steptrace:<name>:<marker>:<args>   rocprofv3 --kernel-trace of bench.py <args>; per-kernel table of the last 3 steps (delimited by the
 #                           once-per-step kernel <marker>) -> <name>_steps.txt
@@ -29,8 +30,12 @@ for STEP in "$@"; do
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.txt ;;
     bench)
       ARGS=${REST//,/ }; NAME=bench$(echo "$REST" | tr -c 'A-Za-z0-9\n' '_' | sed 's/__*/_/g;s/_$//')
-      timeout 900 python bench.py $ARGS > $O/$NAME.json 2> $O/$NAME.err || tail -5 $O/$NAME.err
+      timeout 900 python bench.py --full $ARGS > $O/$NAME.json 2> $O/$NAME.err || tail -5 $O/$NAME.err
       python tools/bench_summary.py $O/$NAME.json ;;
+    torchrun)
+      timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full ${REST//,/ } \
+        > $O/bench_torchrun_n1.json 2> $O/bench_torchrun_n1.err || tail -5 $O/bench_torchrun_n1.err
+      python tools/bench_summary.py $O/bench_torchrun_n1.json | head -3 ;;
     trace)
       NAME=${REST%%:*}; ARGS=${REST#*:}; ARGS=${ARGS//,/ }
       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/trace_$NAME -o trace -- python $GRAFT_REPO_ROOT/bench.py $ARGS > $GRAFT_REPO_ROOT/$O/trace_$NAME.log 2>&1)

@@ -126,6 +126,13 @@ SYMBOLS = {
     "bts_conv3x3_fwd": (C.c_int, [C.POINTER(BtsConv3x3), _P]),
     "bts_conv3x3_bwd_workspace": (C.c_size_t, [C.POINTER(BtsConv3x3)]),
     "bts_conv3x3_bwd": (C.c_int, [C.POINTER(BtsConv3x3), _P, _P, C.c_size_t, _P, _P, _P, _P]),
+    # MLP-predicted colour (sample_color=False)
+    "bts_mlp_color_param_count": (C.c_int64, [C.POINTER(BtsFieldCfg)]),
+    "bts_render_fwd_mlp_color": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsRenderArgs), _P]),
+    "bts_render_bwd_mlp_color_workspace": (C.c_size_t, [C.POINTER(BtsFieldCfg), C.POINTER(BtsRenderArgs)]),
+    "bts_render_bwd_mlp_color": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsRenderArgs),
+                                           C.POINTER(BtsRenderGrads), _P, C.c_size_t, _P]),
+    "bts_field_query_mlp_color": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), _P, _I, _I, _P, _P, _P, _P]),
 }
 
 _lock = threading.Lock()

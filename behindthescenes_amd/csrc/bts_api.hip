@@ -40,6 +40,13 @@ int occupancy_profile_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, con
 size_t render_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
 int render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* ws,
                     size_t ws_bytes, hipStream_t s, bool flush_clean = false);
+// MLP-predicted colour (bts_mlp_color.hip)
+int mlp_color_render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
+int mlp_color_field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
+                               float* invalid, float* sigma, hipStream_t s);
+size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
+int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
+                              hipStream_t s);
 }  // namespace bts
 
 using namespace bts;
@@ -367,6 +374,94 @@ int bts_distance_to_z(const float* depths, const float* inv_K, int32_t N, int32_
 int bts_invert_small(const float* src, float* dst, int32_t N, int32_t dim, void* stream) {
   BTS_CHECK_LAYOUT(src && dst && N > 0 && (dim == 3 || dim == 4), "bts_invert_small");
   BTS_RET_LAUNCH(invert_small_launch(src, dst, N, dim, (hipStream_t)stream), "bts_invert_small");
+}
+
+// ---- MLP-predicted colour (sample_color=False): the field checks of check_cfg plus this head's own (nv = 1, no render view, G required)
+static int check_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const char* who) {
+  if (!cfg || !t) {
+    set_error("%s: NULL cfg/tensors", who);
+    return BTS_E_INVALID;
+  }
+  if (cfg->nv != 1) {
+    set_error("%s: nv=%ld, but MLP-predicted colour has exactly one colour output (nv = 1, models_bts.py:321)", who, (long)cfg->nv);
+    return BTS_E_INVALID;
+  }
+  if (cfg->enc_render_view != -1) {
+    set_error("%s: enc_render_view=%ld must be -1 (this head has no render views)", who, (long)cfg->enc_render_view);
+    return BTS_E_INVALID;
+  }
+  if (int rc = check_cfg(cfg, t, false)) return rc;
+  if (!t->proj_nhwc) {
+    set_error("%s: the projected feature map (proj_nhwc) is required", who);
+    return BTS_E_INVALID;
+  }
+  return BTS_OK;
+}
+
+static int check_mlp_color_args(const BtsRenderArgs* a, const char* who, bool bwd) {
+  if (!a || !a->rays || (bwd ? (!a->z_samp || !a->sigma_raw || !a->trans) : ((!a->z_samp && !a->jitter) || !a->rgb || !a->depth))) {
+    set_error(bwd ? "%s: NULL argument (rays, z_samp and the forward's sigma_raw + trans are required)"
+                  : "%s: NULL render argument (rays, z_samp or jitter, rgb and depth are required)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->rays_per_sample <= 0 || a->K <= 0) {
+    set_error("%s: non-positive rays_per_sample=%ld K=%ld", who, (long)a->rays_per_sample, (long)a->K);
+    return BTS_E_INVALID;
+  }
+  if (a->K > 256) {
+    set_error("%s: K=%ld samples per ray; this head's kernels take whole rays of at most 256 samples per work-group", who, (long)a->K);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (!bwd && (a->invalid_wsum || a->invalid_any)) {
+    set_error("%s: invalid_wsum / invalid_any are not produced for MLP-predicted colour (request weights and invalid)", who);
+    return BTS_E_UNSUPPORTED;
+  }
+  return BTS_OK;
+}
+
+int64_t bts_mlp_color_param_count(const BtsFieldCfg* cfg) {
+  if (!cfg) {
+    set_error("%s: NULL cfg", "bts_mlp_color_param_count");
+    return -1;
+  }
+  return bts_mlp_param_count(cfg) + 3 * (int64_t)cfg->d_hidden + 3;
+}
+
+int bts_render_fwd_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, void* stream) {
+  if (int rc = check_mlp_color(cfg, t, "bts_render_fwd_mlp_color")) return rc;
+  if (int rc = check_mlp_color_args(a, "bts_render_fwd_mlp_color", false)) return rc;
+  return mlp_color_render_fwd_impl(cfg, t, a, (hipStream_t)stream);
+}
+
+size_t bts_render_bwd_mlp_color_workspace(const BtsFieldCfg* cfg, const BtsRenderArgs* a) {
+  if (!cfg || !a || cfg->n <= 0 || a->rays_per_sample <= 0 || a->K <= 0 || cfg->d_hidden <= 0) return 0;
+  return mlp_color_bwd_workspace_impl(cfg, a);
+}
+
+int bts_render_bwd_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_mlp_color(cfg, t, "bts_render_bwd_mlp_color")) return rc;
+  if (int rc = check_mlp_color_args(a, "bts_render_bwd_mlp_color", true)) return rc;
+  if (!g) {
+    set_error("%s: NULL gradient struct", "bts_render_bwd_mlp_color");
+    return BTS_E_INVALID;
+  }
+  const size_t need = mlp_color_bwd_workspace_impl(cfg, a);
+  if (workspace_bytes < need || !workspace) {
+    set_error("%s: workspace too small (%ld bytes needed)", "bts_render_bwd_mlp_color", (long)need);
+    return BTS_E_WORKSPACE;
+  }
+  return mlp_color_render_bwd_impl(cfg, t, a, g, workspace, (hipStream_t)stream);
+}
+
+int bts_field_query_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int32_t P, int32_t only_density,
+                              float* rgb, float* invalid, float* sigma, void* stream) {
+  if (int rc = check_mlp_color(cfg, t, "bts_field_query_mlp_color")) return rc;
+  if (!xyz || !sigma || P <= 0 || (!only_density && !rgb)) {
+    set_error("%s: NULL/empty query argument (P=%ld)", "bts_field_query_mlp_color", (long)P);
+    return BTS_E_INVALID;
+  }
+  return mlp_color_field_query_impl(cfg, t, xyz, P, only_density, rgb, invalid, sigma, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -53,6 +53,9 @@ class BTSNet(nn.Module):
         self.flip_augmentation = conf.get("flip_augmentation", False)
         self.return_sample_depth = conf.get("return_sample_depth", False)
         self.sample_color = conf.get("sample_color", True)
+        # sample_color=False on the HIP kernels (bts_*_mlp_color) instead of the PyTorch composition of torch_modes.py; opt-in, the
+        # composition stays the default
+        self.native_mlp_color = bool(conf.get("native_mlp_color", False))
         if self.return_sample_depth:
             raise NotImplementedError("return_sample_depth is not used by any shipped config")
 
@@ -82,7 +85,7 @@ class BTSNet(nn.Module):
                                      n_blocks=self.mlp_coarse.n_blocks, num_freqs=self.code_xyz.num_freqs,
                                      freq_factor=self.code_xyz.freq_factor, d_min=float(self.d_min), d_max=float(self.d_max),
                                      inv_z=bool(self.inv_z), code_mode=self.code_mode, learn_empty=bool(self.learn_empty),
-                                     empty_empty=bool(self.empty_empty))
+                                     empty_empty=bool(self.empty_empty), mlp_color=not self.sample_color and self.native_mlp_color)
         self.spec_fine = self.spec if self.mlp_fine is None else \
             dataclasses.replace(self.spec, d_hidden=self.mlp_fine.d_hidden, n_blocks=self.mlp_fine.n_blocks)
         if not self.code_xyz.include_input:
@@ -92,8 +95,9 @@ class BTSNet(nn.Module):
     def torch_mode(self):
         """True when the field is served by the PyTorch compositions of torch_modes.py instead of the fused HIP kernels: the two modes
         no shipped config uses -- MLP-predicted colours (`sample_color: false`) and merged encoder views
-        (`encode(..., combine_ids=...)` or more than one encoder view)."""
-        return (not self.sample_color) or self._combined
+        (`encode(..., combine_ids=...)` or more than one encoder view).  `native_mlp_color: true` puts the first of them on the kernels
+        (bts_*_mlp_color)."""
+        return (not self.sample_color and not self.native_mlp_color) or self._combined
 
     def mlp(self, coarse=True):
         """models_bts.py:293-307: the MLP of the coarse pass, or of the fine pass when a separate one was configured."""
@@ -193,7 +197,7 @@ class BTSNet(nn.Module):
         self._native = {}
         nv = src.shape[1]
         native.check_supported(self.spec, nv)
-        if nv:
+        if nv and not self.spec.mlp_color:   # (predicted colours read no frames)
             scale, shift = (0.5, 0.5) if self._grid_c_raw else (1.0, 0.0)   # x * .5 + .5 inside the packing kernel (mul, then add)
             self._imgs_nhwc4 = native.pack_rgb(src.detach().float().contiguous(), scale, shift)
             self._K_r = self.grid_c_Ks.detach().float().contiguous()
@@ -304,7 +308,7 @@ class BTSNet(nn.Module):
         with torch.no_grad(), profiler.record_function("model_inference"):   # models_bts.py:275
             rgb, invalid, sigma = native.field_query(ft, self.mlp(coarse).packed().detach(), xyz.detach().float().contiguous(),
                                                      only_density=only_density)
-        nv = self._grid_c_src.shape[1]
+        nv = 1 if self.spec.mlp_color else self._grid_c_src.shape[1]
         if only_density:
             rgb = torch.zeros((xyz.shape[0], xyz.shape[1], nv * 3), device=sigma.device)
             invalid = invalid.unsqueeze(1)   # the reference returns (n, nv_enc=1, P, 1) here (models_bts.py:337)

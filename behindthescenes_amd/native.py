@@ -31,6 +31,8 @@ class FieldSpec:
     # the geometry of the map's tile flags (BtsFieldCfg.tile_blocks, ABI 9): 16 x 4 blocks (True: faster with a channels-last feature map)
     # or runs of 64 texels (False: faster with an NCHW one).  Every call on one (d_proj, tiles) pair must use the same spec.
     tile_blocks: bool = False
+    # MLP-predicted colour (sample_color=False, models_bts.py:41-42, 315-321): a four-output lin_out, served by the *_mlp_color entries
+    mlp_color: bool = False
 
     @property
     def d_in(self):
@@ -38,7 +40,8 @@ class FieldSpec:
 
     def mlp_param_count(self):
         hd = self.d_hidden
-        return hd * self.d_in + hd + self.n_blocks * (2 * hd * hd + 2 * hd) + hd + 1
+        d_out = 4 if self.mlp_color else 1
+        return hd * self.d_in + hd + self.n_blocks * (2 * hd * hd + 2 * hd) + d_out * hd + d_out
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -362,8 +365,14 @@ class FieldTensors:
         if proj_nhwc is None and ch != spec.C:
             raise BtsNativeError(f"feat_nhwc has {ch} channels, spec says C={spec.C}")
         nv = 0 if imgs_nhwc4 is None else imgs_nhwc4.shape[1]
+        if spec.mlp_color:
+            # the MLP predicts the one colour (nv = 1, models_bts.py:321): no frames, no render cameras
+            if proj_nhwc is None:
+                raise BtsNativeError("MLP-predicted colour needs the projected feature map")
+            imgs_nhwc4 = K_r = w2c_r = None
+            nv, enc_view = 1, -1
         _req(ref.detach(), "proj_nhwc/feat_nhwc"), _req(K_enc, "K_enc", (n, 3, 3)), _req(w2c_enc, "w2c_enc", (n, 4, 4))
-        if nv:
+        if nv and not spec.mlp_color:
             _req(imgs_nhwc4, "imgs_nhwc4", (n, nv, H, W, 4)), _req(K_r, "K_r", (n, nv, 3, 3)), _req(w2c_r, "w2c_r", (n, nv, 4, 4))
         if nv > _lib.BTS_MAX_VIEWS:
             raise BtsNativeError(f"nv={nv} render views exceed BTS_MAX_VIEWS={_lib.BTS_MAX_VIEWS}")
@@ -381,6 +390,12 @@ class FieldTensors:
         # sampled=...): only the tiles those samples read were projected, the rest of proj_nhwc is uninitialised memory), else None.
         # field_query / occupancy_profile reject a partial map, render_fwd / render_bwd check the sample set.
         self.partial = None
+
+    @property
+    def mlp_color(self) -> bool:
+        """True for a four-output MLP that predicts the colour (sample_color=False): render_fwd / render_bwd / field_query then take the
+        bts_*_mlp_color entries."""
+        return self.spec.mlp_color
 
     def cfg(self, nv=None) -> BtsFieldCfg:
         return _spec_cfg(self.spec, self.n, self.H, self.W, self.nv if nv is None else nv, self.feat_shift, self.enc_view)
@@ -446,6 +461,8 @@ def render_fwd(ft: FieldTensors, mlp_params: torch.Tensor, rays: torch.Tensor, z
     def new(*shape):
         return torch.empty(shape, device=dev, dtype=torch.float32)
 
+    if ft.mlp_color and want_invalid_sums:
+        raise BtsNativeError("render_fwd: MLP-predicted colour produces no invalid_wsum / invalid_any (request weights and invalid instead)")
     outs = dict(rgb=new(B, nv * 3), depth=new(B), weights=new(B, K) if want_weights else None,
                 alphas=new(B, K) if want_alphas else None, invalid=new(B, K, nv) if want_invalid else None,
                 rgb_samps=new(B, K, nv * 3) if want_rgb_samps else None, sigma_raw=new(B, K) if want_saved else None,
@@ -454,7 +471,8 @@ def render_fwd(ft: FieldTensors, mlp_params: torch.Tensor, rays: torch.Tensor, z
                 z_samp=new(B, K) if (z_samp is None and want_z) else None)
     cfg, tens = ft.cfg(), ft.tensors(mlp_params)
     args = _render_args(ft, rays, z_samp, hard_alpha_cap, white_bkgd, outs, sigma_noise, jitter, lindisp)
-    _lib.check(_lib.load().bts_render_fwd(C.byref(cfg), C.byref(tens), C.byref(args), _stream(rays)), "bts_render_fwd")
+    fn = "bts_render_fwd_mlp_color" if ft.mlp_color else "bts_render_fwd"
+    _lib.check(getattr(_lib.load(), fn)(C.byref(cfg), C.byref(tens), C.byref(args), _stream(rays)), fn)
     if z_samp is not None:
         outs["z_samp"] = z_samp
     return outs
@@ -501,6 +519,12 @@ def render_bwd(ft: FieldTensors, mlp_params, rays, z_samp, sigma_raw, trans, *, 
     grads = BtsRenderGrads(g_rgb=dp(g_rgb), g_depth=dp(g_depth), g_weights=dp(g_weights), g_alphas=dp(g_alphas),
                            d_proj_nhwc=dp(d_proj), d_mlp_params=dp(d_mlp), d_empty_proj=dp(d_empty), d_proj_tiles=dp(tiles))
     lib = _lib.load()
+    if ft.mlp_color:
+        ws_bytes = lib.bts_render_bwd_mlp_color_workspace(C.byref(cfg), C.byref(args))
+        ws = _workspace(dev, int(ws_bytes))
+        _lib.check(lib.bts_render_bwd_mlp_color(C.byref(cfg), C.byref(tens), C.byref(args), C.byref(grads), _ptr(ws), ws_bytes, _stream(rays)),
+                   "bts_render_bwd_mlp_color")
+        return d_proj, d_mlp, d_empty
     ws_bytes = lib.bts_render_bwd_workspace(C.byref(cfg), C.byref(args))
     ws = _workspace(dev, int(ws_bytes))
     _lib.check(lib.bts_render_bwd(C.byref(cfg), C.byref(tens), C.byref(args), C.byref(grads), _ptr(ws), ws_bytes, _stream(rays)),
@@ -538,6 +562,15 @@ def field_query(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Tensor, o
     _req(xyz, "xyz", (ft.n, P, 3))
     _check_partial(ft, None, None, "field_query")
     dev = xyz.device
+    if ft.mlp_color:
+        # sample_color=False (models_bts.py:315-338): rgb (n, P, 3) from the MLP, zeros with only_density (:336); invalid (n, P, 1)
+        rgb = torch.empty((n, P, 3), device=dev, dtype=torch.float32)
+        invalid = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
+        sigma = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
+        cfg, tens = ft.cfg(), ft.tensors(mlp_params)
+        _lib.check(_lib.load().bts_field_query_mlp_color(C.byref(cfg), C.byref(tens), _ptr(xyz), P, int(only_density), _ptr(rgb), _ptr(invalid),
+                                                         _ptr(sigma), _stream(xyz)), "bts_field_query_mlp_color")
+        return rgb, invalid, sigma
     nv = 0 if only_density else ft.nv
     rgb = torch.empty((n, P, nv * 3), device=dev, dtype=torch.float32) if nv else None
     invalid = torch.empty((n, P, max(nv, 1)), device=dev, dtype=torch.float32)
@@ -556,6 +589,8 @@ def occupancy_profile(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Ten
     [, sigma (n, levels * columns)]  (bts_occupancy_profile: render_profile of scripts/inference_setup.py in one pass)."""
     n, P, _ = xyz.shape
     _req(xyz, "xyz", (ft.n, P, 3))
+    if ft.mlp_color:
+        raise BtsNativeError("occupancy_profile: not available for MLP-predicted colour (sample_color=False); use field_query")
     if levels <= 0 or P % levels:
         raise BtsNativeError(f"{P} points are not {levels} whole levels")
     _check_partial(ft, None, None, "occupancy_profile")

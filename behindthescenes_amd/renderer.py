@@ -185,7 +185,8 @@ class NeRFRenderer(torch.nn.Module):
             ns = prop_weights.shape[-1]
             z_coarse = self.sample_coarse_from_dist(rays, prop_weights.reshape(-1, ns), prop_z.reshape(-1, ns))
             z_coarse, _ = torch.sort(z_coarse, dim=-1)
-        if self.lean_training_outputs and self.training and not self.using_fine and torch.is_grad_enabled() and not getattr(model, "torch_mode", False):
+        if (self.lean_training_outputs and self.training and not self.using_fine and torch.is_grad_enabled() and not getattr(model, "torch_mode", False)
+                and not getattr(getattr(model, "spec", None), "mlp_color", False)):   # (MLP-predicted colour: no per-ray invalid sums)
             # in a training step nothing downstream of the renderer reads the per-sample tensors except the loss'
             # invalid-ray mask, and that only through sum_k weights * invalid / any_k invalid per view -- the render kernel's
             # epilogue emits exactly those (8 B per ray and view), and weights / alphas / invalid are neither written nor returned

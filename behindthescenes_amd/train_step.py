@@ -229,7 +229,7 @@ class FusedTrainStep(torch.nn.Module):
         if (not net.sample_color) or net._d_out != 1:
             # the field's MLP is four outputs wide and served by torch_modes.py: the fused kernels know the one-output
             # density layout only (net._combined is encode's state; the two-call path has exactly one encoder view, checked next)
-            return "sample_color=False (MLP-predicted colours run as a PyTorch composition, torch_modes.py)"
+            return "sample_color=False (MLP-predicted colours: the one-call training step serves sampled colours only)"
         if len(ids_encoder) != 1:
             return "more than one encoder view"
         if not (1 <= len(ids_render) <= _lib.BTS_MAX_VIEWS) or not (1 <= len(ids_loss) <= _lib.BTS_MAX_LOSS_VIEWS):
@@ -437,6 +437,9 @@ class FusedEvalFrame(torch.nn.Module):
             return "fine pass / sampling schedule / white background / density noise"
         if getattr(r.sample_coarse, "__func__", None) is not NeRFRenderer.sample_coarse:
             return "sample_coarse is overridden"
+        if not net.sample_color:
+            # bts_eval_frame knows the sampled-colour field only; native_mlp_color renders entry by entry (bts_render_fwd_mlp_color)
+            return "sample_color=False (MLP-predicted colours: the one-call eval frame serves sampled colours only)"
         if net.torch_mode or net.mlp_fine is not None or net.get_scale() != 0 or (net.flip_augmentation and net.training):
             return "a PyTorch-composed field mode / a separate fine MLP / a scale other than 0 / flip augmentation"
         if len(ids_encoder) != 1 or len(ids_render) > _lib.BTS_MAX_VIEWS or self.sampler.channels != 3:

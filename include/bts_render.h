@@ -501,6 +501,44 @@ typedef struct BtsEvalFrame {
 } BtsEvalFrame;
 int bts_eval_frame(const BtsEvalFrame* f, void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * MLP-predicted colour: BTSNet with sample_color=False (models_bts.py:41-42, 315-321), the PixelNeRF-style head that BTS's sampled
+ * colours are compared against.  The MLP has FOUR outputs: sigma = relu(o0) (:317), rgb = sigmoid(o1..3) (:318-320); there are no
+ * colour taps and one "view" (nv = 1, :321).  Additive to ABI 9: every struct and entry point above is unchanged.
+ *
+ * Packed parameters: as at the top of this file up to lin_out, then w_out (4 x d_hidden, row-major = nn.Linear.weight) and b_out (4);
+ * w_in stays at offset 0, so bts_project_features* and their backwards serve this layout unchanged.
+ * BtsFieldCfg: nv must be 1 and enc_render_view -1 (BTS_E_INVALID otherwise); C, d_hidden, n_blocks inside the envelope of
+ * bts_supported (BTS_E_UNSUPPORTED otherwise).  BtsFieldTensors: proj_nhwc is required; imgs_nhwc4, K_r and w2c_r are not read (NULL is
+ * fine).  Every error leaves a message and launches nothing.
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+/* floats in mlp_params of this head: bts_mlp_param_count(cfg) + 3 d_hidden + 3; -1 for a NULL cfg */
+int64_t bts_mlp_color_param_count(const BtsFieldCfg* cfg);
+
+/* NeRFRenderer.composite (nerf.py:210-313) over BTSNet.forward with sample_color=False: per sample sigma = relu(o0) (empty_empty as in
+ * bts_render_fwd), + sigma_noise, alpha = 1 - exp(-|delta| relu(sigma)) (nerf.py:279-283), hard_alpha_cap, white_bkgd, in-kernel
+ * sample_coarse (jitter, z_samp_out, lindisp) and feat_shift as in bts_render_fwd.  Outputs: rgb (n*Bp, 3) = sum_k w_k sigmoid(o1..3),
+ * depth, weights, alphas, invalid (n*Bp, K, 1) = the encoder view's frustum flag, rgb_samps (n*Bp, K, 3) = the per-sample colours,
+ * sigma_raw = o0 before the relu, trans as in bts_render_fwd.  invalid_wsum / invalid_any are NOT produced (BTS_E_UNSUPPORTED when
+ * given): the photometric loss reads weights and invalid in this mode.  K <= 256. */
+int bts_render_fwd_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, void* stream);
+
+/* Backward of bts_render_fwd_mlp_color.  Inputs: g_rgb (n*Bp, 3), g_depth, g_weights, g_alphas (any may be NULL); `a` carries z_samp and
+ * the forward's sigma_raw and trans; a->rgb_samps, when given, is READ (the forward's colours).  Outputs, ACCUMULATED: d_proj_nhwc with
+ * its tile flags (d_proj_tiles, the geometry of ABI 9), d_mlp_params in the four-output layout, d_empty_proj.  relu'(0) = 0 as in torch.
+ * workspace: bts_render_bwd_mlp_color_workspace(cfg, a) bytes (4 (d_hidden + 1) bytes per sample: the gradient row at lin_in's output
+ * and a liveness slot, + the dW_pe slot copies); contents need no initialisation. */
+size_t bts_render_bwd_mlp_color_workspace(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
+int bts_render_bwd_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* BTSNet.forward on raw points with sample_color=False (models_bts.py:266-338): xyz (n, P, 3) -> rgb (n, P, 3) = sigmoid(o1..3),
+ * invalid (n, P, 1) = the encoder view's frustum flag, sigma (n, P) = relu(o0) (empty_empty applied).  only_density != 0: rgb, when
+ * given, is written with zeros (:336). */
+int bts_field_query_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int32_t P, int32_t only_density,
+                              float* rgb, float* invalid, float* sigma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

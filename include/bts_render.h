@@ -405,7 +405,21 @@ typedef struct BtsTrainStep {
   /* scratch (caller-owned, contents need no initialisation) */
   float* cams;               /* n * (9 + 16 + nv * (9 + 16)) floats: K_enc (n, 9), w2c_enc (n, 16), K_r (n, nv, 9), w2c_r (n, nv, 16) */
   float* imgs_nhwc4;         /* (n, nv, H, W, 4) */
-  void* bwd_workspace;       /* max over the scales of bts_render_bwd_workspace */
+  /* max over the scales of bts_render_bwd_workspace.  BOTH calls write here.  For a scale whose map has n_tiles = n * ceil(h w / 64)
+   * >= 4096 tiles (BTS_LIST_MIN_TILES of csrc/bts_prep.hip) the projection passes take their list-driven form and keep the tile list in
+   * this workspace: L(n_tiles) = (4 + n_tiles) * 4 + n_tiles + 16 bytes -- int32[0] the number of flagged tiles, int32[1 .. 3] zero,
+   * int32[4 ..] their indices in no particular order, and (backward only) at byte (4 + n_tiles) * 4 one byte per tile: the copy of the
+   * flags the backward found in d_proj_tiles.
+   *   forward:  scale s uses the slice of slice = (bwd_workspace_bytes / n_scales) & ~255 bytes that starts at byte s * slice, when
+   *             slice >= L(n_tiles);
+   *   backward: scale s uses the start of the workspace (with concurrent_scales: of its slice of bts_render_bwd_workspace rounded up to
+   *             256 bytes, at s times that), when bts_render_bwd_workspace minus the 8 x 40 x d_hidden floats at its end >= L(n_tiles) --
+   *             after the scale's render passes have read what they parked there.  One after the other, a later scale's passes overwrite
+   *             an earlier scale's list.
+   * A scale whose slice is too small (or whose map is smaller) takes the flag-driven form: the same results, tile by tile.
+   * So a workspace must not be shared between a step whose backward is still to come and another step's forward or backward on
+   * another stream; on ONE stream a forward may reuse the workspace of a pending backward (the lists are rebuilt by each call). */
+  void* bwd_workspace;
   size_t bwd_workspace_bytes;
   float* d_empty_proj;       /* (Hd) or NULL */
   /* outputs of the backward */

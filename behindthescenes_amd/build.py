@@ -97,6 +97,8 @@ def build_library(force: bool = False, verbose: bool = False, probe: bool = Fals
 # differently scheduled builds of the product sources (tests/test_gpu_determinism.py re-runs parity against them)
 SCHEDULE_VARIANTS = {"o2": ["-O2"], "regionbarrier": ["-DBTS_REGION_BARRIER"], "gatherregs": ["-DBTS_GATHER_REGS"],
                      "fetchearly": ["-DBTS_GL_FETCH_EARLY"],
+                     # the render kernel without its second loop for rays whose samples share their texels (tests/test_gpu_shared_texels.py)
+                     "nosharedtexels": ["-DBTS_NO_SHARED_TEXELS"],
                      # not a schedule: the list-driven projection passes at EVERY map size (tests/test_gpu_tile_list.py)
                      "listall": ["-DBTS_LIST_MIN_TILES=1"]}
 # the erratum on purpose: the round-1 flags (SLP vectoriser on) -- tests/test_gpu_determinism.py shows this build is NOT deterministic

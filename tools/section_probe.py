@@ -2,7 +2,9 @@
     python tools/section_probe.py
 Sections (s_memtime deltas accumulated per wave, averaged over waves, per ray iteration):
  0 geometry (ray/camera loads, projection, taps, colour issue, tile broadcast)   1 gather + encoding + MFMA
- 2 lin_out + softplus   3 colour blend + compositing scan   4 per-sample stores   5 per-ray sums + stores"""
+ 2 lin_out + softplus   3 colour blend + compositing scan   4 per-sample stores   5 per-ray sums + stores
+Ablations (BTS_ABLATE bits, probe build only): 1 no gather (register-gather build), 2 no trigonometry, 4 no MFMAs, 64 every ray takes
+the render kernel's shared-texel loop (one fetch of G per ray; wrong rows for view 1 -- what a single fetch would buy there)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,7 +27,7 @@ os.environ["BTS_DBG_PTR"] = str(dbg.data_ptr())
 half = rays.shape[0] // 2
 sets = {"both": (rays, z), "view0": (rays[:half].contiguous(), z[:half].contiguous()), "view1": (rays[half:].contiguous(), z[half:].contiguous())}
 for name, (r_, z_) in sets.items():
-    for extra in ((0, 2, 4, 1, 2 | 4 | 1) if name != "both" else (0,)):
+    for extra in ((0, 2, 4, 1, 2 | 4 | 1, 64) if name != "both" else (0,)):
         os.environ["BTS_ABLATE"] = str(128 | extra)
         for _ in range(2):
             dbg.zero_()

@@ -11,6 +11,8 @@ from .projection import distance_to_z  # noqa: F401
 from .ray_sampler import ImageRaySampler, PatchRaySampler, RandomRaySampler, gen_rays  # noqa: F401
 from .renderer import NeRFRenderer, _RenderWrapper  # noqa: F401
 from .train_step import FusedEvalFrame, FusedTrainStep  # noqa: F401
+from . import lidar_occupancy  # noqa: F401
+from .lidar_occupancy import FusedOccupancyEval  # noqa: F401
 
 __all__ = ["BTSNet", "NeRFRenderer", "PositionalEncoding", "ResnetFC", "ResnetBlockFC", "make_mlp", "make_backbone",
-           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "BtsNativeError"]
+           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "BtsNativeError"]

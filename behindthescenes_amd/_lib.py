@@ -89,6 +89,16 @@ class BtsConv3x3(C.Structure):
                [(k, C.c_void_p) for k in ("x", "weight", "bias", "y")]
 
 
+class BtsOccupancyEval(C.Structure):
+    _fields_ = [("q_pts", C.c_void_p)] + [(k, C.c_int32) for k in ("P", "T", "y_res", "H", "W", "reserved_")] + \
+               [(k, C.c_void_p) for k in ("points", "offsets", "velo_poses", "borders361")] + \
+               [(k, C.c_float) for k in ("y_lo", "y_hi", "max_dist", "min_dist", "occ_threshold")] + [("reserved2_", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("pred_depth_z", "proj", "cam_pose", "counts", "masks", "sigma", "tables")]
+
+
+BTS_LIDAR_MAX_CLOUDS = 32
+BTS_LIDAR_MAX_SLICES = 16
+
 # every symbol include/bts_render.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int32
@@ -133,6 +143,12 @@ SYMBOLS = {
     "bts_render_bwd_mlp_color": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsRenderArgs),
                                            C.POINTER(BtsRenderGrads), _P, C.c_size_t, _P]),
     "bts_field_query_mlp_color": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), _P, _I, _I, _P, _P, _P, _P]),
+    # LiDAR occupancy evaluation (evaluator_lidar.py)
+    "bts_lidar_slices_workspace": (C.c_size_t, [_I, _I]),
+    "bts_lidar_slices": (C.c_int, [_P, C.POINTER(C.c_int32), _I, _P, _P, C.c_float, C.c_float, _I, C.c_float, _P, _P, _P]),
+    "bts_lidar_occupancy": (C.c_int, [_P, _I, _P, _I, _I, _P, C.c_float, _P, _P, _P]),
+    "bts_occupancy_eval_workspace": (C.c_size_t, [_I, _I, _I]),
+    "bts_occupancy_eval": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsOccupancyEval), _P, C.c_size_t, _P]),
 }
 
 _lock = threading.Lock()

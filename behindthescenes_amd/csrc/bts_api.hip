@@ -47,6 +47,15 @@ int mlp_color_field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t,
 size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
 int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
                               hipStream_t s);
+// LiDAR occupancy evaluation (bts_occ.hip)
+size_t lidar_bins_bytes(int T, int y_res);
+int lidar_slices_launch(const float* points, const int* offsets, int T, const float* velo_poses, const float* borders, float y_lo, float y_hi,
+                        int y_res, float max_dist, void* bins_ws, float* tables, hipStream_t s);
+int lidar_occupancy_launch(const float* q_pts, int P, const float* tables, int y_res, int T, const float* world_to_velo, float min_dist,
+                           unsigned char* is_occupied, unsigned char* is_visible, hipStream_t s);
+int occ_metrics_launch(const float* q_pts, int P, const float* sigma, const unsigned char* is_occupied, const unsigned char* is_visible,
+                       const float* depth_z, int H, int W, const float* proj, const float* w2c, float occ_threshold, int* counts,
+                       unsigned char* masks, hipStream_t s);
 }  // namespace bts
 
 using namespace bts;
@@ -462,6 +471,117 @@ int bts_field_query_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, 
     return BTS_E_INVALID;
   }
   return mlp_color_field_query_impl(cfg, t, xyz, P, only_density, rgb, invalid, sigma, (hipStream_t)stream);
+}
+
+// ---- LiDAR occupancy evaluation (evaluator_lidar.py): limits and host-side checks shared by the three entry points
+static int check_lidar_limits(int T, int y_res, const char* who) {
+  if (T <= 0 || y_res <= 0) {
+    set_error("%s: non-positive T=%ld / y_res=%ld", who, (long)T, (long)y_res);
+    return BTS_E_INVALID;
+  }
+  if (T > BTS_LIDAR_MAX_CLOUDS || y_res > BTS_LIDAR_MAX_SLICES) {
+    set_error("%s: T=%ld clouds / y_res=%ld slices; at most 32 clouds and 16 slices are supported", who, (long)T, (long)y_res);
+    return BTS_E_UNSUPPORTED;
+  }
+  return BTS_OK;
+}
+
+static int check_lidar_clouds(const float* points, const int32_t* offsets, int T, const char* who) {
+  if (((uintptr_t)points & 15) != 0) {
+    set_error("%s: points must be 16-byte aligned", who);
+    return BTS_E_INVALID;
+  }
+  if (offsets[0] != 0) {
+    set_error("%s: offsets[0]=%ld must be 0", who, (long)offsets[0]);
+    return BTS_E_INVALID;
+  }
+  for (int t = 0; t < T; ++t)
+    if (offsets[t + 1] < offsets[t]) {
+      set_error("%s: offsets are not monotone at cloud %ld (%ld after %ld)", who, (long)t, (long)offsets[t + 1], (long)offsets[t]);
+      return BTS_E_INVALID;
+    }
+  for (int t = 0; t < T; ++t)
+    if (offsets[t + 1] - offsets[t] < 360) {
+      set_error("%s: cloud %ld has %ld points; the reference's tables need at least 360 selected points per slice and cloud", who, (long)t,
+                (long)(offsets[t + 1] - offsets[t]));
+      return BTS_E_UNSUPPORTED;
+    }
+  return BTS_OK;
+}
+
+static size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+
+size_t bts_lidar_slices_workspace(int32_t T, int32_t y_res) {
+  if (T <= 0 || y_res <= 0 || T > BTS_LIDAR_MAX_CLOUDS || y_res > BTS_LIDAR_MAX_SLICES) return 0;
+  return lidar_bins_bytes(T, y_res);
+}
+
+int bts_lidar_slices(const float* points, const int32_t* offsets, int32_t T, const float* velo_poses, const float* borders361, float y_lo,
+                     float y_hi, int32_t y_res, float max_dist, void* bins_workspace, float* tables, void* stream) {
+  BTS_CHECK_LAYOUT(points && offsets && velo_poses && borders361 && bins_workspace && tables, "bts_lidar_slices");
+  if (int rc = check_lidar_limits(T, y_res, "bts_lidar_slices")) return rc;
+  if (int rc = check_lidar_clouds(points, offsets, T, "bts_lidar_slices")) return rc;
+  BTS_RET_LAUNCH(lidar_slices_launch(points, offsets, T, velo_poses, borders361, y_lo, y_hi, y_res, max_dist, bins_workspace, tables,
+                                     (hipStream_t)stream),
+                 "bts_lidar_slices");
+}
+
+int bts_lidar_occupancy(const float* q_pts, int32_t P, const float* tables, int32_t y_res, int32_t T, const float* world_to_velo,
+                        float min_dist, uint8_t* is_occupied, uint8_t* is_visible, void* stream) {
+  BTS_CHECK_LAYOUT(q_pts && tables && world_to_velo && is_occupied && is_visible && P > 0, "bts_lidar_occupancy");
+  if (int rc = check_lidar_limits(T, y_res, "bts_lidar_occupancy")) return rc;
+  BTS_RET_LAUNCH(lidar_occupancy_launch(q_pts, P, tables, y_res, T, world_to_velo, min_dist, is_occupied, is_visible, (hipStream_t)stream),
+                 "bts_lidar_occupancy");
+}
+
+// workspace of bts_occupancy_eval: bins + keys | tables | world_to_velo (T, 16) | camera w2c (16) | is_occupied (P) | is_visible (P) | sigma (P)
+size_t bts_occupancy_eval_workspace(int32_t P, int32_t T, int32_t y_res) {
+  if (P <= 0 || T <= 0 || y_res <= 0 || T > BTS_LIDAR_MAX_CLOUDS || y_res > BTS_LIDAR_MAX_SLICES) return 0;
+  return align16(lidar_bins_bytes(T, y_res)) + align16((size_t)y_res * T * 362 * 2 * 4) + (size_t)(T + 1) * 64 + 2 * align16((size_t)P) +
+         align16((size_t)P * 4);
+}
+
+int bts_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsOccupancyEval* a, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+  if (int rc = check_cfg(cfg, t, false)) return rc;
+  BTS_CHECK_LAYOUT(a && a->q_pts && a->points && a->offsets && a->velo_poses && a->borders361 && a->pred_depth_z && a->proj && a->cam_pose &&
+                       a->counts && a->P > 0 && a->H > 0 && a->W > 0,
+                   "bts_occupancy_eval");
+  if (cfg->n != 1) {
+    set_error("%s: n=%ld; the evaluator queries one encoded sample (n = 1)", "bts_occupancy_eval", (long)cfg->n);
+    return BTS_E_INVALID;
+  }
+  if (int rc = check_lidar_limits(a->T, a->y_res, "bts_occupancy_eval")) return rc;
+  if (int rc = check_lidar_clouds(a->points, a->offsets, a->T, "bts_occupancy_eval")) return rc;
+  const size_t need = bts_occupancy_eval_workspace(a->P, a->T, a->y_res);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) {
+    set_error("%s: workspace too small or not 16-byte aligned (%ld bytes needed)", "bts_occupancy_eval", (long)need);
+    return BTS_E_WORKSPACE;
+  }
+  const int P = a->P, T = a->T, y_res = a->y_res;
+  hipStream_t s = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(workspace);
+  void* bins = w;
+  w += align16(lidar_bins_bytes(T, y_res));
+  float* tables = a->tables ? a->tables : reinterpret_cast<float*>(w);
+  w += align16((size_t)y_res * T * 362 * 2 * 4);
+  float* w2v = reinterpret_cast<float*>(w);
+  float* w2c = w2v + (size_t)T * 16;
+  w += (size_t)(T + 1) * 64;
+  uint8_t* is_occ = reinterpret_cast<uint8_t*>(w);
+  w += align16((size_t)P);
+  uint8_t* is_vis = reinterpret_cast<uint8_t*>(w);
+  w += align16((size_t)P);
+  float* sigma = a->sigma ? a->sigma : reinterpret_cast<float*>(w);
+
+  if (int rc = field_query_impl(cfg, t, a->q_pts, P, 1, nullptr, nullptr, sigma, s)) return rc;
+  int rc = invert_small_launch(a->velo_poses, w2v, T, 4, s);
+  if (!rc) rc = invert_small_launch(a->cam_pose, w2c, 1, 4, s);
+  if (!rc) rc = lidar_slices_launch(a->points, a->offsets, T, a->velo_poses, a->borders361, a->y_lo, a->y_hi, y_res, a->max_dist, bins, tables, s);
+  if (!rc) rc = lidar_occupancy_launch(a->q_pts, P, tables, y_res, T, w2v, a->min_dist, is_occ, is_vis, s);
+  if (!rc) rc = occ_metrics_launch(a->q_pts, P, sigma, is_occ, is_vis, a->pred_depth_z, a->H, a->W, a->proj, w2c, a->occ_threshold, a->counts, a->masks, s);
+  if (rc) set_error("%s: kernel launch failed", "bts_occupancy_eval");
+  return rc;
 }
 
 }  // extern "C"

@@ -553,6 +553,77 @@ int bts_render_bwd_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, c
 int bts_field_query_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int32_t P, int32_t only_density,
                               float* rgb, float* invalid, float* sigma, void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * LiDAR occupancy evaluation: the ground-truth half of models/bts/evaluator_lidar.py (BTSWrapper.forward :266-340), next to the density
+ * query (bts_field_query) it is compared with.  Additive to ABI 9: every struct and entry point above is unchanged.
+ *
+ * Plain fp32, IEEE division and square root, no contraction; every reduction is an integer or bit-pattern atomic, so a rerun is
+ * bit-identical.  Quirks of the reference that are reproduced ON PURPOSE:
+ *   - check_occupancy measures the query's distance as the norm over all FOUR components of world_to_velo @ [p, 1], the homogeneous 1
+ *     included (torch.norm(pts_velo, dim=-1), :136);
+ *   - the occupancy vote starts at ones_like (:119): is_occupied = (1 + sum_j occupied_by_cloud_j) / T > (T - 2) / T, in fp32;
+ *   - visibility comes from the FIRST cloud only (:153);
+ *   - the carry that fills leading empty bins starts at the distance of the selected point with the smallest angle
+ *     (slice_points_polar[0, 1], :93), not at bin 0's minimum.
+ * Limits: T <= BTS_LIDAR_MAX_CLOUDS clouds, y_res <= BTS_LIDAR_MAX_SLICES slices, every cloud holds at least 360 points (the
+ * reference's [:n_bins] at :90 assumes 360 SELECTED points per slice and cloud, silently) -- anything else is BTS_E_UNSUPPORTED with a
+ * message and launches nothing.  What only the device could know: a (slice, cloud) that selects fewer than 360 points still gets the
+ * carried-forward table of the points it has; one that selects NO point gets +inf in every distance, so `dists > surface` never holds
+ * for that cloud (it can call a point occupied only through `dists < min_dist`).
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_LIDAR_MAX_CLOUDS 32
+#define BTS_LIDAR_MAX_SLICES 16
+
+/* bytes of bts_lidar_slices' bins_workspace (the per-bin minima and the smallest-angle keys; contents need no initialisation);
+ * 0 outside the limits */
+size_t bts_lidar_slices_workspace(int32_t T, int32_t y_res);
+
+/* get_lidar_slices (:57-115).  points (sum N_t, 4): the clouds concatenated, 16-byte aligned; offsets: HOST array of T + 1 int32,
+ * cloud t = points[offsets[t] : offsets[t + 1]], offsets[0] = 0, non-decreasing; velo_poses (T, 4, 4); borders361: the 361 bin borders
+ * on the device, built by the caller as the reference builds them (torch.linspace(-pi, pi, 361), :91); slices as :59-72 from
+ * (y_lo, y_hi, y_res).  Per point and slice: selected when y_world in [min_y, max_y] or |pc_world.xyz| >= max_dist (:79); angle and
+ * distance of the velodyne-frame x, y (:83-84); bin i = [border_i, border_i+1) (:96); minimum distance per bin (:102), empty bins carry
+ * the previous value (:101).  tables (y_res, T, 362, 2): rows of (angle, distance) with the two wrap rows of :109. */
+int bts_lidar_slices(const float* points, const int32_t* offsets, int32_t T, const float* velo_poses, const float* borders361, float y_lo,
+                     float y_hi, int32_t y_res, float max_dist, void* bins_workspace, float* tables, void* stream);
+
+/* check_occupancy (:118-160).  q_pts (P, 3); tables (y_res, T, 362, 2) as above; world_to_velo (T, 4, 4) = the inverses of velo_poses
+ * (bts_invert_small stands in for torch.inverse, :126).  Slice i owns the points [i * step, (i + 1) * step), step = P / y_res; the
+ * remainder keeps is_occupied = (1 / T > thresh), is_visible = 0 as in the reference.  Outputs are bytes (0 / 1) of P entries each. */
+int bts_lidar_occupancy(const float* q_pts, int32_t P, const float* tables, int32_t y_res, int32_t T, const float* world_to_velo,
+                        float min_dist, uint8_t* is_occupied, uint8_t* is_visible, void* stream);
+
+/* The evaluator's frame after the render (:292-330) from one call, nothing synchronised: bts_field_query with only_density on the
+ * caller's encoded field (the SAME kernel with the same arguments: sigma is bit-identical to the stand-alone query; cfg->n must be 1),
+ * the inverses of velo_poses and cam_pose, bts_lidar_slices, bts_lidar_occupancy, and the metrics kernel: per query point
+ *   is_visible_pred = dist <= nearest border-clamped align_corners look-up of pred_depth_z at project_into_cam(p) (:163-168, :296-298)
+ *   P = sigma > occ_threshold (:308),  V = is_visible | is_visible_pred (:314),  O = is_occupied & !V (:317)
+ * counts[6] (zeroed inside the call) = number of points with
+ *   [0] V & P   [1] V & !P   [2] !V & O & P   [3] !V & O & !P   [4] !V & !O & P   [5] !V & !O & !P
+ * from which the nine metrics of :319-330 follow on the host. */
+typedef struct {
+  const float* q_pts;          /* (P, 3) world points (get_pts, :37-50) */
+  int32_t P, T, y_res, H, W;   /* H, W: size of pred_depth_z */
+  int32_t reserved_;
+  const float* points;         /* as bts_lidar_slices */
+  const int32_t* offsets;      /* HOST, T + 1 */
+  const float* velo_poses;     /* (T, 4, 4) */
+  const float* borders361;
+  float y_lo, y_hi, max_dist, min_dist, occ_threshold;
+  int32_t reserved2_;
+  const float* pred_depth_z;   /* (H, W) predicted z-depth of the encoder view (distance_to_z of the rendered depth, :289) */
+  const float* proj;           /* (3, 3) normalised intrinsics of that view, as project_into_cam multiplies them (:165) */
+  const float* cam_pose;       /* (4, 4) its camera-to-world pose */
+  int32_t* counts;             /* (6) */
+  uint8_t* masks;              /* (3, P): P, O, V -- or NULL */
+  float* sigma;                /* (P) or NULL */
+  float* tables;               /* (y_res, T, 362, 2) or NULL (kept in the workspace) */
+} BtsOccupancyEval;
+size_t bts_occupancy_eval_workspace(int32_t P, int32_t T, int32_t y_res);
+int bts_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsOccupancyEval* a, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

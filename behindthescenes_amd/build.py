@@ -1,6 +1,9 @@
 """Builds libbts_render.so (hand-written HIP for gfx950) in-tree with hipcc.  No GPU is needed to build.
 
-    python -m behindthescenes_amd.build [--force]
+    python -m behindthescenes_amd.build [--force]                  the product
+    python -m behindthescenes_amd.build --variants                 the differently scheduled builds the parity tests load
+    python -m behindthescenes_amd.build --probe                    the product's kernels with section ablation bits and cycle counters
+    python -m behindthescenes_amd.build --tag NAME [flags...]      variants/libbts_NAME.so with extra compiler flags (e.g. --tag ticks -DBTS_TICKS)
 
 The shared object is git-ignored but travels to the GPU box with the source snapshot.
 """
@@ -43,8 +46,8 @@ def hipcc():
 
 
 def build_library(force: bool = False, verbose: bool = False, probe: bool = False, tag: str = "", extra_flags=()) -> str:
-    """probe=True builds variants/libbts_probe.so: the same sources with -DBTS_PROBE (section-ablation hooks for tools/ablate_probe.py;
-    never loaded by the product path).  tag="x" builds behindthescenes_amd/variants/libbts_x.so with `extra_flags` appended (or
+    """probe=True builds variants/libbts_probe.so: the same sources and the same kernels with -DBTS_PROBE (section ablation bits and cycle
+    counters of the forward for tools/section_probe.py and tools/section_probe_train.py; never loaded by the product path).  tag="x" builds behindthescenes_amd/variants/libbts_x.so with `extra_flags` appended (or
     replacing -O3 when an -O level is given): differently scheduled builds of the same sources for the second-schedule parity
     tests and for hazard bisection; loaded only through BTS_RENDER_LIB."""
     lib = os.path.join(VARIANTS, "libbts_probe.so") if probe else LIB      # (never in the package directory: the product has ONE library)

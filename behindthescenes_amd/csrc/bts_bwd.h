@@ -1,4 +1,4 @@
-// Shared between the backward's translation units (bts_bwd.hip: lane = ray pass + scatter; bts_bwd_rows.hip: lane = sample passes).
+// Shared between the backward's translation units (bts_bwd.hip: host side; bts_bwd_rows.hip, bts_bwd_blocks.hip: the lane = sample passes).
 #pragma once
 #include "bts_field_kernel.h"
 
@@ -13,8 +13,8 @@ struct BwdParams {
   float* d_proj;          // (n,H,W,HD)
   float* d_mlp;           // packed
   float* d_empty_proj;    // (HD)
-  float* gh_ws;           // lane = ray path: (groups, K, 64, HD) g_h rows for the dG scatter pass, or null: scatter with direct atomics
-  float* gs_ws;           // lane = sample path (bts_bwd_rows.hip): (n*Bp, K) gradient at the pre-softplus density
+  float* gh_ws;           // always null, no reader left (the round-1 lane = ray path's rows); kept so that the kernarg offsets behind it stay
+  float* gs_ws;           // gate-bit passes (bts_bwd_rows.hip):   (n*Bp, K) gradient at the pre-softplus density
   unsigned* mask_ws;      //                    (n*Bp, HD/32, K) relu gates of lin_in's output per sample, one bit per channel
   uint2* pmask_ws;        //                    (n*Bp, HD) the same gates per channel, one bit per sample of the ray
   unsigned char* tiles;   // (n, tiles_per_img) dirty flags of d_proj's 64-texel tiles (BtsRenderGrads.d_proj_tiles), or null
@@ -90,16 +90,11 @@ __device__ __forceinline__ RayIn<NV3> unpack_ray_record(Q q, float rec, int nv3)
 }
 
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) {
-
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // the parameter-gradient flushes at the end of the backward kernels (every work-group -> the same few thousand addresses)
 __device__ __forceinline__ void flush_add_f32(float* p, float v) {
-#ifndef BTS_ABL_NOFLUSH   // timing ablation: what do the same-address atomics of ~500 work-groups cost?
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  if (v == 1.2345e-30f) *p = v;
-#endif
 }
 
 }  // namespace bts

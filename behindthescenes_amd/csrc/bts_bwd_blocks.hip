@@ -1,5 +1,5 @@
 // Backward of the fused renderer, lane = SAMPLE form, general case: ResnetBlockFC layers (the RE10K model) and / or more than 64
-// samples per ray.  Replaces the round-1 lane = ray kernel (bts_bwd.hip, one wave per SIMD, 0.08 of peak) for every shape the
+// samples per ray.  Replaces the round-1 lane = ray kernel (git history; one wave per SIMD, 0.08 of peak) for every shape the
 // gate-bit passes of bts_bwd_rows.hip do not cover.
 //
 // The factorisation of bts_bwd_rows.hip survives the blocks: with the relu gates m0 (lin_in output h0),
@@ -440,11 +440,7 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
       // (Issuing them one chunk ahead, in front of the previous chunk's row stores -- vmcnt retires in order, a load behind the stores
       // is back when they are -- was tried: the nine registers it keeps alive cost more in spills than the wait, 0.676 vs 0.629 ms.)
       float cs_v[NVMAX * 3];
-#ifdef BTS_ABL_B1   // timing ablation: no per-sample colour loads
-      const bool have_cs = false;
-#else
       const bool have_cs = qb->f.rgb_samps != nullptr;
-#endif
 #pragma unroll
       for (int i = 0; i < NVMAX * 3; ++i) cs_v[i] = 0.0f;
       if (have_cs) {
@@ -533,14 +529,12 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
         const float gww = valid ? g_w * (alpha * T) : 0.0f;
         // exclusive suffix sum over the wave + the chunks behind; the wave's total moves on to the chunk in front
         float incl = gww;
-#ifndef BTS_ABL_B6   // timing ablation: no suffix scan
         const int seg_end = mainl && PK ? 48 : 64;   // one past the last lane of this lane's ray
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
           const float y = __shfl_down(incl, off, 64);
           incl += (lane + off < seg_end) ? y : 0.0f;
         }
-#endif
         const float below = __shfl_down(incl, 1, 64);
         const float S = (lane == seg_end - 1 ? 0.0f : below) + (mainl && PK ? 0.0f : S_carry);
         S_carry += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, incl), PK ? 48 : 0));
@@ -657,11 +651,7 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
           // dw_acc[ht] belongs to channel ht*32 + mfma_row(col >> 1, h), on both lanes of the pair
 #pragma unroll
           for (int ht = 0; ht < HT; ++ht) {
-#ifdef BTS_ABL_B4   // timing ablation: no butterfly
-            dw_acc[ht] += r_out[ht][0] + r_out[ht][5] + r_out[ht][15];
-#else
             dw_acc[ht] += half_reduce16(r_out[ht], col);
-#endif
           }
           RB_TICK(4)   // dw_out
         }
@@ -679,19 +669,11 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
             const float* wt = lds + L::BLK + b * L::BLK_STRIDE + lane4t;
             // vn = mn . (W1^T v): the C layout of v is the B operand; the product carries 2^S (and s_v)
             f32x16 vn = zero_acc();
-#ifdef BTS_ABL_B5   // timing ablation: no transposed products
-            vn = v[0];
-#else
             hidden_layer_ht(vn, v[0], wt + L::BLK_LAYER_STRIDE, L::BLK_TERM_STRIDE, 1.0f);
-#endif
 #pragma unroll
             for (int q = 0; q < 16; ++q) vn[q] = net[b][q] > 0.0f ? vn[q] * inv_scale : 0.0f;
             RB_TICK(5)   // v, vn = mn . W1^T v
-#ifdef BTS_ABL_B3   // timing ablation: no fc_0 / fc_1 weight gradients
-            if (false) {
-#else
             if (qb->d_mlp) {
-#endif
               // dW1[out][in] += sum_p (g_s v)[p][out] relu(n)[p][in];  db1[out] += sum_p (g_s v)[p][out]
               wave_lds_fence();
 #pragma unroll
@@ -711,16 +693,8 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
             RB_TICK(6)   // dW1 tiles
             // t2 = W0^T vn;  v <- v + m0 . t2
             f32x16 t2 = zero_acc();
-#ifdef BTS_ABL_B5
-            t2 = vn;
-#else
             hidden_layer_ht(t2, vn, wt, L::BLK_TERM_STRIDE, 1.0f);
-#endif
-#ifdef BTS_ABL_B3
-            if (false) {
-#else
             if (qb->d_mlp) {
-#endif
               // dW0[out][in] += sum_p (g_s vn)[p][out] relu(h0)[p][in];  db0[out] += sum_p (g_s vn)[p][out]
               RB_TICK(7)   // t2 = W0^T vn
               wave_lds_fence();
@@ -749,9 +723,6 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
         // goes through LDS instead, written in the gather ring's own row layout (gl.rd: the inverse of what the forward reads), and
         // comes back as whole rows: eight lanes per 128-byte row, eight full rows per store instruction.
         if (ro.u0_ws) {
-#ifdef BTS_ABL_B2   // timing ablation: no row stores
-          if (gs_v[pt] == 12345.0f)
-#endif
           {
             char* const u0t = gather_lds + wave * kGatherLdsPerWave + (NB > 0 ? 2 * 32 * 33 * 4 : 0);   // behind the contraction tiles
             static_assert((NB > 0 ? 2 * 32 * 33 * 4 : 0) + HT * 4096 <= kGatherLdsPerWave, "u0 tile must fit the wave's ring memory");
@@ -843,10 +814,6 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
 // launch
 // ---------------------------------------------------------------------------------------------------------------
 int launch_scatter_rows(const BwdParams& bp, const float* u0_ws, int HD, int n, hipStream_t s);
-struct PassQueue;
-PassQueue* pass_queue();
-hipStream_t pass_fork(PassQueue* pq, hipStream_t s);
-void pass_join(PassQueue* pq, hipStream_t side, hipStream_t s);
 int launch_dwpe_rows(const FwdParams& p, const float* u0_ws, float* d_mlp, float* flush_ws, int C, int HD, int NB, int n, int grid, hipStream_t s,
                      bool flush_clean);
 
@@ -886,13 +853,10 @@ int launch_bwd_blocks(const BwdParams& bp, float* u0_ws, int C, int HD, int NB, 
   if (C == 64 && HD == 64 && NB == 0) rc = launch_rowsb<64, 64, 0>(bp, ro, grid, s);
   else if (C == 32 && HD == 32 && NB == 1) rc = launch_rowsb<32, 32, 1>(bp, ro, grid, s);
   else if (C == 32 && HD == 32 && NB == 0) rc = launch_rowsb<32, 32, 0>(bp, ro, grid, s);
-  // pass C on a side queue of the library next to pass B (bts_bwd_rows.hip: pass_queue)
+  // pass C, then pass B, on the caller's stream (side by side they measured slower: launch_rows in bts_bwd_rows.hip)
   const bool want_b = bp.d_proj || bp.d_empty_proj, want_c = bp.d_mlp != nullptr;
-  PassQueue* pq = (rc == BTS_OK && want_b && want_c) ? pass_queue() : nullptr;
-  const hipStream_t sc = pq ? pass_fork(pq, s) : s;
-  if (rc == BTS_OK && want_c) rc = launch_dwpe_rows(bp.f, u0_ws, bp.d_mlp, bp.flush_ws, C, HD, NB, n, grid, sc, bp.flush_clean);
+  if (rc == BTS_OK && want_c) rc = launch_dwpe_rows(bp.f, u0_ws, bp.d_mlp, bp.flush_ws, C, HD, NB, n, grid, s, bp.flush_clean);
   if (rc == BTS_OK && want_b) rc = launch_scatter_rows(bp, u0_ws, HD, n, s);
-  pass_join(pq, sc, s);
   return rc;
 }
 

@@ -1,7 +1,7 @@
 // Backward of the fused renderer, lane = SAMPLE form: three passes for the plain MLP (no ResnetBlockFC layers) with K <= 64.
 //
-// The round-1 backward (bts_bwd.hip) walks 64 rays per wave back to front, lane = ray: 392 registers and 138 KB of LDS tiles pin it at
-// one wave per SIMD with every latency exposed, and 1 GB of g_h rows travels between its two passes (2.3 ms at 65 536 x 64).  The
+// The round-1 backward (git history) walked 64 rays per wave back to front, lane = ray: 392 registers and 138 KB of LDS tiles pinned it at
+// one wave per SIMD with every latency exposed, and 1 GB of g_h rows travelled between its two passes (2.3 ms at 65 536 x 64).  The
 // gradient at lin_in's output factorises,  g_h[p][ch] = [h[p][ch] > 0] * w_out[ch] * g_s[p],  so what the passes have to hand each
 // other per sample is ONE float (g_s, the gradient at the pre-softplus density) and ONE BIT per channel (the relu gate):
 //   pass A  rows_kernel      one ray per wave iteration, lane = sample -- the FORWARD's pipeline (f16-split lin_in on the matrix pipe,
@@ -343,10 +343,8 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
     }
 #else
     GBuf ba, bb;
-#ifndef BTS_ROWS_LATE_GATHER
     stage_load<HD, 0>(ba, G, o, h);
     stage_load<HD, 1>(bb, G, o, h);
-#endif
 #endif
 
     BW_TICK(0)
@@ -389,11 +387,7 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
       const float ex = transmittance(delta, sigma);
       const bool capped = (qb->f.hard_cap != 0) & last;
       const float alpha = capped ? 1.0f : 1.0f - ex;
-#ifdef BTS_ABL_R2   // timing ablation: no scan
-      const float S = g_w * alpha;
-#else
       const float S = wave_suffix_excl(valid ? g_w * (alpha * T) : 0.0f, lane);
-#endif
       float g_alpha = g_w * T - S / (capped ? 1e-10f : ex + 1e-10f);
       g_alpha += ga_k;
       if (!capped && !dead && !cut && valid) g_s = g_alpha * fabsf(delta) * ex * (s_raw > 20.0f ? 1.0f : sigmoidf(s_raw));
@@ -416,10 +410,6 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
     // ---------------- h = bilinear(G) + W_pe . PE + b, exactly as render_kernel_p evaluates it (accumulators carry 2^S)
     f32x16 acc[HT][2];
     {
-#if defined(BTS_ROWS_LATE_GATHER) && !defined(BTS_GATHER_LDS)   // A/B: gather issued in front of the MFMA phase
-      stage_load<HD, 0>(ba, G, o, h);
-      stage_load<HD, 1>(bb, G, o, h);
-#endif
       f32x16 bias[HT];
       {
         const float* bl = lh + LH::W_RAW + 3 * HD + 4 * h;
@@ -469,11 +459,7 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
       bcast_tiles(__float_as_uint(g_s * inv_scale), t0, t1);
       gs_t[0] = __uint_as_float(t0), gs_t[1] = __uint_as_float(t1);
     }
-#ifdef BTS_ABL_R1   // timing ablation: no gate masks / dw_out (one store keeps the accumulators alive)
-    if (lane < K) mrow[lane] = __float_as_uint(acc[0][0][0] + acc[0][1][5] + acc[HT - 1][0][9] + acc[HT - 1][1][15]);
-#else
     gates_and_dwout<HD>(acc, gs_t, mrow, prow, K, lane, dw_acc);
-#endif
     BW_TICK(3)
 #ifdef BTS_TICKS
     ++n_iter;
@@ -563,11 +549,7 @@ __device__ __forceinline__ int wave_min_i(int v) {
 // fetched one step ahead.
 template <int HD, bool ROWS = false>
 __global__ __launch_bounds__(64) void scatter_kernel(const ScatterMaskParams sp) {
-#ifndef BTS_SCATTER_CW
-#define BTS_SCATTER_CW 12
-#define BTS_SCATTER_CH 12
-#endif
-  constexpr int CW = BTS_SCATTER_CW, CH = BTS_SCATTER_CH, NSLOT = CW * CH, SCRATCH = NSLOT, EMPTY = NSLOT + 1;   // slot indices; a slot is 32 floats;
+  constexpr int CW = 12, CH = 12, NSLOT = CW * CH, SCRATCH = NSLOT, EMPTY = NSLOT + 1;   // slot indices; a slot is 32 floats;
                                                                                            // EMPTY, EMPTY + 1: one row per lane half
   constexpr int NW = HD / 32;
   __shared__ __attribute__((aligned(128))) float cache[(NSLOT + 3) * 32];   // aligned: see round()
@@ -577,19 +559,8 @@ __global__ __launch_bounds__(64) void scatter_kernel(const ScatterMaskParams sp)
   const int lane = threadIdx.x;
   const int h = lane >> 5, c = lane & 31;
   const unsigned c4 = (unsigned)c * 4u, cbit = 1u << c;
-#ifndef BTS_SCATTER_ORDER
-#define BTS_SCATTER_ORDER 0
-#endif
-  // which (unit, segment) a block takes: blocks are dispatched in index order, and the launch lasts until its last block ends
-#if BTS_SCATTER_ORDER == 1      // segment-major, the segment of the NEAR samples first
-  const int n_units = (int)gridDim.x / sp.nseg;
-  const int seg = blockIdx.x / n_units, unit = blockIdx.x - seg * n_units;
-#elif BTS_SCATTER_ORDER == 2    // segment-major, the segment of the FAR samples first
-  const int n_units = (int)gridDim.x / sp.nseg;
-  const int seg_r = blockIdx.x / n_units, unit = blockIdx.x - seg_r * n_units, seg = sp.nseg - 1 - seg_r;
-#else
+  // which (unit, segment) a block takes: unit-major (segment-major orders, near or far segment first, measured no better: profiles/r06l)
   const int unit = blockIdx.x / sp.nseg, seg = blockIdx.x - unit * sp.nseg;
-#endif
   const int grp = unit / NW, wv = unit - grp * NW;
   const int chg = wv * 32 + c;   // this lane's channel of the row
   const int sample = grp / sp.groups_per_sample;
@@ -761,9 +732,6 @@ __global__ __launch_bounds__(64) void scatter_kernel(const ScatterMaskParams sp)
     if (scatter) {
       const int mnx = wave_min_i(x0), mxx = -wave_min_i(-x1), mny = wave_min_i(y0), mxy = -wave_min_i(-y1);
       fits = (mxx - mnx < CW) && (mxy - mny < CH);
-#ifdef BTS_ABL_S2   // timing ablation: the window never moves (wrong results)
-      if (false)
-#endif
       if (fits && (mnx < wx || mxx >= wx + CW || mny < wy || mxy >= wy + CH)) {
         const int nwx = mnx - (CW - (mxx - mnx + 1)) / 2, nwy = mny - (CH - (mxy - mny + 1)) / 2;
         flush(nwx, nwy, false);
@@ -812,9 +780,6 @@ __global__ __launch_bounds__(64) void scatter_kernel(const ScatterMaskParams sp)
     BW_TICK(2)
     if (amask == 0) {
       // one straight block: the table reads of later pairs may run ahead of the window's read-modify-write rounds
-#ifdef BTS_ABL_S1   // timing ablation: no read-modify-write rounds
-      if (wx == 0x12345678)
-#endif
 #pragma unroll
       for (int i = 0; i < 32; ++i) round(i + 32 * h, cur[ROWS ? i : 0]);
     } else {
@@ -1011,11 +976,6 @@ __global__ __launch_bounds__(256, 2) void dwpe_kernel(const DwpeParams dp) {
       float e[PE_ROWS];
       e[0] = v3[0], e[1] = v3[1], e[2] = v3[2], e[3] = 1.0f;
       float ff = p.freq_factor;
-#ifdef BTS_ABL_D3   // timing ablation: no trigonometry
-#pragma unroll
-      for (int i = 4; i < PE_ROWS; ++i) e[i] = v3[i % 3] * (float)i;
-      if (false)
-#endif
 #pragma unroll
       for (int r = 0; r < kNumFreqs / 2; ++r) {   // octaves 2r (direct) and 2r + 1 (angle doubling), as the forward's regions
         SinCos3 raw, dbl;
@@ -1030,18 +990,12 @@ __global__ __launch_bounds__(256, 2) void dwpe_kernel(const DwpeParams dp) {
         for (int i = 0; i < 6; ++i) e[10 + 12 * r + i] = t[i];
         ff = ff * 4.0f;
       }
-#ifdef BTS_ABL_D1   // timing ablation: no plane writes
-      if (gs == 12345.0f)
-#endif
       write_planes(tile, e, gs, lane);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // ---- four k-slices of 16 samples: A[i = channel][k] = gate, B[k][j = kin] = piece of g_s pe
-#ifdef BTS_ABL_D2   // timing ablation: no MFMA block
-    if (__builtin_amdgcn_readfirstlane(__float_as_int(gs)) == 0x12345678)
-#endif
 #pragma unroll
     for (int sl = 0; sl < 4; ++sl) {
       bf16x8 a[HT];
@@ -1188,11 +1142,7 @@ __global__ __launch_bounds__(256, HD == 32 ? 3 : 2) void dwpe_rows_kernel(const 
         const unsigned row = (unsigned)min(2 * s2 + h, n_valid - 1);
 #pragma unroll
         for (int ht = 0; ht < HT; ++ht)
-#ifdef BTS_ABL_E3   // timing ablation: no row loads
-          a[ht][s2] = (float)(s2 + lane);
-#else
           a[ht][s2] = ur[row * (unsigned)HD + (unsigned)(ht * 32 + col)];
-#endif
       }
     }
     __builtin_amdgcn_sched_barrier(0);   // (the scheduler would sink the row loads to their MFMAs)
@@ -1210,11 +1160,6 @@ __global__ __launch_bounds__(256, HD == 32 ? 3 : 2) void dwpe_rows_kernel(const 
       float* row = tile + lane * kPeLd;
       row[0] = v3[0], row[1] = v3[1], row[2] = v3[2], row[3] = 1.0f;
       float ff = p.freq_factor;
-#ifdef BTS_ABL_E2   // timing ablation: no trigonometry
-#pragma unroll
-      for (int i = 4; i < 40; ++i) row[i] = v3[i % 3] * (float)i;
-      if (false)
-#endif
 #pragma unroll
       for (int r = 0; r < kNumFreqs / 2; ++r) {   // octaves 2r (direct) and 2r + 1 (angle doubling), as the forward's regions
         SinCos3 raw, dbl;
@@ -1234,15 +1179,6 @@ __global__ __launch_bounds__(256, HD == 32 ? 3 : 2) void dwpe_rows_kernel(const 
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // ---- 32 k-steps of two samples each
-#ifdef BTS_ABL_E1   // timing ablation: no MFMA block (one accumulate keeps the operands alive)
-    {
-      float acc1 = 0.0f;
-#pragma unroll
-      for (int s2 = 0; s2 < 32; ++s2) acc1 += a[0][s2] * tile[(2 * s2 + h) * kPeLd + col];
-      dw[0][0][0] += acc1;
-    }
-    if (false)
-#endif
 #pragma unroll
     for (int s2 = 0; s2 < 32; ++s2) {
       const float* brow = tile + (2 * s2 + h) * kPeLd;
@@ -1280,49 +1216,6 @@ __global__ __launch_bounds__(256, HD == 32 ? 3 : 2) void dwpe_rows_kernel(const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// pass B and pass C side by side
-// ---------------------------------------------------------------------------------------------------------------
-// Pass B (scatter: dG) and pass C (dW_pe) both read what pass A left and write different things.  One after the other on the caller's
-// stream, each is bound by latency at its own occupancy -- and the scatter pass ends in a tail of slow blocks (its slowest block lives
-// 1.8 x the average one).  -DBTS_PASS_OVERLAP puts pass C on a side queue of the library (fork after pass A, join before the call's
-// last kernel: the caller's stream sees one ordered sequence) so that it can fill what pass B leaves idle.  MEASURED SLOWER and NOT the
-// default (round 6, profiles/r06o: backward +7 % at exp_kitti_360.yaml, +6 % exp_kitti_raw.yaml, +4 % exp_re10k.yaml): pass C is a
-// persistent grid that takes two work-groups' worth of every CU the moment it starts, and the scatter blocks then queue for what is
-// left -- the same finding as for whole per-scale chains side by side (profiles/r05i).
-struct PassQueue {
-  hipStream_t q;
-  hipEvent_t fork, join;
-  bool ok;
-};
-PassQueue* pass_queue() {
-#ifndef BTS_PASS_OVERLAP
-  return nullptr;
-#else
-  static thread_local PassQueue* per_dev[16] = {nullptr};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!per_dev[dev]) {
-    PassQueue* pq = new PassQueue;
-    pq->ok = hipStreamCreateWithFlags(&pq->q, hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&pq->fork, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&pq->join, hipEventDisableTiming) == hipSuccess;
-    per_dev[dev] = pq;
-  }
-  return per_dev[dev]->ok ? per_dev[dev] : nullptr;
-#endif
-}
-// -> the stream pass C goes to (the side queue, forked from s here; s itself if there is none)
-hipStream_t pass_fork(PassQueue* pq, hipStream_t s) {
-  if (!pq || hipEventRecord(pq->fork, s) != hipSuccess || hipStreamWaitEvent(pq->q, pq->fork, 0) != hipSuccess) return s;
-  return pq->q;
-}
-void pass_join(PassQueue* pq, hipStream_t side, hipStream_t s) {
-  if (side == s) return;
-  (void)hipEventRecord(pq->join, side);
-  (void)hipStreamWaitEvent(s, pq->join, 0);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // launch
 // ---------------------------------------------------------------------------------------------------------------
 static void scatter_segments(ScatterMaskParams& sp, long units, int K);
@@ -1344,18 +1237,19 @@ static int launch_rows(const BwdParams& bp, int n, int grid, hipStream_t s) {
   else if (p.nv <= 4) go(rows_kernel<C, HD, 4>);
   else go(rows_kernel<C, HD, 8>);
   hipError_t e = hipGetLastError();
+  // Pass C and pass B one after the other on the caller's stream.  Pass C on a side queue next to pass B MEASURED SLOWER (round 6,
+  // profiles/r06o: backward +7 % at exp_kitti_360.yaml, +6 % exp_kitti_raw.yaml, +4 % exp_re10k.yaml): pass C is a persistent grid that
+  // takes two work-groups' worth of every CU the moment it starts, and the scatter blocks then queue for what is left.
   const bool want_b = bp.d_proj || bp.d_empty_proj, want_c = bp.d_mlp != nullptr;
-  PassQueue* pq = (want_b && want_c) ? pass_queue() : nullptr;
-  const hipStream_t sc = (e == hipSuccess && pq) ? pass_fork(pq, s) : s;     // pass C's stream
   if (e == hipSuccess && want_c) {
     DwpeParams dp;
     dp.f = p, dp.pmask_ws = bp.pmask_ws, dp.gs_ws = bp.gs_ws, dp.d_mlp = bp.d_mlp, dp.slots = bp.flush_ws, dp.rays = (long)n * p.Bp;
     const long wgs = (dp.rays + 3) / 4;
     auto kern = dwpe_kernel<C, HD>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DwpeLds::TOTAL);
-    if (!bp.flush_clean) (void)hipMemsetAsync(bp.flush_ws, 0, sizeof(float) * kFlushSlots * kFlushRows * HD, sc);
-    kern<<<(int)(wgs < grid ? wgs : grid), 256, DwpeLds::TOTAL, sc>>>(dp);   // grid = 2 work-groups per CU
-    dwpe_reduce_kernel<C, HD><<<(kFlushRows * HD + 255) / 256, 256, 0, sc>>>(bp.flush_ws, bp.d_mlp);
+    if (!bp.flush_clean) (void)hipMemsetAsync(bp.flush_ws, 0, sizeof(float) * kFlushSlots * kFlushRows * HD, s);
+    kern<<<(int)(wgs < grid ? wgs : grid), 256, DwpeLds::TOTAL, s>>>(dp);   // grid = 2 work-groups per CU
+    dwpe_reduce_kernel<C, HD><<<(kFlushRows * HD + 255) / 256, 256, 0, s>>>(bp.flush_ws, bp.d_mlp);
     e = hipGetLastError();
   }
   if (e == hipSuccess && want_b) {
@@ -1372,7 +1266,6 @@ static int launch_rows(const BwdParams& bp, int n, int grid, hipStream_t s) {
     scatter_kernel<HD><<<(int)(units * sp.nseg), 64, 0, s>>>(sp);
     e = hipGetLastError();
   }
-  pass_join(pq, sc, s);
   if (e != hipSuccess) {
     set_error("%s: backward kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
     return BTS_E_LAUNCH;

@@ -16,8 +16,8 @@
 //                           per axis, a fourth for the two lines next to a border (the reflected line folds back onto them); with
 //                           the x2 upsampling the wave accumulates the 2 x 2 children of a source pixel before it stores
 //   conv_wgrad_bf_kernel  : dW[t] = sum_pixels x[reflect(p + t)] (x) dy[p], contraction over the pixels as the MFMA's k axis
-// The first version of this file ran all three on v_mfma_f32_32x32x2_f32 (fp32 inputs, 157 TFLOP/s; kept as the -DBTS_CONV_FP32 A/B build,
-// bts_conv_fp32.h) and won by the traffic and the launches that disappeared.  This one also leaves the fp32 matrix rate behind: every fp32
+// The first version of this file ran all three on v_mfma_f32_32x32x2_f32 (fp32 inputs, 157 TFLOP/s; git
+// history) and won by the traffic and the launches that disappeared.  This one also leaves the fp32 matrix rate behind: every fp32
 // operand is the EXACT sum of three bf16 numbers, six bf16 products reproduce the fp32 product to 2^-24 (see below), and the bf16 pipe
 // is 16 x the fp32 one per instruction -- 0.375 of the matrix time with better sums than before (blocked accumulation).  bf16, not f16:
 // activations and gradients have no bounded range to scale an f16 split on, and bf16 carries fp32's exponent.
@@ -114,11 +114,7 @@ __device__ __forceinline__ void conv_row3_bf(f32x16 (&acc3)[3], const char* wt, 
 #pragma unroll
   for (int sidx = 0; sidx < 4; ++sidx) {
     bf8 xh, xm, xl;
-#if defined(BTS_CONV_ABL) && (BTS_CONV_ABL & 1)   // timing ablation: no split arithmetic
-    xh = __builtin_bit_cast(bf8, xa[2 * sidx]), xm = __builtin_bit_cast(bf8, xa[2 * sidx + 1]), xl = xh;
-#else
     split3_frag(xa[2 * sidx], xa[2 * sidx + 1], xh, xm, xl);
-#endif
 #pragma unroll
     for (int tx = 0; tx < 3; ++tx) {
       const char* f = wt + (tx * 4 + sidx) * (3 * 1024);
@@ -130,11 +126,8 @@ __device__ __forceinline__ void conv_row3_bf(f32x16 (&acc3)[3], const char* wt, 
 
 // How many 32-slot pixel tiles a wave's tile has: 2 (64 slots, 62 outputs; 8 waves per work-group, 256 VGPRs) or 1 (32 slots, 30 outputs;
 // 12 waves per work-group = three per SIMD inside 168 VGPRs -- more waves to hide the loads and the split behind, 3 % more matrix work
-// for the two halo slots).  The product's choice is the measured one (profiles/r05s); the other is an A/B build (-DBTS_CONV_PT=..).
-#ifndef BTS_CONV_PT
-#define BTS_CONV_PT 2
-#endif
-constexpr int kPT = BTS_CONV_PT;
+// for the two halo slots).  2 is the measured choice (profiles/r05s: 1 gains nothing, the kernels are issue-slot bound).
+constexpr int kPT = 2;
 constexpr int kConvSlots = 32 * kPT;
 constexpr int kConvWaves = kPT == 2 ? 8 : 12;
 // tile geometry of the bf16 kernels: a wave's tile = kConvSlots pixel SLOTS of one row, slot j <-> position x0 - 1 + j, x0 = kConvOut *
@@ -258,9 +251,7 @@ __global__ __launch_bounds__(64 * kConvWaves) void conv_fwd_bf_kernel(const Conv
     load_piece(0, 0);
 #pragma unroll
     for (int piece = 0; piece < 3 * kPT; ++piece) {
-#if !(defined(BTS_CONV_ABL) && (BTS_CONV_ABL & 2))   // (timing ablation 2: one piece's loads per tile)
       if (piece + 1 < 3 * kPT) load_piece((piece + 1) & 1, piece + 1);
-#endif
       __builtin_amdgcn_sched_barrier(0);
       const int ty = piece / kPT, pt = piece % kPT;
       f32x16 a3[3] = {acc[0][pt], acc[1][pt], acc[2][pt]};
@@ -279,9 +270,6 @@ __global__ __launch_bounds__(64 * kConvWaves) void conv_fwd_bf_kernel(const Conv
       for (int r = 0; r < 16; ++r) {
         float v = (lo[pt][r] + acc[1][pt][r]) + hi[pt][r];
         if (p.elu) v = v > 0.0f ? v : expm1f(v);
-#if defined(BTS_CONV_ABL) && (BTS_CONV_ABL & 4)   // timing ablation: no stores
-        if (v != 1.2345e-30f) continue;
-#endif
         const int slot = pt * 32 + (OUT_NCHW ? col : mfma_row(r, h));
         const int x = x0 - 1 + slot;
         const bool ok = slot >= 1 && slot <= kConvOut && x < p.W;
@@ -579,9 +567,6 @@ __global__ __launch_bounds__(256) void elu_bwd_kernel(const float4* __restrict__
   }
 }
 
-#ifdef BTS_CONV_FP32
-#include "bts_conv_fp32.h"
-#endif
 
 static int conv_grid() { return device_cu_count(); }   // one persistent work-group of 8 waves per CU (the weights fill its LDS)
 // the bf16 kernels: pairs of work-groups (the two halves of the columns) on the same XCD -> a multiple of 16, two work-groups per `want`ed one
@@ -610,9 +595,6 @@ int conv3x3_fwd_impl(const BtsConv3x3* c, hipStream_t s) {
   memset(&p, 0, sizeof(p));
   p.x = c->x, p.w = c->weight, p.bias = c->bias, p.y = c->y;
   p.N = c->N, p.H = c->H, p.W = c->W, p.up2 = c->up2, p.elu = c->elu, p.out_nchw = c->out_nchw;
-  p.tiles_per_row = (c->W + 63) / 64;
-  p.n_tiles = (long)c->N * c->H * p.tiles_per_row;
-#ifndef BTS_CONV_FP32
   p.tiles_per_row = (c->W + kConvOut - 1) / kConvOut;
   p.n_tiles = (long)c->N * c->H * p.tiles_per_row;
   const int grid = conv_grid_bf((p.n_tiles + kConvWaves - 1) / kConvWaves);
@@ -624,18 +606,6 @@ int conv3x3_fwd_impl(const BtsConv3x3* c, hipStream_t s) {
     (void)hipFuncSetAttribute((const void*)conv_fwd_bf_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kConvBfLds);
     conv_fwd_bf_kernel<false><<<grid, 64 * kConvWaves, kConvBfLds, s>>>(p);
   }
-#else   // A/B build: the fp32-input MFMA kernels of the first version
-  const long want = (p.n_tiles + 7) / 8;
-  const int grid = (int)(want < conv_grid() ? want : conv_grid());
-  const size_t lds = sizeof(float) * kConvLds;
-  if (c->out_nchw) {
-    (void)hipFuncSetAttribute((const void*)conv_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    conv_fwd_kernel<true><<<grid, 512, lds, s>>>(p);
-  } else {
-    (void)hipFuncSetAttribute((const void*)conv_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    conv_fwd_kernel<false><<<grid, 512, lds, s>>>(p);
-  }
-#endif
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("%s: convolution forward launch failed (%ld)", hipGetErrorString(e), (long)e);
@@ -675,42 +645,25 @@ int conv3x3_bwd_impl(const BtsConv3x3* c, const float* g_y, void* workspace, siz
     dy = dyp;
   }
   const int tpr = (c->W + 63) / 64;
-#ifdef BTS_CONV_FP32
-  const size_t lds = sizeof(float) * kConvLds;
-#endif
   if (d_x) {
     ConvParams p;
     memset(&p, 0, sizeof(p));
-    p.x = dy, p.w = c->weight, p.y = d_x, p.N = c->N, p.H = c->H, p.W = c->W, p.up2 = c->up2, p.tiles_per_row = tpr;
-#ifndef BTS_CONV_FP32
+    p.x = dy, p.w = c->weight, p.y = d_x, p.N = c->N, p.H = c->H, p.W = c->W, p.up2 = c->up2;
     const int n_out = c->up2 ? kConvOutUp : kConvOut;
     p.tiles_per_row = (c->W + n_out - 1) / n_out;
     p.n_tiles = (long)c->N * (c->up2 ? c->H / 2 : c->H) * p.tiles_per_row;
     (void)hipFuncSetAttribute((const void*)conv_dgrad_bf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kConvBfLds);
     conv_dgrad_bf_kernel<<<conv_grid_bf((p.n_tiles + kConvWaves - 1) / kConvWaves), 64 * kConvWaves, kConvBfLds, s>>>(p);
-#else
-    p.n_tiles = (long)c->N * (c->up2 ? c->H / 2 : c->H) * tpr;
-    const long want = (p.n_tiles + 7) / 8;
-    (void)hipFuncSetAttribute((const void*)conv_dgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    conv_dgrad_kernel<<<(int)(want < conv_grid() ? want : conv_grid()), 512, lds, s>>>(p);
-#endif
   }
   if (d_weight || d_bias) {
     WgradParams q;
     memset(&q, 0, sizeof(q));
     q.x = c->x, q.dy = dy, q.part = part, q.N = c->N, q.H = c->H, q.W = c->W, q.up2 = c->up2, q.tiles_per_row = tpr;
     q.n_tiles = (long)c->N * c->H * tpr;
-#ifndef BTS_CONV_FP32
     const long n_rows = (long)c->N * c->H;
     const int grid = (int)(n_rows < conv_grid() ? n_rows : conv_grid());
     conv_wgrad_bf_kernel<<<grid, 768, 0, s>>>(q);
     conv_wgrad_reduce_kernel<<<(kWgradPart + 255) / 256, 256, 0, s>>>(part, grid, d_weight, d_bias);
-#else
-    const long want = (q.n_tiles + 1) / 2;
-    const int grid = (int)(want < conv_grid() ? want : conv_grid());
-    conv_wgrad_kernel<<<grid, 512, 0, s>>>(q);
-    conv_wgrad_reduce_kernel<<<(kWgradPart + 255) / 256, 256, 0, s>>>(part, grid * 2, d_weight, d_bias);
-#endif
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

@@ -1,18 +1,22 @@
-// Fused forward of the BehindTheScenes density-field renderer for gfx950 (MI355X) -- kernel template.
+// Fused forward of the BehindTheScenes density-field renderer for gfx950 (MI355X) -- the per-point evaluation and the compact kernels.
 //
-// One lane = one ray (or one query point).  A wave walks its 64 rays front-to-back, one sample per iteration:
+// eval_point: everything between a world point and its pre-softplus density, one lane = one point:
 //   project into the encoder view -> bilinear feature fetch -> positional encoding -> lin_in as
 //   H^T[Hd x 64 pts] = W^T . X^T on v_mfma_f32_32x32x2_f32 (weights = A operand from LDS, the lane's own inputs = B operand
 //   after one v_permlane32_swap per k-pair) -> optional ResnetBlockFC layers (C-layout -> B-layout is free through a k
-//   permutation) -> lin_out as an in-lane dot product over the accumulator registers -> softplus -> colour taps of the nv
-//   render views -> alpha compositing in registers.  sigma / alpha / T never leave the chip.
+//   permutation) -> lin_out as an in-lane dot product over the accumulator registers.
 //
 // Feature fetch, two variants (template PROJ):
 //   PROJ = true  (default path): the caller passes G = F . w_in[:, :C]^T (bts_project_features).  Because bilinear
 //                interpolation and lin_in are linear, lin_in(bilinear(F)) = bilinear(G) + w_in[:, C:] . PE + b_in: the four taps
 //                of G are blended straight into the accumulator layout and only the 40 PE/bias inputs go through MFMA
 //                (5 120 instead of 13 312 FLOP per point).  DECLARED ALGEBRAIC SHORTCUT (changes summation order only).
+//                Used by the pipelined kernels (bts_render_kernel.h, bts_query.hip, the backward) for their out-of-line exact path.
 //   PROJ = false: raw channels-last F; 8 channels per chunk are blended per lane and pushed through MFMA (k = 104).
+//
+// The two kernels of this header serve raw channels-last features only (PROJ = false: callers that cannot pre-project):
+//   field_kernel (QUERY = true): lane = query point, density and colour taps of the nv render views;
+//   render_kernel: lane = SAMPLE, softplus -> colour taps -> alpha compositing as a segmented scan; sigma / alpha / T never leave the chip.
 //
 // Replaces: nerf.py:210-313 (composite), models_bts.py:138-338 (sample_features / sample_colors / forward),
 //           resnetfc.py:132-184, code.py:30-42 of the reference.
@@ -66,7 +70,7 @@ struct FwdParams {
   int tiles_per_sample;
   // lane = sample render kernel
   unsigned long long* dbg;  // probe builds only: per-wave section cycle counters (bit 128 of ablate)
-  int ablate;    // probe builds only (-DBTS_PROBE): bit mask of kernel sections to skip (tools/ablate_probe.py)
+  int ablate;    // probe builds only (-DBTS_PROBE): bit mask of kernel sections to skip (tools/section_probe.py)
   int lpr;       // lanes per ray: 8, 16, 32 or 64 (>= min(K, 64)); 64 / lpr rays share one wave iteration
   int chunk_log2;  // pipelined kernel: ray groups per chunk of the XCD interleave (log2), see render_kernel_p
   long groups;   // number of ray groups (= n * Bp * lpr / 64)
@@ -585,12 +589,13 @@ __device__ __forceinline__ float eval_point(const FwdParams& p, const float* lds
   return (p0 + p1) + b_out;
 }
 
+// The query kernel on raw channels-last features: one lane = one query point.
 template <int C, int HD, int NB, int NVMAX, bool QUERY, bool PROJ>
 __global__ __launch_bounds__(256, 2) void field_kernel(const FwdParams p) {
-  using L = Lds<C, HD, NB, PROJ>;
-  constexpr int HT = HD / 32;
+  static_assert(QUERY && !PROJ, "only the query form on raw features is left: the lane = ray render body and the projected-map form are gone (git history)");
+  using L = Lds<C, HD, NB, false>;
   __shared__ float lds[L::TOTAL];
-  stage_weights<C, HD, NB, PROJ>(lds, p.mlp, p.empty_feature);
+  stage_weights<C, HD, NB, false>(lds, p.mlp, p.empty_feature);
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
@@ -608,47 +613,30 @@ __global__ __launch_bounds__(256, 2) void field_kernel(const FwdParams p) {
 
   // wave-uniform cameras -> scalar registers
   const Cam enc = load_cam(p.w2c_enc + sample * 16, p.K_enc + sample * 9);
-  const float4* __restrict__ featp =
-      PROJ ? reinterpret_cast<const float4*>(p.proj) + (long)sample * H * W * (HD / 4)
-           : reinterpret_cast<const float4*>(p.feat) + (long)sample * H * W * (C / 4);
+  const float4* __restrict__ featp = reinterpret_cast<const float4*>(p.feat) + (long)sample * H * W * (C / 4);
 
   const float b_out = p.mlp[MlpLayout{C + kPeDim, HD, NB}.b_out()];
 
-  float ox, oy, oz, dx, dy, dz;
-  const float* zrow = nullptr;
-  int K = 1;
-  if constexpr (QUERY) {
-    ox = p.xyz[ray * 3 + 0], oy = p.xyz[ray * 3 + 1], oz = p.xyz[ray * 3 + 2];
-    dx = dy = dz = 0.0f;
-  } else {
-    const float4 r0 = reinterpret_cast<const float4*>(p.rays)[ray * 2];
-    const float4 r1 = reinterpret_cast<const float4*>(p.rays)[ray * 2 + 1];
-    ox = r0.x, oy = r0.y, oz = r0.z, dx = r0.w, dy = r1.x, dz = r1.y;
-    K = p.K;
-    zrow = p.z_samp + ray * K;
-  }
+  const float ox = p.xyz[ray * 3 + 0], oy = p.xyz[ray * 3 + 1], oz = p.xyz[ray * 3 + 2];
 
-  float T = 1.0f, depth = 0.0f, wsum = 0.0f;
+  // What is left of the render body this kernel used to share its text with: a one-trip loop over a non-const K, and three values
+  // without a reader (lane_off above, rgb_acc, z).  The saved assembly names its basic blocks after IR value numbers, which each of
+  // them shifts: with them every byte of this file's device assembly is what it was before the render body left.  They go in the
+  // follow-up that drops BwdParams::gh_ws, where no exact comparison is needed.
   float rgb_acc[NVMAX * 3];
 #pragma unroll
   for (int i = 0; i < NVMAX * 3; ++i) rgb_acc[i] = 0.0f;
-  float z_next = QUERY ? 0.0f : zrow[0];
+  float z_next = 0.0f;
+  int K = 1;
 
   for (int k = 0; k < K; ++k) {
     const float z = z_next;
-    if constexpr (!QUERY) z_next = (k + 1 < K) ? zrow[k + 1] : 0.0f;
-    // nerf.py:231  points = o + z * d   (mul, then add)
-    const float px = QUERY ? ox : ox + z * dx;
-    const float py = QUERY ? oy : oy + z * dy;
-    const float pz = QUERY ? oz : oz + z * dz;
+    const float px = ox, py = oy, pz = oz;
 
     Proj pe;
-    const float s_raw = eval_point<C, HD, NB, PROJ>(p, lds, enc, featp, lane, b_out, px, py, pz, pe);
+    const float s_raw = eval_point<C, HD, NB, false>(p, lds, enc, featp, lane, b_out, px, py, pz, pe);
     float sigma = softplus(s_raw);
     if (p.empty_empty) sigma = pe.invalid ? 0.0f : sigma;
-    if constexpr (!QUERY) {
-      if (p.sigma_noise) sigma += p.sigma_noise[ray * K + k];
-    }
 
     // ---------------- colour taps (models_bts.py:218-264)
     float col[NVMAX * 3];
@@ -670,87 +658,37 @@ __global__ __launch_bounds__(256, 2) void field_kernel(const FwdParams p) {
       }
     }
 
-    if constexpr (QUERY) {
-      if (active) {
-        p.q_sigma[ray] = sigma;
-        if (p.only_density) {
-          if (p.invalid) p.invalid[ray] = pe.invalid ? 1.0f : 0.0f;
-        } else {
-#pragma unroll
-          for (int j = 0; j < NVMAX; ++j)
-            if (j < nv) {
-              if (p.invalid) p.invalid[ray * nv + j] = inv[j] ? 1.0f : 0.0f;
-              p.rgb[(ray * nv + j) * 3 + 0] = col[3 * j + 0];
-              p.rgb[(ray * nv + j) * 3 + 1] = col[3 * j + 1];
-              p.rgb[(ray * nv + j) * 3 + 2] = col[3 * j + 2];
-            }
-        }
-      }
-    } else {
-      // ---------------- alpha compositing (nerf.py:225-299)
-      const float delta = (k + 1 < K) ? (z_next - z) : 1e10f;
-      float alpha = 1.0f - transmittance(delta, sigma);
-      if (p.hard_cap && k == K - 1) alpha = 1.0f;
-      const float wgt = alpha * T;
-      const float T_before = T;
-      T = T * ((1.0f - alpha) + 1e-10f);
-      depth = depth + wgt * z;
-      wsum = wsum + wgt;
-#pragma unroll
-      for (int i = 0; i < NVMAX * 3; ++i) rgb_acc[i] = rgb_acc[i] + wgt * col[i];
-      if (active) {
-        const long pk = ray * K + k;
-        if (p.weights) p.weights[pk] = wgt;
-        if (p.alphas) p.alphas[pk] = alpha;
-        if (p.sigma_raw) p.sigma_raw[pk] = s_raw;
-        if (p.trans) p.trans[pk] = T_before;
-        if (p.invalid) {
-#pragma unroll
-          for (int j = 0; j < NVMAX; ++j)
-            if (j < nv) p.invalid[pk * nv + j] = inv[j] ? 1.0f : 0.0f;
-        }
-        if (p.rgb_samps) {
-#pragma unroll
-          for (int j = 0; j < NVMAX; ++j)
-            if (j < nv) {
-              p.rgb_samps[(pk * nv + j) * 3 + 0] = col[3 * j + 0];
-              p.rgb_samps[(pk * nv + j) * 3 + 1] = col[3 * j + 1];
-              p.rgb_samps[(pk * nv + j) * 3 + 2] = col[3 * j + 2];
-            }
-        }
-      }
-    }
-  }
-
-  if constexpr (!QUERY) {
     if (active) {
-      p.depth[ray] = depth;
+      p.q_sigma[ray] = sigma;
+      if (p.only_density) {
+        if (p.invalid) p.invalid[ray] = pe.invalid ? 1.0f : 0.0f;
+      } else {
 #pragma unroll
-      for (int j = 0; j < NVMAX; ++j)
-        if (j < nv) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            float v = rgb_acc[3 * j + c];
-            if (p.white_bkgd) v = (v + 1.0f) - wsum;  // nerf.py:301-304
-            p.rgb[(ray * nv + j) * 3 + c] = v;
+        for (int j = 0; j < NVMAX; ++j)
+          if (j < nv) {
+            if (p.invalid) p.invalid[ray * nv + j] = inv[j] ? 1.0f : 0.0f;
+            p.rgb[(ray * nv + j) * 3 + 0] = col[3 * j + 0];
+            p.rgb[(ray * nv + j) * 3 + 1] = col[3 * j + 1];
+            p.rgb[(ray * nv + j) * 3 + 2] = col[3 * j + 2];
           }
-        }
+      }
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The render kernel: lane = SAMPLE.  A wave takes one ray (or 64/lpr short rays) per iteration and evaluates its K samples at
+// The render kernel on raw channels-last features: lane = SAMPLE.  A wave takes one ray (or 64/lpr short rays) per iteration and evaluates its K samples at
 // once: z / weights / alphas / invalid rows are read and written as contiguous rows, all samples of a ray that originates at the
 // encoder camera hit the SAME four texels (one broadcast load instead of 64 gathers), and the waves resident at any moment work
 // on consecutive rays, so their texel footprints overlap in L1/L2 instead of evicting each other (with lane = ray every sample
 // step of every resident wave re-touched ~1 KB per ray: 19 % L2 hit rate, >100x the compulsory HBM/MALL traffic).
 // Alpha compositing is a segmented prefix product / sum over the lanes of a ray.
 // ---------------------------------------------------------------------------------------------------------------
-// One ray group (lpr lanes per ray, all chunks of K) rendered front to back -- the body of render_kernel, also used (out of line) by
-// the pipelined kernel to re-render the rare rays whose encoding needs libm range reduction (eval_point handles that internally).
+// One ray group (lpr lanes per ray, all chunks of K) rendered front to back -- the body of render_kernel (encodings that need libm
+// range reduction are handled inside eval_point).
 template <int C, int HD, int NB, int NVMAX, bool PROJ>
 __device__ __forceinline__ void render_group(const FwdParams& p, const float* lds, long g, int lane, float b_out) {
+  static_assert(!PROJ, "raw features only: the projected map is rendered by render_kernel_p (bts_render_kernel.h)");
   const int lpr = p.lpr, R = 64 / lpr;
   const int kl = lane & (lpr - 1);
   const int Bp = p.Bp, K = p.K, H = p.H, W = p.W, nv = p.nv;
@@ -758,9 +696,7 @@ __device__ __forceinline__ void render_group(const FwdParams& p, const float* ld
     const long ray = g * R + lane / lpr;
     const int sample = __builtin_amdgcn_readfirstlane((int)((g * R) / Bp));  // all rays of a group belong to one batch element
     const Cam enc = load_cam(p.w2c_enc + sample * 16, p.K_enc + sample * 9);
-    const float4* __restrict__ featp =
-        PROJ ? reinterpret_cast<const float4*>(p.proj) + (long)sample * H * W * (HD / 4)
-             : reinterpret_cast<const float4*>(p.feat) + (long)sample * H * W * (C / 4);
+    const float4* __restrict__ featp = reinterpret_cast<const float4*>(p.feat) + (long)sample * H * W * (C / 4);
     const float4 r0 = reinterpret_cast<const float4*>(p.rays)[ray * 2];
     const float4 r1 = reinterpret_cast<const float4*>(p.rays)[ray * 2 + 1];
     const float ox = r0.x, oy = r0.y, oz = r0.z, dx = r0.w, dy = r1.x, dz = r1.y;
@@ -780,7 +716,7 @@ __device__ __forceinline__ void render_group(const FwdParams& p, const float* ld
       // nerf.py:231  points = o + z * d   (mul, then add)
       const float px = ox + z * dx, py = oy + z * dy, pz = oz + z * dz;
       Proj pe;
-      const float s_raw = eval_point<C, HD, NB, PROJ>(p, lds, enc, featp, lane, b_out, px, py, pz, pe);
+      const float s_raw = eval_point<C, HD, NB, false>(p, lds, enc, featp, lane, b_out, px, py, pz, pe);
       float sigma = softplus(s_raw);
       if (p.empty_empty) sigma = pe.invalid ? 0.0f : sigma;
       if (p.sigma_noise) sigma += p.sigma_noise[ray * K + kk];
@@ -865,9 +801,10 @@ __device__ __forceinline__ void render_group(const FwdParams& p, const float* ld
 
 template <int C, int HD, int NB, int NVMAX, bool PROJ>
 __global__ __launch_bounds__(256, 2) void render_kernel(const FwdParams p) {
-  using L = Lds<C, HD, NB, PROJ>;
+  static_assert(!PROJ, "raw features only: the projected map is rendered by render_kernel_p (bts_render_kernel.h)");
+  using L = Lds<C, HD, NB, false>;
   __shared__ float lds[L::TOTAL];
-  stage_weights<C, HD, NB, PROJ>(lds, p.mlp, p.empty_feature);
+  stage_weights<C, HD, NB, false>(lds, p.mlp, p.empty_feature);
   __syncthreads();
 
   const int lane = threadIdx.x & 63;
@@ -885,7 +822,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(const FwdParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// launch dispatch (instantiated per translation unit for one value of PROJ)
+// launch dispatch (instantiated in bts_fwd.hip: launch_field<true, false>, launch_render<false>)
 // ---------------------------------------------------------------------------------------------------------------
 void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
 

@@ -19,14 +19,9 @@ bool shape_supported(int C, int HD, int NB) {
 }
 
 // raw channels-last features (feat_nhwc, for callers that cannot pre-project): the compact lane = sample render kernel and the
-// lane = point query kernel; everything else of bts_field_kernel.h is instantiated in the probe build only
+// lane = point query kernel, the only instantiations of bts_field_kernel.h's kernels
 template int launch_field<true, false>(const FwdParams&, int, int, int, int, hipStream_t);
 template int launch_render<false>(const FwdParams&, int, int, int, int, hipStream_t);
-#ifdef BTS_PROBE
-template int launch_field<false, false>(const FwdParams&, int, int, int, int, hipStream_t);
-extern template int launch_field<false, true>(const FwdParams&, int, int, int, int, hipStream_t);
-extern template int launch_render<true>(const FwdParams&, int, int, int, int, hipStream_t);
-#endif
 int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s);
 
 FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t) {
@@ -74,7 +69,7 @@ int device_cu_count() {
 }
 
 int render_grid(const FwdParams& p) {
-  const long cap = (long)BTS_FWD_WAVES * device_cu_count();
+  const long cap = (long)kFwdWaves * device_cu_count();
   const long want = (p.groups + 3) / 4;
   long g = want < cap ? want : cap;
   g = (g + 7) / 8 * 8;
@@ -103,13 +98,7 @@ int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsR
   p.invalid_wsum = a->invalid_wsum, p.invalid_any = a->invalid_any;
   p.sigma_noise = a->sigma_noise;
   p.tiles_per_sample = (a->rays_per_sample + 255) / 256;
-#ifdef BTS_PROBE   // A/B switches exist only in the probe build (python -m behindthescenes_amd.build --probe); the product has one path
-  if (getenv("BTS_LANE_IS_RAY") && !p.fs) {  // round-1a mapping (one lane = one ray); the legacy kernels know full-size maps only
-    if (p.proj) return launch_field<false, true>(p, cfg->C, cfg->d_hidden, cfg->n_blocks, p.tiles_per_sample * cfg->n, s);
-    return launch_field<false, false>(p, cfg->C, cfg->d_hidden, cfg->n_blocks, p.tiles_per_sample * cfg->n, s);
-  }
-#endif
-#ifdef BTS_PROBE
+#ifdef BTS_PROBE   // the instruments of the probe build (python -m behindthescenes_amd.build --probe): section ablation bits, cycle counters
   if (const char* e = getenv("BTS_ABLATE")) p.ablate |= atoi(e);
   if (const char* e = getenv("BTS_DBG_PTR")) p.dbg = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
@@ -121,9 +110,6 @@ int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsR
   }
   const int grid = render_grid(p);
   p.chunk_log2 = render_chunk_log2(grid, p.groups);
-#ifdef BTS_PROBE
-  if (p.proj && !p.fs && getenv("BTS_RENDER_V1")) return launch_render<true>(p, cfg->C, cfg->d_hidden, cfg->n_blocks, grid, s);  // compact lane = sample kernel
-#endif
   if (p.proj) return launch_render_pipelined(p, cfg->C, cfg->d_hidden, cfg->n_blocks, grid, s);
   if (p.invalid_wsum || p.invalid_any) {
     set_error("%s: invalid_wsum / invalid_any need the projected feature map (proj_nhwc)", "bts_render_fwd");

@@ -8,7 +8,6 @@
 // v_mfma_f32_32x32x2_f32 so that the pass costs what the plain NCHW<->NHWC transposes it replaces would cost.  Layouts
 // are chosen so that every global access is a coalesced row: F is read along pixels (NCHW rows), G / dG along channels.
 #include "bts_common.h"
-#include <cstdlib>
 
 namespace bts {
 
@@ -373,11 +372,7 @@ __device__ __forceinline__ void project_dw_flush(float* red, const f32x16 (&accw
   __syncthreads();
   for (int i = threadIdx.x; i < HD * C; i += blockDim.x) {
     const int hid = i / C, c = i % C;
-#ifndef BTS_ABL_NOFLUSH
     if (red[i] != 0.0f) atomicAdd(&d_mlp[hid * D_IN + c], red[i]);
-#else
-    if (red[i] == 1.2345e-30f) d_mlp[hid * D_IN + c] = red[i];
-#endif
   }
 }
 
@@ -561,17 +556,10 @@ __global__ __launch_bounds__(256) void compact_tiles_kernel(unsigned char* __res
 
 // below this many tiles the flag form stays (a wave holds a tile or two).  A compile-time constant: the "listall" variant of
 // behindthescenes_amd/build.py sets it to 1 so that tests/test_gpu_tile_list.py can put the list form through every small geometry
+// (A/B without the list form: build.py --tag nolist -DBTS_LIST_MIN_TILES=2147483647)
 #ifndef BTS_LIST_MIN_TILES
 #define BTS_LIST_MIN_TILES 4096
 #endif
-// (A/B switch of the list-driven forms: the product reads no environment variables -- probe build only, as every other switch)
-static bool tile_list_on() {
-#ifdef BTS_PROBE
-  return getenv("BTS_NO_TILE_LIST") == nullptr;
-#else
-  return true;
-#endif
-}
 // workspace of the LIST form for a map of n_tiles tiles: the count (16 bytes), the indices, the copy of the flags
 size_t project_bwd_list_bytes(long n_tiles) { return (size_t)(4 + n_tiles) * sizeof(int) + (size_t)n_tiles + 16; }
 
@@ -594,7 +582,7 @@ static int run_fwd(const float* feat, const float* mlp, int N, int HW, float* pr
   const long n_tiles = (long)N * tpi;
   const long want = (n_tiles + 3) / 4, cap = 4L * prep_cus();     // persistent: <= 4 work-groups per CU (16 KB of LDS each)
   const int grid = (int)(want < cap ? want : cap);
-  if (list_ws && tiles && n_tiles >= BTS_LIST_MIN_TILES && list_ws_bytes >= project_bwd_list_bytes(n_tiles) && tile_list_on()) {
+  if (list_ws && tiles && n_tiles >= BTS_LIST_MIN_TILES && list_ws_bytes >= project_bwd_list_bytes(n_tiles)) {
     int* list = static_cast<int*>(list_ws);    // the balanced form (see project_bwd_tiles_kernel): the flags stay as they are
     if (hipMemsetAsync(list, 0, 16, s) != hipSuccess) return BTS_E_LAUNCH;
     compact_tiles_kernel<<<(int)((n_tiles + 255) / 256), 256, 0, s>>>(const_cast<unsigned char*>(tiles), (int)n_tiles, list, nullptr);
@@ -628,7 +616,7 @@ static int run_bwd_tiles(const float* feat, float* dproj, unsigned char* tiles, 
   const long want = (n_tiles + 3) / 4, cap = 2L * prep_cus();
   const int grid = (int)(want < cap ? want : cap);
   // the balanced form: worth its two small extra launches on maps of a few thousand tiles and more (below that a wave holds a tile or two)
-  if (list_ws && tiles && clear && n_tiles >= BTS_LIST_MIN_TILES && list_ws_bytes >= project_bwd_list_bytes(n_tiles) && tile_list_on()) {
+  if (list_ws && tiles && clear && n_tiles >= BTS_LIST_MIN_TILES && list_ws_bytes >= project_bwd_list_bytes(n_tiles)) {
     int* list = static_cast<int*>(list_ws);
     unsigned char* copy = reinterpret_cast<unsigned char*>(list + 4 + n_tiles);
     if (hipMemsetAsync(list, 0, 16, s) != hipSuccess) return BTS_E_LAUNCH;

@@ -342,27 +342,19 @@ __device__ __forceinline__ void hidden_layer_h(f32x16 (&out)[1][2], const f32x16
 
 // The octave chain of the three encoding regions (region R = octaves 2R, 2R + 1).  Direct evaluations (Cody-Waite + polynomials, ~26
 // instructions per argument) at octaves 0 and 3 only; 1, 2 and 4, 5 by angle doubling (fl(v 2f) = 2 fl(v f) exactly; ~1e-7 absolute error
-// per doubling, two in a row at most).  -DBTS_PE_DIRECT3 restores rounds 1 - 2: direct at 0, 2, 4, one doubling each (+69 instructions
-// per ray).  `raw` = octave 2R on entry and octave 2R + 2 on exit; `pre` carries octave 3 from region 0 (where it is evaluated, a region
+// per doubling, two in a row at most).  Rounds 1 - 2 evaluated directly at 0, 2, 4 with one doubling each: +69 instructions
+// per ray.  `raw` = octave 2R on entry and octave 2R + 2 on exit; `pre` carries octave 3 from region 0 (where it is evaluated, a region
 // ahead of its use like every direct evaluation) to region 1.
 template <int R>
 __device__ __forceinline__ void pe_second_octave(SinCos3& r1, const SinCos3& raw, const SinCos3& pre) {
-#ifdef BTS_PE_DIRECT3
-  pe_double(r1, raw);
-#else
   if constexpr (R == 1) r1 = pre;
   else pe_double(r1, raw);
-#endif
 }
 template <int R>
 __device__ __forceinline__ void pe_advance(SinCos3& raw, SinCos3& pre, const SinCos3& r1, const float (&v3)[3], float ff) {
   if constexpr (R + 1 < 3) {
-#ifdef BTS_PE_DIRECT3
-    pe_direct(raw, v3, ff * 4.0f);
-#else
     pe_double(raw, r1);                                   // octave 2R + 2 from octave 2R + 1
     if constexpr (R == 0) pe_direct(pre, v3, ff * 8.0f);  // octave 3
-#endif
   }
 }
 
@@ -726,7 +718,7 @@ using IterHead = IterHeadT<false>;
 // EPI: also reduce weights * invalid and max invalid over each ray's samples (BtsRenderArgs.invalid_wsum / invalid_any).  A template
 // parameter, not a run-time test: the evaluation instantiations carry no trace of it (16 more spilled SGPRs otherwise).
 template <int C, int HD, int NB, int NVMAX, bool ONE_RAY, bool F16, bool EPI = false>
-__global__ __launch_bounds__(256, BTS_FWD_WAVES) void render_kernel_p(const FwdParams p) {
+__global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParams p) {
   static_assert(F16, "lin_in runs on the f16 matrix pipe in split precision: the fp32-input-MFMA form of rounds 1 - 2 is gone (git history)");
   using L = Lds<C, HD, NB, true>;
   using LH = LdsH<C, HD, NB>;

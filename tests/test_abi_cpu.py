@@ -320,8 +320,8 @@ def test_drop_in_emits_the_reference_profiler_ranges():
 
 
 def test_the_product_library_reads_no_environment_variables():
-    """A/B switches (BTS_RENDER_V1, BTS_BWD_V1, BTS_ABLATE, BTS_DBG_PTR ...) exist only in the probe and diagnostic builds: the shipped
-    library does not even import getenv.  (The loader's BTS_RENDER_LIB is Python-side, honoured only with BTS_ALLOW_LIB_OVERRIDE=1 and documented in README.md.)"""
+    """The instruments' switches (BTS_ABLATE, BTS_DBG_PTR) exist only in the probe and diagnostic builds: the shipped library does not
+    even import getenv.  (The loader's BTS_RENDER_LIB is Python-side, honoured only with BTS_ALLOW_LIB_OVERRIDE=1 and documented in README.md.)"""
     import shutil
     nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
     lib = os.path.join(ROOT, "behindthescenes_amd", "libbts_render.so")

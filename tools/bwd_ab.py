@@ -1,6 +1,7 @@
 """A/B timing of differently built libraries on bts_render_bwd within ONE gpurun call: every library runs tools/bwd_probe.py in its own
-subprocess (BTS_RENDER_LIB), interleaved over passes.  Used with the timing-ablation builds of the row backward (-DBTS_ABL_B1 .. B6).
-    python tools/bwd_ab.py <shape> <K> default b1 b2 ...      (names under behindthescenes_amd/variants/, or "default")"""
+subprocess (BTS_RENDER_LIB), interleaved over passes.  Generic over whatever `python -m behindthescenes_amd.build --tag NAME flags...`
+has put under behindthescenes_amd/variants/.
+    python tools/bwd_ab.py <shape> <K> default NAME1 NAME2 ...      (names under behindthescenes_amd/variants/, or "default")"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 shape, K, names = sys.argv[1], sys.argv[2], sys.argv[3:]

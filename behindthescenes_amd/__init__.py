@@ -13,6 +13,8 @@ from .renderer import NeRFRenderer, _RenderWrapper  # noqa: F401
 from .train_step import FusedEvalFrame, FusedTrainStep  # noqa: F401
 from . import lidar_occupancy  # noqa: F401
 from .lidar_occupancy import FusedOccupancyEval  # noqa: F401
+from . import depth_metrics  # noqa: F401
+from .depth_metrics import FusedDepthEval, compute_depth_metrics  # noqa: F401
 
 __all__ = ["BTSNet", "NeRFRenderer", "PositionalEncoding", "ResnetFC", "ResnetBlockFC", "make_mlp", "make_backbone",
-           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "BtsNativeError"]
+           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "FusedDepthEval", "compute_depth_metrics", "depth_metrics", "BtsNativeError"]

@@ -96,7 +96,15 @@ class BtsOccupancyEval(C.Structure):
                [(k, C.c_void_p) for k in ("pred_depth_z", "proj", "cam_pose", "counts", "masks", "sigma", "tables")]
 
 
+class BtsDepthMetrics(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("gt", C.c_void_p), ("Hg", C.c_int32), ("Wg", C.c_int32),
+                ("B", C.c_int32), ("mode", C.c_int32), ("clamp_lo", C.c_float), ("clamp_hi", C.c_float), ("metrics", C.c_void_p),
+                ("counts", C.c_void_p)]
+
+
 BTS_LIDAR_MAX_CLOUDS = 32
+BTS_DEPTH_METRICS_MAX_FRAMES = 64
+BTS_DEPTH_METRICS_ROW = 12
 BTS_LIDAR_MAX_SLICES = 16
 
 # every symbol include/bts_render.h declares: name -> (restype, argtypes)
@@ -149,6 +157,9 @@ SYMBOLS = {
     "bts_lidar_occupancy": (C.c_int, [_P, _I, _P, _I, _I, _P, C.c_float, _P, _P, _P]),
     "bts_occupancy_eval_workspace": (C.c_size_t, [_I, _I, _I]),
     "bts_occupancy_eval": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsOccupancyEval), _P, C.c_size_t, _P]),
+    # depth evaluation metrics (evaluator.py:96-151)
+    "bts_depth_metrics_workspace": (C.c_size_t, [_I, _I, _I, _I]),
+    "bts_depth_metrics": (C.c_int, [C.POINTER(BtsDepthMetrics), _P, C.c_size_t, _P]),
 }
 
 _lock = threading.Lock()

@@ -56,6 +56,9 @@ int lidar_occupancy_launch(const float* q_pts, int P, const float* tables, int y
 int occ_metrics_launch(const float* q_pts, int P, const float* sigma, const unsigned char* is_occupied, const unsigned char* is_visible,
                        const float* depth_z, int H, int W, const float* proj, const float* w2c, float occ_threshold, int* counts,
                        unsigned char* masks, hipStream_t s);
+// depth evaluation metrics (bts_depth_metrics.hip)
+size_t depth_metrics_bytes(int B, int Hg, int Wg);
+int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t s);
 }  // namespace bts
 
 using namespace bts;
@@ -582,6 +585,40 @@ int bts_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const B
   if (!rc) rc = occ_metrics_launch(a->q_pts, P, sigma, is_occ, is_vis, a->pred_depth_z, a->H, a->W, a->proj, w2c, a->occ_threshold, a->counts, a->masks, s);
   if (rc) set_error("%s: kernel launch failed", "bts_occupancy_eval");
   return rc;
+}
+
+// ---- depth evaluation metrics (evaluator.py:96-151)
+static bool depth_metrics_sizes_ok(long B, long H, long W, long Hg, long Wg, int mode) {
+  const long max_px = 1L << 30;
+  return B > 0 && B <= BTS_DEPTH_METRICS_MAX_FRAMES && H > 0 && W > 0 && Hg > 0 && Wg > 0 && H * W <= max_px && Hg * Wg <= max_px && mode >= 0 &&
+         mode <= 2;
+}
+
+size_t bts_depth_metrics_workspace(int32_t B, int32_t Hg, int32_t Wg, int32_t mode) {
+  if (!depth_metrics_sizes_ok(B, 1, 1, Hg, Wg, mode)) return 0;
+  return depth_metrics_bytes(B, Hg, Wg);
+}
+
+int bts_depth_metrics(const BtsDepthMetrics* a, void* workspace, size_t workspace_bytes, void* stream) {
+  BTS_CHECK_LAYOUT(a && a->pred && a->gt && a->metrics && a->B > 0 && a->H > 0 && a->W > 0 && a->Hg > 0 && a->Wg > 0, "bts_depth_metrics");
+  if (a->B > BTS_DEPTH_METRICS_MAX_FRAMES) {
+    set_error("%s: B=%ld frames; at most 64 per call", "bts_depth_metrics", (long)a->B);
+    return BTS_E_INVALID;
+  }
+  if (a->mode < 0 || a->mode > 2) {
+    set_error("%s: unknown mode %ld (0 none, 1 median, 2 l2)", "bts_depth_metrics", (long)a->mode);
+    return BTS_E_INVALID;
+  }
+  if (!depth_metrics_sizes_ok(a->B, a->H, a->W, a->Hg, a->Wg, a->mode)) {
+    set_error("%s: more than 2^30 pixels per frame (pred %ld, gt %ld)", "bts_depth_metrics", (long)a->H * a->W, (long)a->Hg * a->Wg);
+    return BTS_E_INVALID;
+  }
+  const size_t need = depth_metrics_bytes(a->B, a->Hg, a->Wg);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) {
+    set_error("%s: workspace NULL, too small or not 16-byte aligned (%ld bytes needed)", "bts_depth_metrics", (long)need);
+    return BTS_E_INVALID;
+  }
+  BTS_RET_LAUNCH(depth_metrics_launch(a, workspace, (hipStream_t)stream), "bts_depth_metrics");
 }
 
 }  // extern "C"

@@ -1,0 +1,105 @@
+"""The depth evaluation of the reference (BTSWrapper.compute_depth_metrics, models/bts/evaluator.py:96-151; evaluator_nvs.py:96-139 is
+the same function without scaling) on the HIP kernels of csrc/bts_depth_metrics.hip.
+
+``compute_depth_metrics`` keeps the reference's shapes and keys, so its evaluator binds with
+
+    from behindthescenes_amd.depth_metrics import compute_depth_metrics
+    metrics = compute_depth_metrics(data["fine"][0]["depth"][:, :1], data["depths"][0], self.depth_scaling)
+
+``FusedDepthEval`` runs the frame (``FusedEvalFrame``) and its metrics on one stream with nothing synchronised between them and keeps
+one row per frame in a device buffer; ``compute()`` is the ONE device-to-host copy of an evaluation run.
+There is no torch fallback: CPU tensors are rejected, as everywhere else in this package."""
+import torch
+
+from . import _lib, native
+from ._lib import BtsNativeError
+from .train_step import FusedEvalFrame
+
+METRIC_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+
+
+def _frame(t, name):
+    """(1, 1, H, W) -- or anything whose leading dimensions are 1 -- as a contiguous (1, H, W) view"""
+    if not isinstance(t, torch.Tensor):
+        raise BtsNativeError(f"{name}: expected a tensor")
+    if t.dim() < 2 or t.numel() != t.shape[-2] * t.shape[-1]:
+        raise BtsNativeError(f"{name}: one frame expected ((1, 1, H, W), the reference evaluates batch 1), got {tuple(t.shape)}")
+    return t.reshape(1, t.shape[-2], t.shape[-1])
+
+
+def _as_dict(row):
+    return {k: row[i] for i, k in enumerate(METRIC_KEYS)}
+
+
+def compute_depth_metrics(depth_pred, depth_gt, depth_scaling=None):
+    """evaluator.py:96-151 on ``depth_pred (1, 1, H, W)`` and ``depth_gt (1, 1, Hg, Wg)``: the seven metrics as 0-dim device tensors
+    (views of one row) under the reference's keys.  ``depth_scaling``: None, "median" or "l2".  Nothing synchronises."""
+    row = native.depth_metrics(_frame(depth_pred, "depth_pred"), _frame(depth_gt, "depth_gt"), depth_scaling)[0]
+    return _as_dict(row)
+
+
+class FusedDepthEval:
+    """An eval_depth frame that ends in one row of metrics on the device.
+
+        ev = FusedDepthEval(wrapped, sampler, depth_scaling="median")
+        for images, projs, poses, depth_gt in loader:
+            data = ev.frame(images, projs, poses, depth_gt)      # the render dict of FusedEvalFrame + the seven metrics of this frame
+        means = ev.compute()                                     # one device-to-host copy
+
+    ``frame`` runs ``FusedEvalFrame`` and ``bts_depth_metrics`` on the same stream; the metrics read the frame's z-depth where the render
+    wrote it and write row ``n_frames`` of a ``(capacity, 12)`` buffer.  ``compute`` returns, per metric, the mean over the frames seen
+    as the reference's ``MeanMetric`` forms it: an fp64 sum of the per-frame values, frames whose value is NaN left out
+    (utils/metrics.py:25-35).  Past ``capacity`` frames ``frame`` raises; it never wraps."""
+
+    def __init__(self, wrapped, sampler, depth_scaling=None, capacity=4096):
+        if depth_scaling not in native.DEPTH_SCALING_MODES:
+            raise BtsNativeError(f"depth_scaling: expected None, 'median' or 'l2', got {depth_scaling!r}")
+        if int(capacity) <= 0:
+            raise BtsNativeError(f"capacity: a positive number of frames expected, got {capacity}")
+        self.eval_frame = FusedEvalFrame(wrapped, sampler)
+        self.depth_scaling, self.capacity = depth_scaling, int(capacity)
+        self.rows = None
+        self.n_frames = 0
+
+    def reset(self):
+        if self.rows is not None:
+            self.rows.zero_()
+        self.n_frames = 0
+
+    def update(self, depth_pred, depth_gt):
+        """The metrics of one frame from a z-depth the caller already holds (``depth_pred (1, 1, H, W)``): the next row of the buffer."""
+        if self.n_frames >= self.capacity:
+            raise BtsNativeError(f"FusedDepthEval: {self.capacity} frames are stored; compute() / reset() first or construct with a larger capacity")
+        pred, gt = _frame(depth_pred, "depth_pred"), _frame(depth_gt, "depth_gt")
+        native._req(pred, "depth_pred"), native._req(gt, "depth_gt")
+        if self.rows is None or self.rows.device != pred.device:
+            self.rows = torch.zeros((self.capacity, _lib.BTS_DEPTH_METRICS_ROW), device=pred.device, dtype=torch.float32)
+            self.n_frames = 0
+        row = self.rows[self.n_frames:self.n_frames + 1]
+        native.depth_metrics(pred, gt, self.depth_scaling, out=row)
+        self.n_frames += 1
+        return row[0]
+
+    def frame(self, images, projs, poses, depth_gt, **kwargs):
+        """``kwargs`` go to ``FusedEvalFrame.forward`` (ids_encoder, ids_render, jitter, ...); the depth must be the z-depth (to_z)."""
+        if not kwargs.get("to_z", True):
+            raise BtsNativeError("FusedDepthEval: the metrics are defined on the z-depth (to_z=True)")
+        if self.n_frames >= self.capacity:      # before the render, not after it
+            raise BtsNativeError(f"FusedDepthEval: {self.capacity} frames are stored; compute() / reset() first or construct with a larger capacity")
+        native._req(_frame(depth_gt, "depth_gt"), "depth_gt")
+        data = self.eval_frame(images, projs, poses, **kwargs)
+        depth = data["fine"][0]["depth"]                 # (n, v, H, W); the reference takes [:, :1] of batch 1 (evaluator.py:99)
+        if depth.shape[0] != 1:
+            raise BtsNativeError(f"FusedDepthEval: the reference evaluates batch 1, this frame holds {depth.shape[0]} samples")
+        row = self.update(depth[:, :1], depth_gt)
+        data.update(_as_dict(row))
+        data["depth_metrics_row"] = row
+        return data
+
+    def compute(self):
+        if self.n_frames == 0:
+            raise BtsNativeError("FusedDepthEval.compute: no frame has been evaluated")
+        host = self.rows[:self.n_frames, :len(METRIC_KEYS)].cpu().double()      # the ONE device-to-host copy
+        keep = ~torch.isnan(host)
+        sums, n = torch.where(keep, host, torch.zeros_like(host)).sum(dim=0), keep.sum(dim=0)
+        return {k: (sums[i].item() / int(n[i]) if int(n[i]) else float("nan")) for i, k in enumerate(METRIC_KEYS)}

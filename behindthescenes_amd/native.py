@@ -603,6 +603,39 @@ def occupancy_profile(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Ten
     return (profile, sigma) if want_sigma else profile
 
 
+DEPTH_SCALING_MODES = {None: 0, "median": 1, "l2": 2}
+
+
+def depth_metrics(pred: torch.Tensor, gt: torch.Tensor, depth_scaling=None, clamp=(1e-3, 80.0), out=None, counts=None):
+    """pred (B, H, W) z-depth, gt (B, Hg, Wg) with 0 = no measurement -> rows (B, 12): abs_rel sq_rel rmse rmse_log a1 a2 a3 scale shift
+    n_metric n_scale 0 -- compute_depth_metrics of models/bts/evaluator.py:96-151 per frame (bts_depth_metrics).  ``out`` / ``counts``:
+    the caller's (B, 12) float32 / (B, 5) int32 buffers (n_metric, n_scale and the three threshold counts as integers).  The workspace is
+    the cached per-stream scratch of this module; nothing synchronises."""
+    _req(pred, "depth_pred"), _req(gt, "depth_gt")
+    if pred.dim() != 3 or gt.dim() != 3 or pred.shape[0] != gt.shape[0]:
+        raise BtsNativeError(f"depth_metrics: expected (B, H, W) and (B, Hg, Wg), got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if depth_scaling not in DEPTH_SCALING_MODES:
+        raise BtsNativeError(f"depth_scaling: expected None, 'median' or 'l2', got {depth_scaling!r}")
+    if pred.device != gt.device:
+        raise BtsNativeError(f"depth_pred on {pred.device}, depth_gt on {gt.device}")
+    B, H, W = pred.shape
+    Hg, Wg = gt.shape[1:]
+    mode = DEPTH_SCALING_MODES[depth_scaling]
+    if out is None:
+        out = torch.empty((B, _lib.BTS_DEPTH_METRICS_ROW), device=pred.device, dtype=torch.float32)
+    else:
+        _req(out, "out", (B, _lib.BTS_DEPTH_METRICS_ROW))
+    if counts is not None and (not counts.is_cuda or counts.dtype != torch.int32 or not counts.is_contiguous() or tuple(counts.shape) != (B, 5)):
+        raise BtsNativeError("counts: expected a contiguous (B, 5) int32 tensor on the GPU")
+    lib = _lib.load()
+    ws_bytes = int(lib.bts_depth_metrics_workspace(B, Hg, Wg, mode))
+    ws = _workspace(pred.device, max(ws_bytes, 16))
+    args = _lib.BtsDepthMetrics(pred=pred.data_ptr(), H=H, W=W, gt=gt.data_ptr(), Hg=Hg, Wg=Wg, B=B, mode=mode, clamp_lo=float(clamp[0]),
+                                clamp_hi=float(clamp[1]), metrics=out.data_ptr(), counts=None if counts is None else counts.data_ptr())
+    _lib.check(lib.bts_depth_metrics(C.byref(args), _ptr(ws), ws_bytes, _stream(pred)), "bts_depth_metrics")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------------------
 # the Monodepth2 decoder's tail (SURVEY 8 row f4): reflect-pad 3x3 convolution [+ nearest x2 in front] [+ ELU], channels-last
 # --------------------------------------------------------------------------------------------------------------

@@ -624,6 +624,50 @@ size_t bts_occupancy_eval_workspace(int32_t P, int32_t T, int32_t y_res);
 int bts_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsOccupancyEval* a, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Depth evaluation metrics: BTSWrapper.compute_depth_metrics of models/bts/evaluator.py:96-151 (models/bts/evaluator_nvs.py:96-139 is
+ * the same function without scaling) -- what follows bts_eval_frame's depth_z in an eval_depth frame.  Additive to ABI 9: every struct
+ * and entry point above is unchanged.
+ *
+ * Per frame: F.interpolate(pred, gt's size), nearest (:101); scaling by the ratio of the medians (:103-106) or by the least-squares
+ * line (:107-114) over gt > 0; clamp (:116); over gt != 0 (:117) the terms of :122-139 in plain fp32 with IEEE division and no
+ * contraction; their sums in fp64 in a fixed order.  No float atomics anywhere, so a rerun is bit-identical; nothing synchronises.
+ * Quirks of the reference that are reproduced ON PURPOSE:
+ *   - the scaling is fitted over gt > 0, the metrics run over gt != 0: a negative ground-truth value enters the metrics (rmse_log is
+ *     then NaN, as the reference's) but not the scaling;
+ *   - torch.median is the LOWER median, the element of rank (N - 1) / 2; it is found by exact radix selection on the bit patterns, so
+ *     `scale` is bit-equal to the reference's, ties included;
+ *   - the nearest source index is min((int)floorf(dst * scale), in - 1) with scale = (float)in / (float)out in fp32, as PyTorch computes
+ *     it, not the exact rational (the two differ e.g. for 26 -> 44 and 30 -> 58);
+ *   - l2: x = lstsq([p, 1], g) from the five moments in fp64 (normal equations), rounded to fp32, then pred * x0 + x1 as two rounded
+ *     fp32 operations.
+ * Outside the contract: NaN / inf in pred or gt (nothing faults, the row is unspecified); l2 scaling with fewer than two distinct
+ * predictions under the mask (non-finite coefficients where LAPACK returns the minimum-norm solution).  N = 0 gives a NaN row and zero
+ * counts; N = 1 works.
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_DEPTH_METRICS_MAX_FRAMES 64
+#define BTS_DEPTH_METRICS_ROW 12
+
+typedef struct {
+  const float* pred;  int32_t H, W;      /* (B, H, W) predicted z-depth */
+  const float* gt;    int32_t Hg, Wg;    /* (B, Hg, Wg) ground truth, 0 = no measurement */
+  int32_t B, mode;                       /* frames, each evaluated on its own (the reference: batch 1); mode 0 none, 1 median, 2 l2 */
+  float clamp_lo, clamp_hi;              /* 1e-3, 80 (:116) */
+  float* metrics;                        /* (B, 12): abs_rel sq_rel rmse rmse_log a1 a2 a3 scale shift n_metric n_scale reserved */
+  int32_t* counts;                       /* (B, 5): n_metric, n_scale, a1, a2, a3 as integers -- or NULL */
+} BtsDepthMetrics;
+
+/* bytes of bts_depth_metrics' workspace (histograms of the radix passes, per-work-group partial sums; contents need no
+ * initialisation); 0 for non-positive sizes, B > 64, an unknown mode or more than 2^30 pixels per frame */
+size_t bts_depth_metrics_workspace(int32_t B, int32_t Hg, int32_t Wg, int32_t mode);
+
+/* Enqueues, on `stream`: mode 1 -- one clear, three radix passes (11 + 11 + 10 key bits, both medians at once), the metrics pass,
+ * finish; mode 2 -- the moments pass, the 2 x 2 solve, the metrics pass, finish; mode 0 -- the metrics pass, finish.  Everything is
+ * validated before anything is enqueued: BTS_E_INVALID with a message for a NULL pointer, a non-positive size, B > 64, an unknown mode,
+ * more than 2^30 pixels per frame or a workspace that is NULL, too small or not 16-byte aligned. */
+int bts_depth_metrics(const BtsDepthMetrics* a, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ from . import lidar_occupancy  # noqa: F401
 from .lidar_occupancy import FusedOccupancyEval  # noqa: F401
 from . import depth_metrics  # noqa: F401
 from .depth_metrics import FusedDepthEval, compute_depth_metrics  # noqa: F401
+from . import nvs_metrics  # noqa: F401
+from .nvs_metrics import FusedNVSEval, compute_nvs_metrics  # noqa: F401
 
 __all__ = ["BTSNet", "NeRFRenderer", "PositionalEncoding", "ResnetFC", "ResnetBlockFC", "make_mlp", "make_backbone",
-           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "FusedDepthEval", "compute_depth_metrics", "depth_metrics", "BtsNativeError"]
+           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "FusedDepthEval", "compute_depth_metrics", "depth_metrics", "FusedNVSEval", "compute_nvs_metrics", "nvs_metrics", "BtsNativeError"]

@@ -102,9 +102,18 @@ class BtsDepthMetrics(C.Structure):
                 ("counts", C.c_void_p)]
 
 
+class BtsNvsMetrics(C.Structure):
+    _fields_ = [("pred", C.c_void_p)] + [(k, C.c_int64) for k in ("pred_sb", "pred_sy", "pred_sx", "pred_sc")] + \
+               [("gt", C.c_void_p)] + [(k, C.c_int64) for k in ("gt_sb", "gt_sy", "gt_sx", "gt_sc")] + \
+               [(k, C.c_int32) for k in ("B", "H", "W", "He", "We", "y0", "y1", "x0", "x1")] + \
+               [("data_range", C.c_double), ("metrics", C.c_void_p)]
+
+
 BTS_LIDAR_MAX_CLOUDS = 32
 BTS_DEPTH_METRICS_MAX_FRAMES = 64
 BTS_DEPTH_METRICS_ROW = 12
+BTS_NVS_METRICS_MAX_FRAMES = 64
+BTS_NVS_METRICS_ROW = 8
 BTS_LIDAR_MAX_SLICES = 16
 
 # every symbol include/bts_render.h declares: name -> (restype, argtypes)
@@ -160,6 +169,9 @@ SYMBOLS = {
     # depth evaluation metrics (evaluator.py:96-151)
     "bts_depth_metrics_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "bts_depth_metrics": (C.c_int, [C.POINTER(BtsDepthMetrics), _P, C.c_size_t, _P]),
+    # NVS evaluation metrics (evaluator_nvs.py:141-178 without LPIPS)
+    "bts_nvs_metrics_workspace": (C.c_size_t, [_I, _I, _I]),
+    "bts_nvs_metrics": (C.c_int, [C.POINTER(BtsNvsMetrics), _P, C.c_size_t, _P]),
 }
 
 _lock = threading.Lock()

@@ -59,6 +59,9 @@ int occ_metrics_launch(const float* q_pts, int P, const float* sigma, const unsi
 // depth evaluation metrics (bts_depth_metrics.hip)
 size_t depth_metrics_bytes(int B, int Hg, int Wg);
 int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t s);
+// NVS evaluation metrics (bts_nvs_metrics.hip)
+size_t nvs_metrics_bytes(int B, int He, int We);
+int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s);
 }  // namespace bts
 
 using namespace bts;
@@ -619,6 +622,47 @@ int bts_depth_metrics(const BtsDepthMetrics* a, void* workspace, size_t workspac
     return BTS_E_INVALID;
   }
   BTS_RET_LAUNCH(depth_metrics_launch(a, workspace, (hipStream_t)stream), "bts_depth_metrics");
+}
+
+// ---- NVS evaluation metrics (evaluator_nvs.py:141-178 without LPIPS)
+static bool nvs_metrics_sizes_ok(long B, long H, long W, long He, long We) {
+  const long max_px = 1L << 30;
+  return B > 0 && B <= BTS_NVS_METRICS_MAX_FRAMES && H > 0 && W > 0 && He > 0 && We > 0 && H * W <= max_px && He * We <= max_px;
+}
+
+size_t bts_nvs_metrics_workspace(int32_t B, int32_t He, int32_t We) {
+  if (!nvs_metrics_sizes_ok(B, 1, 1, He, We)) return 0;
+  return nvs_metrics_bytes(B, He, We);
+}
+
+int bts_nvs_metrics(const BtsNvsMetrics* a, void* workspace, size_t workspace_bytes, void* stream) {
+  BTS_CHECK_LAYOUT(a && a->pred && a->gt && a->metrics && a->B > 0 && a->H > 0 && a->W > 0 && a->He > 0 && a->We > 0, "bts_nvs_metrics");
+  if (a->B > BTS_NVS_METRICS_MAX_FRAMES) {
+    set_error("%s: B=%ld frames; at most 64 per call", "bts_nvs_metrics", (long)a->B);
+    return BTS_E_INVALID;
+  }
+  if (!nvs_metrics_sizes_ok(a->B, a->H, a->W, a->He, a->We)) {
+    set_error("%s: more than 2^30 pixels per frame (source %ld, eval_resolution %ld)", "bts_nvs_metrics", (long)a->H * a->W, (long)a->He * a->We);
+    return BTS_E_INVALID;
+  }
+  if (a->y0 < 0 || a->x0 < 0 || a->y1 > a->He || a->x1 > a->We || a->y1 < a->y0 || a->x1 < a->x0) {
+    set_error("%s: the crop box leaves eval_resolution (%ld x %ld)", "bts_nvs_metrics", (long)a->He, (long)a->We);
+    return BTS_E_INVALID;
+  }
+  if (a->y1 - a->y0 < 7 || a->x1 - a->x0 < 7) {
+    set_error("%s: crop of %ld x %ld pixels; a side below the 7-pixel window", "bts_nvs_metrics", (long)(a->y1 - a->y0), (long)(a->x1 - a->x0));
+    return BTS_E_INVALID;
+  }
+  if (!(a->data_range > 0.0)) {
+    set_error("%s: data_range must be positive", "bts_nvs_metrics");
+    return BTS_E_INVALID;
+  }
+  const size_t need = nvs_metrics_bytes(a->B, a->He, a->We);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) {
+    set_error("%s: workspace NULL, too small or not 16-byte aligned (%ld bytes needed)", "bts_nvs_metrics", (long)need);
+    return BTS_E_INVALID;
+  }
+  BTS_RET_LAUNCH(nvs_metrics_launch(a, workspace, (hipStream_t)stream), "bts_nvs_metrics");
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ from dataclasses import dataclass
 from typing import Optional
 
 import ctypes as C
+import math
 import weakref
 
 import torch
@@ -633,6 +634,50 @@ def depth_metrics(pred: torch.Tensor, gt: torch.Tensor, depth_scaling=None, clam
     args = _lib.BtsDepthMetrics(pred=pred.data_ptr(), H=H, W=W, gt=gt.data_ptr(), Hg=Hg, Wg=Wg, B=B, mode=mode, clamp_lo=float(clamp[0]),
                                 clamp_hi=float(clamp[1]), metrics=out.data_ptr(), counts=None if counts is None else counts.data_ptr())
     _lib.check(lib.bts_depth_metrics(C.byref(args), _ptr(ws), ws_bytes, _stream(pred)), "bts_depth_metrics")
+    return out
+
+
+def nvs_crop_box(eval_resolution):
+    """The 5 % crop of evaluator_nvs.py:158-161 at ``eval_resolution = (h, w)``: (y0, y1, x0, x1), the reference's own expressions on
+    Python floats; bts_nvs_metrics takes the box from here and derives none of its own."""
+    h, w = int(eval_resolution[0]), int(eval_resolution[1])
+    return int(math.ceil(0.05 * h)), int(math.floor(0.95 * h)), int(math.ceil(0.05 * w)), int(math.floor(0.95 * w))
+
+
+def nvs_metrics(pred: torch.Tensor, gt: torch.Tensor, eval_resolution, out=None):
+    """pred, gt (B, H, W, 3) float32 VIEWS of any strides (a slice of the render's output, a permuted channel-planar image) -> rows
+    (B, 8) float64: ssim psnr mse ssim_c0 ssim_c1 ssim_c2 n_interior n_crop -- the image half of compute_nvs_metrics of
+    models/bts/evaluator_nvs.py:141-178 per frame (bts_nvs_metrics): nearest resize to ``eval_resolution``, the 5 % crop, skimage's
+    SSIM (7 x 7 uniform window, fp64) and PSNR.  ``out``: the caller's (B, 8) float64 buffer.  Nothing is copied and nothing synchronises."""
+    for t, name in ((pred, "rgb_pred"), (gt, "rgb_gt")):
+        if not isinstance(t, torch.Tensor):
+            raise BtsNativeError(f"{name}: expected a tensor")
+        if not t.is_cuda:
+            raise BtsNativeError(f"{name}: must live on the GPU (got {t.device}); the HIP renderer has no CPU path")
+        if t.dtype != torch.float32:
+            raise BtsNativeError(f"{name}: must be float32 (got {t.dtype})")
+    if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape != gt.shape:
+        raise BtsNativeError(f"nvs_metrics: expected two (B, H, W, 3) views of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if pred.device != gt.device:
+        raise BtsNativeError(f"rgb_pred on {pred.device}, rgb_gt on {gt.device}")
+    if len(eval_resolution) != 2:
+        raise BtsNativeError(f"eval_resolution: (height, width) expected, got {eval_resolution!r}")
+    B, H, W, _ = pred.shape
+    He, We = int(eval_resolution[0]), int(eval_resolution[1])
+    y0, y1, x0, x1 = nvs_crop_box((He, We))
+    if out is None:
+        out = torch.empty((B, _lib.BTS_NVS_METRICS_ROW), device=pred.device, dtype=torch.float64)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64 or not out.is_contiguous() or \
+            tuple(out.shape) != (B, _lib.BTS_NVS_METRICS_ROW) or out.device != pred.device:
+        raise BtsNativeError(f"out: expected a contiguous ({B}, {_lib.BTS_NVS_METRICS_ROW}) float64 tensor on {pred.device}")
+    lib = _lib.load()
+    ws_bytes = int(lib.bts_nvs_metrics_workspace(B, He, We))
+    ws = _workspace(pred.device, max(ws_bytes, 16))
+    ps, gs = pred.stride(), gt.stride()
+    args = _lib.BtsNvsMetrics(pred=pred.data_ptr(), pred_sb=ps[0], pred_sy=ps[1], pred_sx=ps[2], pred_sc=ps[3], gt=gt.data_ptr(), gt_sb=gs[0],
+                              gt_sy=gs[1], gt_sx=gs[2], gt_sc=gs[3], B=B, H=H, W=W, He=He, We=We, y0=y0, y1=y1, x0=x0, x1=x1,
+                              data_range=1.0, metrics=out.data_ptr())
+    _lib.check(lib.bts_nvs_metrics(C.byref(args), _ptr(ws), ws_bytes, _stream(pred)), "bts_nvs_metrics")
     return out
 
 

@@ -668,6 +668,56 @@ size_t bts_depth_metrics_workspace(int32_t B, int32_t Hg, int32_t Wg, int32_t mo
  * more than 2^30 pixels per frame or a workspace that is NULL, too small or not 16-byte aligned. */
 int bts_depth_metrics(const BtsDepthMetrics* a, void* workspace, size_t workspace_bytes, void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * NVS evaluation metrics: the image half of BTSWrapper.compute_nvs_metrics of models/bts/evaluator_nvs.py:141-178 -- PSNR and SSIM of
+ * the rendered target view against its ground truth over the 5 % crop at eval_resolution.  (Its depth half, :96-139, is
+ * bts_depth_metrics in mode 0; LPIPS, :171, stays with the caller.)  Additive to ABI 9: every struct and entry point above is unchanged.
+ *
+ * Per frame, with both images read where they lie through element strides (the prediction a view slice of the render's
+ * (n, v, H, W, nv, 3) output, the ground truth a channel-planar view): the value at eval pixel (y, x, c) is
+ * src[nearest(y)][nearest(x)][c] (F.interpolate, :154-155); the crop [y0, y1) x [x0, x1) of size h x w (:158-164);
+ *   mse  = mean over the crop and the 3 channels of (pred - gt)^2,  psnr = 10 log10(R^2 / mse), +inf for mse == 0  (:170);
+ *   ssim = structural_similarity(win_size=7, gaussian_weights=False, data_range=R) per channel, then the mean over channels (:169):
+ *          for every crop pixel whose 7 x 7 window lies inside the crop (the interior, (h - 6) x (w - 6) pixels) the window means
+ *          ux, uy, uxx, uyy, uxy of x, y, x^2, y^2, xy;  vx = cov_norm (uxx - ux^2), vy likewise, vxy = cov_norm (uxy - ux uy);
+ *          C1 = (0.01 R)^2, C2 = (0.03 R)^2;  S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2));  the mean of S.
+ * All arithmetic is fp64 from the fp32 inputs (skimage's, which promoted float32 images before 0.19), with no contraction; the sums
+ * are per-work-group partials added in a fixed order by a second launch.  No float atomics, so a rerun is bit-identical; no resized
+ * or cropped image is ever written; nothing synchronises.
+ * Quirks of the reference that are reproduced ON PURPOSE:
+ *   - the nearest source index is min((int)floorf(dst * scale), in - 1) with scale = (float)in / (float)out in fp32, as PyTorch computes
+ *     it, not the exact rational (the index of bts_depth_metrics); the same map serves both images;
+ *   - the crop box is the caller's: y0 = ceil(0.05 * He), y1 = floor(0.95 * He) as the reference's Python evaluates them on doubles,
+ *     x0 and x1 likewise from We; the library takes the box and does not derive it a second time;
+ *   - cov_norm = 49 / 48, the sample covariance (skimage's default use_sample_covariance=True);
+ *   - the mean of S runs over the interior only: skimage crops (win_size - 1) // 2 = 3 pixels from every side before it averages, so
+ *     its filter's reflect border never reaches the result and there is no border mode here.
+ * Outside the contract: NaN / inf in either image (nothing faults, the row is unspecified).
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_NVS_METRICS_MAX_FRAMES 64
+#define BTS_NVS_METRICS_ROW 8
+
+typedef struct {
+  const float* pred; int64_t pred_sb, pred_sy, pred_sx, pred_sc;   /* element strides: frame, row, column, channel */
+  const float* gt;   int64_t gt_sb,   gt_sy,   gt_sx,   gt_sc;
+  int32_t B, H, W;            /* frames (each on its own), source size */
+  int32_t He, We;             /* eval_resolution */
+  int32_t y0, y1, x0, x1;     /* crop box at eval_resolution */
+  double data_range;          /* 1 */
+  double* metrics;            /* (B, 8): ssim psnr mse ssim_c0 ssim_c1 ssim_c2 n_interior n_crop */
+} BtsNvsMetrics;
+
+/* bytes of bts_nvs_metrics' workspace (per-work-group partial sums for the largest crop eval_resolution admits; contents need no
+ * initialisation); 0 for non-positive sizes, B > 64 or more than 2^30 pixels per frame */
+size_t bts_nvs_metrics_workspace(int32_t B, int32_t He, int32_t We);
+
+/* Enqueues, on `stream`: the tile pass (one work-group per 16 x 32 tile of the interior and frame) and finish.  Everything is validated
+ * before anything is enqueued: BTS_E_INVALID with a message for a NULL pointer, a non-positive size, B > 64, a crop box outside
+ * [0, He] x [0, We], a crop side below 7 (skimage raises there), a non-positive data_range, more than 2^30 pixels per frame (source or
+ * eval_resolution) or a workspace that is NULL, too small or not 16-byte aligned. */
+int bts_nvs_metrics(const BtsNvsMetrics* a, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,9 @@ class BtsEvalFrame(C.Structure):
                [(k, C.c_void_p) for k in ("images", "Ks", "poses_c2w", "feat_nchw", "mlp_params", "empty_feature", "jitter", "cams", "imgs_nhwc4",
                                           "proj_nhwc", "inv_K", "rays", "rgb", "depth", "depth_z", "weights", "alphas", "invalid")] + \
                [("feat_channels_last", C.c_int32), ("reserved_", C.c_int32)]      # ABI 9 (appended)
+    # NOT a field of the C struct (ABI 9 pins its layout): the (n, v, 3, H, W) output tensor of bts_eval_frame_gt's `rgb_gt` argument, carried
+    # on the host object so that native.eval_frame(fr, stream) keeps its two-argument form for whoever wraps it
+    rgb_gt = None
 
 
 class BtsConv3x3(C.Structure):
@@ -150,6 +153,7 @@ SYMBOLS = {
     "bts_train_step_fwd": (C.c_int, [C.POINTER(BtsTrainStep), _P]),
     "bts_train_step_bwd": (C.c_int, [C.POINTER(BtsTrainStep), _P, _P]),
     "bts_eval_frame": (C.c_int, [C.POINTER(BtsEvalFrame), _P]),
+    "bts_eval_frame_gt": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P]),
     "bts_conv3x3_fwd": (C.c_int, [C.POINTER(BtsConv3x3), _P]),
     "bts_conv3x3_bwd_workspace": (C.c_size_t, [C.POINTER(BtsConv3x3)]),
     "bts_conv3x3_bwd": (C.c_int, [C.POINTER(BtsConv3x3), _P, _P, C.c_size_t, _P, _P, _P, _P]),

@@ -102,18 +102,6 @@ int pack_rgb_launch(const float* src, float* dst, int N, int H, int W, float sca
   return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
 }
 
-// frames (n, v, 3, H, W) -> (n, nv, H, W, 4): frame ids[j] of every batch element
-int pack_rgb_views_launch(const float* src, float* dst, int n, int v, int nv, const int* ids, int H, int W, float scale, float shift, hipStream_t s) {
-  const long HW = (long)H * W, total = HW * n * nv;
-  if (total == 0) return BTS_OK;
-  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  FrameIds f;
-  f.nv = nv, f.v = v;
-  for (int j = 0; j < BTS_MAX_VIEWS; ++j) f.ids[j] = j < nv ? ids[j] : 0;
-  pack_rgb_kernel<<<grid, 256, 0, s>>>(src, reinterpret_cast<float4*>(dst), HW, total, scale, shift, f);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
-}
-
 // the ray of pixel (x, y) of a view: [c2w translation, R @ unproj(pixel), near, far]  (util.py:113-149, 244-273)
 __device__ __forceinline__ void ray_of_pixel(const float* __restrict__ P, const float* __restrict__ Kp, int H, int W, int x, int y,
                                              float z_near, float z_far, int norm_dir, float4& a, float4& b) {
@@ -138,10 +126,10 @@ __device__ __forceinline__ void ray_of_pixel(const float* __restrict__ P, const 
 }
 
 // gen_rays: rays (V, H, W, 8)
-__global__ __launch_bounds__(256) void gen_rays_kernel(const float* __restrict__ poses, const float* __restrict__ projs, int V, int H, int W,
-                                                       float z_near, float z_far, int norm_dir, float4* __restrict__ rays) {
+__device__ __forceinline__ void gen_rays_body(const float* __restrict__ poses, const float* __restrict__ projs, int V, int H, int W, float z_near,
+                                              float z_far, int norm_dir, float4* __restrict__ rays, long block, long n_blocks) {
   const long total = (long)V * H * W;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+  for (long i = block * 256L + threadIdx.x; i < total; i += n_blocks * 256) {
     const int v = (int)(i / ((long)H * W));
     const int rem = (int)(i - (long)v * H * W);
     const int y = rem / W, x = rem - y * W;
@@ -150,6 +138,10 @@ __global__ __launch_bounds__(256) void gen_rays_kernel(const float* __restrict__
     rays[2 * i] = a;
     rays[2 * i + 1] = b;
   }
+}
+__global__ __launch_bounds__(256) void gen_rays_kernel(const float* __restrict__ poses, const float* __restrict__ projs, int V, int H, int W,
+                                                       float z_near, float z_far, int norm_dir, float4* __restrict__ rays) {
+  gen_rays_body(poses, projs, V, H, W, z_near, z_far, norm_dir, rays, blockIdx.x, gridDim.x);
 }
 
 int gen_rays_launch(const float* poses, const float* projs, int V, int H, int W, float zn, float zf, int norm_dir, float* rays,
@@ -346,10 +338,6 @@ __device__ __forceinline__ void camera_prep_body(const float* __restrict__ Ks, c
   for (int e = 0; e < 9; ++e) Kd[e] = Ksrc[e];
   invert_small_dev<4>(poses + ((long)smp * f.v + frame) * 16, Pd);
 }
-__global__ __launch_bounds__(64) void camera_prep_kernel(const float* __restrict__ Ks, const float* __restrict__ poses, int n, const CamIds f,
-                                                        float* __restrict__ cams) {
-  camera_prep_body(Ks, poses, n, f, cams, blockIdx.x * 64 + threadIdx.x);
-}
 
 // ---- the hand-over of a training step in ONE launch (bts_train_step_fwd): cameras, rgb0 packing of the render frames, patch rays + colours
 // and the zero fill of every scale's tile flags are independent of each other; as four launches on one queue each paid its own dispatch
@@ -425,12 +413,90 @@ int handover_launch(const float* Ks, const float* poses, const float* images, co
   return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
 }
 
-int camera_prep_launch(const float* Ks, const float* poses, int n, int v, int id_enc, int nv, const int* ids, float* cams, hipStream_t s) {
-  CamIds f;
-  f.nv = nv, f.v = v, f.id_enc = id_enc;
-  for (int j = 0; j < BTS_MAX_VIEWS; ++j) f.ids[j] = j < nv ? ids[j] : 0;
-  const int total = n * (1 + nv);
-  camera_prep_kernel<<<(total + 63) / 64, 64, 0, s>>>(Ks, poses, n, f, cams);
+// ---- the hand-over of an evaluation frame in ONE launch (bts_eval_frame_gt): cameras, the inverse intrinsics distance_to_z reads behind the
+// render, rgb0 packing of the render frames, the rays of every pixel and the ground-truth colours (images * scale + shift over the frames as
+// they lie: the two torch kernels of `images * .5 + .5`) are independent of each other; as six dispatches on one queue they took 0.032 ms
+// of a 0.93 ms frame for a few microseconds of work (profiles/r11a).  Work-group ranges take the roles, the device bodies are the
+// single entry points' own.
+struct EvalHandoverParams {
+  const float* Ks;
+  const float* poses;
+  const float* images;
+  float* cams;
+  float* inv_K;      // NULL: no distance_to_z behind the render
+  float4* imgs;
+  float4* rays;
+  float* rgb_gt;     // NULL: not wanted
+  CamIds cam;
+  FrameIds frames;
+  int n, v, H, W, norm_dir, gt_vec;
+  long gt_total;
+  float z_near, z_far, scale, shift;
+  int b_cam, b_inv, b_pack, b_rays, b_gt;    // work-groups per role, in this order
+};
+__global__ __launch_bounds__(256) void eval_handover_kernel(const EvalHandoverParams p) {
+  int b = blockIdx.x;
+  if (b < p.b_cam) {
+    camera_prep_body(p.Ks, p.poses, p.n, p.cam, p.cams, b * 256 + threadIdx.x);
+    return;
+  }
+  b -= p.b_cam;
+  if (b < p.b_inv) {
+    const int i = b * 256 + threadIdx.x;
+    if (i < p.n * p.v) invert_small_dev<3>(p.Ks + (long)i * 9, p.inv_K + (long)i * 9);
+    return;
+  }
+  b -= p.b_inv;
+  if (b < p.b_pack) {
+    const long HW = (long)p.H * p.W;
+    pack_rgb_body(p.images, p.imgs, HW, HW * p.n * p.frames.nv, p.scale, p.shift, p.frames, b, p.b_pack);
+    return;
+  }
+  b -= p.b_pack;
+  if (b < p.b_rays) {
+    gen_rays_body(p.poses, p.Ks, p.n * p.v, p.H, p.W, p.z_near, p.z_far, p.norm_dir, p.rays, b, p.b_rays);
+    return;
+  }
+  b -= p.b_rays;
+  // mul, then add, each rounded: what torch's two element-wise kernels write
+  if (p.gt_vec) {
+    const float4* s4 = reinterpret_cast<const float4*>(p.images);
+    float4* d4 = reinterpret_cast<float4*>(p.rgb_gt);
+    const long quads = p.gt_total >> 2;
+    for (long i = b * 256L + threadIdx.x; i < quads; i += (long)p.b_gt * 256) {
+      const float4 x = s4[i];
+      d4[i] = make_float4(__fadd_rn(__fmul_rn(x.x, p.scale), p.shift), __fadd_rn(__fmul_rn(x.y, p.scale), p.shift),
+                          __fadd_rn(__fmul_rn(x.z, p.scale), p.shift), __fadd_rn(__fmul_rn(x.w, p.scale), p.shift));
+    }
+    if (b == 0 && threadIdx.x < (p.gt_total & 3)) {      // the ragged end of a count that is no multiple of 4
+      const long i = (quads << 2) + threadIdx.x;
+      p.rgb_gt[i] = __fadd_rn(__fmul_rn(p.images[i], p.scale), p.shift);
+    }
+  } else {      // a frame tensor or an output that does not start on 16 bytes
+    for (long i = b * 256L + threadIdx.x; i < p.gt_total; i += (long)p.b_gt * 256) p.rgb_gt[i] = __fadd_rn(__fmul_rn(p.images[i], p.scale), p.shift);
+  }
+}
+
+int eval_handover_launch(const float* Ks, const float* poses, const float* images, int n, int v, int id_enc, int nv, const int* ids_render, int H, int W,
+                         float z_near, float z_far, int norm_dir, float scale, float shift, float* cams, float* inv_K, float* imgs, float* rays,
+                         float* rgb_gt, hipStream_t s) {
+  EvalHandoverParams p;
+  p.Ks = Ks, p.poses = poses, p.images = images, p.cams = cams, p.inv_K = inv_K, p.rgb_gt = rgb_gt;
+  p.imgs = reinterpret_cast<float4*>(imgs), p.rays = reinterpret_cast<float4*>(rays);
+  p.cam.nv = nv, p.cam.v = v, p.cam.id_enc = id_enc, p.frames.nv = nv, p.frames.v = v;
+  for (int j = 0; j < BTS_MAX_VIEWS; ++j) p.cam.ids[j] = p.frames.ids[j] = j < nv ? ids_render[j] : 0;
+  p.n = n, p.v = v, p.H = H, p.W = W, p.norm_dir = norm_dir;
+  p.z_near = z_near, p.z_far = z_far, p.scale = scale, p.shift = shift;
+  const long HW = (long)H * W, px_total = HW * n * nv, ray_total = HW * n * v;
+  p.gt_total = rgb_gt ? 3 * ray_total : 0;
+  p.gt_vec = ((reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(rgb_gt)) & 15) == 0;
+  const long gt_items = p.gt_vec ? (p.gt_total + 3) >> 2 : p.gt_total;
+  p.b_cam = (n * (1 + nv) + 255) / 256;
+  p.b_inv = inv_K ? (n * v + 255) / 256 : 0;
+  p.b_pack = (int)((px_total + 1023) / 1024 < 2048 ? (px_total + 1023) / 1024 : 2048);      // (a trip of pack_rgb_body is 1024 pixels)
+  p.b_rays = (int)((ray_total + 255) / 256 < 2048 ? (ray_total + 255) / 256 : 2048);
+  p.b_gt = (int)((gt_items + 255) / 256 < 2048 ? (gt_items + 255) / 256 : 2048);
+  eval_handover_kernel<<<p.b_cam + p.b_inv + p.b_pack + p.b_rays + p.b_gt, 256, 0, s>>>(p);
   return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
 }
 

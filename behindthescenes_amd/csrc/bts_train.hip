@@ -17,8 +17,6 @@ namespace bts {
 void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
 bool shape_supported(int C, int HD, int NB);
 
-int camera_prep_launch(const float* Ks, const float* poses, int n, int v, int id_enc, int nv, const int* ids, float* cams, hipStream_t s);
-int pack_rgb_views_launch(const float* src, float* dst, int n, int v, int nv, const int* ids, int H, int W, float scale, float shift, hipStream_t s);
 int patch_rays_views_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
                             int c, int H, int W, int P, int ph, int pw, float zn, float zf, int norm_dir, float* rays, float* gt, int n_ids,
                             const int* ids, float gt_scale, float gt_shift, hipStream_t s);
@@ -410,20 +408,21 @@ int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t
   return BTS_OK;
 }
 
-int gen_rays_launch(const float* poses, const float* projs, int V, int H, int W, float zn, float zf, int norm_dir, float* rays, hipStream_t s);
+int eval_handover_launch(const float* Ks, const float* poses, const float* images, int n, int v, int id_enc, int nv, const int* ids_render, int H, int W,
+                         float z_near, float z_far, int norm_dir, float scale, float shift, float* cams, float* inv_K, float* imgs, float* rays,
+                         float* rgb_gt, hipStream_t s);
 int distance_to_z_launch(const float* depths, const float* invK, int N, int H, int W, float* out, hipStream_t s);
-int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_t s);
 int project_features_plain(int C, int HD, const float* feat, const float* mlp, int N, int HW, float* proj, hipStream_t s, bool channels_last) {
   return project_features_impl(C, HD, feat, mlp, N, HW, proj, nullptr, s, channels_last);
 }
 
-int eval_frame_impl(const BtsEvalFrame* f, hipStream_t stream) {
+int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, hipStream_t stream) {
   const BtsFieldCfg& c = f->cfg;
   const int n = c.n, nv = c.nv;
-  int rc = camera_prep_launch(f->Ks, f->poses_c2w, n, f->v, f->id_encoder, nv, f->ids_render, f->cams, stream);
-  if (!rc && nv) rc = pack_rgb_views_launch(f->images, f->imgs_nhwc4, n, f->v, nv, f->ids_render, c.H, c.W, f->img_scale, f->img_shift, stream);
+  // cameras, inverse intrinsics (for distance_to_z behind the render), rgb0 packing, rays and rgb_gt: one launch
+  int rc = eval_handover_launch(f->Ks, f->poses_c2w, f->images, n, f->v, f->id_encoder, nv, f->ids_render, c.H, c.W, f->z_near, f->z_far, f->norm_dir,
+                                f->img_scale, f->img_shift, f->cams, f->depth_z ? f->inv_K : nullptr, f->imgs_nhwc4, f->rays, rgb_gt, stream);
   if (!rc) rc = project_features_plain(c.C, c.d_hidden, f->feat_nchw, f->mlp_params, n, c.H * c.W, f->proj_nhwc, stream, f->feat_channels_last != 0);
-  if (!rc) rc = gen_rays_launch(f->poses_c2w, f->Ks, n * f->v, c.H, c.W, f->z_near, f->z_far, f->norm_dir, f->rays, stream);
   if (rc) {
     set_error("%s: a hand-over kernel launch failed", "bts_eval_frame");
     return rc;
@@ -445,8 +444,7 @@ int eval_frame_impl(const BtsEvalFrame* f, hipStream_t stream) {
   rc = render_fwd_impl(&cfg, &t, &a, stream);
   if (rc) return rc;
   if (f->depth_z) {
-    rc = invert_small_launch(f->Ks, f->inv_K, n * f->v, 3, stream);
-    if (!rc) rc = distance_to_z_launch(f->depth, f->inv_K, n * f->v, c.H, c.W, f->depth_z, stream);
+    rc = distance_to_z_launch(f->depth, f->inv_K, n * f->v, c.H, c.W, f->depth_z, stream);
     if (rc) {
       set_error("%s: distance_to_z launch failed", "bts_eval_frame");
       return rc;
@@ -461,7 +459,7 @@ using namespace bts;
 
 extern "C" {
 
-int bts_eval_frame(const BtsEvalFrame* f, void* stream) {
+int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream) {
   if (!f) {
     set_error("%s: NULL frame", "bts_eval_frame");
     return BTS_E_INVALID;
@@ -490,8 +488,10 @@ int bts_eval_frame(const BtsEvalFrame* f, void* stream) {
     set_error("%s: too many rays in one call (%ld)", "bts_eval_frame", (long)c.n * f->v * c.H * c.W);
     return BTS_E_UNSUPPORTED;
   }
-  return eval_frame_impl(f, (hipStream_t)stream);
+  return eval_frame_impl(f, rgb_gt, (hipStream_t)stream);
 }
+
+int bts_eval_frame(const BtsEvalFrame* f, void* stream) { return bts_eval_frame_gt(f, nullptr, stream); }
 
 int bts_train_step_fwd(const BtsTrainStep* st, void* stream) {
   if (int rc = check_step(st, "bts_train_step_fwd", false)) return rc;

@@ -744,9 +744,18 @@ class Conv3x3Function(torch.autograd.Function):
         return d_x, d_w, d_b, None, None, None
 
 
-def eval_frame(fr, stream):
-    """bts_eval_frame on a filled ``_lib.BtsEvalFrame`` (behindthescenes_amd.train_step.FusedEvalFrame builds it)."""
-    _lib.check(_lib.load().bts_eval_frame(C.byref(fr), stream), "bts_eval_frame")
+def eval_frame(fr, stream, rgb_gt=None):
+    """bts_eval_frame on a filled ``_lib.BtsEvalFrame`` (behindthescenes_amd.train_step.FusedEvalFrame builds it).  With ``rgb_gt`` -- a
+    contiguous float32 (n, v, 3, H, W) tensor, given here or set as ``fr.rgb_gt`` -- bts_eval_frame_gt: the hand-over launch also writes
+    ``images * img_scale + img_shift`` into it."""
+    if rgb_gt is None:
+        rgb_gt = fr.rgb_gt
+    if rgb_gt is None:
+        _lib.check(_lib.load().bts_eval_frame(C.byref(fr), stream), "bts_eval_frame")
+        return
+    c = fr.cfg
+    _req(rgb_gt, "rgb_gt", (c.n, fr.v, 3, c.H, c.W))
+    _lib.check(_lib.load().bts_eval_frame_gt(C.byref(fr), _ptr(rgb_gt), stream), "bts_eval_frame_gt")
 
 
 def train_step_fwd(st, stream):

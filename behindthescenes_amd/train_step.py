@@ -411,8 +411,9 @@ def native_take(x, ids):
 
 class FusedEvalFrame(torch.nn.Module):
     """``data = frame(images, projs, poses, ids_encoder=[0], ids_render=[0])`` -- the evaluator's forward after the data loader
-    (``BTSWrapper.forward``, models/bts/evaluator.py:60-79) in ONE library call (``bts_eval_frame``, ABI 7): encode's hand-over, the rays
-    of every pixel of every frame (``ImageRaySampler.sample``), the render with ``sample_coarse`` inside, ``distance_to_z``.  The same
+    (``BTSWrapper.forward``, models/bts/evaluator.py:60-79) in ONE library call (``bts_eval_frame_gt``: ABI 7's ``bts_eval_frame`` plus ``rgb_gt``): encode's
+    hand-over, the rays and ground-truth colours of every pixel of every frame (``ImageRaySampler.sample``) -- one launch,
+    ``eval_handover_kernel`` --, the projection, the render with ``sample_coarse`` inside, ``distance_to_z``: four dispatches.  The same
     kernels with the same arguments as the entry-by-entry sequence (bit-identical outputs, tests/test_gpu_train_fused.py); what goes away
     is the host work between them -- 8 % of a 1.1 ms frame.  The jitter is the caller's ``torch.rand`` draw, as in the reference.
 
@@ -492,7 +493,6 @@ class FusedEvalFrame(torch.nn.Module):
         feat = native.as_feature_map(feat.detach())           # NCHW or channels-last (the shipped decoder's format), read as it is: ABI 9
         net.invalidate_field_state()                          # (this call bypasses encode: nothing it cached describes this frame)
         # the reference's order of draws: ImageRaySampler draws nothing, the renderer's jitter is one torch.rand (nerf.py:112)
-        rgb_gt = (images * .5 + .5).permute(0, 1, 3, 4, 2)                     # (n, v, H, W, 3): ray_sampler.py:253-258 (a view, as there)
         B = n * v * H * W
         jitter = torch.rand((B, K), device=dev, dtype=torch.float32) if jitter is None else jitter.to(dev, torch.float32).contiguous()
         f32 = dict(device=dev, dtype=torch.float32)
@@ -503,7 +503,8 @@ class FusedEvalFrame(torch.nn.Module):
                                            proj=torch.empty((n, H, W, spec.d_hidden), **f32), inv_K=torch.empty((n, v, 3, 3), **f32))
         out = dict(rays=torch.empty((n, v * H * W, 8), **f32), rgb=torch.empty((n, v, H, W, nv, 3), **f32), depth=torch.empty((n, v, H, W), **f32),
                    depth_z=torch.empty((n, v, H, W), **f32) if to_z else None, weights=torch.empty((n, v, H, W, K), **f32) if want_weights else None,
-                   alphas=torch.empty((n, v, H, W, K), **f32) if want_alphas else None, invalid=torch.empty((n, v, H, W, K, nv), **f32))
+                   alphas=torch.empty((n, v, H, W, K), **f32) if want_alphas else None, invalid=torch.empty((n, v, H, W, K, nv), **f32),
+                   rgb_gt=torch.empty((n, v, 3, H, W), **f32))          # images * .5 + .5, written by the hand-over launch
         fr = _lib.BtsEvalFrame()
         fr.cfg = native._spec_cfg(spec, n, H, W, nv, 0, ids_render.index(id_enc) if id_enc in ids_render else -1)
         fr.v, fr.id_encoder = v, id_enc
@@ -522,10 +523,12 @@ class FusedEvalFrame(torch.nn.Module):
         fr.cams, fr.imgs_nhwc4, fr.proj_nhwc, fr.inv_K = dp(sc["cams"]), dp(sc["imgs"]), dp(sc["proj"]), dp(sc["inv_K"])
         for k_ in ("rays", "rgb", "depth", "depth_z", "weights", "alphas", "invalid"):
             setattr(fr, k_, dp(out[k_]))
+        fr.rgb_gt = out["rgb_gt"]          # (host-side attribute, no struct field: selects bts_eval_frame_gt in native.eval_frame)
         native.eval_frame(fr, native._stream(images))
         part = dict(rgb=out["rgb"], depth=out["depth_z"] if to_z else out["depth"], invalid=out["invalid"])
         if want_weights:
             part["weights"] = out["weights"]
         if want_alphas:
             part["alphas"] = out["alphas"]
+        rgb_gt = out["rgb_gt"].permute(0, 1, 3, 4, 2)                          # (n, v, H, W, 3): ray_sampler.py:253-258 (a view, as there)
         return dict(coarse=[part], fine=[dict(part)], rgb_gt=rgb_gt, rays=out["rays"])

@@ -513,6 +513,13 @@ typedef struct BtsEvalFrame {
                               * (as BtsTrainScale.feat_channels_last, ABI 8): read as it is, no layout pass.  Appended: every ABI 8 offset stands */
   int32_t reserved_;
 } BtsEvalFrame;
+/* bts_eval_frame_gt (additive to ABI 9, the struct is unchanged): the same frame plus the ground-truth colours of ImageRaySampler.sample
+ * (ray_sampler.py:253-258).  rgb_gt: (n, v, 3, H, W) floats, the frames' own layout, rgb_gt[i] = images[i] * img_scale + img_shift (multiply,
+ * then add, each rounded: bit for bit torch's `images * .5 + .5`); the caller views it as (n, v, H, W, 3).  NULL skips it.  It is written by
+ * the hand-over launch (eval_handover_kernel: cameras, inv_K, rgb0 packing, rays and rgb_gt as work-group ranges of ONE dispatch in front of
+ * the projection and the render), so the frame is four dispatches: hand-over, projection, render, distance_to_z.
+ * bts_eval_frame(f, stream) = bts_eval_frame_gt(f, NULL, stream). */
+int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream);
 int bts_eval_frame(const BtsEvalFrame* f, void* stream);
 
 

@@ -2,7 +2,7 @@
 
     python tools/trace_steps.py <kernel_trace.csv> <marker> [last_steps]
 
-`marker` = substring of a kernel that runs exactly ONCE per step (e.g. patch_rays_kernel for the training workloads, gen_rays_kernel for
+`marker` = substring of a kernel that runs exactly ONCE per step (e.g. patch_rays_kernel for the training workloads, eval_handover_kernel for
 the eval frame): its dispatches delimit the steps.  Only the LAST `last_steps` complete steps (default 3) are aggregated, so warm-up
 work -- MIOpen's solver search runs every candidate, naive ones included, and would otherwise dominate a --stats summary -- stays out.
 Prints ms per step per kernel (names shortened), the sums per group (bts:: / convolution + GEMM / RCCL / other torch) and the GPU-busy

@@ -112,7 +112,17 @@ class BtsNvsMetrics(C.Structure):
                [("data_range", C.c_double), ("metrics", C.c_void_p)]
 
 
+class BtsBBoxOccupancyEval(C.Structure):
+    _fields_ = [("q_pts", C.c_void_p)] + [(k, C.c_int32) for k in ("P", "B", "ph", "pw", "hs", "ws")] + \
+               [(k, C.c_void_p) for k in ("vertices", "faces", "v_offsets", "f_offsets", "semantic_id", "rays", "seg")] + \
+               [("max_d", C.c_float), ("occ_threshold", C.c_float)] + \
+               [(k, C.c_void_p) for k in ("pred_depth_z", "proj", "cam_pose", "counts", "masks", "sigma", "pseudo_depth", "tables")]
+
+
 BTS_LIDAR_MAX_CLOUDS = 32
+BTS_BBOX_MAX_BOXES = 4096
+BTS_BBOX_MAX_VERTS = 64
+BTS_BBOX_MAX_FACES = 32
 BTS_DEPTH_METRICS_MAX_FRAMES = 64
 BTS_DEPTH_METRICS_ROW = 12
 BTS_NVS_METRICS_MAX_FRAMES = 64
@@ -176,6 +186,11 @@ SYMBOLS = {
     # NVS evaluation metrics (evaluator_nvs.py:141-178 without LPIPS)
     "bts_nvs_metrics_workspace": (C.c_size_t, [_I, _I, _I]),
     "bts_nvs_metrics": (C.c_int, [C.POINTER(BtsNvsMetrics), _P, C.c_size_t, _P]),
+    # 3D-bounding-box occupancy evaluation (evaluator_3dbb.py)
+    "bts_bbox_bounds": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, C.c_float, _P, _P, _P, _P]),
+    "bts_bbox_pseudo_depth": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "bts_bbox_occupancy_eval_workspace": (C.c_size_t, [_I, _I, _I, _I]),
+    "bts_bbox_occupancy_eval": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsBBoxOccupancyEval), _P, C.c_size_t, _P]),
 }
 
 _lock = threading.Lock()

@@ -62,6 +62,14 @@ int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t 
 // NVS evaluation metrics (bts_nvs_metrics.hip)
 size_t nvs_metrics_bytes(int B, int He, int We);
 int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s);
+// 3D-bounding-box occupancy evaluation (bts_bbox_occ.hip)
+int bbox_bounds_launch(const float* vertices, const int* faces, const int* v_offsets, const int* f_offsets, int B, const float* to_key,
+                       const float* proj, float max_d, float* tables, int* n_faces, unsigned char* active, int* n_active, hipStream_t s);
+int bbox_pseudo_depth_launch(const float* rays, int ph, int pw, const float* seg, int hs, int ws, const float* tables, const int* n_faces,
+                             const unsigned char* active, const float* semantic_id, int B, float* pseudo_depth, hipStream_t s);
+int bbox_metrics_launch(const float* q_pts, int P, const float* sigma, const float* pseudo, const float* depth_z, int H, int W, const float* proj,
+                        const float* tables, const int* n_faces, const unsigned char* active, int B, float occ_threshold, int* counts,
+                        unsigned char* masks, hipStream_t s);
 }  // namespace bts
 
 using namespace bts;
@@ -663,6 +671,119 @@ int bts_nvs_metrics(const BtsNvsMetrics* a, void* workspace, size_t workspace_by
     return BTS_E_INVALID;
   }
   BTS_RET_LAUNCH(nvs_metrics_launch(a, workspace, (hipStream_t)stream), "bts_nvs_metrics");
+}
+
+// ---- 3D-bounding-box occupancy evaluation (evaluator_3dbb.py): limits and host-side checks shared by the entry points
+static int check_bbox_boxes(const int32_t* v_offsets, const int32_t* f_offsets, int B, const char* who) {
+  if (B > BTS_BBOX_MAX_BOXES) {
+    set_error("%s: B=%ld boxes; at most 4096 are supported", who, (long)B);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (v_offsets[0] != 0 || f_offsets[0] != 0) {
+    set_error("%s: offsets[0] must be 0 (vertices %ld, faces %ld)", who, (long)v_offsets[0], (long)f_offsets[0]);
+    return BTS_E_INVALID;
+  }
+  for (int b = 0; b < B; ++b)
+    if (v_offsets[b + 1] <= v_offsets[b] || f_offsets[b + 1] <= f_offsets[b]) {
+      set_error("%s: offsets are not monotone at box %ld (a box needs at least one vertex and one face)", who, (long)b);
+      return BTS_E_INVALID;
+    }
+  for (int b = 0; b < B; ++b)
+    if (v_offsets[b + 1] - v_offsets[b] > BTS_BBOX_MAX_VERTS || f_offsets[b + 1] - f_offsets[b] > BTS_BBOX_MAX_FACES) {
+      set_error("%s: box %ld has %ld vertices / %ld faces; at most 64 vertices and 32 faces per box are supported", who, (long)b,
+                (long)(v_offsets[b + 1] - v_offsets[b]), (long)(f_offsets[b + 1] - f_offsets[b]));
+      return BTS_E_UNSUPPORTED;
+    }
+  return BTS_OK;
+}
+
+static bool bbox_grid_ok(long ph, long pw, long hs, long ws) {
+  const long max_px = 1L << 27;   // ray r reads floats 8 r + 3 .. 8 r + 5
+  return ph > 0 && pw > 0 && hs > 0 && ws > 0 && ph * pw <= max_px && hs * ws <= (1L << 30);
+}
+
+int bts_bbox_bounds(const float* vertices, const int32_t* faces, const int32_t* v_offsets, const int32_t* f_offsets, int32_t B,
+                    const float* to_keyframe, const float* proj, float max_d, float* tables, int32_t* n_faces, uint8_t* active, void* stream) {
+  BTS_CHECK_LAYOUT(vertices && faces && v_offsets && f_offsets && to_keyframe && proj && tables && n_faces && active && B > 0, "bts_bbox_bounds");
+  if (int rc = check_bbox_boxes(v_offsets, f_offsets, B, "bts_bbox_bounds")) return rc;
+  BTS_RET_LAUNCH(bbox_bounds_launch(vertices, faces, v_offsets, f_offsets, B, to_keyframe, proj, max_d, tables, n_faces, active, nullptr,
+                                    (hipStream_t)stream),
+                 "bts_bbox_bounds");
+}
+
+int bts_bbox_pseudo_depth(const float* rays, int32_t ph, int32_t pw, const float* seg, int32_t hs, int32_t ws, const float* tables,
+                          const int32_t* n_faces, const uint8_t* active, const float* semantic_id, int32_t B, float* pseudo_depth, void* stream) {
+  BTS_CHECK_LAYOUT(rays && seg && tables && n_faces && active && semantic_id && pseudo_depth && B > 0 && ph > 0 && pw > 0 && hs > 0 && ws > 0,
+                   "bts_bbox_pseudo_depth");
+  if (B > BTS_BBOX_MAX_BOXES) {
+    set_error("%s: B=%ld boxes; at most 4096 are supported", "bts_bbox_pseudo_depth", (long)B);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (!bbox_grid_ok(ph, pw, hs, ws)) {
+    set_error("%s: more than 2^27 rays or 2^30 label pixels (%ld, %ld)", "bts_bbox_pseudo_depth", (long)ph * pw, (long)hs * ws);
+    return BTS_E_INVALID;
+  }
+  BTS_RET_LAUNCH(bbox_pseudo_depth_launch(rays, ph, pw, seg, hs, ws, tables, n_faces, active, semantic_id, B, pseudo_depth, (hipStream_t)stream),
+                 "bts_bbox_pseudo_depth");
+}
+
+// workspace of bts_bbox_occupancy_eval: to_keyframe (16) | tables (B, 32, 5) | n_faces (B) | active (B) | pseudo depth (ph, pw) | sigma (P)
+size_t bts_bbox_occupancy_eval_workspace(int32_t P, int32_t B, int32_t ph, int32_t pw) {
+  if (P <= 0 || B <= 0 || B > BTS_BBOX_MAX_BOXES || !bbox_grid_ok(ph, pw, 1, 1)) return 0;
+  return 64 + align16((size_t)B * BTS_BBOX_MAX_FACES * 5 * 4) + align16((size_t)B * 4) + align16((size_t)B) + align16((size_t)ph * pw * 4) +
+         align16((size_t)P * 4);
+}
+
+int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsBBoxOccupancyEval* a, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (int rc = check_cfg(cfg, t, false)) return rc;
+  BTS_CHECK_LAYOUT(a && a->q_pts && a->vertices && a->faces && a->v_offsets && a->f_offsets && a->semantic_id && a->rays && a->seg &&
+                       a->pred_depth_z && a->proj && a->cam_pose && a->counts && a->P > 0 && a->B > 0 && a->ph > 0 && a->pw > 0 && a->hs > 0 &&
+                       a->ws > 0,
+                   "bts_bbox_occupancy_eval");
+  if (cfg->n != 1) {
+    set_error("%s: n=%ld; the evaluator queries one encoded sample (n = 1)", "bts_bbox_occupancy_eval", (long)cfg->n);
+    return BTS_E_INVALID;
+  }
+  if (int rc = check_bbox_boxes(a->v_offsets, a->f_offsets, a->B, "bts_bbox_occupancy_eval")) return rc;
+  if (!bbox_grid_ok(a->ph, a->pw, a->hs, a->ws)) {
+    set_error("%s: more than 2^27 rays or 2^30 label pixels (%ld, %ld)", "bts_bbox_occupancy_eval", (long)a->ph * a->pw, (long)a->hs * a->ws);
+    return BTS_E_INVALID;
+  }
+  const size_t need = bts_bbox_occupancy_eval_workspace(a->P, a->B, a->ph, a->pw);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) {
+    set_error("%s: workspace too small or not 16-byte aligned (%ld bytes needed)", "bts_bbox_occupancy_eval", (long)need);
+    return BTS_E_WORKSPACE;
+  }
+  const int P = a->P, B = a->B;
+  hipStream_t s = (hipStream_t)stream;
+  char* w = reinterpret_cast<char*>(workspace);
+  float* to_key = reinterpret_cast<float*>(w);
+  w += 64;
+  float* tables = a->tables ? a->tables : reinterpret_cast<float*>(w);
+  w += align16((size_t)B * BTS_BBOX_MAX_FACES * 5 * 4);
+  int32_t* n_faces = reinterpret_cast<int32_t*>(w);
+  w += align16((size_t)B * 4);
+  uint8_t* active = reinterpret_cast<uint8_t*>(w);
+  w += align16((size_t)B);
+  float* pseudo = a->pseudo_depth ? a->pseudo_depth : reinterpret_cast<float*>(w);
+  w += align16((size_t)a->ph * a->pw * 4);
+  float* sigma = a->sigma ? a->sigma : reinterpret_cast<float*>(w);
+
+  if (int rc = field_query_impl(cfg, t, a->q_pts, P, 1, nullptr, nullptr, sigma, s)) return rc;
+  if (hipMemsetAsync(a->counts, 0, 7 * sizeof(int32_t), s) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: kernel launch failed", "bts_bbox_occupancy_eval");
+    return BTS_E_LAUNCH;
+  }
+  int rc = invert_small_launch(a->cam_pose, to_key, 1, 4, s);
+  if (!rc) rc = bbox_bounds_launch(a->vertices, a->faces, a->v_offsets, a->f_offsets, B, to_key, a->proj, a->max_d, tables, n_faces, active,
+                                   a->counts + 6, s);
+  if (!rc) rc = bbox_pseudo_depth_launch(a->rays, a->ph, a->pw, a->seg, a->hs, a->ws, tables, n_faces, active, a->semantic_id, B, pseudo, s);
+  if (!rc) rc = bbox_metrics_launch(a->q_pts, P, sigma, pseudo, a->pred_depth_z, a->ph, a->pw, a->proj, tables, n_faces, active, B,
+                                    a->occ_threshold, a->counts, a->masks, s);
+  if (rc) set_error("%s: kernel launch failed", "bts_bbox_occupancy_eval");
+  return rc;
 }
 
 }  // extern "C"

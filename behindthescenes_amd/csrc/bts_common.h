@@ -51,6 +51,24 @@ __device__ __forceinline__ f32x16 zero_acc() {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// look-ups the evaluators share
+// ---------------------------------------------------------------------------------------------------------------
+// F.interpolate(mode="nearest")'s source index (upsample_nearest2d): scale = (float)in / (float)out in fp32, the identity when in == out
+__device__ __forceinline__ int nearest_src(int dst, float scale, int in) { return min((int)floorf((float)dst * scale), in - 1); }
+
+// F.grid_sample(mode="nearest", padding_mode="border", align_corners=True) on an (H, W) map at the normalised (gx, gy): unnormalise,
+// clip, round half to even -> the texel's index y * W + x
+__device__ __forceinline__ long nearest_border_texel(float gx, float gy, int H, int W) {
+  float fx = ((gx + 1.0f) / 2.0f) * (float)(W - 1);
+  float fy = ((gy + 1.0f) / 2.0f) * (float)(H - 1);
+  fx = fminf((float)(W - 1), fmaxf(fx, 0.0f));
+  fy = fminf((float)(H - 1), fmaxf(fy, 0.0f));
+  const int xi = min(max((int)nearbyintf(fx), 0), W - 1);
+  const int yi = min(max((int)nearbyintf(fy), 0), H - 1);
+  return (long)yi * W + xi;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // camera: rows of w2c[:3,:4] and K(3x3) kept in scalar registers (wave-uniform batch element)
 // ---------------------------------------------------------------------------------------------------------------
 struct Cam {

@@ -52,9 +52,7 @@ __device__ __forceinline__ unsigned depth_key(float f) {
 }
 __device__ __forceinline__ float depth_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
-// upsample_nearest2d's source index (:101)
-__device__ __forceinline__ int nearest_src(int dst, float scale, int in) { return min((int)floorf((float)dst * scale), in - 1); }
-
+// (upsample_nearest2d's source index of :101 is bts_common.h's nearest_src)
 __device__ __forceinline__ float pred_at(const DepthGeom& g, const float* pred_f, int i) {
   const int y = i / g.Wg, x = i - y * g.Wg;
   return pred_f[(size_t)nearest_src(y, g.sh, g.H) * g.W + nearest_src(x, g.sw, g.W)];

@@ -206,14 +206,8 @@ __global__ __launch_bounds__(256) void occ_metrics_kernel(const float* __restric
     const float uy = (proj[3] * cx + proj[4] * cy) + proj[5] * cz;
     const float dist = (proj[6] * cx + proj[7] * cy) + proj[8] * cz;
     const float gx = ux / dist, gy = uy / dist;
-    // grid_sample(mode="nearest", padding_mode="border", align_corners=True) (:297): unnormalise, clip, round half to even
-    float fx = ((gx + 1.0f) / 2.0f) * (float)(W - 1);
-    float fy = ((gy + 1.0f) / 2.0f) * (float)(H - 1);
-    fx = fminf((float)(W - 1), fmaxf(fx, 0.0f));
-    fy = fminf((float)(H - 1), fmaxf(fy, 0.0f));
-    const int xi = min(max((int)nearbyintf(fx), 0), W - 1);
-    const int yi = min(max((int)nearbyintf(fy), 0), H - 1);
-    const float pred_dist = depth_z[(long)yi * W + xi];
+    // grid_sample(mode="nearest", padding_mode="border", align_corners=True) (:297)
+    const float pred_dist = depth_z[nearest_border_texel(gx, gy, H, W)];
     const bool vis_pred = dist <= pred_dist;
     const bool Pm = sigma[i] > occ_threshold;
     const bool V = (is_visible[i] != 0) | vis_pred;

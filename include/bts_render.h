@@ -725,6 +725,81 @@ size_t bts_nvs_metrics_workspace(int32_t B, int32_t He, int32_t We);
  * eval_resolution) or a workspace that is NULL, too small or not 16-byte aligned. */
 int bts_nvs_metrics(const BtsNvsMetrics* a, void* workspace, size_t workspace_bytes, void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * 3D-bounding-box occupancy evaluation: the ground-truth half of models/bts/evaluator_3dbb.py (BTSWrapper.forward :212-241, :253-299)
+ * -- occupancy against KITTI-360's annotated boxes -- next to the density query it is compared with.  Additive to ABI 9: every struct
+ * and entry point above is unchanged.
+ *
+ * Plain fp32, IEEE division and square root, no contraction; three-term dot products are summed left to right.  The only reductions are
+ * int32 adds and a bit-pattern minimum of positive floats, so a rerun is bit-identical.  Everything happens in the key frame (the
+ * encoder view's camera frame): rays start at the origin, the query points are given in it.  Quirks of the reference that are
+ * reproduced ON PURPOSE:
+ *   - EPS = 1e-4 widens BOTH sides of every slab test, lo - EPS <= n . p <= hi + EPS (:70), for the ray intercepts and for the query
+ *     points alike;
+ *   - an intercept counts only with p_z > 0 (:119), whatever the sign of the ray parameter;
+ *   - a ray meets only the boxes whose semanticId EQUALS its label, and the label is the one of the nearest-resized label map
+ *     (F.interpolate to the ray grid, :231; the fp32 source index of bts_depth_metrics, the identity when the sizes agree);
+ *   - a box takes part when ANY of its vertices projects into [-1, 1]^2 with 0 < z <= max_d, and max_d is z_range[0] = 20 (:216), not
+ *     the far plane: a box can be active while the rays hit it beyond max_d, and inactive while it is in view further away;
+ *   - a degenerate face (two parallel edges) has the normal 0 / 0 = NaN (:54); every comparison with it is false, so that box holds
+ *     no query point and stops no ray.  Nothing special-cases it: the NaN travels through the arithmetic;
+ *   - a ray that no box stops has the pseudo depth +inf, and dist <= +inf calls every point on it visible (:261).
+ * Limits: B <= BTS_BBOX_MAX_BOXES boxes, 1 <= V <= BTS_BBOX_MAX_VERTS vertices and 1 <= F <= BTS_BBOX_MAX_FACES faces per box --
+ * beyond them BTS_E_UNSUPPORTED with a message, nothing launched.  A face index outside its box's vertices is outside the contract (it
+ * is clamped into them; nothing faults).
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_BBOX_MAX_BOXES 4096
+#define BTS_BBOX_MAX_VERTS 64
+#define BTS_BBOX_MAX_FACES 32
+
+/* verts_to_cam (:30-35), bbox_in_frustum (:38-44), compute_bounds (:47-60), one wave per box.  vertices (sum V_b, 3) world coordinates,
+ * faces (sum F_b, 3) int32 indices LOCAL to their box; v_offsets, f_offsets: HOST arrays of B + 1 int32, offsets[0] = 0, increasing;
+ * to_keyframe (4, 4) = inverse(poses[0, 0]) (bts_invert_small stands in for torch.inverse, :212); proj (3, 3) = projs[0, 0].
+ * tables (B, 32, 5): (nx, ny, nz, lo, hi) per face, zeros in the rows past F_b; n_faces (B) int32; active (B) bytes. */
+int bts_bbox_bounds(const float* vertices, const int32_t* faces, const int32_t* v_offsets, const int32_t* f_offsets, int32_t B,
+                    const float* to_keyframe, const float* proj, float max_d, float* tables, int32_t* n_faces, uint8_t* active, void* stream);
+
+/* bbox_intercept_labeled over all active boxes and the argmin over boxes (:102-128, :236-241), of which the reference keeps z.
+ * rays (ph * pw, 8) in the library's ray layout (direction = floats 3..5; the origin is not read), ray y * pw + x; seg (hs, ws) the
+ * label map as fp32; semantic_id (B) fp32.  pseudo_depth (ph, pw): min p_z over the valid candidates p = (bound_j / (n_j . d)) d of the
+ * label-matching active boxes, +inf where there is none. */
+int bts_bbox_pseudo_depth(const float* rays, int32_t ph, int32_t pw, const float* seg, int32_t hs, int32_t ws, const float* tables,
+                          const int32_t* n_faces, const uint8_t* active, const float* semantic_id, int32_t B, float* pseudo_depth, void* stream);
+
+/* The evaluator's frame after the render from one call, nothing synchronised: the inverse of cam_pose, bts_bbox_bounds,
+ * bts_bbox_pseudo_depth, bts_field_query with only_density on the caller's encoded field (the SAME kernel with the arguments
+ * bts_occupancy_eval passes; cfg->n must be 1), and the metrics kernel: per query point (key frame)
+ *   dist, (gx, gy) = project_into_cam(p) (:146-150); gt, pred = the nearest border-clamped align_corners look-up of the pseudo depth and
+ *   of pred_depth_z (:259-260);  V = dist <= gt | dist <= pred (:261);  O = (in_bbox of any active box) & !V (:264-275);
+ *   P = sigma > occ_threshold (:286)
+ * counts[7] (zeroed inside the call): [0..5] the cells of bts_occupancy_eval, in its order; [6] the number of active boxes.  The nine
+ * metrics of :288-299 follow from the six cells on the host. */
+typedef struct {
+  const float* q_pts;             /* (P, 3) key-frame points (get_pts, :131-143) */
+  int32_t P, B, ph, pw, hs, ws;   /* query points, boxes, ray grid (= size of pred_depth_z), size of seg */
+  const float* vertices;          /* as bts_bbox_bounds */
+  const int32_t* faces;
+  const int32_t* v_offsets;       /* HOST, B + 1 */
+  const int32_t* f_offsets;       /* HOST, B + 1 */
+  const float* semantic_id;       /* (B) */
+  const float* rays;              /* (ph * pw, 8) */
+  const float* seg;               /* (hs, ws) */
+  float max_d, occ_threshold;     /* z_range[0] (:216), 0.5 (:177) */
+  const float* pred_depth_z;      /* (ph, pw) predicted z-depth of the half-resolution render (:251) */
+  const float* proj;              /* (3, 3) normalised intrinsics of the encoder view */
+  const float* cam_pose;          /* (4, 4) its camera-to-world pose, poses[0, 0] */
+  int32_t* counts;                /* (7) */
+  uint8_t* masks;                 /* (3, P): P, O, V -- or NULL */
+  float* sigma;                   /* (P) or NULL */
+  float* pseudo_depth;            /* (ph, pw) or NULL (kept in the workspace) */
+  float* tables;                  /* (B, 32, 5) or NULL (kept in the workspace) */
+} BtsBBoxOccupancyEval;
+/* 0 outside the limits or for non-positive sizes */
+size_t bts_bbox_occupancy_eval_workspace(int32_t P, int32_t B, int32_t ph, int32_t pw);
+int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsBBoxOccupancyEval* a, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,9 @@ SYMBOLS = {
     "bts_gen_rays": (C.c_int, [_P, _P, _I, _I, _I, C.c_float, C.c_float, _I, _P, _P]),
     "bts_patch_rays": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _I, _P, _P, _P]),
     "bts_photometric_loss": (C.c_int, [C.POINTER(BtsLossArgs), _P]),
+    # the same loss for patches of any size (16 x 16 tiles, csrc/bts_loss_tiled.hip)
+    "bts_photometric_loss_tiled_workspace": (C.c_size_t, [_I, _I, _I, _I]),
+    "bts_photometric_loss_tiled": (C.c_int, [C.POINTER(BtsLossArgs), _P, C.c_size_t, _P]),
     "bts_sample_coarse": (C.c_int, [_P, _P, C.c_int64, _I, _I, _P, _P]),
     "bts_distance_to_z": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
     "bts_invert_small": (C.c_int, [_P, _P, _I, _I, _P]),

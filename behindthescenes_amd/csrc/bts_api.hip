@@ -16,6 +16,9 @@ int pack_rgb_launch(const float* src, float* dst, int N, int H, int W, float sca
 int patch_rays_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
                       int c, int H, int W, int P, int ph, int pw, float zn, float zf, int norm_dir, float* rays, float* gt, hipStream_t s);
 int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s);
+// the same loss for patches of any size (bts_loss_tiled.hip)
+size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv);
+int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s);
 int gen_rays_launch(const float* poses, const float* projs, int V, int H, int W, float zn, float zf, int norm_dir, float* rays,
                     hipStream_t s);
 int sample_coarse_launch(const float* rays, const float* u, long B, int K, int lindisp, float* z, hipStream_t s);
@@ -384,6 +387,31 @@ int bts_photometric_loss(const BtsLossArgs* a, void* stream) {
                        (!a->edge_aware_smoothness || a->depth),
                    "bts_photometric_loss");
   BTS_RET_LAUNCH(photometric_loss_impl(a, (hipStream_t)stream), "bts_photometric_loss");
+}
+size_t bts_photometric_loss_tiled_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv) {
+  return loss_tiled_bytes(n_patches, patch_h, patch_w, nv);
+}
+int bts_photometric_loss_tiled(const BtsLossArgs* a, void* workspace, size_t workspace_bytes, void* stream) {
+  BTS_CHECK_LAYOUT(a && a->rgb && a->rgb_gt && a->parts && a->n_patches >= 0 && a->patch_h > 0 && a->patch_w > 0 && a->nv > 0 &&
+                       a->invalid_policy >= 0 && a->invalid_policy <= 2 && (!a->edge_aware_smoothness || a->depth),
+                   "bts_photometric_loss_tiled");
+  if ((a->invalid_policy == 1 && !a->invalid_any && !(a->invalid && a->K > 0)) ||
+      (a->invalid_policy == 2 && !a->invalid_wsum && !(a->invalid && a->weights && a->K > 0))) {
+    set_error("%s: invalid_policy %ld needs invalid_any / invalid_wsum, or invalid (and weights) with K > 0", "bts_photometric_loss_tiled",
+              (long)a->invalid_policy);
+    return BTS_E_INVALID;
+  }
+  if ((long)a->n_patches * a->patch_h * a->patch_w > 2147483647L) {
+    set_error("%s: %ld patches of %ld x %ld pixels are more than 2^31 - 1 rays", "bts_photometric_loss_tiled", (long)a->n_patches, (long)a->patch_h,
+              (long)a->patch_w);
+    return BTS_E_INVALID;
+  }
+  const size_t need = loss_tiled_bytes(a->n_patches, a->patch_h, a->patch_w, a->nv);
+  if (!workspace || workspace_bytes < need) {
+    set_error("%s: workspace too small (%ld bytes needed, see bts_photometric_loss_tiled_workspace)", "bts_photometric_loss_tiled", (long)need);
+    return BTS_E_INVALID;
+  }
+  BTS_RET_LAUNCH(photometric_loss_tiled_impl(a, workspace, (hipStream_t)stream), "bts_photometric_loss_tiled");
 }
 int bts_sample_coarse(const float* rays, const float* u, int64_t B, int32_t K, int32_t lindisp, float* z_samp, void* stream) {
   BTS_CHECK_LAYOUT(rays && u && z_samp && B > 0 && K > 0, "bts_sample_coarse");

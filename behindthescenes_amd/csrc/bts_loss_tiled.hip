@@ -1,0 +1,482 @@
+// bts_loss_tiled.hip -- the photometric loss of bts_loss.hip for patches of ANY size (the trainer's default 16 x 16 patch, sample_mode
+// "image", the validation loss on whole 192 x 640 frames): a patch is cut into 16 x 16 tiles, one work-group of 256 threads per tile,
+// thread = pixel.  The arithmetic per pixel is that of bts_loss.hip (read its header: formulas, closed-interval clamp gradient,
+// sign(0) = 0); what is new is that 3x3 neighbourhoods cross tile borders and that the smoothness term needs the PATCH's mean inverse
+// depth.  Up to four launches on one stream (a kernel boundary is the only hand-over between work-groups; no float atomics, every sum
+// is a fixed-order sum of partials, reruns are bit-identical):
+//   keep, per ray      the invalid-ray policy once per ray (thread = ray, the samples in bts_loss.hip's order; 16-byte loads of the
+//                      weights / invalid rows when nv = 1 and K is a multiple of 4: the validation frame) -> one byte per ray; not
+//                      launched with policy none
+//   pass 1, per tile   stages ground truth, that keep flag and d = 1 / clamp(depth) of the 18 x 18 halo in LDS, then one view's colours at a
+//                      time; per pixel: e_v for every view, v*, the rgb term; with gradients the three SSIM backward coefficients
+//                      per channel of v* (workspace, nine planes) and v* itself (-1: no gradient leaves this pixel); the
+//                      UN-normalised smoothness edges |d_p - d_q| w keep and u_p = d (sum of edges) / d d_p up to the factor 1 / m.
+//                      Per tile: [sum rgb term, sum un-normalised edges, sum d, invalid rays] -> workspace.
+//   pass 2, per patch  adds the tile partials (one wave: lane l takes tiles l, l + 64, ... in order, then the butterfly), m = mean d,
+//                      parts[patch] = [rgb, edges / m, invalid, 0].  |dn_p - dn_q| = |d_p - d_q| / m, so no pre-pass for m is needed,
+//                      and since the smoothness sum E is homogeneous of degree 1 in dn, sum_p u_p d_p = m E = the un-normalised sum.
+//   pass 3, per tile   only with gradients: g_rgb[p, v, c] gathers the coefficients of the nine neighbours whose v* is v (staged with
+//                      their halo in LDS); g_depth[p] = s_eas * (u_p / m - S / (m^2 N)) * d clamp / d depth.
+// One difference from the wave kernel in the last bit: it takes sign(dn_p - dn_q), this file sign(d_p - d_q) -- equal unless two
+// different d round to the same dn, where the reference sits on the kink of |.| anyway.
+// LDS: pass 1 8 planes of 324 floats + 16 partials = 10 432 bytes; pass 3 10 planes of 324 = 12 960 bytes.  Four waves share the
+// planes, so every hand-over is a real __syncthreads() (the wave kernel's wave-scope fence is not enough here).
+#include <hip/hip_runtime.h>
+
+#include "../../include/bts_render.h"
+
+namespace bts {
+
+void set_error(const char* fmt, const char* what, long a = 0, long b = 0, long c = 0);
+
+namespace {
+
+constexpr int kTile = 16;              // interior pixels per tile side (256 threads, thread = pixel)
+constexpr int kLd = kTile + 2;         // row length of a plane with its one-pixel halo
+constexpr int kHalo = kLd * kLd;       // 324
+
+struct TiledParams {
+  const float* rgb;
+  const float* depth;
+  const float* weights;
+  const float* invalid;
+  const float* invalid_wsum;
+  const float* invalid_any;
+  const float* rgb_gt;
+  float* parts;
+  float* g_rgb;
+  float* g_depth;
+  int n_patches, ph, pw, nv, K, policy;
+  float s_rgb, s_eas;
+  int has_eas;
+  int tiles_x, tiles;      // tiles per patch row, tiles per patch
+  long B;                  // rays
+  // workspace
+  float4* tile_parts;      // (n_patches * tiles): sum rgb term, sum un-normalised edges, sum d, invalid rays
+  float4* patch_stats;     // (n_patches): m, un-normalised edge sum, 0, 0
+  int* vstar;              // (B)
+  float* coef;             // (9, B): plane c * 3 + {mu, xx, xy}
+  float* u;                // (B)
+  unsigned char* keep;     // (B): 0 = invalid ray
+  int vec4;                // weights / invalid rows can be read as float4 (nv == 1, K % 4 == 0, 16-byte aligned bases)
+};
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+constexpr float kGa = 0.0947f, kGb = 0.1183f, kGc = 0.1478f;   // layers.py:92-101 window
+
+// Gaussian-weighted sums over the 3x3 neighbourhood of `ctr` in zero-bordered planes, in bts_loss.hip's order of additions
+__device__ __forceinline__ float gauss9(const float* pl, int ctr) {
+  const float* r0 = pl + ctr - kLd;
+  const float* r1 = pl + ctr;
+  const float* r2 = pl + ctr + kLd;
+  float s = kGa * r0[-1];
+  s += kGb * r0[0], s += kGa * r0[1];
+  s += kGb * r1[-1], s += kGc * r1[0], s += kGb * r1[1];
+  s += kGa * r2[-1], s += kGb * r2[0], s += kGa * r2[1];
+  return s;
+}
+__device__ __forceinline__ float gauss9_prod(const float* pa, const float* pb, int ctr) {
+  const float* a0 = pa + ctr - kLd;
+  const float* a1 = pa + ctr;
+  const float* a2 = pa + ctr + kLd;
+  const float* b0 = pb + ctr - kLd;
+  const float* b1 = pb + ctr;
+  const float* b2 = pb + ctr + kLd;
+  float s = kGa * (a0[-1] * b0[-1]);
+  s += kGb * (a0[0] * b0[0]), s += kGa * (a0[1] * b0[1]);
+  s += kGb * (a1[-1] * b1[-1]), s += kGc * (a1[0] * b1[0]), s += kGb * (a1[1] * b1[1]);
+  s += kGa * (a2[-1] * b2[-1]), s += kGb * (a2[0] * b2[0]), s += kGa * (a2[1] * b2[1]);
+  return s;
+}
+// ... of a plane of which only the neighbours flagged in `m` (bit 3 * row + column) count
+__device__ __forceinline__ float gauss9_masked(const float* pl, int ctr, unsigned m) {
+  const float* r0 = pl + ctr - kLd;
+  const float* r1 = pl + ctr;
+  const float* r2 = pl + ctr + kLd;
+  float s = kGa * ((m & 1u) ? r0[-1] : 0.0f);
+  s += kGb * ((m & 2u) ? r0[0] : 0.0f), s += kGa * ((m & 4u) ? r0[1] : 0.0f);
+  s += kGb * ((m & 8u) ? r1[-1] : 0.0f), s += kGc * ((m & 16u) ? r1[0] : 0.0f), s += kGb * ((m & 32u) ? r1[1] : 0.0f);
+  s += kGa * ((m & 64u) ? r2[-1] : 0.0f), s += kGb * ((m & 128u) ? r2[0] : 0.0f), s += kGa * ((m & 256u) ? r2[1] : 0.0f);
+  return s;
+}
+
+__device__ __forceinline__ float sign0(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+
+// invalid ray?  (loss.py:100-118; bts_loss.hip)
+__device__ __forceinline__ bool ray_invalid(const TiledParams& p, long ray) {
+  if (p.policy == 0) return false;
+  const int nv = p.nv, K = p.K;
+  if (p.vec4 && !(p.policy == 2 ? p.invalid_wsum : p.invalid_any)) {      // one view: the rows of K floats as 16-byte loads, same order of sums
+    const float4* i4 = reinterpret_cast<const float4*>(p.invalid + ray * K);
+    if (p.policy == 2) {
+      const float4* w4 = reinterpret_cast<const float4*>(p.weights + ray * K);
+      float s = 0.0f;
+      for (int k = 0; k < K / 4; ++k) {
+        const float4 i = i4[k], w = w4[k];
+        s += i.x * w.x, s += i.y * w.y, s += i.z * w.z, s += i.w * w.w;
+      }
+      return s > 0.9f;
+    }
+    bool any_k = false;
+    for (int k = 0; k < K / 4; ++k) {
+      const float4 i = i4[k];
+      any_k = any_k || (i.x > 0.5f) || (i.y > 0.5f) || (i.z > 0.5f) || (i.w > 0.5f);
+    }
+    return any_k;
+  }
+  bool all_v = true;
+  for (int v = 0; v < nv; ++v) {
+    if (p.policy == 2 && p.invalid_wsum) {
+      all_v = all_v && (p.invalid_wsum[ray * nv + v] > 0.9f);
+    } else if (p.policy == 1 && p.invalid_any) {
+      all_v = all_v && (p.invalid_any[ray * nv + v] > 0.5f);
+    } else if (p.policy == 2) {
+      float s = 0.0f;
+      for (int k = 0; k < K; ++k) s += p.invalid[(ray * K + k) * nv + v] * p.weights[ray * K + k];
+      all_v = all_v && (s > 0.9f);
+    } else {
+      bool any_k = false;
+      for (int k = 0; k < K; ++k) any_k = any_k || (p.invalid[(ray * K + k) * nv + v] > 0.5f);
+      all_v = all_v && any_k;
+    }
+  }
+  return all_v;
+}
+
+// which tile of which patch a work-group takes (1-D grid over n_patches x tiles; beyond kMaxGrid work-groups each takes several)
+constexpr long kMaxGrid = 1L << 20;
+struct TilePos {
+  int patch, y0, x0;
+  long base;     // first ray of the patch
+};
+__device__ __forceinline__ TilePos tile_pos(const TiledParams& p, long blk) {
+  TilePos t;
+  t.patch = (int)(blk / p.tiles);
+  const int r = (int)(blk - (long)t.patch * p.tiles);
+  const int ty = r / p.tiles_x;
+  t.y0 = ty * kTile, t.x0 = (r - ty * p.tiles_x) * kTile;
+  t.base = (long)t.patch * ((long)p.ph * p.pw);
+  return t;
+}
+
+__global__ __launch_bounds__(256) void loss_tiled_keep(const TiledParams p) {
+  for (long ray = blockIdx.x * 256L + threadIdx.x; ray < p.B; ray += gridDim.x * 256L) p.keep[ray] = ray_invalid(p, ray) ? 0 : 1;
+}
+
+__global__ __launch_bounds__(256) void loss_tiled_pass1(const TiledParams p, const long n_tiles) {
+  __shared__ float sY[3][kHalo], sX[3][kHalo], sD[kHalo], sK[kHalo];
+  __shared__ float sRed[4][4];
+  const int tid = threadIdx.x;
+  for (long blk = blockIdx.x; blk < n_tiles; blk += gridDim.x) {
+  if (blk != blockIdx.x) __syncthreads();      // the previous tile's readers are done with the planes and sRed
+  const TilePos tp = tile_pos(p, blk);
+  const int ph = p.ph, pw = p.pw, nv = p.nv;
+
+  // ---- halo: ground truth, keep flag, d = 1 / clamp(depth); zero outside the patch (the SSIM window's zero padding)
+  for (int i = tid; i < kHalo; i += 256) {
+    const int hy = i / kLd, hx = i - hy * kLd;
+    const int py = tp.y0 + hy - 1, px = tp.x0 + hx - 1;
+    float y0 = 0.0f, y1 = 0.0f, y2 = 0.0f, d = 0.0f, k = 0.0f;
+    if (py >= 0 && py < ph && px >= 0 && px < pw) {
+      const long ray = tp.base + (long)py * pw + px;
+      y0 = p.rgb_gt[ray * 3], y1 = p.rgb_gt[ray * 3 + 1], y2 = p.rgb_gt[ray * 3 + 2];
+      k = (p.policy == 0 || p.keep[ray]) ? 1.0f : 0.0f;
+      if (p.has_eas) d = 1.0f / fminf(fmaxf(p.depth[ray], 1e-3f), 80.0f);
+    }
+    sY[0][i] = y0, sY[1][i] = y1, sY[2][i] = y2, sD[i] = d, sK[i] = k;
+  }
+  __syncthreads();
+
+  const int ly = tid >> 4, lx = tid & 15;
+  const int py = tp.y0 + ly, px = tp.x0 + lx;
+  const bool act = py < ph && px < pw;
+  const int ctr = (ly + 1) * kLd + lx + 1;
+  const long ray = tp.base + (act ? (long)py * pw + px : 0);
+  const float keep = act ? sK[ctr] : 0.0f;
+
+  float y[3], mu_y[3], gyy[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    y[c] = sY[c][ctr];
+    mu_y[c] = gauss9(sY[c], ctr);
+    gyy[c] = gauss9_prod(sY[c], sY[c], ctr);
+  }
+
+  constexpr float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
+  // ---- e_v, the minimum over the views (loss.py:152-153); the statistics of v* stay in registers for the coefficients
+  float e_min = 0.0f;
+  int v_star = 0;
+  float b_x[3], b_mu[3], b_gxx[3], b_gxy[3];
+  for (int v = 0; v < nv; ++v) {
+    __syncthreads();      // the previous view's readers are done with sX
+    for (int i = tid; i < kHalo; i += 256) {
+      const int hy = i / kLd, hx = i - hy * kLd;
+      const int qy = tp.y0 + hy - 1, qx = tp.x0 + hx - 1;
+      float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f;
+      if (qy >= 0 && qy < ph && qx >= 0 && qx < pw) {
+        const float* src = p.rgb + ((tp.base + (long)qy * pw + qx) * nv + v) * 3;
+        x0 = src[0], x1 = src[1], x2 = src[2];
+      }
+      sX[0][i] = x0, sX[1][i] = x1, sX[2][i] = x2;
+    }
+    __syncthreads();
+    float ss = 0.0f, l1 = 0.0f;
+    float x[3], mu[3], gxx[3], gxy[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      x[c] = sX[c][ctr];
+      mu[c] = gauss9(sX[c], ctr);
+      gxx[c] = gauss9_prod(sX[c], sX[c], ctr);
+      gxy[c] = gauss9_prod(sX[c], sY[c], ctr);
+      const float mxx = mu[c] * mu[c], myy = mu_y[c] * mu_y[c], mxy = mu[c] * mu_y[c];
+      const float sx = gxx[c] - mxx, sy = gyy[c] - myy, sxy = gxy[c] - mxy;
+      const float nn = (2.0f * mxy + c1) * (2.0f * sxy + c2);
+      const float dd = (mxx + myy + c1) * (sx + sy + c2);
+      ss += fminf(fmaxf(1.0f - nn / dd, 0.0f), 1.0f) / 2.0f;
+      l1 += fabsf(x[c] - y[c]);
+    }
+    const float e = 0.85f * (ss / 3.0f) + 0.15f * (l1 / 3.0f);
+    if (v == 0 || e < e_min) {
+      e_min = e, v_star = v;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) b_x[c] = x[c], b_mu[c] = mu[c], b_gxx[c] = gxx[c], b_gxy[c] = gxy[c];
+    }
+  }
+  const float L = e_min * keep;
+  const float up = keep * p.s_rgb;       // d loss / d e_{v*}(this pixel)
+
+  // ---- the SSIM backward coefficients of v* (gathered by the neighbours in pass 3)
+  if (p.g_rgb && act) {
+    const bool live = up != 0.0f;
+    p.vstar[ray] = live ? v_star : -1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float k_mu = 0.0f, k_xx = 0.0f, k_xy = 0.0f;
+      if (live) {
+        const float mxx = b_mu[c] * b_mu[c], myy = mu_y[c] * mu_y[c], mxy = b_mu[c] * mu_y[c];
+        const float sx = b_gxx[c] - mxx, sy = gyy[c] - myy, sxy = b_gxy[c] - mxy;
+        const float A1 = 2.0f * mxy + c1, A2 = 2.0f * sxy + c2, B1 = mxx + myy + c1, B2 = sx + sy + c2;
+        const float nn = A1 * A2, dd = B1 * B2;
+        const float t = 1.0f - nn / dd;
+        if (t >= 0.0f && t <= 1.0f) {   // torch.clamp passes the gradient on the closed interval
+          const float gs = up * (0.85f / 3.0f) * (-0.5f);
+          const float dn_mu = 2.0f * mu_y[c] * (A2 - A1), dn_xy = 2.0f * A1;
+          const float dd_mu = 2.0f * b_mu[c] * (B2 - B1), dd_xx = B1;
+          const float inv_d = 1.0f / dd, n_d2 = nn * inv_d * inv_d;
+          k_mu = gs * (dn_mu * inv_d - n_d2 * dd_mu);
+          k_xy = gs * (dn_xy * inv_d);
+          k_xx = gs * (-n_d2 * dd_xx);
+        }
+      }
+      p.coef[(long)(c * 3 + 0) * p.B + ray] = k_mu;
+      p.coef[(long)(c * 3 + 1) * p.B + ray] = k_xx;
+      p.coef[(long)(c * 3 + 2) * p.B + ray] = k_xy;
+    }
+  }
+
+  // ---- edge-aware smoothness (loss.py:21-40, masked as in :262-266) on the un-normalised inverse depth
+  float eas = 0.0f, d = 0.0f;
+  if (p.has_eas && act) {
+    d = sD[ctr];
+    const bool has_r = px + 1 < pw, has_b = py + 1 < ph;
+    float idx = 0.0f, idy = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      idx += fabsf(y[c] - sY[c][ctr + 1]);
+      idy += fabsf(y[c] - sY[c][ctr + kLd]);
+    }
+    const float wx = has_r ? expf(-(idx / 3.0f)) : 0.0f, wy = has_b ? expf(-(idy / 3.0f)) : 0.0f;
+    const float ex = d - sD[ctr + 1], ey = d - sD[ctr + kLd];
+    eas = (fabsf(ex) * wx + fabsf(ey) * wy) * keep;
+    if (p.g_depth) {
+      // u_p: this pixel's own edges and the edges its left / upper neighbour owns
+      float u = sign0(ex) * wx * keep + sign0(ey) * wy * keep;
+      if (px > 0) {
+        float il = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) il += fabsf(sY[c][ctr - 1] - y[c]);
+        u -= sign0(sD[ctr - 1] - d) * expf(-(il / 3.0f)) * sK[ctr - 1];
+      }
+      if (py > 0) {
+        float iu = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) iu += fabsf(sY[c][ctr - kLd] - y[c]);
+        u -= sign0(sD[ctr - kLd] - d) * expf(-(iu / 3.0f)) * sK[ctr - kLd];
+      }
+      p.u[ray] = u;
+    }
+  }
+
+  // ---- the tile's partial sums: butterfly per wave, then the four waves in order
+  const float r0 = wave_sum(L), r1 = wave_sum(eas), r2 = wave_sum(d), r3 = wave_sum((act && keep == 0.0f) ? 1.0f : 0.0f);
+  const int wave = tid >> 6;
+  if ((tid & 63) == 0) sRed[wave][0] = r0, sRed[wave][1] = r1, sRed[wave][2] = r2, sRed[wave][3] = r3;
+  __syncthreads();
+  if (tid == 0) {
+    float4 o;
+    o.x = ((sRed[0][0] + sRed[1][0]) + sRed[2][0]) + sRed[3][0];
+    o.y = ((sRed[0][1] + sRed[1][1]) + sRed[2][1]) + sRed[3][1];
+    o.z = ((sRed[0][2] + sRed[1][2]) + sRed[2][2]) + sRed[3][2];
+    o.w = ((sRed[0][3] + sRed[1][3]) + sRed[2][3]) + sRed[3][3];
+    p.tile_parts[blk] = o;
+  }
+  }
+}
+
+// one wave per patch
+__global__ __launch_bounds__(64) void loss_tiled_pass2(const TiledParams p) {
+  const int lane = threadIdx.x;
+  for (long patch = blockIdx.x; patch < p.n_patches; patch += gridDim.x) {
+  const float4* tp = p.tile_parts + patch * p.tiles;
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+  for (int t = lane; t < p.tiles; t += 64) {
+    const float4 q = tp[t];
+    a0 += q.x, a1 += q.y, a2 += q.z, a3 += q.w;
+  }
+  a0 = wave_sum(a0), a1 = wave_sum(a1), a2 = wave_sum(a2), a3 = wave_sum(a3);
+  if (lane == 0) {
+    const float area = (float)((long)p.ph * p.pw);
+    const float m = a2 / area;
+    p.parts[patch * 4L + 0] = a0;
+    p.parts[patch * 4L + 1] = p.has_eas ? a1 / m : 0.0f;
+    p.parts[patch * 4L + 2] = a3;
+    p.parts[patch * 4L + 3] = 0.0f;
+    p.patch_stats[patch] = make_float4(m, a1, 0.0f, 0.0f);
+  }
+  }
+}
+
+__global__ __launch_bounds__(256) void loss_tiled_pass3(const TiledParams p, const long n_tiles) {
+  __shared__ float sC[9][kHalo];
+  __shared__ int sV[kHalo];
+  const int tid = threadIdx.x;
+  for (long blk = blockIdx.x; blk < n_tiles; blk += gridDim.x) {
+  if (blk != blockIdx.x) __syncthreads();      // the previous tile's readers are done with the planes
+  const TilePos tp = tile_pos(p, blk);
+  const int ph = p.ph, pw = p.pw, nv = p.nv;
+  if (p.g_rgb) {
+    for (int i = tid; i < kHalo; i += 256) {
+      const int hy = i / kLd, hx = i - hy * kLd;
+      const int qy = tp.y0 + hy - 1, qx = tp.x0 + hx - 1;
+      int vs = -1;
+      float k[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+      if (qy >= 0 && qy < ph && qx >= 0 && qx < pw) {
+        const long q = tp.base + (long)qy * pw + qx;
+        vs = p.vstar[q];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) k[j] = p.coef[(long)j * p.B + q];
+      }
+      sV[i] = vs;
+#pragma unroll
+      for (int j = 0; j < 9; ++j) sC[j][i] = k[j];
+    }
+  }
+  __syncthreads();
+  const int ly = tid >> 4, lx = tid & 15;
+  const int py = tp.y0 + ly, px = tp.x0 + lx;
+  if (py >= ph || px >= pw) continue;    // (the next barrier is the loop's, which every thread reaches)
+  const int ctr = (ly + 1) * kLd + lx + 1;
+  const long ray = tp.base + (long)py * pw + px;
+
+  if (p.g_rgb) {
+    int vq[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) vq[r * 3 + c] = sV[ctr + (r - 1) * kLd + (c - 1)];
+    const float y[3] = {p.rgb_gt[ray * 3], p.rgb_gt[ray * 3 + 1], p.rgb_gt[ray * 3 + 2]};
+    for (int v = 0; v < nv; ++v) {
+      unsigned m = 0;
+#pragma unroll
+      for (int j = 0; j < 9; ++j) m |= (vq[j] == v) ? (1u << j) : 0u;
+      const float* src = p.rgb + (ray * nv + v) * 3;
+      float* dst = p.g_rgb + (ray * nv + v) * 3;
+      if (m == 0) {                       // no neighbour chose this view
+        dst[0] = 0.0f, dst[1] = 0.0f, dst[2] = 0.0f;
+        continue;
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float x = src[c];
+        const float t_mu = gauss9_masked(sC[c * 3 + 0], ctr, m), t_xx = gauss9_masked(sC[c * 3 + 1], ctr, m),
+                    t_xy = gauss9_masked(sC[c * 3 + 2], ctr, m);
+        // the L1 term's gradient: a centre with v* >= 0 is kept, so its upstream gradient is s_rgb
+        const float g_l1 = (m & 16u) ? p.s_rgb * (0.15f / 3.0f) * sign0(x - y[c]) : 0.0f;
+        dst[c] = t_mu + 2.0f * x * t_xx + y[c] * t_xy + g_l1;
+      }
+    }
+  }
+  if (p.g_depth) {
+    float g = 0.0f;
+    if (p.has_eas) {
+      // dn_p = d_p / m, m = mean d:  d E / d d_j = u_j / m - (sum_p u_p d_p) / (m^2 N), and sum_p u_p d_p = the un-normalised edge sum
+      const float4 st = p.patch_stats[tp.patch];
+      const float m = st.x, S = st.y;
+      const float dep = p.depth[ray];
+      const float dcl = fminf(fmaxf(dep, 1e-3f), 80.0f);
+      const float gd = p.u[ray] / m - S / (m * m * (float)((long)ph * pw));
+      g = ((dep >= 1e-3f && dep <= 80.0f) ? -gd / (dcl * dcl) : 0.0f) * p.s_eas;
+    }
+    p.g_depth[ray] = g;
+  }
+  }
+}
+
+constexpr size_t kAlign = 256;
+inline size_t up256(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
+inline long tiles_of(int ph, int pw) { return (long)((ph + kTile - 1) / kTile) * ((pw + kTile - 1) / kTile); }
+
+}  // namespace
+
+// bytes of bts_photometric_loss_tiled's workspace: tile partials, patch statistics, v*, nine coefficient planes, u, keep flags
+size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv) {
+  if (n_patches < 0 || ph <= 0 || pw <= 0 || nv <= 0) return 0;
+  const size_t B = (size_t)n_patches * (size_t)ph * (size_t)pw;
+  const size_t nt = (size_t)n_patches * (size_t)tiles_of(ph, pw);
+  return kAlign + up256(nt * sizeof(float4)) + up256((size_t)n_patches * sizeof(float4)) + up256(B * sizeof(int)) + up256(B * 9 * sizeof(float)) +
+         up256(B * sizeof(float)) + up256(B);
+}
+
+int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s) {
+  if (a->n_patches == 0) return BTS_OK;
+  TiledParams p;
+  p.rgb = a->rgb, p.depth = a->depth, p.weights = a->weights, p.invalid = a->invalid, p.rgb_gt = a->rgb_gt;
+  p.invalid_wsum = a->invalid_wsum, p.invalid_any = a->invalid_any;
+  p.parts = a->parts, p.g_rgb = a->g_rgb, p.g_depth = a->g_depth;
+  p.n_patches = a->n_patches, p.ph = a->patch_h, p.pw = a->patch_w, p.nv = a->nv, p.K = a->K, p.policy = a->invalid_policy;
+  p.s_rgb = a->scale_rgb, p.s_eas = a->scale_eas, p.has_eas = a->edge_aware_smoothness;
+  p.tiles_x = (p.pw + kTile - 1) / kTile;
+  p.tiles = (int)tiles_of(p.ph, p.pw);
+  p.B = (long)p.n_patches * p.ph * p.pw;
+  const size_t nt = (size_t)p.n_patches * (size_t)p.tiles;
+  char* w = (char*)(((uintptr_t)workspace + kAlign - 1) & ~(uintptr_t)(kAlign - 1));
+  p.tile_parts = (float4*)w, w += up256(nt * sizeof(float4));
+  p.patch_stats = (float4*)w, w += up256((size_t)p.n_patches * sizeof(float4));
+  p.vstar = (int*)w, w += up256((size_t)p.B * sizeof(int));
+  p.coef = (float*)w, w += up256((size_t)p.B * 9 * sizeof(float));
+  p.u = (float*)w, w += up256((size_t)p.B * sizeof(float));
+  p.keep = (unsigned char*)w;
+  p.vec4 = p.nv == 1 && p.K > 0 && (p.K & 3) == 0 && ((uintptr_t)p.invalid & 15) == 0 && ((uintptr_t)p.weights & 15) == 0;
+  const unsigned grid = (unsigned)((long)nt < kMaxGrid ? (long)nt : kMaxGrid);
+  const unsigned grid2 = (unsigned)(p.n_patches < kMaxGrid ? (long)p.n_patches : kMaxGrid);
+  if (p.policy != 0) {
+    const long kb = (p.B + 255) / 256;
+    loss_tiled_keep<<<(unsigned)(kb < kMaxGrid ? kb : kMaxGrid), 256, 0, s>>>(p);
+  }
+  loss_tiled_pass1<<<grid, 256, 0, s>>>(p, (long)nt);
+  loss_tiled_pass2<<<grid2, 64, 0, s>>>(p);
+  if (p.g_rgb || p.g_depth) loss_tiled_pass3<<<grid, 256, 0, s>>>(p, (long)nt);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("%s: tiled loss kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
+    return BTS_E_LAUNCH;
+  }
+  return BTS_OK;
+}
+
+}  // namespace bts

@@ -3,7 +3,11 @@
 For the criterion every shipped config trains with ("l1+ssim") the whole photometric term -- SSIM + L1 per patch, minimum over the
 render views, invalid-ray masking, edge-aware smoothness -- and its gradient with respect to ``rgb`` / ``depth`` come from ONE HIP
 pass per scale (``bts_photometric_loss``, csrc/bts_loss.hip); the ~60 small kernels and nine ``.item()`` synchronisations of the
-reference become one launch, one reduction and one device-to-host copy for the logging dict.  The optional regularisers (depth /
+reference become one launch, one reduction and one device-to-host copy for the logging dict.  The patch may have any size: up to 64
+pixels (every shipped config: ``patch_size: 8``) one wave takes one patch; above that -- the trainer's default ``patch_size = 16``,
+``sample_mode: image``, and the validation loss, where ``ImageRaySampler.reconstruct`` hands over whole frames as ``(n, v, H, W, nv, 3)``
+-- the patch is cut into 16 x 16 tiles (``bts_photometric_loss_tiled``, csrc/bts_loss_tiled.hip: four launches, under ``no_grad``
+three); ``native.photometric_loss`` chooses.  The optional regularisers (depth /
 alpha / surfaceness / depth-smoothness / ray-entropy, all off in the shipped configs) are a few elementwise torch expressions on
 top.  Same constructor keys, same call signature, same ``(loss, loss_dict)`` result as the reference."""
 import math

@@ -145,9 +145,13 @@ def patch_rays(poses_c2w, projs, images, patch_v, patch_y, patch_x, ph: int, pw:
 INVALID_POLICIES = {None: 0, "none": 0, "strict": 1, "weight_guided": 2}
 
 
+WAVE_PATCH_PIXELS = 64      # bts_photometric_loss: one wave per patch, lane = pixel
+
+
 def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w: int, invalid_policy, eas: bool,
                      scale_rgb: float, scale_eas: float, need_grad: bool = True, invalid_wsum=None, invalid_any=None):
-    """Patch-ordered renderer outputs -> per-patch partial sums and the loss gradients (bts_photometric_loss).
+    """Patch-ordered renderer outputs -> per-patch partial sums and the loss gradients (bts_photometric_loss for patches of up to 64
+    pixels, bts_photometric_loss_tiled above that: any (patch_h, patch_w), whole frames included).
     rgb (B, nv*3), depth (B) | None, weights (B, K) | None, invalid (B, K, nv) | None, rgb_gt (B, 3)
     -> parts (B / (ph*pw), 4), g_rgb (B, nv*3) | None, g_depth (B) | None."""
     B = rgb_gt.shape[0]
@@ -182,7 +186,21 @@ def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w
                          nv=nv, K=K, invalid_policy=policy, edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
                          scale_eas=scale_eas, invalid_wsum=invalid_wsum.data_ptr() if (sums and policy == 2) else None,
                          invalid_any=invalid_any.data_ptr() if (sums and policy == 1) else None)
+    if area > WAVE_PATCH_PIXELS:
+        # larger patches and whole frames: 16 x 16 tiles of each patch (bts_photometric_loss_tiled)
+        return photometric_loss_tiled(a, parts, g_rgb, g_depth, _stream(rgb))
     _lib.check(_lib.load().bts_photometric_loss(C.byref(a), _stream(rgb)), "bts_photometric_loss")
+    return parts, g_rgb, g_depth
+
+
+def photometric_loss_tiled(a, parts, g_rgb, g_depth, stream):
+    """bts_photometric_loss_tiled on a filled BtsLossArgs: any patch size, with a scratch workspace from torch's allocator (the library
+    allocates nothing).  ``native.photometric_loss`` routes patches of more than 64 pixels here; tests call it directly to cross-check the
+    two kernels on small patches."""
+    lib = _lib.load()
+    need = lib.bts_photometric_loss_tiled_workspace(a.n_patches, a.patch_h, a.patch_w, a.nv)
+    ws = torch.empty((max(int(need), 1),), device=parts.device, dtype=torch.uint8)
+    _lib.check(lib.bts_photometric_loss_tiled(C.byref(a), ws.data_ptr(), ws.numel(), stream), "bts_photometric_loss_tiled")
     return parts, g_rgb, g_depth
 
 

@@ -289,6 +289,19 @@ typedef struct {
 } BtsLossArgs;
 int bts_photometric_loss(const BtsLossArgs* args, void* stream);
 
+/* The same loss for patches of ANY size (the trainer's default patch_size 16, sample_mode "image", the validation loss on whole frames,
+ * where the "patch" of ImageRaySampler.reconstruct is the 192 x 640 frame): same BtsLossArgs, same meaning of parts (n_patches, 4),
+ * same scale_rgb / scale_eas semantics of g_rgb / g_depth; every patch_h, patch_w >= 1 is accepted (areas of 64 and below too: the
+ * cross-check against bts_photometric_loss, which keeps its patch_h * patch_w <= 64 limit and stays the path of the shipped
+ * patch_size 8 steps).  A patch is cut into 16 x 16 tiles over up to four launches (csrc/bts_loss_tiled.hip): no float atomics, reruns
+ * are bit-identical; with g_rgb == NULL and g_depth == NULL (validation under no_grad) only the forward runs.  `workspace`: at least
+ * bts_photometric_loss_tiled_workspace(n_patches, patch_h, patch_w, nv) bytes of device memory (about 45 bytes per ray; any
+ * alignment; contents need not be initialised or kept).  BTS_E_INVALID with a bts_last_error text, nothing launched, for: a NULL
+ * required pointer or non-positive size, a workspace that is NULL or too small, more than 2^31 - 1 rays, an invalid_policy without the
+ * tensors it reads (the combinations bts_photometric_loss checks). */
+size_t bts_photometric_loss_tiled_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv);
+int bts_photometric_loss_tiled(const BtsLossArgs* args, void* workspace, size_t workspace_bytes, void* stream);
+
 /* PatchRaySampler.sample (models/bts/model/ray_sampler.py:125-162) on device: for each of the n samples, P patches given by
  * (view, y0, x0) triples (int32, (n, P) each; the caller draws them -- the reference uses the CPU RNG) of ph x pw pixels.
  * poses_c2w (n, v, 4, 4), projs (n, v, 3, 3), images (n, v, c, H, W) or NULL -> rays (n, P*ph*pw, 8) and, with images,

@@ -119,6 +119,14 @@ class BtsBBoxOccupancyEval(C.Structure):
                [(k, C.c_void_p) for k in ("pred_depth_z", "proj", "cam_pose", "counts", "masks", "sigma", "pseudo_depth", "tables")]
 
 
+class BtsNovelViews(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("P", "h", "w", "K", "lindisp", "hard_alpha_cap", "norm_dir", "black_invalid", "write_masked", "finish_only",
+                                         "lut_N", "reserved_")] + \
+               [(k, C.c_void_p) for k in ("poses_c2w", "Ks", "near_far", "norm_range", "jitter", "rays", "invalid_wsum", "frame_max", "rgb", "depth",
+                                          "lut_u8", "canvas")] + \
+               [(k, C.c_int32) for k in ("Hc", "Wc", "img_row0", "img_col0", "depth_row0", "depth_col0")]
+
+
 BTS_LIDAR_MAX_CLOUDS = 32
 BTS_BBOX_MAX_BOXES = 4096
 BTS_BBOX_MAX_VERTS = 64
@@ -128,6 +136,8 @@ BTS_DEPTH_METRICS_ROW = 12
 BTS_NVS_METRICS_MAX_FRAMES = 64
 BTS_NVS_METRICS_ROW = 8
 BTS_LIDAR_MAX_SLICES = 16
+BTS_FRAMES_PARTIALS = 64
+BTS_CMAP_MAX_N = 65536
 
 # every symbol include/bts_render.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -194,6 +204,10 @@ SYMBOLS = {
     "bts_bbox_pseudo_depth": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "bts_bbox_occupancy_eval_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "bts_bbox_occupancy_eval": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsBBoxOccupancyEval), _P, C.c_size_t, _P]),
+    # novel-view frames and colour-mapped depth (scripts/inference_setup.py:182-198, utils/plotting.py:41-46)
+    "bts_colorize": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "bts_pack_u8": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _I, _I, _I, C.c_float, C.c_float, _P, _I, _I, _I, _I, _P]),
+    "bts_novel_views": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsNovelViews), _P]),
 }
 
 _lock = threading.Lock()

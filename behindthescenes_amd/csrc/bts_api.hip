@@ -73,6 +73,14 @@ int bbox_pseudo_depth_launch(const float* rays, int ph, int pw, const float* seg
 int bbox_metrics_launch(const float* q_pts, int P, const float* sigma, const float* pseudo, const float* depth_z, int H, int W, const float* proj,
                         const float* tables, const int* n_faces, const unsigned char* active, int B, float occ_threshold, int* counts,
                         unsigned char* masks, hipStream_t s);
+// novel-view frames and colour-mapped depth (bts_frames.hip; the per-pose near / far ray kernel lives in bts_aux.hip)
+int gen_rays_nf_launch(const float* poses, const float* projs, const float* near_far, int V, int H, int W, int norm_dir, float* rays,
+                       hipStream_t s);
+int colorize_launch(const float* x, int B, int h, int w, int norm, int N, const double* lut, const unsigned char* lut_u8, float* partials,
+                    double* out, unsigned char* canvas, int Hc, int Wc, int row0, int col0, hipStream_t s);
+int pack_u8_launch(const float* x, long sb, long sy, long sx, long sc, int B, int h, int w, float scale, float shift, unsigned char* canvas,
+                   int Hc, int Wc, int row0, int col0, hipStream_t s);
+int novel_view_finish_launch(const BtsNovelViews* a, hipStream_t s);
 }  // namespace bts
 
 using namespace bts;
@@ -812,6 +820,92 @@ int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, co
                                     a->occ_threshold, a->counts, a->masks, s);
   if (rc) set_error("%s: kernel launch failed", "bts_bbox_occupancy_eval");
   return rc;
+}
+
+// ---- novel-view frames and colour-mapped depth (scripts/inference_setup.py:182-198, utils/plotting.py:41-46)
+static int check_panel(const char* who, int depth_panel, long h, long w, long Hc, long Wc, long row0, long col0) {
+  if (row0 < 0 || col0 < 0 || row0 + h > Hc || col0 + w > Wc) {
+    set_error(depth_panel ? "%s: the depth panel at (%ld, %ld) leaves the canvas" : "%s: the panel at (%ld, %ld) leaves the canvas", who, row0, col0);
+    return BTS_E_INVALID;
+  }
+  return BTS_OK;
+}
+static bool frames_sizes_ok(long B, long h, long w) { return B > 0 && B <= 65535 && h > 0 && w > 0 && h * w <= (1L << 30); }
+
+int bts_colorize(const float* x, int32_t B, int32_t h, int32_t w, int32_t norm, int32_t N, const double* lut_f64, const uint8_t* lut_u8,
+                 float* minmax_scratch, double* out, uint8_t* canvas, int32_t Hc, int32_t Wc, int32_t row0, int32_t col0, void* stream) {
+  BTS_CHECK_LAYOUT(x && B > 0 && h > 0 && w > 0 && (out || canvas) && (!out || lut_f64) && (!canvas || lut_u8) && (!norm || minmax_scratch),
+                   "bts_colorize");
+  if (!frames_sizes_ok(B, h, w) || N < 1 || N > BTS_CMAP_MAX_N) {
+    set_error("%s: more than 65535 images, more than 2^30 pixels per image, or a table of N=%ld outside [1, 65536]", "bts_colorize", (long)N);
+    return BTS_E_INVALID;
+  }
+  if (canvas)
+    if (int rc = check_panel("bts_colorize", 0, h, w, Hc, Wc, row0, col0)) return rc;
+  BTS_RET_LAUNCH(colorize_launch(x, B, h, w, norm, N, lut_f64, lut_u8, minmax_scratch, out, canvas, Hc, Wc, row0, col0, (hipStream_t)stream),
+                 "bts_colorize");
+}
+
+int bts_pack_u8(const float* x, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int32_t B, int32_t h, int32_t w, float scale, float shift,
+                uint8_t* canvas, int32_t Hc, int32_t Wc, int32_t row0, int32_t col0, void* stream) {
+  BTS_CHECK_LAYOUT(x && canvas && B > 0 && h > 0 && w > 0, "bts_pack_u8");
+  if (!frames_sizes_ok(B, h, w)) {
+    set_error("%s: more than 65535 images or more than 2^30 pixels per image", "bts_pack_u8");
+    return BTS_E_INVALID;
+  }
+  if (int rc = check_panel("bts_pack_u8", 0, h, w, Hc, Wc, row0, col0)) return rc;
+  BTS_RET_LAUNCH(pack_u8_launch(x, (long)sb, (long)sy, (long)sx, (long)sc, B, h, w, scale, shift, canvas, Hc, Wc, row0, col0, (hipStream_t)stream),
+                 "bts_pack_u8");
+}
+
+int bts_novel_views(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsNovelViews* a, void* stream) {
+  const char* who = "bts_novel_views";
+  BTS_CHECK_LAYOUT(a && a->P > 0 && a->h > 0 && a->w > 0 && a->rgb && a->depth && a->invalid_wsum, who);
+  if (!frames_sizes_ok(a->P, a->h, a->w) || (long)a->P * a->h * a->w > (1L << 30)) {
+    set_error("%s: more than 65535 poses or more than 2^30 rays per chunk", who);
+    return BTS_E_INVALID;
+  }
+  if (a->black_invalid && !a->frame_max) {
+    set_error("%s: black_invalid needs the frame_max scratch", who);
+    return BTS_E_INVALID;
+  }
+  const bool img = a->canvas && a->img_row0 >= 0, dep = a->canvas && a->depth_row0 >= 0;
+  if (img)
+    if (int rc = check_panel(who, 0, a->h, a->w, a->Hc, a->Wc, a->img_row0, a->img_col0)) return rc;
+  if (dep) {
+    if (int rc = check_panel(who, 1, a->h, a->w, a->Hc, a->Wc, a->depth_row0, a->depth_col0)) return rc;
+    if (!a->lut_u8 || !a->norm_range || a->lut_N < 1 || a->lut_N > BTS_CMAP_MAX_N) {
+      set_error("%s: the depth panel needs lut_u8, norm_range and 1 <= lut_N <= 65536 (got %ld)", who, (long)a->lut_N);
+      return BTS_E_INVALID;
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (!a->finish_only) {
+    if (int rc = check_cfg(cfg, t, true)) return rc;
+    if (cfg->n != 1 || cfg->nv != 1) {
+      set_error("%s: n=%ld, nv=%ld; a chunk of novel views renders from ONE encoded sample with ONE colour view (ids_encoder=[0], ids_render=[0])",
+                who, (long)cfg->n, (long)cfg->nv);
+      return BTS_E_UNSUPPORTED;
+    }
+    if (!t->proj_nhwc) {
+      set_error("%s: the projected feature map (proj_nhwc) is required (sampling inside the kernel, the invalid_wsum epilogue)", who);
+      return BTS_E_UNSUPPORTED;
+    }
+    if (!a->poses_c2w || !a->Ks || !a->near_far || !a->jitter || !a->rays || a->K <= 0) {
+      set_error("%s: NULL pointer or non-positive K (poses_c2w, Ks, near_far, jitter and the rays scratch are required)", who);
+      return BTS_E_INVALID;
+    }
+    if (gen_rays_nf_launch(a->poses_c2w, a->Ks, a->near_far, a->P, a->h, a->w, a->norm_dir, a->rays, s)) {
+      set_error("%s: kernel launch failed", who);
+      return BTS_E_LAUNCH;
+    }
+    BtsRenderArgs r;
+    memset(&r, 0, sizeof(r));
+    r.rays_per_sample = a->P * a->h * a->w, r.K = a->K, r.hard_alpha_cap = a->hard_alpha_cap, r.white_bkgd = 0, r.lindisp = a->lindisp;
+    r.rays = a->rays, r.jitter = a->jitter, r.rgb = a->rgb, r.depth = a->depth, r.invalid_wsum = a->invalid_wsum;
+    if (int rc = render_fwd_impl(cfg, t, &r, s)) return rc;
+  }
+  BTS_RET_LAUNCH(novel_view_finish_launch(a, s), who);
 }
 
 }  // extern "C"

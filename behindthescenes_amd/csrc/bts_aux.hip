@@ -508,4 +508,29 @@ int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_
   return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
 }
 
+// gen_rays with the near / far planes per view from a (V, 2) device array (bts_novel_views: gen_vid_transition.py:126-138 moves them
+// every frame).  Origins and directions through ray_of_pixel, so bit-identical to gen_rays_kernel's.
+__global__ __launch_bounds__(256) void gen_rays_nf_kernel(const float* __restrict__ poses, const float* __restrict__ projs,
+                                                          const float* __restrict__ near_far, int V, int H, int W, int norm_dir,
+                                                          float4* __restrict__ rays) {
+  const long total = (long)V * H * W;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    const int v = (int)(i / ((long)H * W));
+    const int rem = (int)(i - (long)v * H * W);
+    const int y = rem / W, x = rem - y * W;
+    float4 a, b;
+    ray_of_pixel(poses + v * 16, projs + v * 9, H, W, x, y, near_far[2 * v], near_far[2 * v + 1], norm_dir, a, b);
+    rays[2 * i] = a;
+    rays[2 * i + 1] = b;
+  }
+}
+
+int gen_rays_nf_launch(const float* poses, const float* projs, const float* near_far, int V, int H, int W, int norm_dir, float* rays,
+                       hipStream_t s) {
+  const long total = (long)V * H * W;
+  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  gen_rays_nf_kernel<<<grid, 256, 0, s>>>(poses, projs, near_far, V, H, W, norm_dir, reinterpret_cast<float4*>(rays));
+  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+}
+
 }  // namespace bts

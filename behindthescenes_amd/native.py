@@ -700,6 +700,83 @@ def nvs_metrics(pred: torch.Tensor, gt: torch.Tensor, eval_resolution, out=None)
 
 
 # --------------------------------------------------------------------------------------------------------------
+# novel-view frames and colour-mapped depth (csrc/bts_frames.hip; the host mirrors live in novel_views.py)
+# --------------------------------------------------------------------------------------------------------------
+def _req_as(t, name, dtype, shape=None):
+    if not isinstance(t, torch.Tensor):
+        raise BtsNativeError(f"{name}: expected a tensor")
+    if not t.is_cuda:
+        raise BtsNativeError(f"{name}: must live on the GPU (got {t.device}); the HIP renderer has no CPU path")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise BtsNativeError(f"{name}: must be a contiguous {dtype} tensor (got {t.dtype})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise BtsNativeError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _req_canvas(canvas, B, h, w, row0, col0, what):
+    if not isinstance(canvas, torch.Tensor) or canvas.dim() != 4 or canvas.shape[0] != B or canvas.shape[3] != 3:
+        raise BtsNativeError(f"canvas: a ({B}, Hc, Wc, 3) uint8 tensor expected")
+    _req_as(canvas, "canvas", torch.uint8)
+    Hc, Wc = int(canvas.shape[1]), int(canvas.shape[2])
+    if row0 < 0 or col0 < 0 or row0 + h > Hc or col0 + w > Wc:
+        raise BtsNativeError(f"the {what} panel ({h} x {w} at ({row0}, {col0})) leaves the {Hc} x {Wc} canvas")
+    return Hc, Wc
+
+
+def colorize(x: torch.Tensor, N: int, lut_f64=None, lut_u8=None, norm: bool = False, want_f64: bool = True, canvas=None, row0: int = 0,
+             col0: int = 0):
+    """x (B, h, w) float32 -> matplotlib's colour map per pixel (bts_colorize): a fresh (B, h, w, 3) float64 tensor from ``lut_f64``
+    (N + 3, 3) when ``want_f64``, and / or the bytes of ``lut_u8`` (N + 3, 3) into ``canvas`` (B, Hc, Wc, 3) at (row0, col0).  ``norm``:
+    (x - min) / (max - min) per image first.  Nothing synchronises."""
+    _req(x, "x")
+    if x.dim() != 3:
+        raise BtsNativeError(f"x: (B, h, w) expected, got {tuple(x.shape)}")
+    B, h, w = (int(s) for s in x.shape)
+    if B == 0 or h * w == 0:
+        raise BtsNativeError("x: an empty image")
+    dev, out, Hc, Wc = x.device, None, 0, 0
+    if want_f64:
+        _req_as(lut_f64, "lut_f64", torch.float64, (N + 3, 3))
+        out = torch.empty((B, h, w, 3), device=dev, dtype=torch.float64)
+    if canvas is not None:
+        _req_as(lut_u8, "lut_u8", torch.uint8, (N + 3, 3))
+        Hc, Wc = _req_canvas(canvas, B, h, w, row0, col0, "colour")
+    if out is None and canvas is None:
+        raise BtsNativeError("colorize: neither the float64 output nor a canvas was requested")
+    scratch = _workspace(dev, B * _lib.BTS_FRAMES_PARTIALS * 3 * 4) if norm else None
+    _lib.check(_lib.load().bts_colorize(_ptr(x), B, h, w, int(bool(norm)), int(N), _ptr(lut_f64) if want_f64 else None,
+                                        _ptr(lut_u8) if canvas is not None else None, _ptr(scratch), _ptr(out), _ptr(canvas), Hc, Wc, int(row0),
+                                        int(col0), _stream(x)), "bts_colorize")
+    return out
+
+
+def pack_u8(x: torch.Tensor, canvas: torch.Tensor, row0: int = 0, col0: int = 0, scale: float = 1.0, shift: float = 0.0):
+    """x (B, h, w, 3) float32 VIEW of any strides (a permuted channel-planar image) -> uint8 of x * scale + shift into ``canvas``
+    (B, Hc, Wc, 3) at (row0, col0) (bts_pack_u8)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        raise BtsNativeError("x: a float32 tensor on the GPU expected; the HIP renderer has no CPU path")
+    if x.dim() != 4 or x.shape[-1] != 3 or x.numel() == 0:
+        raise BtsNativeError(f"x: a non-empty (B, h, w, 3) view expected, got {tuple(x.shape)}")
+    B, h, w, _ = (int(s) for s in x.shape)
+    Hc, Wc = _req_canvas(canvas, B, h, w, row0, col0, "image")
+    st = x.stride()
+    _lib.check(_lib.load().bts_pack_u8(_ptr(x), st[0], st[1], st[2], st[3], B, h, w, float(scale), float(shift), _ptr(canvas), Hc, Wc, int(row0),
+                                       int(col0), _stream(x)), "bts_pack_u8")
+    return canvas
+
+
+def novel_views(ft: Optional["FieldTensors"], mlp_params, a: "_lib.BtsNovelViews", stream):
+    """One chunk of novel views (bts_novel_views); ``a`` is filled by novel_views.py.  ``ft`` None: finish_only."""
+    if ft is None:
+        _lib.check(_lib.load().bts_novel_views(None, None, C.byref(a), stream), "bts_novel_views")
+        return
+    _check_partial(ft, None, None, "novel_views")
+    cfg, tens = ft.cfg(), ft.tensors(mlp_params)
+    _lib.check(_lib.load().bts_novel_views(C.byref(cfg), C.byref(tens), C.byref(a), stream), "bts_novel_views")
+
+
+# --------------------------------------------------------------------------------------------------------------
 # the Monodepth2 decoder's tail (SURVEY 8 row f4): reflect-pad 3x3 convolution [+ nearest x2 in front] [+ ELU], channels-last
 # --------------------------------------------------------------------------------------------------------------
 def _conv_struct(x, weight, bias, y, N, H, W, up2, elu, out_nchw):

@@ -813,6 +813,79 @@ size_t bts_bbox_occupancy_eval_workspace(int32_t P, int32_t B, int32_t ph, int32
 int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsBBoxOccupancyEval* a, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Novel-view frames and colour-mapped depth: what the demo scripts do around a render -- render_poses (scripts/inference_setup.py:
+ * 182-198), color_tensor (utils/plotting.py:41-46) and the per-frame lines of scripts/videos/gen_vid_nvs.py:102-120,
+ * gen_vid_transition.py:111-171 and gen_vid_seq.py:108-137 -- ending in uint8 panels of a (P, Hc, Wc, 3) canvas on the device.
+ * Additive to ABI 9: every struct and entry point above is unchanged.  Nothing synchronises, nothing is allocated; the only
+ * reductions are minima and maxima (two stages, no atomics), so a rerun is bit-identical.
+ *
+ * The colour map is the CALLER's table, as matplotlib holds it (Colormap._lut after _init()): N + 3 rows of three channels, rows N,
+ * N + 1, N + 2 the under, over and bad colours.  The float64 output takes the float64 table, the uint8 outputs take
+ * (lut * 255).astype(uint8), formed once on the host.  Index of a value x, in fp32 as numpy evaluates it on a float32 array:
+ *   t = x * N;  t == N -> N - 1;  t < 0 -> under;  t >= N -> over;  NaN -> bad;  otherwise trunc(t).
+ * Bytes: uint8(trunc((double)c * 255.0)), saturated to [0, 255], NaN -> 0.  A panel is written at (row0, col0) of its pose's
+ * canvas; the caller zero-fills the canvas and keeps every panel inside it (checked: BTS_E_INVALID otherwise).
+ * Quirks of the reference that are reproduced ON PURPOSE:
+ *   - color_tensor's norm is (x - min) / (max - min) in fp32 with the image's own extrema: a constant image is 0 / 0 = NaN and takes
+ *     the bad colour, and one NaN makes the whole image bad (torch's min() / max() propagate it);
+ *   - x = 1 exactly folds to the last colour, nextafter(1, 2) is already "over" (matplotlib's xa == N test after the fp32 product);
+ *   - the invalid mask is sum_k invalid * weights > 0.8 with the threshold as fp32 (a comparison on a float32 tensor, :192), the sum
+ *     being the render epilogue's invalid_wsum;
+ *   - black_invalid gives an invalid pixel the frame's maximum depth, taken over ALL pixels before any assignment (depth.max(), :195),
+ *     so a maximum that sits on an invalid pixel is kept, and the colour 0;
+ *   - the depth panel is ((1 / depth - 1 / d_max) / (1 / d_min - 1 / d_max)).clamp(0, 1): 1 / d_max and the denominator are Python
+ *     doubles rounded ONCE to fp32 (norm_range holds the two), the per-pixel operations are fp32 with IEEE division;
+ *   - the image panel is converted through double ((frame * 255).astype(uint8) on the float64 concatenation of gen_vid_nvs.py:110-120).
+ * Outside the contract: NaN in the rendered depth with black_invalid (torch's max() would propagate it: so does this), values outside
+ * [0, 1] in an image panel (saturated here, unspecified in numpy).
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_FRAMES_PARTIALS 64      /* per image: work-groups of the min / max pre-pass; scratch is (images, 64, 3) floats */
+#define BTS_CMAP_MAX_N 65536
+
+/* color_tensor.  x (B, h, w) fp32; norm != 0: per-image min / max first (minmax_scratch (B, 64, 3) floats, contents need no
+ * initialisation; may be NULL without norm).  Outputs, at least one: out (B, h * w, 3) float64 from lut_f64 (N + 3, 3), and / or the
+ * bytes of lut_u8 (N + 3, 3) into canvas (B, Hc, Wc, 3) at (row0, col0). */
+int bts_colorize(const float* x, int32_t B, int32_t h, int32_t w, int32_t norm, int32_t N, const double* lut_f64, const uint8_t* lut_u8,
+                 float* minmax_scratch, double* out, uint8_t* canvas, int32_t Hc, int32_t Wc, int32_t row0, int32_t col0, void* stream);
+
+/* A float image as bytes of x * scale + shift (fp32: multiply, then add; the input panel's images * .5 + .5) into canvas (B, Hc, Wc, 3)
+ * at (row0, col0).  x is read through element strides (image, row, column, channel), three channels. */
+int bts_pack_u8(const float* x, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int32_t B, int32_t h, int32_t w, float scale, float shift,
+                uint8_t* canvas, int32_t Hc, int32_t Wc, int32_t row0, int32_t col0, void* stream);
+
+/* One chunk of P novel poses at one (h, w), from ONE call: the rays of every pose (bts_gen_rays' ray_of_pixel with the near / far
+ * planes per pose), bts_render_fwd with sample_coarse inside from `jitter` and the epilogue's invalid_wsum (weights, alphas, invalid
+ * and rgb_samps are neither written nor requested), the per-frame maximum depth (black_invalid only) and the finish kernel.
+ * Four launches, three without black_invalid.  finish_only != 0 skips rays and render: rgb, depth and invalid_wsum are then the caller's
+ * inputs and cfg / t may be NULL.
+ * Requires cfg->n == 1 and cfg->nv == 1 (the scripts' ids_encoder=[0], ids_render=[0]), sampled colours (this is bts_render_fwd's
+ * field) and the projected feature map: BTS_E_UNSUPPORTED with a message otherwise. */
+typedef struct {
+  int32_t P, h, w, K;              /* poses of the chunk, render size, samples per ray */
+  int32_t lindisp, hard_alpha_cap, norm_dir, black_invalid;
+  int32_t write_masked;            /* black_invalid: also write the masked values back into rgb / depth (render_poses' return values) */
+  int32_t finish_only;
+  int32_t lut_N, reserved_;
+  const float* poses_c2w;          /* (P, 4, 4) */
+  const float* Ks;                 /* (P, 3, 3) normalised intrinsics */
+  const float* near_far;           /* (P, 2) */
+  const float* norm_range;         /* (P, 2): (float)(1 / d_max), (float)(1 / d_min - 1 / d_max), evaluated in double; NULL without depth panel */
+  const float* jitter;             /* (P * h * w, K) of U[0, 1) */
+  float* rays;                     /* scratch (P * h * w, 8) */
+  float* invalid_wsum;             /* scratch (P * h * w) */
+  float* frame_max;                /* scratch (P, 64, 3); may be NULL without black_invalid */
+  float* rgb;                      /* out (P, h, w, 3) */
+  float* depth;                    /* out (P, h, w) ray distance */
+  const uint8_t* lut_u8;           /* (lut_N + 3, 3); NULL without depth panel */
+  uint8_t* canvas;                 /* (P, Hc, Wc, 3) or NULL (no panels) */
+  int32_t Hc, Wc;
+  int32_t img_row0, img_col0;      /* image panel; a negative row0 = panel off */
+  int32_t depth_row0, depth_col0;  /* depth panel; a negative row0 = panel off */
+} BtsNovelViews;
+int bts_novel_views(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsNovelViews* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,8 @@ class BtsEvalFrame(C.Structure):
     # NOT a field of the C struct (ABI 9 pins its layout): the (n, v, 3, H, W) output tensor of bts_eval_frame_gt's `rgb_gt` argument, carried
     # on the host object so that native.eval_frame(fr, stream) keeps its two-argument form for whoever wraps it
     rgb_gt = None
+    # likewise: the 256-word int32 device tensor of bts_eval_frame_sched's `sched` argument (None: the render's fixed ray lists alone)
+    sched = None
 
 
 class BtsConv3x3(C.Structure):
@@ -177,6 +179,8 @@ SYMBOLS = {
     "bts_train_step_bwd": (C.c_int, [C.POINTER(BtsTrainStep), _P, _P]),
     "bts_eval_frame": (C.c_int, [C.POINTER(BtsEvalFrame), _P]),
     "bts_eval_frame_gt": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P]),
+    "bts_eval_frame_sched": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P, _P]),
+    "bts_render_dyn_first": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "bts_conv3x3_fwd": (C.c_int, [C.POINTER(BtsConv3x3), _P]),
     "bts_conv3x3_bwd_workspace": (C.c_size_t, [C.POINTER(BtsConv3x3)]),
     "bts_conv3x3_bwd": (C.c_int, [C.POINTER(BtsConv3x3), _P, _P, C.c_size_t, _P, _P, _P, _P]),

@@ -427,6 +427,7 @@ struct EvalHandoverParams {
   float4* imgs;
   float4* rays;
   float* rgb_gt;     // NULL: not wanted
+  unsigned* sched;   // NULL, or the 256 words of the render's ticket counters (bts_eval_frame_sched): zeroed here, in front of the render
   CamIds cam;
   FrameIds frames;
   int n, v, H, W, norm_dir, gt_vec;
@@ -437,6 +438,7 @@ struct EvalHandoverParams {
 __global__ __launch_bounds__(256) void eval_handover_kernel(const EvalHandoverParams p) {
   int b = blockIdx.x;
   if (b < p.b_cam) {
+    if (b == 0 && p.sched) p.sched[threadIdx.x] = 0u;   // 256 threads, 256 words
     camera_prep_body(p.Ks, p.poses, p.n, p.cam, p.cams, b * 256 + threadIdx.x);
     return;
   }
@@ -479,8 +481,9 @@ __global__ __launch_bounds__(256) void eval_handover_kernel(const EvalHandoverPa
 
 int eval_handover_launch(const float* Ks, const float* poses, const float* images, int n, int v, int id_enc, int nv, const int* ids_render, int H, int W,
                          float z_near, float z_far, int norm_dir, float scale, float shift, float* cams, float* inv_K, float* imgs, float* rays,
-                         float* rgb_gt, hipStream_t s) {
+                         float* rgb_gt, unsigned* sched, hipStream_t s) {
   EvalHandoverParams p;
+  p.sched = sched;
   p.Ks = Ks, p.poses = poses, p.images = images, p.cams = cams, p.inv_K = inv_K, p.rgb_gt = rgb_gt;
   p.imgs = reinterpret_cast<float4*>(imgs), p.rays = reinterpret_cast<float4*>(rays);
   p.cam.nv = nv, p.cam.v = v, p.cam.id_enc = id_enc, p.frames.nv = nv, p.frames.v = v;

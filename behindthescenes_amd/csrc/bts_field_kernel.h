@@ -63,8 +63,13 @@ struct FwdParams {
   float* invalid_wsum; // (n*Bp, nv) sum_k w_k invalid_k,v } per-ray reductions for the loss' invalid-ray policies (pipelined
   float* invalid_any;  // (n*Bp, nv) max_k invalid_k,v     } kernel only)
   const float* sigma_noise;  // (n*Bp, K) or null: added to the density before relu / alpha (nerf.py:279-280)
-  // query
-  const float* xyz;
+  // query -- or, in a render launch (which has no points), the ticket counter of its claimed tail.  One slot for both: FwdParams keeps
+  // its size and every offset, so the parameter blocks that embed it and all their kernels are what they were.
+  union {
+    const float* xyz;
+    unsigned* sched;  // render: null = every group is on a wave's static list; else sched[32 x] counts XCD x's tickets for the groups
+                      // [dyn_first, groups) (256 words, a cache line per counter, zero at launch: bts_eval_frame_sched)
+  };
   float* q_sigma;
   int only_density;
   int tiles_per_sample;
@@ -73,6 +78,7 @@ struct FwdParams {
   int ablate;    // probe builds only (-DBTS_PROBE): bit mask of kernel sections to skip (tools/section_probe.py)
   int lpr;       // lanes per ray: 8, 16, 32 or 64 (>= min(K, 64)); 64 / lpr rays share one wave iteration
   int chunk_log2;  // pipelined kernel: ray groups per chunk of the XCD interleave (log2), see render_kernel_p
+  int dyn_first;   // pipelined kernel with `sched`: first group of the claimed tail (render_dyn_first), a multiple of 8 << chunk_log2
   long groups;   // number of ray groups (= n * Bp * lpr / 64)
 };
 

@@ -23,6 +23,7 @@ bool shape_supported(int C, int HD, int NB) {
 template int launch_field<true, false>(const FwdParams&, int, int, int, int, hipStream_t);
 template int launch_render<false>(const FwdParams&, int, int, int, int, hipStream_t);
 int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s);
+int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s);
 
 FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t) {
   FwdParams p;
@@ -88,7 +89,24 @@ int render_chunk_log2(int grid, long groups) {
   return l;
 }
 
-int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s) {
+// The claimed tail of a launch with a ticket counter (FwdParams::sched): the first group that is NOT on a wave's static list.  The last
+// 1 / kDynTailDiv of the groups are claimed, rounded so that the static part is whole chunks on every XCD (a multiple of 8 << chunk_log2).
+// No tail -- dyn_first = groups, the static walk alone -- where that leaves some wave without a group of its own in front of its
+// first ticket (the claim is drawn two groups ahead so that its round trip hides behind a ray) or where the tail would be empty.
+// kDynTailDiv: profiles/r15a/fraction.txt.
+constexpr int kDynTailDiv = 8;
+long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div) {
+  if (tail_div <= 0) tail_div = kDynTailDiv;
+  const long unit = 8L << chunk_log2;
+  const long waves = (long)grid * 4;
+  const long first = (groups - groups / tail_div) / unit * unit;
+  if (first >= groups || first < waves) return groups;
+  return first;
+}
+
+int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s) { return render_fwd_sched_impl(cfg, t, a, nullptr, s); }
+
+int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s) {
   FwdParams p = make_params(cfg, t);
   p.rays = a->rays, p.z_samp = a->z_samp;
   p.jitter = a->z_samp ? nullptr : a->jitter, p.z_out = a->z_samp ? nullptr : a->z_samp_out, p.lindisp = a->lindisp;
@@ -110,6 +128,15 @@ int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsR
   }
   const int grid = render_grid(p);
   p.chunk_log2 = render_chunk_log2(grid, p.groups);
+  p.dyn_first = (int)p.groups;
+  if (sched && p.proj && p.lpr == 64) {
+    int div = 0;
+#ifdef BTS_PROBE   // tail fraction 1 / BTS_DYN_TAIL_DIV instead of the constant (profiles/r15a/fraction.txt)
+    if (const char* e = getenv("BTS_DYN_TAIL_DIV")) div = atoi(e);
+#endif
+    p.dyn_first = (int)render_dyn_first(grid, p.chunk_log2, p.groups, div);
+    if (p.dyn_first < p.groups) p.sched = sched;
+  }
   if (p.proj) return launch_render_pipelined(p, cfg->C, cfg->d_hidden, cfg->n_blocks, grid, s);
   if (p.invalid_wsum || p.invalid_any) {
     set_error("%s: invalid_wsum / invalid_any need the projected feature map (proj_nhwc)", "bts_render_fwd");

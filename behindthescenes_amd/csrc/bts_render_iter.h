@@ -39,7 +39,7 @@
       if (from_jitter) z_pre = ih.jitter[row + kk];
       else z_pre = ih.z_samp[row + kk], zn_pre = ih.z_samp[row + min(kk + 1, K - 1)];
     };
-    const int g_next = group_of(idx + waves_per_xcd);
+    const int g_next = DYN ? g_nx : group_of(idx + waves_per_xcd);   // (DYN: the successor may be a claimed group, see `next_group`)
     if (!pk48 && g_next >= 0) prefetch_z(g_next, 0);
     if constexpr (ONE_RAY) {
       if (g_next >= 0) nrec = ih.rays[(long)g_next * 8 + (lane & 7)];

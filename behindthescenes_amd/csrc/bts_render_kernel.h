@@ -717,7 +717,9 @@ using IterHead = IterHeadT<false>;
 
 // EPI: also reduce weights * invalid and max invalid over each ray's samples (BtsRenderArgs.invalid_wsum / invalid_any).  A template
 // parameter, not a run-time test: the evaluation instantiations carry no trace of it (16 more spilled SGPRs otherwise).
-template <int C, int HD, int NB, int NVMAX, bool ONE_RAY, bool F16, bool EPI = false>
+// DYN: the groups behind FwdParams::dyn_first are not on the waves' lists, they are claimed from the counter FwdParams::sched (below:
+// "Work distribution").  Built for the evaluation frame's kernels only; every other instantiation carries no trace of it.
+template <int C, int HD, int NB, int NVMAX, bool ONE_RAY, bool F16, bool EPI = false, bool DYN = false>
 __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParams p) {
   static_assert(F16, "lin_in runs on the f16 matrix pipe in split precision: the fp32-input-MFMA form of rounds 1 - 2 is gone (git history)");
   using L = Lds<C, HD, NB, true>;
@@ -796,12 +798,55 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   unsigned long long t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long t_last = __builtin_readcyclecounter();
   const unsigned long long t_begin = t_last;
+  // where the wave runs (tools/section_probe.py --lifetimes: per-XCD and per-CU lifetimes): XCC_ID << 32 | HW_ID
+  unsigned hw_id = 0, xcc_id = 0;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc_id));
 #endif
   const int groups_per_sample = Bp / R;   // Bp % R == 0 (render_geometry)
   int sample_end = groups_per_sample;
   int sample = 0;
   int idx = lw;
   int g = group_of(idx);
+  // DYN: a static part and a claimed tail.  Groups [0, dyn_first) -- whole chunks on every XCD, positions [0, dyn_first / 8) of its
+  // chunk list -- are walked as above; when a wave's list runs out it takes tickets from its XCD's counter sched[32 * xcd]: ticket t is
+  // position dyn_first / 8 + t of the XCD's chunk list, a position past the list's end ends the wave.  (A persistent launch lasts as
+  // long as its slowest wave, and on equal lists the two waves of a SIMD finish a fifth of the launch apart: profiles/r15a.)  One
+  // counter per XCD, each on a cache line of its own, not one for the chip: 2 048 waves' claims on ONE line serialise at 11.5 ns each
+  // (profiles/r05n), three times the 3.5 ns in which the chip finishes a ray -- measured, a chip-wide counter, and eight counters in
+  // one line alike, made the launch 10 - 30 % longer (profiles/r15a/fraction.txt) -- and the imbalance is inside every CU, the XCDs'
+  // sums are equal to half a percent; the tail keeps the static part's locality in L2.
+  // The iteration prefetches its successor's ray record and jitter row, so the group of iteration i + 1 has to be known at the top
+  // of iteration i: its ticket is drawn at the top of iteration i - 1 (`pend`, one lane's atomicAdd, the one VGPR this costs across
+  // the back-edge) and read a whole iteration later, where the prefetched record is waited for anyway.
+  // g_nx is the successor of g; both loops advance through `next_group`, and an iteration that leaves its loop for the other one does
+  // not advance: g, g_nx and the pending ticket stay what they are, nothing is claimed twice and nothing is dropped.
+  int g_nx = -1;
+  unsigned pend = 0u;
+  // (dyn_first and the counters are read from the kernarg segment where they are used, like the iteration's parameters: kernarg_view)
+  auto n_static = [&]() -> int { return kernarg_view<FwdParams>()->dyn_first >> 3; };   // the static part in positions of an XCD's chunk list
+  auto claim = [&]() -> unsigned {
+    unsigned t = 0u;
+    if (lane == 0) t = atomicAdd(kernarg_view<FwdParams>()->sched + 32 * xcd, 1u);
+    return t;
+  };
+  auto claimed_group = [&](unsigned ticket) -> int { return group_of(n_static() + (int)__builtin_amdgcn_readfirstlane(ticket)); };
+  // the successor of the group an iteration has just finished (the loops' latch; idx is that successor's position already)
+  auto next_group = [&]() -> int {
+    const int gn = g_nx;
+    if (gn >= 0) {
+      const int ns = n_static();
+      g_nx = idx + waves_per_xcd < ns ? group_of(idx + waves_per_xcd) : claimed_group(pend);
+      if (g_nx >= 0 && idx + 2 * waves_per_xcd >= ns) pend = claim();
+    }
+    return gn;
+  };
+  if constexpr (DYN) {
+    const int ns = n_static();
+    g = idx < ns ? group_of(idx) : claimed_group(claim());
+    if (g >= 0) g_nx = idx + waves_per_xcd < ns ? group_of(idx + waves_per_xcd) : claimed_group(claim());
+    if (g_nx >= 0 && idx + 2 * waves_per_xcd >= ns) pend = claim();
+  }
   // z of the first ray group -- or, without z_samp, its jitter u: sample_coarse then runs at the top of the iteration (coarse_depth)
   float z_pre = 0.0f, zn_pre = 0.0f;
   if (g >= 0) {
@@ -839,18 +884,18 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
     bool shared_loop = p.K <= 64;
     while (g >= 0) {
       if (shared_loop) {
-        for (; g >= 0; idx += waves_per_xcd, g = group_of(idx))
+        for (; g >= 0; idx += waves_per_xcd, g = DYN ? next_group() : group_of(idx))
 #define BTS_ITER_SHARED true
 #include "bts_render_iter.h"
       } else {
-        for (; g >= 0; idx += waves_per_xcd, g = group_of(idx))
+        for (; g >= 0; idx += waves_per_xcd, g = DYN ? next_group() : group_of(idx))
 #define BTS_ITER_SHARED false
 #include "bts_render_iter.h"
       }
       shared_loop = !shared_loop;
     }
   } else {
-    for (; g >= 0; idx += waves_per_xcd, g = group_of(idx))
+    for (; g >= 0; idx += waves_per_xcd, g = DYN ? next_group() : group_of(idx))
 #define BTS_ITER_SHARED false
 #include "bts_render_iter.h"
   }
@@ -860,11 +905,21 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
 #pragma unroll
     for (int i = 0; i < 6; ++i) d[i] = t_acc[i];
     d[6] = __builtin_readcyclecounter() - t_begin;
+    d[7] = ((unsigned long long)xcc_id << 32) | hw_id;
   }
 #endif
 }
 
 #ifndef BTS_NO_LAUNCH_GLUE
+static inline int launch_render_p_check() {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("%s: kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
+    return BTS_E_LAUNCH;
+  }
+  return BTS_OK;
+}
+
 template <int C, int HD, int NB, int NVMAX, bool EPI>
 static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
 #ifdef BTS_GATHER_LDS
@@ -873,18 +928,20 @@ static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
     kern<<<grid, 256, dyn, s>>>(p);
   };
+  // the claimed tail (FwdParams::sched): the evaluation frame's one-ray kernels with two loops only
+  if constexpr (!EPI && NB == 0 && NVMAX <= 2) {
+    if (p.lpr == 64 && p.sched && p.dyn_first < p.groups) {
+      go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true>);
+      return launch_render_p_check();
+    }
+  }
   if (p.lpr == 64) go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI>);
   else go(render_kernel_p<C, HD, NB, NVMAX, false, true, EPI>);
 #else
   if (p.lpr == 64) render_kernel_p<C, HD, NB, NVMAX, true, true, EPI><<<grid, 256, 0, s>>>(p);
   else render_kernel_p<C, HD, NB, NVMAX, false, true, EPI><<<grid, 256, 0, s>>>(p);
 #endif
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
+  return launch_render_p_check();
 }
 
 template <int C, int HD, int NB, bool EPI>

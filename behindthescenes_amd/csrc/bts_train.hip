@@ -410,18 +410,22 @@ int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t
 
 int eval_handover_launch(const float* Ks, const float* poses, const float* images, int n, int v, int id_enc, int nv, const int* ids_render, int H, int W,
                          float z_near, float z_far, int norm_dir, float scale, float shift, float* cams, float* inv_K, float* imgs, float* rays,
-                         float* rgb_gt, hipStream_t s);
+                         float* rgb_gt, unsigned* sched, hipStream_t s);
+int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s);   // bts_fwd.hip
+int render_chunk_log2(int grid, long groups);
+long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div);
 int distance_to_z_launch(const float* depths, const float* invK, int N, int H, int W, float* out, hipStream_t s);
 int project_features_plain(int C, int HD, const float* feat, const float* mlp, int N, int HW, float* proj, hipStream_t s, bool channels_last) {
   return project_features_impl(C, HD, feat, mlp, N, HW, proj, nullptr, s, channels_last);
 }
 
-int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, hipStream_t stream) {
+int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipStream_t stream) {
   const BtsFieldCfg& c = f->cfg;
   const int n = c.n, nv = c.nv;
-  // cameras, inverse intrinsics (for distance_to_z behind the render), rgb0 packing, rays and rgb_gt: one launch
+  // cameras, inverse intrinsics (for distance_to_z behind the render), rgb0 packing, rays and rgb_gt: one launch (it also zeroes `sched`,
+  // the render's ticket counter)
   int rc = eval_handover_launch(f->Ks, f->poses_c2w, f->images, n, f->v, f->id_encoder, nv, f->ids_render, c.H, c.W, f->z_near, f->z_far, f->norm_dir,
-                                f->img_scale, f->img_shift, f->cams, f->depth_z ? f->inv_K : nullptr, f->imgs_nhwc4, f->rays, rgb_gt, stream);
+                                f->img_scale, f->img_shift, f->cams, f->depth_z ? f->inv_K : nullptr, f->imgs_nhwc4, f->rays, rgb_gt, sched, stream);
   if (!rc) rc = project_features_plain(c.C, c.d_hidden, f->feat_nchw, f->mlp_params, n, c.H * c.W, f->proj_nhwc, stream, f->feat_channels_last != 0);
   if (rc) {
     set_error("%s: a hand-over kernel launch failed", "bts_eval_frame");
@@ -441,7 +445,7 @@ int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, hipStream_t stream) {
   memset(&a, 0, sizeof(a));
   a.rays_per_sample = f->v * c.H * c.W, a.K = f->K, a.hard_alpha_cap = f->hard_alpha_cap, a.rays = f->rays, a.jitter = f->jitter, a.lindisp = f->lindisp;
   a.rgb = f->rgb, a.depth = f->depth, a.weights = f->weights, a.alphas = f->alphas, a.invalid = f->invalid;
-  rc = render_fwd_impl(&cfg, &t, &a, stream);
+  rc = render_fwd_sched_impl(&cfg, &t, &a, sched, stream);
   if (rc) return rc;
   if (f->depth_z) {
     rc = distance_to_z_launch(f->depth, f->inv_K, n * f->v, c.H, c.W, f->depth_z, stream);
@@ -459,7 +463,7 @@ using namespace bts;
 
 extern "C" {
 
-int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream) {
+int bts_eval_frame_sched(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, void* stream) {
   if (!f) {
     set_error("%s: NULL frame", "bts_eval_frame");
     return BTS_E_INVALID;
@@ -488,10 +492,19 @@ int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream) {
     set_error("%s: too many rays in one call (%ld)", "bts_eval_frame", (long)c.n * f->v * c.H * c.W);
     return BTS_E_UNSUPPORTED;
   }
-  return eval_frame_impl(f, rgb_gt, (hipStream_t)stream);
+  return eval_frame_impl(f, rgb_gt, sched, (hipStream_t)stream);
 }
 
-int bts_eval_frame(const BtsEvalFrame* f, void* stream) { return bts_eval_frame_gt(f, nullptr, stream); }
+int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream) { return bts_eval_frame_sched(f, rgb_gt, nullptr, stream); }
+int bts_eval_frame(const BtsEvalFrame* f, void* stream) { return bts_eval_frame_sched(f, nullptr, nullptr, stream); }
+
+// the host's split of a render launch into static lists and a claimed tail, for tests: grid work-groups, `groups` ray groups -> the
+// first claimed group (= groups: no tail); *chunk_log2 (may be NULL) receives the chunk size the split is aligned to
+int64_t bts_render_dyn_first(int32_t grid, int64_t groups, int32_t* chunk_log2) {
+  const int l = render_chunk_log2(grid, groups);
+  if (chunk_log2) *chunk_log2 = l;
+  return render_dyn_first(grid, l, groups, 0);
+}
 
 int bts_train_step_fwd(const BtsTrainStep* st, void* stream) {
   if (int rc = check_step(st, "bts_train_step_fwd", false)) return rc;

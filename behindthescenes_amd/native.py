@@ -842,14 +842,22 @@ class Conv3x3Function(torch.autograd.Function):
 def eval_frame(fr, stream, rgb_gt=None):
     """bts_eval_frame on a filled ``_lib.BtsEvalFrame`` (behindthescenes_amd.train_step.FusedEvalFrame builds it).  With ``rgb_gt`` -- a
     contiguous float32 (n, v, 3, H, W) tensor, given here or set as ``fr.rgb_gt`` -- bts_eval_frame_gt: the hand-over launch also writes
-    ``images * img_scale + img_shift`` into it."""
+    ``images * img_scale + img_shift`` into it.  With ``fr.sched`` -- 256 int32 words on the device, the frame's own while it runs --
+    bts_eval_frame_sched: the render's waves claim the last part of the rays from its counters instead of walking fixed lists to the end."""
     if rgb_gt is None:
         rgb_gt = fr.rgb_gt
+    sched = getattr(fr, "sched", None)
+    if rgb_gt is not None:
+        c = fr.cfg
+        _req(rgb_gt, "rgb_gt", (c.n, fr.v, 3, c.H, c.W))
+    if sched is not None:
+        if not sched.is_cuda or sched.dtype != torch.int32 or sched.numel() < 256 or not sched.is_contiguous():
+            raise BtsNativeError("sched: 256 contiguous int32 words on the device expected")
+        _lib.check(_lib.load().bts_eval_frame_sched(C.byref(fr), None if rgb_gt is None else _ptr(rgb_gt), C.c_void_p(sched.data_ptr()), stream), "bts_eval_frame_sched")
+        return
     if rgb_gt is None:
         _lib.check(_lib.load().bts_eval_frame(C.byref(fr), stream), "bts_eval_frame")
         return
-    c = fr.cfg
-    _req(rgb_gt, "rgb_gt", (c.n, fr.v, 3, c.H, c.W))
     _lib.check(_lib.load().bts_eval_frame_gt(C.byref(fr), _ptr(rgb_gt), stream), "bts_eval_frame_gt")
 
 

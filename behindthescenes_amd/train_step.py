@@ -426,6 +426,8 @@ class FusedEvalFrame(torch.nn.Module):
         self.wrapped, self.sampler, self.fused = wrapped, sampler, bool(fused)
         self.last_path = None
         self._scratch = {}
+        # the render launch's claimed tail (bts_eval_frame_sched; False: fixed ray lists to the end, bts_eval_frame_gt).  Same outputs.
+        self.dynamic_tail = True
 
     def why_not(self, images=None, ids_encoder=(0,), ids_render=(0,)):
         from .ray_sampler import ImageRaySampler
@@ -500,7 +502,8 @@ class FusedEvalFrame(torch.nn.Module):
         sc = self._scratch.get(key)
         if sc is None:
             sc = self._scratch[key] = dict(cams=torch.empty(n * (25 + nv * 25), **f32), imgs=torch.empty((n, max(nv, 1), H, W, 4), **f32),
-                                           proj=torch.empty((n, H, W, spec.d_hidden), **f32), inv_K=torch.empty((n, v, 3, 3), **f32))
+                                           proj=torch.empty((n, H, W, spec.d_hidden), **f32), inv_K=torch.empty((n, v, 3, 3), **f32),
+                                           sched=torch.zeros(256, device=dev, dtype=torch.int32))
         out = dict(rays=torch.empty((n, v * H * W, 8), **f32), rgb=torch.empty((n, v, H, W, nv, 3), **f32), depth=torch.empty((n, v, H, W), **f32),
                    depth_z=torch.empty((n, v, H, W), **f32) if to_z else None, weights=torch.empty((n, v, H, W, K), **f32) if want_weights else None,
                    alphas=torch.empty((n, v, H, W, K), **f32) if want_alphas else None, invalid=torch.empty((n, v, H, W, K, nv), **f32),
@@ -524,6 +527,7 @@ class FusedEvalFrame(torch.nn.Module):
         for k_ in ("rays", "rgb", "depth", "depth_z", "weights", "alphas", "invalid"):
             setattr(fr, k_, dp(out[k_]))
         fr.rgb_gt = out["rgb_gt"]          # (host-side attribute, no struct field: selects bts_eval_frame_gt in native.eval_frame)
+        fr.sched = sc["sched"] if self.dynamic_tail else None      # (likewise: bts_eval_frame_sched)
         native.eval_frame(fr, native._stream(images))
         part = dict(rgb=out["rgb"], depth=out["depth_z"] if to_z else out["depth"], invalid=out["invalid"])
         if want_weights:

@@ -534,6 +534,16 @@ typedef struct BtsEvalFrame {
  * bts_eval_frame(f, stream) = bts_eval_frame_gt(f, NULL, stream). */
 int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream);
 int bts_eval_frame(const BtsEvalFrame* f, void* stream);
+/* bts_eval_frame_sched (additive to ABI 9, the struct is unchanged): the same frame with ticket counters for the render launch.  sched: 1 024
+ * bytes (256 words) of device memory owned by the caller, used by one frame at a time; the hand-over launch zeroes them.  With it the render kernel's
+ * waves walk fixed lists over the first part of the rays only and claim the rest ray by ray, from one counter per XCD (sched[32 x], x = 0 .. 7: a cache line each -- claims on one line serialise),
+ * as they run out (a persistent launch lasts as long as its slowest wave); a ray is still evaluated by exactly one wave iteration, every output is the same bits.  Frames
+ * with too few rays per wave for a tail take the fixed lists alone.  NULL: the fixed lists alone;
+ * bts_eval_frame_gt(f, rgb_gt, stream) = bts_eval_frame_sched(f, rgb_gt, NULL, stream). */
+int bts_eval_frame_sched(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, void* stream);
+/* The split that launch uses, on the host (no GPU): `grid` work-groups of four waves, `groups` rays -> the first claimed ray (= groups: no
+ * tail), a multiple of 8 << *chunk_log2 (the XCD interleave's chunk, written when chunk_log2 is not NULL). */
+int64_t bts_render_dyn_first(int32_t grid, int64_t groups, int32_t* chunk_log2);
 
 
 /* ---------------------------------------------------------------------------------------------------------------------------------

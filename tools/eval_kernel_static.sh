@@ -9,5 +9,5 @@ mkdir -p /tmp/ek && cd /tmp/ek
 S=/tmp/ek/bts_fwd_proj-hip-amdgcn-amd-amdhsa-gfx950.s
 python $REPO/tools/check_pk_opsel.py $S
 python $REPO/tools/asm_line_hist.py $S render_kernel_pILi64ELi64ELi0ELi1ELb1ELb1ELb0 loop
-awk '/^_ZN3bts15render_kernel_pILi64ELi64ELi0ELi1ELb1ELb1ELb0EEEvNS_9FwdParamsE:/{f=1} f&&/\.(sgpr_spill_count|vgpr_spill_count|vgpr_count|sgpr_count)|; (NumVgprs|NumSgprs|ScratchSize|Occupancy|SGPRSpill|VGPRSpill)/{print} /\.end_amdhsa_kernel/{if(f) exit}' $S | head
-grep -A60 "_ZN3bts15render_kernel_pILi64ELi64ELi0ELi1ELb1ELb1ELb0EEEvNS_9FwdParamsE$" $S | grep -E "sgpr_spill|vgpr_spill|\.vgpr_count|\.sgpr_count" | head
+awk '/^_ZN3bts15render_kernel_pILi64ELi64ELi0ELi1ELb1ELb1ELb0ELb0EEEvNS_9FwdParamsE:/{f=1} f&&/\.(sgpr_spill_count|vgpr_spill_count|vgpr_count|sgpr_count)|; (NumVgprs|NumSgprs|ScratchSize|Occupancy|SGPRSpill|VGPRSpill)/{print} /\.end_amdhsa_kernel/{if(f) exit}' $S | head
+grep -A60 "_ZN3bts15render_kernel_pILi64ELi64ELi0ELi1ELb1ELb1ELb0ELb0EEEvNS_9FwdParamsE$" $S | grep -E "sgpr_spill|vgpr_spill|\.vgpr_count|\.sgpr_count" | head

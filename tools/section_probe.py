@@ -4,7 +4,10 @@ Sections (s_memtime deltas accumulated per wave, averaged over waves, per ray it
  0 geometry (ray/camera loads, projection, taps, colour issue, tile broadcast)   1 gather + encoding + MFMA
  2 lin_out + softplus   3 colour blend + compositing scan   4 per-sample stores   5 per-ray sums + stores
 Ablations (BTS_ABLATE bits, probe build only): 1 no gather (register-gather build), 2 no trigonometry, 4 no MFMAs, 64 every ray takes
-the render kernel's shared-texel loop (one fetch of G per ray; wrong rows for view 1 -- what a single fetch would buy there)."""
+the render kernel's shared-texel loop (one fetch of G per ray; wrong rows for view 1 -- what a single fetch would buy there).
+    python tools/section_probe.py --lifetimes [--no-tail] [--out FILE]
+the flagship evaluation frame instead: per-wave lifetimes of its render launch over the chip, per XCD and per CU (the probe build stores
+XCC_ID and HW_ID next to the counters); --no-tail: fixed ray lists to the end; BTS_DYN_TAIL_DIV=d: a claimed tail of 1 / d of the rays."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,8 +18,80 @@ import behindthescenes_amd as bts
 from behindthescenes_amd import native
 from behindthescenes_amd import synthetic as S
 
+
+
+def lifetime_table(d, out=sys.stdout):
+    """Per-wave lifetime (d[6]) over the chip, per XCD and per CU.  d[7] = XCC_ID << 32 | HW_ID as the wave read them at kernel start
+    (HW_ID: SIMD 5:4, CU 11:8, SH 12, SE 15:13).  gap = (max - mean) / max: the share of the launch a persistent grid idles away."""
+    life, hw = d[:, 6], d[:, 7].long()
+    xcd, cu = (hw >> 32) & 15, (hw >> 8) & 255
+
+    def row(name, x):
+        return (f"{name:<14s} waves {x.numel():5d}  mean {x.mean():10.0f}  min {x.min():10.0f}  max {x.max():10.0f}  "
+                f"max/mean {x.max() / x.mean():.4f}  gap {(x.max() - x.mean()) / x.max() * 100:5.2f} %")
+    print(row("chip", life), file=out)
+    q = torch.quantile(life, torch.tensor([0.01, 0.1, 0.25, 0.5, 0.75, 0.9, 0.99], dtype=life.dtype))
+    print("   quantiles 1 10 25 50 75 90 99 %: " + " ".join(f"{v:.0f}" for v in q.tolist()), file=out)
+    for x in sorted(set(xcd.tolist())):
+        print(row(f"xcd {x}", life[xcd == x]), file=out)
+    cu_mean, cu_max = [], []
+    for x in sorted(set(xcd.tolist())):
+        for c in sorted(set(cu[xcd == x].tolist())):
+            sel = life[(xcd == x) & (cu == c)]
+            cu_mean.append(sel.mean()), cu_max.append(sel.max())
+            print(row(f"xcd {x} cu {c:3d}", sel), file=out)
+    cu_mean, cu_max = torch.stack(cu_mean), torch.stack(cu_max)
+    print(f"per-CU means: {cu_mean.numel()} CUs, min {cu_mean.min():.0f} mean {cu_mean.mean():.0f} max {cu_mean.max():.0f}; "
+          f"slowest CU's mean over the chip mean {cu_mean.max() / life.mean():.4f}; mean over CUs of (CU max / CU mean) {(cu_max / cu_mean).mean():.4f}", file=out)
+    return (life.max() - life.mean()) / life.max()
+
+
+def eval_frame_lifetimes(argv):
+    """python tools/section_probe.py --lifetimes [--no-tail] [--out FILE]: the flagship frame (bench.py's KITTI eval_depth workload through
+    FusedEvalFrame) on the probe build; per-wave lifetimes of its render launch."""
+    H, W, K, V, C, HD = 192, 640, 64, 2, 64, 64
+    dev = torch.device("cuda")
+    scene = S.synthetic_scene(1, V, H, W, C, seed=1000, intrinsics=S.K_KITTIRAW)
+    torch.manual_seed(4242)
+    net = bts.BTSNet(S.field_conf(C, HD, 0, H, W, z_near=3.0, z_far=80.0, learn_empty=True))
+    S.init_mlp_(net.mlp_coarse, seed=7)
+    S.set_feature_map(net, scene["feat"])
+    net = net.to(dev).eval()
+    wrapped = bts.NeRFRenderer.from_conf(dict(n_coarse=K, lindisp=True, hard_alpha_cap=True)).bind_parallel(net).eval().to(dev)
+    frame = bts.FusedEvalFrame(wrapped, bts.ImageRaySampler(3.0, 80.0))
+    if "--no-tail" in argv and hasattr(frame, "dynamic_tail"):
+        frame.dynamic_tail = False
+    images, projs, poses = scene["images"].to(dev), scene["projs"].to(dev), scene["poses"].to(dev)
+    dbg = torch.zeros(512 * 4 * 8, dtype=torch.int64, device=dev)
+    os.environ["BTS_DBG_PTR"] = str(dbg.data_ptr())
+    os.environ["BTS_ABLATE"] = "128"
+    torch.manual_seed(4242)
+    for _ in range(30):   # the device's steady state (bench.py: SETTLE_FRAMES)
+        frame(images, projs, poses, ids_encoder=[0], ids_render=[0])
+    out = open(argv[argv.index("--out") + 1], "w") if "--out" in argv else sys.stdout
+    gaps = []
+    for rep in range(3):
+        dbg.zero_()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        frame(images, projs, poses, ids_encoder=[0], ids_render=[0])
+        e1.record()
+        torch.cuda.synchronize()
+        assert frame.last_path == "fused", frame.last_path
+        d = dbg.view(-1, 8).double().cpu()
+        d = d[d[:, 6] > 0]
+        print(f"--- frame {rep}: {e0.elapsed_time(e1):.3f} ms (probe build, counters on), {V * H * W / d.shape[0]:.1f} rays per wave, "
+              f"one ray = {d[:, 6].mean() * d.shape[0] / (V * H * W):.0f} ticks of wave time", file=out)
+        gaps.append(float(lifetime_table(d, out)))
+    print("gap (max - mean) / max per frame: " + " ".join(f"{100 * g:.2f} %" for g in gaps), file=out)
+
+
+if "--lifetimes" in sys.argv:
+    eval_frame_lifetimes(sys.argv)
+    sys.exit(0)
+
 H, W, K, V = 192, 640, 64, 2
-scene = S.synthetic_scene(1, V, H, W, 64, seed=1, intrinsics=S.K_KITTIRAW)
+scene =S.synthetic_scene(1, V, H, W, 64, seed=1, intrinsics=S.K_KITTIRAW)
 net = S.build_net(scene, 64, 0, [0])
 ft = net.native_field()
 params = net.mlp_coarse.packed().detach()

@@ -1,87 +1,9 @@
 // extern "C" entry points of libbts_render.so (declared in include/bts_render.h): argument validation and launch
 // geometry only -- no allocation, no synchronisation, no exceptions.
-#include "bts_common.h"
+#include "bts_host.h"
 
 #include <cstdio>
 #include <cstring>
-
-namespace bts {
-struct FwdParams;
-void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
-const char* last_error();
-bool shape_supported(int C, int HD, int NB);
-
-int transpose_launch(const float* src, float* dst, int N, int C, int H, int W, bool to_nhwc, hipStream_t s);
-int pack_rgb_launch(const float* src, float* dst, int N, int H, int W, float scale, float shift, hipStream_t s);
-int patch_rays_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
-                      int c, int H, int W, int P, int ph, int pw, float zn, float zf, int norm_dir, float* rays, float* gt, hipStream_t s);
-int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s);
-// the same loss for patches of any size (bts_loss_tiled.hip)
-size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv);
-int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s);
-int gen_rays_launch(const float* poses, const float* projs, int V, int H, int W, float zn, float zf, int norm_dir, float* rays,
-                    hipStream_t s);
-int sample_coarse_launch(const float* rays, const float* u, long B, int K, int lindisp, float* z, hipStream_t s);
-int distance_to_z_launch(const float* depths, const float* invK, int N, int H, int W, float* out, hipStream_t s);
-int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_t s);
-
-int project_features_impl(int C, int HD, const float* feat, const float* mlp, int N, int HW, float* proj, const unsigned char* tiles, hipStream_t s,
-                          bool feat_cl = false, int Wm = 0,     // Wm: the map's width when `tiles` are 16 x 4 blocks (BtsFieldCfg.tile_blocks), 0 = runs of 64 texels
-                          void* list_ws = nullptr, size_t list_ws_bytes = 0);   // scratch for the balanced (list-driven) form
-int mark_tiles_impl(const float* rays, const float* z_samp, const float* jitter, const float* w2c_enc, const float* K_enc, long B, int Bp, int K, int lindisp,
-                    int H, int W, int fs, unsigned char* tiles, hipStream_t s, int blocks);
-int project_features_bwd_tiles_impl(int C, int HD, const float* feat, float* dproj, unsigned char* tiles, const float* mlp, int N, int HW, float* dfeat,
-                                    float* d_mlp, int clear, hipStream_t s, bool feat_cl = false, int Wm = 0, void* list_ws = nullptr,
-                                    size_t list_ws_bytes = 0);   // list_ws: scratch for the balanced (list-driven) form, project_bwd_list_bytes(N * tiles) bytes
-int project_features_bwd_impl(int C, int HD, const float* feat, const float* dproj, const float* mlp, int N, int HW, float* dfeat,
-                              float* d_mlp, hipStream_t s);
-int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
-int field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
-                     float* invalid, float* sigma, hipStream_t s);
-int occupancy_profile_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int Y, int cols, float threshold,
-                           int only_density, float* profile, float* sigma, hipStream_t s);
-size_t render_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
-int render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* ws,
-                    size_t ws_bytes, hipStream_t s, bool flush_clean = false);
-// MLP-predicted colour (bts_mlp_color.hip)
-int mlp_color_render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
-int mlp_color_field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
-                               float* invalid, float* sigma, hipStream_t s);
-size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
-int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
-                              hipStream_t s);
-// LiDAR occupancy evaluation (bts_occ.hip)
-size_t lidar_bins_bytes(int T, int y_res);
-int lidar_slices_launch(const float* points, const int* offsets, int T, const float* velo_poses, const float* borders, float y_lo, float y_hi,
-                        int y_res, float max_dist, void* bins_ws, float* tables, hipStream_t s);
-int lidar_occupancy_launch(const float* q_pts, int P, const float* tables, int y_res, int T, const float* world_to_velo, float min_dist,
-                           unsigned char* is_occupied, unsigned char* is_visible, hipStream_t s);
-int occ_metrics_launch(const float* q_pts, int P, const float* sigma, const unsigned char* is_occupied, const unsigned char* is_visible,
-                       const float* depth_z, int H, int W, const float* proj, const float* w2c, float occ_threshold, int* counts,
-                       unsigned char* masks, hipStream_t s);
-// depth evaluation metrics (bts_depth_metrics.hip)
-size_t depth_metrics_bytes(int B, int Hg, int Wg);
-int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t s);
-// NVS evaluation metrics (bts_nvs_metrics.hip)
-size_t nvs_metrics_bytes(int B, int He, int We);
-int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s);
-// 3D-bounding-box occupancy evaluation (bts_bbox_occ.hip)
-int bbox_bounds_launch(const float* vertices, const int* faces, const int* v_offsets, const int* f_offsets, int B, const float* to_key,
-                       const float* proj, float max_d, float* tables, int* n_faces, unsigned char* active, int* n_active, hipStream_t s);
-int bbox_pseudo_depth_launch(const float* rays, int ph, int pw, const float* seg, int hs, int ws, const float* tables, const int* n_faces,
-                             const unsigned char* active, const float* semantic_id, int B, float* pseudo_depth, hipStream_t s);
-int bbox_metrics_launch(const float* q_pts, int P, const float* sigma, const float* pseudo, const float* depth_z, int H, int W, const float* proj,
-                        const float* tables, const int* n_faces, const unsigned char* active, int B, float occ_threshold, int* counts,
-                        unsigned char* masks, hipStream_t s);
-// novel-view frames and colour-mapped depth (bts_frames.hip; the per-pose near / far ray kernel lives in bts_aux.hip)
-int gen_rays_nf_launch(const float* poses, const float* projs, const float* near_far, int V, int H, int W, int norm_dir, float* rays,
-                       hipStream_t s);
-int colorize_launch(const float* x, int B, int h, int w, int norm, int N, const double* lut, const unsigned char* lut_u8, float* partials,
-                    double* out, unsigned char* canvas, int Hc, int Wc, int row0, int col0, hipStream_t s);
-int pack_u8_launch(const float* x, long sb, long sy, long sx, long sc, int B, int h, int w, float scale, float shift, unsigned char* canvas,
-                   int Hc, int Wc, int row0, int col0, hipStream_t s);
-int novel_view_finish_launch(const BtsNovelViews* a, hipStream_t s);
-}  // namespace bts
 
 using namespace bts;
 
@@ -138,6 +60,39 @@ static int check_cfg(const BtsFieldCfg* cfg, const BtsFieldTensors* t, bool need
   return BTS_OK;
 }
 
+// The render arguments of the forward (rays, z_samp or jitter, rgb, depth) or backward form (rays, z_samp, the forward's sigma_raw and
+// trans), then the sizes.  rest_ok: what else the entry requires under the same message; null_fmt: that message in the entry's wording.
+static const char kFwdArgsNull[] = "%s: NULL render argument (rays, z_samp or jitter, rgb and depth are required)";
+static int check_render_args(const BtsRenderArgs* a, const char* who, bool bwd, bool rest_ok, const char* null_fmt) {
+  if (!a || !rest_ok || !a->rays || (bwd ? (!a->z_samp || !a->sigma_raw || !a->trans) : ((!a->z_samp && !a->jitter) || !a->rgb || !a->depth))) {
+    set_error(null_fmt, who);
+    return BTS_E_INVALID;
+  }
+  if (a->rays_per_sample <= 0 || a->K <= 0) {
+    set_error("%s: non-positive rays_per_sample=%ld K=%ld", who, (long)a->rays_per_sample, (long)a->K);
+    return BTS_E_INVALID;
+  }
+  return BTS_OK;
+}
+
+// What the five bts_project_features* entries check before they launch: the entry's own pointers (ptrs_ok) and the sizes, the compiled
+// envelope, feat_shift.  launched(): the launch's code with the entry's message.
+static int check_projection(const BtsFieldCfg* cfg, bool ptrs_ok, int N, const char* who) {
+  if (!cfg || !ptrs_ok || N <= 0 || cfg->H <= 0 || cfg->W <= 0) {
+    set_error("%s: NULL pointer or non-positive size", who);
+    return BTS_E_INVALID;
+  }
+  if (!bts_supported(cfg)) {
+    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", who, cfg->C, cfg->d_hidden, cfg->n_blocks);
+    return BTS_E_UNSUPPORTED;
+  }
+  return check_shift(cfg, who);
+}
+static int launched(int rc, const char* who) {
+  if (rc) set_error("%s: kernel launch failed", who);
+  return rc;
+}
+
 extern "C" {
 
 int bts_abi_version(void) { return BTS_ABI_VERSION; }
@@ -154,16 +109,8 @@ int64_t bts_mlp_param_count(const BtsFieldCfg* cfg) {
 }
 
 int bts_render_fwd(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, void* stream) {
-  int rc = check_cfg(cfg, t, true);
-  if (rc) return rc;
-  if (!a || !a->rays || (!a->z_samp && !a->jitter) || !a->rgb || !a->depth) {
-    set_error("%s: NULL render argument (rays, z_samp or jitter, rgb and depth are required)", "bts_render_fwd");
-    return BTS_E_INVALID;
-  }
-  if (a->rays_per_sample <= 0 || a->K <= 0) {
-    set_error("%s: non-positive rays_per_sample=%ld K=%ld", "bts_render_fwd", a->rays_per_sample, a->K);
-    return BTS_E_INVALID;
-  }
+  if (int rc = check_cfg(cfg, t, true)) return rc;
+  if (int rc = check_render_args(a, "bts_render_fwd", false, true, kFwdArgsNull)) return rc;
   return render_fwd_impl(cfg, t, a, (hipStream_t)stream);
 }
 
@@ -174,56 +121,34 @@ size_t bts_render_bwd_workspace(const BtsFieldCfg* cfg, const BtsRenderArgs* a) 
 
 int bts_render_bwd(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g,
                    void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = check_cfg(cfg, t, true);
-  if (rc) return rc;
-  if (!a || !g || !a->rays || !a->z_samp || !a->sigma_raw || !a->trans || !t->proj_nhwc) {
-    set_error("%s: NULL argument (rays, z_samp, the forward's sigma_raw + trans and proj_nhwc are required)", "bts_render_bwd");
-    return BTS_E_INVALID;
-  }
-  if (a->rays_per_sample <= 0 || a->K <= 0) {
-    set_error("%s: non-positive rays_per_sample=%ld K=%ld", "bts_render_bwd", a->rays_per_sample, a->K);
-    return BTS_E_INVALID;
-  }
-  if (workspace_bytes < render_bwd_workspace_impl(cfg, a) || (!workspace && render_bwd_workspace_impl(cfg, a) > 0)) {
-    set_error("%s: workspace too small (%ld bytes needed)", "bts_render_bwd", (long)render_bwd_workspace_impl(cfg, a));
+  if (int rc = check_cfg(cfg, t, true)) return rc;
+  // (this entry names its gradient struct and the map in the same breath as the render arguments)
+  if (int rc = check_render_args(a, "bts_render_bwd", true, g && t->proj_nhwc,
+                                 "%s: NULL argument (rays, z_samp, the forward's sigma_raw + trans and proj_nhwc are required)"))
+    return rc;
+  const size_t need = render_bwd_workspace_impl(cfg, a);
+  if (workspace_bytes < need || (!workspace && need > 0)) {
+    set_error("%s: workspace too small (%ld bytes needed)", "bts_render_bwd", (long)need);
     return BTS_E_WORKSPACE;
   }
-  return render_bwd_impl(cfg, t, a, g, workspace, workspace_bytes, (hipStream_t)stream);
+  return render_bwd_impl(cfg, t, a, g, workspace, (hipStream_t)stream);
 }
 
 int bts_project_features(const BtsFieldCfg* cfg, const float* feat_nchw, const float* mlp_params, int32_t N, float* proj_nhwc,
                          void* stream) {
-  if (!cfg || !feat_nchw || !mlp_params || !proj_nhwc || N <= 0 || cfg->H <= 0 || cfg->W <= 0) {
-    set_error("%s: NULL pointer or non-positive size", "bts_project_features");
-    return BTS_E_INVALID;
-  }
-  if (!bts_supported(cfg)) {
-    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", "bts_project_features", cfg->C,
-              cfg->d_hidden, cfg->n_blocks);
-    return BTS_E_UNSUPPORTED;
-  }
-  if (int rc = check_shift(cfg, "bts_project_features")) return rc;
-  int rc = project_features_impl(cfg->C, cfg->d_hidden, feat_nchw, mlp_params, N, (int)feat_texels(cfg), proj_nhwc, nullptr, (hipStream_t)stream);
-  if (rc) set_error("%s: kernel launch failed", "bts_project_features");
-  return rc;
+  const char* who = "bts_project_features";
+  if (int rc = check_projection(cfg, feat_nchw && mlp_params && proj_nhwc, N, who)) return rc;
+  return launched(project_features_impl(cfg->C, cfg->d_hidden, feat_nchw, mlp_params, N, (int)feat_texels(cfg), proj_nhwc, nullptr, (hipStream_t)stream),
+                  who);
 }
 
 int bts_project_features_tiles(const BtsFieldCfg* cfg, const float* feat_nchw, const float* mlp_params, int32_t N, const uint8_t* tiles, float* proj_nhwc,
                                void* stream) {
-  if (!cfg || !feat_nchw || !mlp_params || !proj_nhwc || !tiles || N <= 0 || cfg->H <= 0 || cfg->W <= 0) {
-    set_error("%s: NULL pointer or non-positive size", "bts_project_features_tiles");
-    return BTS_E_INVALID;
-  }
-  if (!bts_supported(cfg)) {
-    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", "bts_project_features_tiles", cfg->C, cfg->d_hidden,
-              cfg->n_blocks);
-    return BTS_E_UNSUPPORTED;
-  }
-  if (int rc = check_shift(cfg, "bts_project_features_tiles")) return rc;
-  int rc = project_features_impl(cfg->C, cfg->d_hidden, feat_nchw, mlp_params, N, (int)feat_texels(cfg), proj_nhwc, tiles, (hipStream_t)stream, false,
-                                 cfg->tile_blocks ? cfg->W >> cfg->feat_shift : 0);
-  if (rc) set_error("%s: kernel launch failed", "bts_project_features_tiles");
-  return rc;
+  const char* who = "bts_project_features_tiles";
+  if (int rc = check_projection(cfg, feat_nchw && mlp_params && proj_nhwc && tiles, N, who)) return rc;
+  return launched(project_features_impl(cfg->C, cfg->d_hidden, feat_nchw, mlp_params, N, (int)feat_texels(cfg), proj_nhwc, tiles, (hipStream_t)stream,
+                                        false, tile_geometry_width(cfg)),
+                  who);
 }
 
 int bts_mark_sampled_tiles(const BtsFieldCfg* cfg, const float* K_enc, const float* w2c_enc, const BtsRenderArgs* a, uint8_t* tiles, void* stream) {
@@ -233,28 +158,18 @@ int bts_mark_sampled_tiles(const BtsFieldCfg* cfg, const float* K_enc, const flo
     return BTS_E_INVALID;
   }
   if (int rc = check_shift(cfg, "bts_mark_sampled_tiles")) return rc;
-  int rc = mark_tiles_impl(a->rays, a->z_samp, a->z_samp ? nullptr : a->jitter, w2c_enc, K_enc, (long)cfg->n * a->rays_per_sample, a->rays_per_sample, a->K,
-                           a->lindisp, cfg->H, cfg->W, cfg->feat_shift, tiles, (hipStream_t)stream, cfg->tile_blocks);
-  if (rc) set_error("%s: kernel launch failed", "bts_mark_sampled_tiles");
-  return rc;
+  return launched(mark_tiles_impl(a->rays, a->z_samp, a->z_samp ? nullptr : a->jitter, w2c_enc, K_enc, (long)cfg->n * a->rays_per_sample,
+                                  a->rays_per_sample, a->K, a->lindisp, cfg->H, cfg->W, cfg->feat_shift, tiles, (hipStream_t)stream, cfg->tile_blocks),
+                  "bts_mark_sampled_tiles");
 }
 
 int bts_project_features_bwd(const BtsFieldCfg* cfg, const float* feat_nchw, const float* d_proj_nhwc, const float* mlp_params,
                              int32_t N, float* d_feat_nchw, float* d_mlp_params, void* stream) {
-  if (!cfg || !d_proj_nhwc || !mlp_params || N <= 0 || cfg->H <= 0 || cfg->W <= 0 || (d_mlp_params && !feat_nchw)) {
-    set_error("%s: NULL pointer or non-positive size", "bts_project_features_bwd");
-    return BTS_E_INVALID;
-  }
-  if (!bts_supported(cfg)) {
-    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", "bts_project_features_bwd", cfg->C,
-              cfg->d_hidden, cfg->n_blocks);
-    return BTS_E_UNSUPPORTED;
-  }
-  if (int rc = check_shift(cfg, "bts_project_features_bwd")) return rc;
-  int rc = project_features_bwd_impl(cfg->C, cfg->d_hidden, feat_nchw, d_proj_nhwc, mlp_params, N, (int)feat_texels(cfg), d_feat_nchw,
-                                     d_mlp_params, (hipStream_t)stream);
-  if (rc) set_error("%s: kernel launch failed", "bts_project_features_bwd");
-  return rc;
+  const char* who = "bts_project_features_bwd";
+  if (int rc = check_projection(cfg, d_proj_nhwc && mlp_params && !(d_mlp_params && !feat_nchw), N, who)) return rc;
+  return launched(project_features_bwd_impl(cfg->C, cfg->d_hidden, feat_nchw, d_proj_nhwc, mlp_params, N, (int)feat_texels(cfg), d_feat_nchw,
+                                            d_mlp_params, (hipStream_t)stream),
+                  who);
 }
 
 int64_t bts_proj_tile_count(const BtsFieldCfg* cfg) {
@@ -265,61 +180,34 @@ int64_t bts_proj_tile_count(const BtsFieldCfg* cfg) {
     return -1;
   }
   if (check_shift(cfg, "bts_proj_tile_count")) return -1;
-  return (feat_texels(cfg) + 63) / 64;
+  return map_tiles(cfg->H, cfg->W, cfg->feat_shift);
 }
 
 int bts_project_features_bwd_tiles(const BtsFieldCfg* cfg, const float* feat_nchw, float* d_proj_nhwc, uint8_t* tiles, const float* mlp_params,
                                    int32_t N, float* d_feat_nchw, float* d_mlp_params, int32_t clear_after, void* stream) {
-  if (!cfg || !d_proj_nhwc || !tiles || !mlp_params || N <= 0 || cfg->H <= 0 || cfg->W <= 0 || (d_mlp_params && !feat_nchw)) {
-    set_error("%s: NULL pointer or non-positive size", "bts_project_features_bwd_tiles");
-    return BTS_E_INVALID;
-  }
-  if (!bts_supported(cfg)) {
-    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", "bts_project_features_bwd_tiles", cfg->C,
-              cfg->d_hidden, cfg->n_blocks);
-    return BTS_E_UNSUPPORTED;
-  }
-  if (int rc = check_shift(cfg, "bts_project_features_bwd_tiles")) return rc;
-  int rc = project_features_bwd_tiles_impl(cfg->C, cfg->d_hidden, feat_nchw, d_proj_nhwc, tiles, mlp_params, N, (int)feat_texels(cfg), d_feat_nchw,
-                                           d_mlp_params, clear_after, (hipStream_t)stream, false, cfg->tile_blocks ? cfg->W >> cfg->feat_shift : 0);
-  if (rc) set_error("%s: kernel launch failed", "bts_project_features_bwd_tiles");
-  return rc;
+  const char* who = "bts_project_features_bwd_tiles";
+  if (int rc = check_projection(cfg, d_proj_nhwc && tiles && mlp_params && !(d_mlp_params && !feat_nchw), N, who)) return rc;
+  return launched(project_features_bwd_tiles_impl(cfg->C, cfg->d_hidden, feat_nchw, d_proj_nhwc, tiles, mlp_params, N, (int)feat_texels(cfg), d_feat_nchw,
+                                                  d_mlp_params, clear_after, (hipStream_t)stream, false, tile_geometry_width(cfg)),
+                  who);
 }
 
 int bts_project_features_cl(const BtsFieldCfg* cfg, const float* feat_nhwc, const float* mlp_params, int32_t N, const uint8_t* tiles, float* proj_nhwc,
                             void* stream) {
-  if (!cfg || !feat_nhwc || !mlp_params || !proj_nhwc || N <= 0 || cfg->H <= 0 || cfg->W <= 0) {
-    set_error("%s: NULL pointer or non-positive size", "bts_project_features_cl");
-    return BTS_E_INVALID;
-  }
-  if (!bts_supported(cfg)) {
-    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", "bts_project_features_cl", cfg->C, cfg->d_hidden,
-              cfg->n_blocks);
-    return BTS_E_UNSUPPORTED;
-  }
-  if (int rc = check_shift(cfg, "bts_project_features_cl")) return rc;
-  int rc = project_features_impl(cfg->C, cfg->d_hidden, feat_nhwc, mlp_params, N, (int)feat_texels(cfg), proj_nhwc, tiles, (hipStream_t)stream, true,
-                                 cfg->tile_blocks ? cfg->W >> cfg->feat_shift : 0);
-  if (rc) set_error("%s: kernel launch failed", "bts_project_features_cl");
-  return rc;
+  const char* who = "bts_project_features_cl";
+  if (int rc = check_projection(cfg, feat_nhwc && mlp_params && proj_nhwc, N, who)) return rc;
+  return launched(project_features_impl(cfg->C, cfg->d_hidden, feat_nhwc, mlp_params, N, (int)feat_texels(cfg), proj_nhwc, tiles, (hipStream_t)stream,
+                                        true, tile_geometry_width(cfg)),
+                  who);
 }
 
 int bts_project_features_bwd_cl(const BtsFieldCfg* cfg, const float* feat_nhwc, float* d_proj_nhwc, uint8_t* tiles, const float* mlp_params, int32_t N,
                                 float* d_feat_nhwc, float* d_mlp_params, int32_t clear_after, void* stream) {
-  if (!cfg || !d_proj_nhwc || !mlp_params || N <= 0 || cfg->H <= 0 || cfg->W <= 0 || (d_mlp_params && !feat_nhwc)) {
-    set_error("%s: NULL pointer or non-positive size", "bts_project_features_bwd_cl");
-    return BTS_E_INVALID;
-  }
-  if (!bts_supported(cfg)) {
-    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", "bts_project_features_bwd_cl", cfg->C, cfg->d_hidden,
-              cfg->n_blocks);
-    return BTS_E_UNSUPPORTED;
-  }
-  if (int rc = check_shift(cfg, "bts_project_features_bwd_cl")) return rc;
-  int rc = project_features_bwd_tiles_impl(cfg->C, cfg->d_hidden, feat_nhwc, d_proj_nhwc, tiles, mlp_params, N, (int)feat_texels(cfg), d_feat_nhwc,
-                                           d_mlp_params, clear_after, (hipStream_t)stream, true, cfg->tile_blocks ? cfg->W >> cfg->feat_shift : 0);
-  if (rc) set_error("%s: kernel launch failed", "bts_project_features_bwd_cl");
-  return rc;
+  const char* who = "bts_project_features_bwd_cl";
+  if (int rc = check_projection(cfg, d_proj_nhwc && mlp_params && !(d_mlp_params && !feat_nhwc), N, who)) return rc;
+  return launched(project_features_bwd_tiles_impl(cfg->C, cfg->d_hidden, feat_nhwc, d_proj_nhwc, tiles, mlp_params, N, (int)feat_texels(cfg), d_feat_nhwc,
+                                                  d_mlp_params, clear_after, (hipStream_t)stream, true, tile_geometry_width(cfg)),
+                  who);
 }
 
 int bts_field_query(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int32_t P, int32_t only_density,
@@ -353,29 +241,23 @@ int bts_occupancy_profile(const BtsFieldCfg* cfg, const BtsFieldTensors* t, cons
     set_error("%s: NULL pointer or non-positive size", name); \
     return BTS_E_INVALID;                                 \
   }
-#define BTS_RET_LAUNCH(expr, name)                              \
-  {                                                             \
-    int rc_ = (expr);                                           \
-    if (rc_) set_error("%s: kernel launch failed", name);       \
-    return rc_;                                                 \
-  }
 
 int bts_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream) {
   BTS_CHECK_LAYOUT(src && dst && N > 0 && C > 0 && H > 0 && W > 0, "bts_nchw_to_nhwc");
-  BTS_RET_LAUNCH(transpose_launch(src, dst, N, C, H, W, true, (hipStream_t)stream), "bts_nchw_to_nhwc");
+  return launched(transpose_launch(src, dst, N, C, H, W, true, (hipStream_t)stream), "bts_nchw_to_nhwc");
 }
 int bts_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream) {
   BTS_CHECK_LAYOUT(src && dst && N > 0 && C > 0 && H > 0 && W > 0, "bts_nhwc_to_nchw");
-  BTS_RET_LAUNCH(transpose_launch(src, dst, N, C, H, W, false, (hipStream_t)stream), "bts_nhwc_to_nchw");
+  return launched(transpose_launch(src, dst, N, C, H, W, false, (hipStream_t)stream), "bts_nhwc_to_nchw");
 }
 int bts_pack_rgb(const float* src, float* dst, int32_t N, int32_t H, int32_t W, float scale, float shift, void* stream) {
   BTS_CHECK_LAYOUT(src && dst && N > 0 && H > 0 && W > 0, "bts_pack_rgb");
-  BTS_RET_LAUNCH(pack_rgb_launch(src, dst, N, H, W, scale, shift, (hipStream_t)stream), "bts_pack_rgb");
+  return launched(pack_rgb_launch(src, dst, N, H, W, scale, shift, (hipStream_t)stream), "bts_pack_rgb");
 }
 int bts_gen_rays(const float* poses, const float* projs, int32_t V, int32_t H, int32_t W, float z_near, float z_far,
                  int32_t norm_dir, float* rays, void* stream) {
   BTS_CHECK_LAYOUT(poses && projs && rays && V > 0 && H > 0 && W > 0, "bts_gen_rays");
-  BTS_RET_LAUNCH(gen_rays_launch(poses, projs, V, H, W, z_near, z_far, norm_dir, rays, (hipStream_t)stream), "bts_gen_rays");
+  return launched(gen_rays_launch(poses, projs, V, H, W, z_near, z_far, norm_dir, rays, (hipStream_t)stream), "bts_gen_rays");
 }
 int bts_patch_rays(const float* poses, const float* projs, const float* images, const int32_t* patch_v, const int32_t* patch_y,
                    const int32_t* patch_x, int32_t n, int32_t v, int32_t c, int32_t H, int32_t W, int32_t P, int32_t ph, int32_t pw,
@@ -383,9 +265,9 @@ int bts_patch_rays(const float* poses, const float* projs, const float* images, 
   BTS_CHECK_LAYOUT(poses && projs && patch_v && patch_y && patch_x && rays && n > 0 && v > 0 && H > 0 && W > 0 && P >= 0 && ph > 0 && pw > 0 &&
                        ph <= H && pw <= W && (!images || (rgb_gt && c > 0)),
                    "bts_patch_rays");
-  BTS_RET_LAUNCH(patch_rays_launch(poses, projs, images, patch_v, patch_y, patch_x, n, v, c, H, W, P, ph, pw, z_near, z_far, norm_dir, rays,
-                                   rgb_gt, (hipStream_t)stream),
-                 "bts_patch_rays");
+  return launched(patch_rays_launch(poses, projs, images, patch_v, patch_y, patch_x, n, v, c, H, W, P, ph, pw, z_near, z_far, norm_dir, rays,
+                                    rgb_gt, (hipStream_t)stream),
+                  "bts_patch_rays");
 }
 int bts_photometric_loss(const BtsLossArgs* a, void* stream) {
   BTS_CHECK_LAYOUT(a && a->rgb && a->rgb_gt && a->parts && a->n_patches >= 0 && a->patch_h > 0 && a->patch_w > 0 &&
@@ -394,7 +276,7 @@ int bts_photometric_loss(const BtsLossArgs* a, void* stream) {
                        (a->invalid_policy != 2 || a->invalid_wsum || (a->invalid && a->weights && a->K > 0)) &&
                        (!a->edge_aware_smoothness || a->depth),
                    "bts_photometric_loss");
-  BTS_RET_LAUNCH(photometric_loss_impl(a, (hipStream_t)stream), "bts_photometric_loss");
+  return launched(photometric_loss_impl(a, (hipStream_t)stream), "bts_photometric_loss");
 }
 size_t bts_photometric_loss_tiled_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv) {
   return loss_tiled_bytes(n_patches, patch_h, patch_w, nv);
@@ -419,20 +301,20 @@ int bts_photometric_loss_tiled(const BtsLossArgs* a, void* workspace, size_t wor
     set_error("%s: workspace too small (%ld bytes needed, see bts_photometric_loss_tiled_workspace)", "bts_photometric_loss_tiled", (long)need);
     return BTS_E_INVALID;
   }
-  BTS_RET_LAUNCH(photometric_loss_tiled_impl(a, workspace, (hipStream_t)stream), "bts_photometric_loss_tiled");
+  return launched(photometric_loss_tiled_impl(a, workspace, (hipStream_t)stream), "bts_photometric_loss_tiled");
 }
 int bts_sample_coarse(const float* rays, const float* u, int64_t B, int32_t K, int32_t lindisp, float* z_samp, void* stream) {
   BTS_CHECK_LAYOUT(rays && u && z_samp && B > 0 && K > 0, "bts_sample_coarse");
-  BTS_RET_LAUNCH(sample_coarse_launch(rays, u, (long)B, K, lindisp, z_samp, (hipStream_t)stream), "bts_sample_coarse");
+  return launched(sample_coarse_launch(rays, u, (long)B, K, lindisp, z_samp, (hipStream_t)stream), "bts_sample_coarse");
 }
 int bts_distance_to_z(const float* depths, const float* inv_K, int32_t N, int32_t H, int32_t W, float* out, void* stream) {
   BTS_CHECK_LAYOUT(depths && inv_K && out && N > 0 && H > 0 && W > 0, "bts_distance_to_z");
-  BTS_RET_LAUNCH(distance_to_z_launch(depths, inv_K, N, H, W, out, (hipStream_t)stream), "bts_distance_to_z");
+  return launched(distance_to_z_launch(depths, inv_K, N, H, W, out, (hipStream_t)stream), "bts_distance_to_z");
 }
 
 int bts_invert_small(const float* src, float* dst, int32_t N, int32_t dim, void* stream) {
   BTS_CHECK_LAYOUT(src && dst && N > 0 && (dim == 3 || dim == 4), "bts_invert_small");
-  BTS_RET_LAUNCH(invert_small_launch(src, dst, N, dim, (hipStream_t)stream), "bts_invert_small");
+  return launched(invert_small_launch(src, dst, N, dim, (hipStream_t)stream), "bts_invert_small");
 }
 
 // ---- MLP-predicted colour (sample_color=False): the field checks of check_cfg plus this head's own (nv = 1, no render view, G required)
@@ -458,15 +340,8 @@ static int check_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, con
 }
 
 static int check_mlp_color_args(const BtsRenderArgs* a, const char* who, bool bwd) {
-  if (!a || !a->rays || (bwd ? (!a->z_samp || !a->sigma_raw || !a->trans) : ((!a->z_samp && !a->jitter) || !a->rgb || !a->depth))) {
-    set_error(bwd ? "%s: NULL argument (rays, z_samp and the forward's sigma_raw + trans are required)"
-                  : "%s: NULL render argument (rays, z_samp or jitter, rgb and depth are required)", who);
-    return BTS_E_INVALID;
-  }
-  if (a->rays_per_sample <= 0 || a->K <= 0) {
-    set_error("%s: non-positive rays_per_sample=%ld K=%ld", who, (long)a->rays_per_sample, (long)a->K);
-    return BTS_E_INVALID;
-  }
+  if (int rc = check_render_args(a, who, bwd, true, bwd ? "%s: NULL argument (rays, z_samp and the forward's sigma_raw + trans are required)" : kFwdArgsNull))
+    return rc;
   if (a->K > 256) {
     set_error("%s: K=%ld samples per ray; this head's kernels take whole rays of at most 256 samples per work-group", who, (long)a->K);
     return BTS_E_UNSUPPORTED;
@@ -559,8 +434,6 @@ static int check_lidar_clouds(const float* points, const int32_t* offsets, int T
   return BTS_OK;
 }
 
-static size_t align16(size_t b) { return (b + 15) / 16 * 16; }
-
 size_t bts_lidar_slices_workspace(int32_t T, int32_t y_res) {
   if (T <= 0 || y_res <= 0 || T > BTS_LIDAR_MAX_CLOUDS || y_res > BTS_LIDAR_MAX_SLICES) return 0;
   return lidar_bins_bytes(T, y_res);
@@ -571,17 +444,17 @@ int bts_lidar_slices(const float* points, const int32_t* offsets, int32_t T, con
   BTS_CHECK_LAYOUT(points && offsets && velo_poses && borders361 && bins_workspace && tables, "bts_lidar_slices");
   if (int rc = check_lidar_limits(T, y_res, "bts_lidar_slices")) return rc;
   if (int rc = check_lidar_clouds(points, offsets, T, "bts_lidar_slices")) return rc;
-  BTS_RET_LAUNCH(lidar_slices_launch(points, offsets, T, velo_poses, borders361, y_lo, y_hi, y_res, max_dist, bins_workspace, tables,
-                                     (hipStream_t)stream),
-                 "bts_lidar_slices");
+  return launched(lidar_slices_launch(points, offsets, T, velo_poses, borders361, y_lo, y_hi, y_res, max_dist, bins_workspace, tables,
+                                      (hipStream_t)stream),
+                  "bts_lidar_slices");
 }
 
 int bts_lidar_occupancy(const float* q_pts, int32_t P, const float* tables, int32_t y_res, int32_t T, const float* world_to_velo,
                         float min_dist, uint8_t* is_occupied, uint8_t* is_visible, void* stream) {
   BTS_CHECK_LAYOUT(q_pts && tables && world_to_velo && is_occupied && is_visible && P > 0, "bts_lidar_occupancy");
   if (int rc = check_lidar_limits(T, y_res, "bts_lidar_occupancy")) return rc;
-  BTS_RET_LAUNCH(lidar_occupancy_launch(q_pts, P, tables, y_res, T, world_to_velo, min_dist, is_occupied, is_visible, (hipStream_t)stream),
-                 "bts_lidar_occupancy");
+  return launched(lidar_occupancy_launch(q_pts, P, tables, y_res, T, world_to_velo, min_dist, is_occupied, is_visible, (hipStream_t)stream),
+                  "bts_lidar_occupancy");
 }
 
 // workspace of bts_occupancy_eval: bins + keys | tables | world_to_velo (T, 16) | camera w2c (16) | is_occupied (P) | is_visible (P) | sigma (P)
@@ -665,7 +538,7 @@ int bts_depth_metrics(const BtsDepthMetrics* a, void* workspace, size_t workspac
     set_error("%s: workspace NULL, too small or not 16-byte aligned (%ld bytes needed)", "bts_depth_metrics", (long)need);
     return BTS_E_INVALID;
   }
-  BTS_RET_LAUNCH(depth_metrics_launch(a, workspace, (hipStream_t)stream), "bts_depth_metrics");
+  return launched(depth_metrics_launch(a, workspace, (hipStream_t)stream), "bts_depth_metrics");
 }
 
 // ---- NVS evaluation metrics (evaluator_nvs.py:141-178 without LPIPS)
@@ -706,7 +579,7 @@ int bts_nvs_metrics(const BtsNvsMetrics* a, void* workspace, size_t workspace_by
     set_error("%s: workspace NULL, too small or not 16-byte aligned (%ld bytes needed)", "bts_nvs_metrics", (long)need);
     return BTS_E_INVALID;
   }
-  BTS_RET_LAUNCH(nvs_metrics_launch(a, workspace, (hipStream_t)stream), "bts_nvs_metrics");
+  return launched(nvs_metrics_launch(a, workspace, (hipStream_t)stream), "bts_nvs_metrics");
 }
 
 // ---- 3D-bounding-box occupancy evaluation (evaluator_3dbb.py): limits and host-side checks shared by the entry points
@@ -742,9 +615,9 @@ int bts_bbox_bounds(const float* vertices, const int32_t* faces, const int32_t* 
                     const float* to_keyframe, const float* proj, float max_d, float* tables, int32_t* n_faces, uint8_t* active, void* stream) {
   BTS_CHECK_LAYOUT(vertices && faces && v_offsets && f_offsets && to_keyframe && proj && tables && n_faces && active && B > 0, "bts_bbox_bounds");
   if (int rc = check_bbox_boxes(v_offsets, f_offsets, B, "bts_bbox_bounds")) return rc;
-  BTS_RET_LAUNCH(bbox_bounds_launch(vertices, faces, v_offsets, f_offsets, B, to_keyframe, proj, max_d, tables, n_faces, active, nullptr,
-                                    (hipStream_t)stream),
-                 "bts_bbox_bounds");
+  return launched(bbox_bounds_launch(vertices, faces, v_offsets, f_offsets, B, to_keyframe, proj, max_d, tables, n_faces, active, nullptr,
+                                     (hipStream_t)stream),
+                  "bts_bbox_bounds");
 }
 
 int bts_bbox_pseudo_depth(const float* rays, int32_t ph, int32_t pw, const float* seg, int32_t hs, int32_t ws, const float* tables,
@@ -759,8 +632,8 @@ int bts_bbox_pseudo_depth(const float* rays, int32_t ph, int32_t pw, const float
     set_error("%s: more than 2^27 rays or 2^30 label pixels (%ld, %ld)", "bts_bbox_pseudo_depth", (long)ph * pw, (long)hs * ws);
     return BTS_E_INVALID;
   }
-  BTS_RET_LAUNCH(bbox_pseudo_depth_launch(rays, ph, pw, seg, hs, ws, tables, n_faces, active, semantic_id, B, pseudo_depth, (hipStream_t)stream),
-                 "bts_bbox_pseudo_depth");
+  return launched(bbox_pseudo_depth_launch(rays, ph, pw, seg, hs, ws, tables, n_faces, active, semantic_id, B, pseudo_depth, (hipStream_t)stream),
+                  "bts_bbox_pseudo_depth");
 }
 
 // workspace of bts_bbox_occupancy_eval: to_keyframe (16) | tables (B, 32, 5) | n_faces (B) | active (B) | pseudo depth (ph, pw) | sigma (P)
@@ -842,8 +715,8 @@ int bts_colorize(const float* x, int32_t B, int32_t h, int32_t w, int32_t norm, 
   }
   if (canvas)
     if (int rc = check_panel("bts_colorize", 0, h, w, Hc, Wc, row0, col0)) return rc;
-  BTS_RET_LAUNCH(colorize_launch(x, B, h, w, norm, N, lut_f64, lut_u8, minmax_scratch, out, canvas, Hc, Wc, row0, col0, (hipStream_t)stream),
-                 "bts_colorize");
+  return launched(colorize_launch(x, B, h, w, norm, N, lut_f64, lut_u8, minmax_scratch, out, canvas, Hc, Wc, row0, col0, (hipStream_t)stream),
+                  "bts_colorize");
 }
 
 int bts_pack_u8(const float* x, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int32_t B, int32_t h, int32_t w, float scale, float shift,
@@ -854,8 +727,8 @@ int bts_pack_u8(const float* x, int64_t sb, int64_t sy, int64_t sx, int64_t sc, 
     return BTS_E_INVALID;
   }
   if (int rc = check_panel("bts_pack_u8", 0, h, w, Hc, Wc, row0, col0)) return rc;
-  BTS_RET_LAUNCH(pack_u8_launch(x, (long)sb, (long)sy, (long)sx, (long)sc, B, h, w, scale, shift, canvas, Hc, Wc, row0, col0, (hipStream_t)stream),
-                 "bts_pack_u8");
+  return launched(pack_u8_launch(x, (long)sb, (long)sy, (long)sx, (long)sc, B, h, w, scale, shift, canvas, Hc, Wc, row0, col0, (hipStream_t)stream),
+                  "bts_pack_u8");
 }
 
 int bts_novel_views(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsNovelViews* a, void* stream) {
@@ -905,7 +778,7 @@ int bts_novel_views(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsN
     r.rays = a->rays, r.jitter = a->jitter, r.rgb = a->rgb, r.depth = a->depth, r.invalid_wsum = a->invalid_wsum;
     if (int rc = render_fwd_impl(cfg, t, &r, s)) return rc;
   }
-  BTS_RET_LAUNCH(novel_view_finish_launch(a, s), who);
+  return launched(novel_view_finish_launch(a, s), who);
 }
 
 }  // extern "C"

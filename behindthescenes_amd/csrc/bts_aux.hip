@@ -1,12 +1,11 @@
 // Small HBM-bound kernels at the edges of the render path: layout changes at the hand-off from the PyTorch encoder,
 // ray generation (util.py:113-149, 244-273), stratified depth sampling (nerf.py:103-123) and distance->z
 // (projection_operations.py:4-16).  All are coalesced streaming kernels; none does arithmetic worth an MFMA.
-#include "bts_common.h"
+#include "bts_host.h"
 #include <cstdint>
 
 namespace bts {
 
-void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
 
 // ----------------------------------------------------------------------------------------------------------------
 // (N, C, HW) <-> (N, HW, C) through a 64x65 LDS tile: both the read and the write are 256-byte coalesced rows.
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(256) void patch_rays_kernel(const float* __restrict
   patch_rays_body(poses, projs, images, pv, py, px, n, v, c, H, W, P, ph, pw, z_near, z_far, norm_dir, rays, gt, m, gt_scale, gt_shift, blockIdx.x, gridDim.x);
 }
 
-int patch_rays_views_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
+static int patch_rays_views_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
                             int c, int H, int W, int P, int ph, int pw, float zn, float zf, int norm_dir, float* rays, float* gt, int n_ids,
                             const int* ids, float gt_scale, float gt_shift, hipStream_t s) {
   const long total = (long)n * P * ph * pw;

@@ -3,7 +3,7 @@
 // (the z of its nearest valid slab intercept among the boxes that carry the ray's label), and the classification of the query points
 // into the six counters of occ_metrics_kernel.  No matrix pipe, no inline assembly; the only reductions are an int32 add and a
 // bit-pattern minimum of positive floats, so reruns are bit-identical.
-#include "bts_common.h"
+#include "bts_host.h"
 
 namespace bts {
 

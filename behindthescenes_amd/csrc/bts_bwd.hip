@@ -4,15 +4,10 @@
 //
 // What torch.autograd would do for nerf.py:283-299 + models_bts.py:266-338 + resnetfc.py:132-184 of the reference.
 #include "bts_bwd.h"
+#include "bts_host.h"
 #include <cstdlib>
 
 namespace bts {
-
-FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t);
-int render_grid(const FwdParams& p);
-int render_chunk_log2(int grid, long groups);
-int launch_bwd_rows(const BwdParams& bp, int C, int HD, int n, int grid, hipStream_t s);
-int launch_bwd_blocks(const BwdParams& bp, float* u0_ws, int C, int HD, int NB, int n, int grid, hipStream_t s);
 
 // plain MLP and at most one wave of samples per ray: the gate-bit passes of bts_bwd_rows.hip; ResnetBlockFC layers (RE10K) and K > 64:
 // the row passes of bts_bwd_blocks.hip
@@ -22,7 +17,6 @@ static bool bits_path(const BtsFieldCfg* cfg, const BtsRenderArgs* a) { return c
 // and once per channel -- 20 bytes at d_hidden 64.  Row path: the gradient row at lin_in's output (4 d_hidden bytes) + g_s.
 // + pass C's slot copies of dW_pe (bts_bwd.h: kFlushSlots x 40 x d_hidden floats, 80 KB at d_hidden 64), behind the per-sample part
 static size_t flush_bytes(const BtsFieldCfg* cfg) { return sizeof(float) * kFlushSlots * kFlushRows * (size_t)cfg->d_hidden; }
-static size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 size_t render_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a) {
   const size_t rays = (size_t)cfg->n * (size_t)a->rays_per_sample;
   // gate-bit path: g_s + the per-sample masks, rounded up to 8 bytes (the per-channel masks behind them are read as 64-bit words)
@@ -40,7 +34,7 @@ void render_bwd_flush_region(const BtsFieldCfg* cfg, const BtsRenderArgs* a, voi
 }
 
 int render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
-                    size_t, hipStream_t s, bool flush_clean) {
+                    hipStream_t s, bool flush_clean) {
   BwdParams bp;
   bp.flush_clean = flush_clean;
   bp.f = make_params(cfg, t);
@@ -58,7 +52,7 @@ int render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsR
   if (const char* e = getenv("BTS_DBG_PTR")) bp.ticks = (unsigned long long*)strtoull(e, nullptr, 0);   // diagnostic build only
 #endif
   bp.tiles = bp.d_proj ? g->d_proj_tiles : nullptr;
-  bp.tiles_per_img = (int)((((long)(cfg->H >> cfg->feat_shift) * (cfg->W >> cfg->feat_shift)) + 63) / 64);
+  bp.tiles_per_img = (int)map_tiles(cfg->H, cfg->W, cfg->feat_shift);
   bp.tile_tw = tile_cols(cfg->H >> cfg->feat_shift, cfg->W >> cfg->feat_shift, cfg->tile_blocks);
   bp.f.lpr = 64, bp.f.groups = (long)cfg->n * a->rays_per_sample;
   if (bp.f.groups > 0x7FF00000L) {

@@ -25,6 +25,7 @@
 #undef BTS_GATHER_REGS   // (the register-gather A/B build, variants/libbts_gatherregs.so, concerns the render kernels: the row passes of the backward exist in the LDS-gather form only)
 #include "bts_render_kernel.h"
 #include "bts_bwd.h"
+#include "bts_host.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -813,10 +814,6 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
 // ---------------------------------------------------------------------------------------------------------------
 // launch
 // ---------------------------------------------------------------------------------------------------------------
-int launch_scatter_rows(const BwdParams& bp, const float* u0_ws, int HD, int n, hipStream_t s);
-int launch_dwpe_rows(const FwdParams& p, const float* u0_ws, float* d_mlp, float* flush_ws, int C, int HD, int NB, int n, int grid, hipStream_t s,
-                     bool flush_clean);
-
 template <int C, int HD, int NB>
 static int launch_rowsb(const BwdParams& bp, const RowsbOut& ro, int grid, hipStream_t s) {
   constexpr int dyn = 4 * kGatherLdsPerWave;

@@ -17,6 +17,7 @@
 #define BTS_NO_LAUNCH_GLUE
 #include "bts_render_kernel.h"
 #include "bts_bwd.h"
+#include "bts_host.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1276,7 +1277,6 @@ static int launch_rows(const BwdParams& bp, int n, int grid, hipStream_t s) {
 // segments of the K steps per ray group: as many waves as the chip holds AT ONCE -- eight per CU, 20 KB of LDS each -- and not one more
 // (rounding up gave exp_re10k.yaml's 384 patches six segments = 2 304 waves on 2 048 places: a second round for the last 256, i.e. twice
 // the steps on the critical path; five segments = 1 920 waves finish in one), at least 8 steps each (window set-up + final flush)
-int device_cu_count();
 static void scatter_segments(ScatterMaskParams& sp, long units, int K) {
   long want = 8L * device_cu_count() / units;
   // ... unless the patches alone (nearly) fill the chip: then FOUR segments each, i.e. several rounds of short waves.  A wave's time

@@ -22,14 +22,11 @@
 // is 16 x the fp32 one per instruction -- 0.375 of the matrix time with better sums than before (blocked accumulation).  bf16, not f16:
 // activations and gradients have no bounded range to scale an f16 split on, and bf16 carries fp32's exponent.
 #include "bts_bf16x3.h"
+#include "bts_host.h"
 
 #include <cstring>
 
 namespace bts {
-
-void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
-int device_cu_count();
-int transpose_launch(const float* src, float* dst, int N, int C, int H, int W, bool to_nhwc, hipStream_t s);
 
 constexpr int kTapFloats = 64 * 64;          // one tap's weights
 

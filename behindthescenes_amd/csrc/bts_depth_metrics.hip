@@ -23,7 +23,7 @@
 // faults, the row is unspecified), -0.0 in pred next to +0.0 at the median's rank (torch's sort calls them equal), and l2 scaling of a
 // rank-deficient system (fewer than two distinct predictions under the mask: the coefficients are not finite here, LAPACK returns the
 // minimum-norm solution).  N = 0 gives a NaN row and zero counts.
-#include "bts_common.h"
+#include "bts_host.h"
 
 namespace bts {
 
@@ -346,7 +346,6 @@ __global__ __launch_bounds__(64) void depth_finish_kernel(DepthGeom g, float* __
 }
 
 static int launched() { return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH; }
-static size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 static int n_blocks(int Hg, int Wg) { return (int)(((long)Hg * Wg + kPerBlock - 1) / kPerBlock); }
 
 // histograms | notes | partials of the metrics pass | partials of the moments pass, each per frame

@@ -22,6 +22,7 @@
 //           resnetfc.py:132-184, code.py:30-42 of the reference.
 #pragma once
 #include "bts_common.h"
+#include "bts_host.h"
 
 #include <cstdio>
 #include <cstring>
@@ -830,8 +831,6 @@ __global__ __launch_bounds__(256, 2) void render_kernel(const FwdParams p) {
 // ---------------------------------------------------------------------------------------------------------------
 // launch dispatch (instantiated in bts_fwd.hip: launch_field<true, false>, launch_render<false>)
 // ---------------------------------------------------------------------------------------------------------------
-void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
-
 template <int C, int HD, int NB, bool QUERY, bool PROJ>
 static int launch_nv(const FwdParams& p, int grid, hipStream_t s) {
   if (p.nv <= 1) field_kernel<C, HD, NB, 1, QUERY, PROJ><<<grid, 256, 0, s>>>(p);

@@ -14,7 +14,7 @@
 //
 // Plain fp32 with correctly rounded division (__fdiv_rn), no contraction, no reciprocal approximations: the panels are compared byte
 // for byte with numpy / torch on the host.  Quirks of the reference that are reproduced ON PURPOSE are listed in include/bts_render.h.
-#include "bts_common.h"
+#include "bts_host.h"
 
 namespace bts {
 

@@ -1,5 +1,6 @@
 // Host side of the fused forward + the PROJ = false instantiations (raw channels-last features).
 #include "bts_field_kernel.h"
+#include "bts_host.h"
 
 #include <cstdlib>
 
@@ -22,8 +23,6 @@ bool shape_supported(int C, int HD, int NB) {
 // lane = point query kernel, the only instantiations of bts_field_kernel.h's kernels
 template int launch_field<true, false>(const FwdParams&, int, int, int, int, hipStream_t);
 template int launch_render<false>(const FwdParams&, int, int, int, int, hipStream_t);
-int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s);
-int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s);
 
 FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t) {
   FwdParams p;
@@ -44,7 +43,7 @@ FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t) {
 
 // lanes per ray / ray groups of the lane = sample kernels: short rays (K <= 32) share a wave iteration when the per-sample ray
 // count allows whole groups
-void render_geometry(FwdParams& p, int n) {
+static void render_geometry(FwdParams& p, int n) {
   int lpr = 64;
   if (p.K <= 32) {
     lpr = p.K <= 8 ? 8 : (p.K <= 16 ? 16 : 32);
@@ -148,9 +147,6 @@ int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, cons
   }
   return launch_render<false>(p, cfg->C, cfg->d_hidden, cfg->n_blocks, grid, s);
 }
-
-int query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb, float* invalid,
-               float* sigma, int cols, int col_len, float threshold, float* profile, hipStream_t s);   // bts_query.hip
 
 int field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
                      float* invalid, float* sigma, hipStream_t s) {

@@ -1,0 +1,149 @@
+// Host functions of libbts_render.so that one translation unit defines and another calls: each is declared HERE and nowhere else,
+// with its default arguments.  Every .hip file that defines or calls one includes this header, so the compiler sees declaration and
+// definition together (a changed parameter is a compile error at the definition, not a link error -- or, for a default, nothing at all).
+// Behind them: the small inline helpers of the host layer.  No device code.
+#pragma once
+#include "bts_common.h"
+
+namespace bts {
+
+struct FwdParams;   // bts_field_kernel.h
+struct BwdParams;   // bts_bwd.h
+
+// ---- bts_fwd.hip: the error text of bts_last_error() (thread-local; printf-style, one string and up to three longs), the compiled
+// envelope, the persistent grids' geometry, the render forward and the field queries
+void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
+const char* last_error();
+bool shape_supported(int C, int HD, int NB);
+FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t);
+int device_cu_count();
+int render_grid(const FwdParams& p);
+int render_chunk_log2(int grid, long groups);
+long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div);
+int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
+int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s);
+int field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
+                     float* invalid, float* sigma, hipStream_t s);
+int occupancy_profile_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int Y, int cols, float threshold,
+                           int only_density, float* profile, float* sigma, hipStream_t s);
+// bts_fwd_proj.hip, bts_fwd_epi.hip: the pipelined render kernel without / with the loss epilogue
+int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s);
+int launch_render_pipelined_epi(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s);
+// bts_query.hip.  Plain query: cols = 0; profile: cols = columns per sample, col_len = Y, P = Y * cols
+int query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb, float* invalid,
+               float* sigma, int cols, int col_len, float threshold, float* profile, hipStream_t s);
+
+// ---- bts_bwd.hip: the render backward; render_bwd_flush_region: where pass C's slot copies sit inside a workspace
+size_t render_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
+void render_bwd_flush_region(const BtsFieldCfg* cfg, const BtsRenderArgs* a, void* workspace, float** ptr, size_t* bytes);
+int render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
+                    hipStream_t s, bool flush_clean = false);   // flush_clean: the caller zeroed the slot copies on this stream
+// bts_bwd_rows.hip (gate-bit passes; the row forms of passes B and C), bts_bwd_blocks.hip (row passes)
+int launch_bwd_rows(const BwdParams& bp, int C, int HD, int n, int grid, hipStream_t s);
+int launch_scatter_rows(const BwdParams& bp, const float* u0_ws, int HD, int n, hipStream_t s);
+int launch_dwpe_rows(const FwdParams& p, const float* u0_ws, float* d_mlp, float* flush_ws, int C, int HD, int NB, int n, int grid, hipStream_t s,
+                     bool flush_clean);
+int launch_bwd_blocks(const BwdParams& bp, float* u0_ws, int C, int HD, int NB, int n, int grid, hipStream_t s);
+
+// ---- bts_prep.hip: the projection G = F . w_in[:, :C]^T, its backward and the tile flags.  Wm: the map's width when `tiles` are
+// 16 x 4 blocks (BtsFieldCfg.tile_blocks), 0 = runs of 64 texels; list_ws: scratch for the balanced (list-driven) form
+int project_features_impl(int C, int HD, const float* feat, const float* mlp, int N, int HW, float* proj, const unsigned char* tiles, hipStream_t s,
+                          bool feat_cl = false, int Wm = 0, void* list_ws = nullptr, size_t list_ws_bytes = 0);
+int mark_tiles_impl(const float* rays, const float* z_samp, const float* jitter, const float* w2c_enc, const float* K_enc, long B, int Bp, int K, int lindisp,
+                    int H, int W, int fs, unsigned char* tiles, hipStream_t s, int blocks);
+int project_features_bwd_impl(int C, int HD, const float* feat, const float* dproj, const float* mlp, int N, int HW, float* dfeat,
+                              float* d_mlp, hipStream_t s);
+int project_features_bwd_tiles_impl(int C, int HD, const float* feat, float* dproj, unsigned char* tiles, const float* mlp, int N, int HW, float* dfeat,
+                                    float* d_mlp, int clear, hipStream_t s, bool feat_cl = false, int Wm = 0, void* list_ws = nullptr,
+                                    size_t list_ws_bytes = 0);
+
+// ---- bts_aux.hip: layout changes, rays, sampling, the hand-over kernels of the training step and the eval frame
+int transpose_launch(const float* src, float* dst, int N, int C, int H, int W, bool to_nhwc, hipStream_t s);
+int pack_rgb_launch(const float* src, float* dst, int N, int H, int W, float scale, float shift, hipStream_t s);
+int gen_rays_launch(const float* poses, const float* projs, int V, int H, int W, float zn, float zf, int norm_dir, float* rays,
+                    hipStream_t s);
+int gen_rays_nf_launch(const float* poses, const float* projs, const float* near_far, int V, int H, int W, int norm_dir, float* rays,
+                       hipStream_t s);
+int patch_rays_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
+                      int c, int H, int W, int P, int ph, int pw, float zn, float zf, int norm_dir, float* rays, float* gt, hipStream_t s);
+int sample_coarse_launch(const float* rays, const float* u, long B, int K, int lindisp, float* z, hipStream_t s);
+int distance_to_z_launch(const float* depths, const float* invK, int N, int H, int W, float* out, hipStream_t s);
+int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_t s);
+int handover_launch(const float* Ks, const float* poses, const float* images, const int* pv, const int* py, const int* px, int n, int v, int id_enc, int nv,
+                    const int* ids_render, int n_loss, const int* ids_loss, int H, int W, int P, int ph, int pw, float z_near, float z_far, float scale,
+                    float shift, float* cams, float* imgs, float* rays, float* gt, int n_zero, unsigned char* const* zero, const long* zero_bytes,
+                    hipStream_t s);
+int eval_handover_launch(const float* Ks, const float* poses, const float* images, int n, int v, int id_enc, int nv, const int* ids_render, int H, int W,
+                         float z_near, float z_far, int norm_dir, float scale, float shift, float* cams, float* inv_K, float* imgs, float* rays,
+                         float* rgb_gt, unsigned* sched, hipStream_t s);
+
+// ---- bts_loss.hip (patches of at most 64 pixels), bts_loss_tiled.hip (patches of any size)
+int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s);
+size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv);
+int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s);
+
+// ---- bts_mlp_color.hip: MLP-predicted colour
+int mlp_color_render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
+int mlp_color_field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
+                               float* invalid, float* sigma, hipStream_t s);
+size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
+int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
+                              hipStream_t s);
+
+// ---- bts_occ.hip: LiDAR occupancy evaluation
+size_t lidar_bins_bytes(int T, int y_res);
+int lidar_slices_launch(const float* points, const int* offsets, int T, const float* velo_poses, const float* borders, float y_lo, float y_hi,
+                        int y_res, float max_dist, void* bins_ws, float* tables, hipStream_t s);
+int lidar_occupancy_launch(const float* q_pts, int P, const float* tables, int y_res, int T, const float* world_to_velo, float min_dist,
+                           unsigned char* is_occupied, unsigned char* is_visible, hipStream_t s);
+int occ_metrics_launch(const float* q_pts, int P, const float* sigma, const unsigned char* is_occupied, const unsigned char* is_visible,
+                       const float* depth_z, int H, int W, const float* proj, const float* w2c, float occ_threshold, int* counts,
+                       unsigned char* masks, hipStream_t s);
+
+// ---- bts_depth_metrics.hip, bts_nvs_metrics.hip: depth and NVS evaluation metrics
+size_t depth_metrics_bytes(int B, int Hg, int Wg);
+int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t s);
+size_t nvs_metrics_bytes(int B, int He, int We);
+int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s);
+
+// ---- bts_bbox_occ.hip: 3D-bounding-box occupancy evaluation
+int bbox_bounds_launch(const float* vertices, const int* faces, const int* v_offsets, const int* f_offsets, int B, const float* to_key,
+                       const float* proj, float max_d, float* tables, int* n_faces, unsigned char* active, int* n_active, hipStream_t s);
+int bbox_pseudo_depth_launch(const float* rays, int ph, int pw, const float* seg, int hs, int ws, const float* tables, const int* n_faces,
+                             const unsigned char* active, const float* semantic_id, int B, float* pseudo_depth, hipStream_t s);
+int bbox_metrics_launch(const float* q_pts, int P, const float* sigma, const float* pseudo, const float* depth_z, int H, int W, const float* proj,
+                        const float* tables, const int* n_faces, const unsigned char* active, int B, float occ_threshold, int* counts,
+                        unsigned char* masks, hipStream_t s);
+
+// ---- bts_frames.hip: novel-view frames and colour-mapped depth
+int colorize_launch(const float* x, int B, int h, int w, int norm, int N, const double* lut, const unsigned char* lut_u8, float* partials,
+                    double* out, unsigned char* canvas, int Hc, int Wc, int row0, int col0, hipStream_t s);
+int pack_u8_launch(const float* x, long sb, long sy, long sx, long sc, int B, int h, int w, float scale, float shift, unsigned char* canvas,
+                   int Hc, int Wc, int row0, int col0, hipStream_t s);
+int novel_view_finish_launch(const BtsNovelViews* a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------------------------
+// small helpers of the host layer
+// ---------------------------------------------------------------------------------------------------------------
+inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// tiles (64 texels each, either geometry: bts_common.h) of the map of an H x W frame at feat_shift fs
+inline long map_tiles(int H, int W, int fs) { return ((long)(H >> fs) * (W >> fs) + 63) / 64; }
+
+// the `Wm` of the projection passes: the map's width where the cfg's tile flags are 16 x 4 blocks, 0 where they are runs of 64 texels
+inline int tile_geometry_width(const BtsFieldCfg* cfg) { return cfg->tile_blocks ? cfg->W >> cfg->feat_shift : 0; }
+
+// the cameras the hand-over kernels leave in one block: K_enc (n, 9) | w2c_enc (n, 16) | K_r (n, nv, 9) | w2c_r (n, nv, 16)
+struct CamBlock {
+  float *K_enc, *w2c_enc, *K_r, *w2c_r;
+};
+inline CamBlock split_cams(float* cams, int n, int nv) {
+  CamBlock c;
+  c.K_enc = cams;
+  c.w2c_enc = c.K_enc + (long)n * 9;
+  c.K_r = c.w2c_enc + (long)n * 16;
+  c.w2c_r = c.K_r + (long)n * nv * 9;
+  return c;
+}
+
+}  // namespace bts

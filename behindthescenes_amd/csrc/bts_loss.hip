@@ -13,11 +13,10 @@
 // 3x3 neighbourhoods go through zero-bordered LDS planes private to the wave (LDS operations of one wave execute in order: no barrier).
 #include <hip/hip_runtime.h>
 
-#include "../../include/bts_render.h"
+#include "bts_host.h"
 
 namespace bts {
 
-void set_error(const char* fmt, const char* what, long a = 0, long b = 0, long c = 0);
 
 struct LossParams {
   const float* rgb;      // (B, nv, 3)

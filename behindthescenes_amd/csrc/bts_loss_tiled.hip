@@ -23,11 +23,10 @@
 // planes, so every hand-over is a real __syncthreads() (the wave kernel's wave-scope fence is not enough here).
 #include <hip/hip_runtime.h>
 
-#include "../../include/bts_render.h"
+#include "bts_host.h"
 
 namespace bts {
 
-void set_error(const char* fmt, const char* what, long a = 0, long b = 0, long c = 0);
 
 namespace {
 

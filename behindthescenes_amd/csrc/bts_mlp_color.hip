@@ -13,15 +13,9 @@
 // Passes B (scatter_kernel<HD, true>: dG += w_tap u0) and C (dwpe_rows_kernel: dW_pe, db_in) of bts_bwd_rows.hip run unchanged on
 // what pass A leaves.  Replaces nerf.py:210-313 + models_bts.py:266-338 (sample_color=False) + resnetfc.py:132-184 of the reference.
 #include "bts_bwd.h"
+#include "bts_host.h"
 
 namespace bts {
-
-FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t);
-int render_grid(const FwdParams& p);
-int device_cu_count();
-int launch_scatter_rows(const BwdParams& bp, const float* u0_ws, int HD, int n, hipStream_t s);
-int launch_dwpe_rows(const FwdParams& p, const float* u0_ws, float* d_mlp, float* flush_ws, int C, int HD, int NB, int n, int grid, hipStream_t s,
-                     bool flush_clean);
 
 constexpr int kMcThreads = 256;   // samples of one work-group iteration (whole rays: K <= 256)
 constexpr int kMcOut = 4;         // lin_out rows: density + three colour channels
@@ -546,13 +540,12 @@ int mlp_color_field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t,
   });
 }
 
-static size_t mc_align16(size_t b) { return (b + 15) & ~(size_t)15; }
 static size_t mc_flush_bytes(const BtsFieldCfg* cfg) { return sizeof(float) * kFlushSlots * kFlushRows * (size_t)cfg->d_hidden; }
 
 // the row layout of bts_render_bwd's general path: u0 (B, K, HD), g_s (B, K), pass C's slot copies
 size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a) {
   const size_t samples = (size_t)cfg->n * (size_t)a->rays_per_sample * (size_t)a->K;
-  return mc_align16(samples * ((size_t)cfg->d_hidden + 1) * sizeof(float)) + mc_flush_bytes(cfg);
+  return align16(samples * ((size_t)cfg->d_hidden + 1) * sizeof(float)) + mc_flush_bytes(cfg);
 }
 
 int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
@@ -596,9 +589,9 @@ int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, 
   bp.g_rgb = g->g_rgb, bp.g_depth = g->g_depth;
   bp.d_proj = g->d_proj_nhwc, bp.d_mlp = g->d_mlp_params, bp.d_empty_proj = g->d_empty_proj;
   bp.gs_ws = mp.gs_ws;
-  bp.flush_ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + mc_align16(samples * ((size_t)cfg->d_hidden + 1) * sizeof(float)));
+  bp.flush_ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + align16(samples * ((size_t)cfg->d_hidden + 1) * sizeof(float)));
   bp.tiles = bp.d_proj ? g->d_proj_tiles : nullptr;
-  bp.tiles_per_img = (int)((((long)(cfg->H >> cfg->feat_shift) * (cfg->W >> cfg->feat_shift)) + 63) / 64);
+  bp.tiles_per_img = (int)map_tiles(cfg->H, cfg->W, cfg->feat_shift);
   bp.tile_tw = tile_cols(cfg->H >> cfg->feat_shift, cfg->W >> cfg->feat_shift, cfg->tile_blocks);
   if (want_c) rc = launch_dwpe_rows(bp.f, mp.u0_ws, bp.d_mlp, bp.flush_ws, cfg->C, cfg->d_hidden, cfg->n_blocks, cfg->n, grid, s, false);
   if (rc == BTS_OK && want_b) rc = launch_scatter_rows(bp, mp.u0_ws, cfg->d_hidden, cfg->n, s);

@@ -22,7 +22,7 @@
 //   - the mean of S runs over the interior only (skimage crops (win_size - 1) // 2 = 3 pixels from every side), so the filter's
 //     reflect border never reaches the result and no border mode exists here.
 // Outside the contract: NaN or inf in either image (nothing faults, the row is unspecified).
-#include "bts_common.h"
+#include "bts_host.h"
 
 namespace bts {
 

@@ -2,7 +2,7 @@
 // fp32 kernels: bin the clouds by angle and take a minimum per bin, finish one (362, 2) table per (slice, cloud), look every query
 // point up in the tables of its slice, classify the points into six counters.  No matrix pipe, no inline assembly; every reduction is
 // an integer / bit-pattern atomic, so reruns are bit-identical.
-#include "bts_common.h"
+#include "bts_host.h"
 
 namespace bts {
 

@@ -7,11 +7,10 @@
 // These are HBM-bound streaming kernels (read 4*C + write 4*Hd bytes per pixel); the contraction rides along on
 // v_mfma_f32_32x32x2_f32 so that the pass costs what the plain NCHW<->NHWC transposes it replaces would cost.  Layouts
 // are chosen so that every global access is a coalesced row: F is read along pixels (NCHW rows), G / dG along channels.
-#include "bts_common.h"
+#include "bts_host.h"
 
 namespace bts {
 
-void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
 
 // texel (index inside its image) of slot i of the tile whose first texel is p0: bts_common.h, tile_rs
 __device__ __forceinline__ int tile_px(int p0, int i, int rs) { return p0 + i + (i >> 4) * rs; }
@@ -561,18 +560,7 @@ __global__ __launch_bounds__(256) void compact_tiles_kernel(unsigned char* __res
 #define BTS_LIST_MIN_TILES 4096
 #endif
 // workspace of the LIST form for a map of n_tiles tiles: the count (16 bytes), the indices, the copy of the flags
-size_t project_bwd_list_bytes(long n_tiles) { return (size_t)(4 + n_tiles) * sizeof(int) + (size_t)n_tiles + 16; }
-
-static int prep_cus() {
-  static thread_local int cus[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
+static size_t project_bwd_list_bytes(long n_tiles) { return (size_t)(4 + n_tiles) * sizeof(int) + (size_t)n_tiles + 16; }
 
 template <int C, int HD>
 static int run_fwd(const float* feat, const float* mlp, int N, int HW, float* proj, const unsigned char* tiles, bool feat_cl, hipStream_t s, int Wm,
@@ -580,7 +568,7 @@ static int run_fwd(const float* feat, const float* mlp, int N, int HW, float* pr
   const int tpi = (HW + 63) / 64;
   const int tw = Wm > 0 && HW % Wm == 0 ? tile_cols(HW / Wm, Wm, 1) : 0;   // (Wm = 0: runs of 64 consecutive texels)
   const long n_tiles = (long)N * tpi;
-  const long want = (n_tiles + 3) / 4, cap = 4L * prep_cus();     // persistent: <= 4 work-groups per CU (16 KB of LDS each)
+  const long want = (n_tiles + 3) / 4, cap = 4L * device_cu_count();     // persistent: <= 4 work-groups per CU (16 KB of LDS each)
   const int grid = (int)(want < cap ? want : cap);
   if (list_ws && tiles && n_tiles >= BTS_LIST_MIN_TILES && list_ws_bytes >= project_bwd_list_bytes(n_tiles)) {
     int* list = static_cast<int*>(list_ws);    // the balanced form (see project_bwd_tiles_kernel): the flags stay as they are
@@ -601,7 +589,7 @@ static int run_bwd(const float* feat, const float* dproj, const float* mlp, int 
   const int tiles = (HW + 63) / 64;
   const long n_tiles = (long)N * tiles;
   const int nr = (dfeat && d_mlp) ? 2 : 4;
-  const long want = (n_tiles + nr - 1) / nr, cap = 2L * prep_cus();   // <= 2 work-groups per CU: the roles hold up to 256 VGPRs
+  const long want = (n_tiles + nr - 1) / nr, cap = 2L * device_cu_count();   // <= 2 work-groups per CU: the roles hold up to 256 VGPRs
   project_bwd_kernel<C, HD><<<(int)(want < cap ? want : cap), 256, 0, s>>>(feat, dproj, mlp, dfeat, d_mlp, HW, tiles, (int)n_tiles);
   return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
 }
@@ -613,7 +601,7 @@ static int run_bwd_tiles(const float* feat, float* dproj, unsigned char* tiles, 
   const int tpi = (HW + 63) / 64;
   const int tw = Wm > 0 && HW % Wm == 0 ? tile_cols(HW / Wm, Wm, 1) : 0;
   const long n_tiles = (long)N * tpi;
-  const long want = (n_tiles + 3) / 4, cap = 2L * prep_cus();
+  const long want = (n_tiles + 3) / 4, cap = 2L * device_cu_count();
   const int grid = (int)(want < cap ? want : cap);
   // the balanced form: worth its two small extra launches on maps of a few thousand tiles and more (below that a wave holds a tile or two)
   if (list_ws && tiles && clear && n_tiles >= BTS_LIST_MIN_TILES && list_ws_bytes >= project_bwd_list_bytes(n_tiles)) {
@@ -674,10 +662,8 @@ __global__ __launch_bounds__(256) void mark_tiles_kernel(const float* __restrict
 
 int mark_tiles_impl(const float* rays, const float* z_samp, const float* jitter, const float* w2c_enc, const float* K_enc, long B, int Bp, int K, int lindisp,
                     int H, int W, int fs, unsigned char* tiles, hipStream_t s, int blocks) {
-  const long total = B * K;
-  const int tpi = (int)((((long)(H >> fs) * (W >> fs)) + 63) / 64);
+  const int tpi = (int)map_tiles(H, W, fs);
   const long want = (B + 3) / 4;   // one ray per wave iteration
-  (void)total;
   mark_tiles_kernel<<<(int)(want < 8192 ? want : 8192), 256, 0, s>>>(rays, z_samp, jitter, w2c_enc, K_enc, B, Bp, K, lindisp, H, W, fs, tpi, tiles,
                                                                      tile_cols(H >> fs, W >> fs, blocks));
   return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;

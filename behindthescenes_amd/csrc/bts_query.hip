@@ -14,6 +14,7 @@
 #define BTS_NO_LAUNCH_GLUE
 #undef BTS_GATHER_REGS   // (the register-gather A/B build, variants/libbts_gatherregs.so, concerns the render kernels: the query kernel exist in the LDS-gather form only)
 #include "bts_render_kernel.h"
+#include "bts_host.h"
 
 namespace bts {
 
@@ -276,10 +277,6 @@ __global__ __launch_bounds__(256, 2) void query_kernel_p(const QueryParams qp) {
     }
   }
 }
-
-FwdParams make_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t);
-int render_grid(const FwdParams& p);
-int render_chunk_log2(int grid, long groups);
 
 template <int C, int HD, int NB>
 static int launch_query_nv(const QueryParams& qp, int grid, hipStream_t s) {

@@ -8,36 +8,11 @@
 // between them: ~20 ctypes calls, ~40 allocator round trips, the autograd nodes and ~25 small torch kernels per exp_kitti_raw.yaml
 // step, which took longer to issue (1.1 ms) than the GPU needed to run the step's kernels (0.5 ms).
 // Reference: BTSWrapper.forward (models/bts/trainer.py:208-259) + the criterion call of utils/base_trainer.py:287-297.
-#include "bts_common.h"
+#include "bts_host.h"
 
 #include <cstring>
 
 namespace bts {
-
-void set_error(const char* fmt, const char* a = "", long b = 0, long c = 0, long d = 0);
-bool shape_supported(int C, int HD, int NB);
-
-int patch_rays_views_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
-                            int c, int H, int W, int P, int ph, int pw, float zn, float zf, int norm_dir, float* rays, float* gt, int n_ids,
-                            const int* ids, float gt_scale, float gt_shift, hipStream_t s);
-int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s);
-int project_features_impl(int C, int HD, const float* feat, const float* mlp, int N, int HW, float* proj, const unsigned char* tiles, hipStream_t s,
-                          bool feat_cl = false, int Wm = 0,     // Wm: the map's width when `tiles` are 16 x 4 blocks (BtsFieldCfg.tile_blocks), 0 = runs of 64 texels
-                          void* list_ws = nullptr, size_t list_ws_bytes = 0);   // scratch for the balanced (list-driven) form
-int mark_tiles_impl(const float* rays, const float* z_samp, const float* jitter, const float* w2c_enc, const float* K_enc, long B, int Bp, int K, int lindisp,
-                    int H, int W, int fs, unsigned char* tiles, hipStream_t s, int blocks);
-int project_features_bwd_tiles_impl(int C, int HD, const float* feat, float* dproj, unsigned char* tiles, const float* mlp, int N, int HW, float* dfeat,
-                                    float* d_mlp, int clear, hipStream_t s, bool feat_cl = false, int Wm = 0, void* list_ws = nullptr,
-                                    size_t list_ws_bytes = 0);   // list_ws: scratch for the balanced (list-driven) form, project_bwd_list_bytes(N * tiles) bytes
-int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
-size_t render_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
-int render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* ws, size_t ws_bytes,
-                    hipStream_t s, bool flush_clean);
-void render_bwd_flush_region(const BtsFieldCfg* cfg, const BtsRenderArgs* a, void* workspace, float** ptr, size_t* bytes);
-int handover_launch(const float* Ks, const float* poses, const float* images, const int* pv, const int* py, const int* px, int n, int v, int id_enc, int nv,
-                    const int* ids_render, int n_loss, const int* ids_loss, int H, int W, int P, int ph, int pw, float z_near, float z_far, float scale,
-                    float shift, float* cams, float* imgs, float* rays, float* gt, int n_zero, unsigned char* const* zero, const long* zero_bytes,
-                    hipStream_t s);
 
 // ---- loss_vals = loss_matrix . [per-scale sums of the loss pass' per-patch parts]: one work-group, lanes stride the patches
 struct FinishParams {
@@ -226,17 +201,13 @@ static ScaleView scale_view(const BtsTrainStep* st, int s) {
   ScaleView v;
   memset(&v, 0, sizeof(v));
   const BtsTrainScale& q = st->scale[s];
-  const int n = st->cfg.n, nv = st->cfg.nv;
   v.cfg = st->cfg;
   v.cfg.feat_shift = q.feat_shift;
   // the scale's tile geometry: 16 x 4 blocks for a channels-last map, runs of 64 texels for an NCHW one (BtsFieldCfg.tile_blocks: what each
   // layout is faster with); the step's own flag arrays never leave the two calls, so the step decides for itself
   v.cfg.tile_blocks = q.feat_channels_last != 0;
-  float* K_enc = st->cams;
-  float* w2c_enc = K_enc + (long)n * 9;
-  float* K_r = w2c_enc + (long)n * 16;
-  float* w2c_r = K_r + (long)n * nv * 9;
-  v.t.proj_nhwc = q.proj_nhwc, v.t.K_enc = K_enc, v.t.w2c_enc = w2c_enc, v.t.imgs_nhwc4 = st->imgs_nhwc4, v.t.K_r = K_r, v.t.w2c_r = w2c_r;
+  const CamBlock cam = split_cams(st->cams, st->cfg.n, st->cfg.nv);
+  v.t.proj_nhwc = q.proj_nhwc, v.t.K_enc = cam.K_enc, v.t.w2c_enc = cam.w2c_enc, v.t.imgs_nhwc4 = st->imgs_nhwc4, v.t.K_r = cam.K_r, v.t.w2c_r = cam.w2c_r;
   v.t.empty_feature = st->cfg.learn_empty ? st->empty_feature : nullptr, v.t.mlp_params = st->mlp_params;
   v.a.rays_per_sample = st->P * st->ph * st->pw, v.a.K = st->K, v.a.hard_alpha_cap = st->hard_alpha_cap, v.a.white_bkgd = 0;
   v.a.rays = st->rays, v.a.lindisp = st->lindisp;
@@ -249,7 +220,7 @@ int train_step_fwd_impl(const BtsTrainStep* st, hipStream_t main_stream) {
   const int n = c.n, nv = c.nv, Bp = st->P * st->ph * st->pw;
   unsigned char* zero[BTS_MAX_SCALES];
   long zero_bytes[BTS_MAX_SCALES];
-  for (int s = 0; s < st->n_scales; ++s) zero[s] = st->scale[s].sampled_tiles, zero_bytes[s] = (long)n * ((map_texels(st, s) + 63) / 64);
+  for (int s = 0; s < st->n_scales; ++s) zero[s] = st->scale[s].sampled_tiles, zero_bytes[s] = (long)n * map_tiles(c.H, c.W, st->scale[s].feat_shift);
   int rc = handover_launch(st->Ks, st->poses_c2w, st->images, st->patch_v, st->patch_y, st->patch_x, n, st->v, st->id_encoder, nv, st->ids_render, st->n_loss,
                            st->ids_loss, c.H, c.W, st->P, st->ph, st->pw, st->z_near, st->z_far, st->img_scale, st->img_shift, st->cams, st->imgs_nhwc4,
                            st->rays, st->rgb_gt, st->n_scales, zero, zero_bytes, stream);
@@ -275,7 +246,7 @@ int train_step_fwd_impl(const BtsTrainStep* st, hipStream_t main_stream) {
     rc = mark_tiles_impl(st->rays, nullptr, q.jitter, v.t.w2c_enc, v.t.K_enc, (long)n * Bp, Bp, st->K, st->lindisp, c.H, c.W, q.feat_shift, q.sampled_tiles,
                          stream, v.cfg.tile_blocks);
     if (!rc) rc = project_features_impl(c.C, c.d_hidden, q.feat_nchw, st->mlp_params, n, (int)texels, q.proj_nhwc, q.sampled_tiles, stream, q.feat_channels_last != 0,
-                                        v.cfg.tile_blocks ? c.W >> q.feat_shift : 0,
+                                        tile_geometry_width(&v.cfg),
                                         // the backward's workspace is idle during the forward: the scale's slice of it holds the tile list
                                         fwd_ws ? static_cast<char*>(st->bwd_workspace) + fwd_ws * (size_t)s : nullptr, fwd_ws);
     if (rc) {
@@ -377,14 +348,14 @@ int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t
       set_error("%s: bwd_workspace too small (%ld bytes needed)", "bts_train_step_bwd", (long)need);
       return BTS_E_WORKSPACE;
     }
-    int rc = render_bwd_impl(&v.cfg, &v.t, &v.a, &g, ws, ws_bytes, stream, true);
+    int rc = render_bwd_impl(&v.cfg, &v.t, &v.a, &g, ws, stream, true);
     if (rc) return rc;
     if (need_map) {
       float* slots;
       size_t slot_bytes;
       render_bwd_flush_region(&v.cfg, &v.a, ws, &slots, &slot_bytes);   // (pass C's slot copies at the END of the slice stay zero between the scales)
       rc = project_features_bwd_tiles_impl(c.C, c.d_hidden, q.feat_nchw, q.d_proj_nhwc, q.d_proj_tiles, st->mlp_params, n, (int)map_texels(st, s),
-                                           q.d_feat_nchw, st->d_mlp_params, 1, stream, q.feat_channels_last != 0, v.cfg.tile_blocks ? c.W >> q.feat_shift : 0,
+                                           q.d_feat_nchw, st->d_mlp_params, 1, stream, q.feat_channels_last != 0, tile_geometry_width(&v.cfg),
                                            // the scale's slice of the backward workspace is dead by now (everything bts_render_bwd parked there was
                                            // read by its own passes, enqueued above on this stream) except pass C's slot copies at its END
                                            ws, need > slot_bytes ? need - slot_bytes : 0);
@@ -408,17 +379,6 @@ int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t
   return BTS_OK;
 }
 
-int eval_handover_launch(const float* Ks, const float* poses, const float* images, int n, int v, int id_enc, int nv, const int* ids_render, int H, int W,
-                         float z_near, float z_far, int norm_dir, float scale, float shift, float* cams, float* inv_K, float* imgs, float* rays,
-                         float* rgb_gt, unsigned* sched, hipStream_t s);
-int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s);   // bts_fwd.hip
-int render_chunk_log2(int grid, long groups);
-long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div);
-int distance_to_z_launch(const float* depths, const float* invK, int N, int H, int W, float* out, hipStream_t s);
-int project_features_plain(int C, int HD, const float* feat, const float* mlp, int N, int HW, float* proj, hipStream_t s, bool channels_last) {
-  return project_features_impl(C, HD, feat, mlp, N, HW, proj, nullptr, s, channels_last);
-}
-
 int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipStream_t stream) {
   const BtsFieldCfg& c = f->cfg;
   const int n = c.n, nv = c.nv;
@@ -426,7 +386,7 @@ int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipSt
   // the render's ticket counter)
   int rc = eval_handover_launch(f->Ks, f->poses_c2w, f->images, n, f->v, f->id_encoder, nv, f->ids_render, c.H, c.W, f->z_near, f->z_far, f->norm_dir,
                                 f->img_scale, f->img_shift, f->cams, f->depth_z ? f->inv_K : nullptr, f->imgs_nhwc4, f->rays, rgb_gt, sched, stream);
-  if (!rc) rc = project_features_plain(c.C, c.d_hidden, f->feat_nchw, f->mlp_params, n, c.H * c.W, f->proj_nhwc, stream, f->feat_channels_last != 0);
+  if (!rc) rc = project_features_impl(c.C, c.d_hidden, f->feat_nchw, f->mlp_params, n, c.H * c.W, f->proj_nhwc, nullptr, stream, f->feat_channels_last != 0);
   if (rc) {
     set_error("%s: a hand-over kernel launch failed", "bts_eval_frame");
     return rc;
@@ -435,11 +395,8 @@ int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipSt
   cfg.feat_shift = 0;
   BtsFieldTensors t;
   memset(&t, 0, sizeof(t));
-  float* K_enc = f->cams;
-  float* w2c_enc = K_enc + (long)n * 9;
-  float* K_r = w2c_enc + (long)n * 16;
-  float* w2c_r = K_r + (long)n * nv * 9;
-  t.proj_nhwc = f->proj_nhwc, t.K_enc = K_enc, t.w2c_enc = w2c_enc, t.imgs_nhwc4 = f->imgs_nhwc4, t.K_r = K_r, t.w2c_r = w2c_r;
+  const CamBlock cam = split_cams(f->cams, n, nv);
+  t.proj_nhwc = f->proj_nhwc, t.K_enc = cam.K_enc, t.w2c_enc = cam.w2c_enc, t.imgs_nhwc4 = f->imgs_nhwc4, t.K_r = cam.K_r, t.w2c_r = cam.w2c_r;
   t.empty_feature = c.learn_empty ? f->empty_feature : nullptr, t.mlp_params = f->mlp_params;
   BtsRenderArgs a;
   memset(&a, 0, sizeof(a));

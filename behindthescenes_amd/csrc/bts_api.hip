@@ -681,7 +681,7 @@ int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, co
 
   if (int rc = field_query_impl(cfg, t, a->q_pts, P, 1, nullptr, nullptr, sigma, s)) return rc;
   if (hipMemsetAsync(a->counts, 0, 7 * sizeof(int32_t), s) != hipSuccess) {
-    (void)hipGetLastError();
+    (void)launch_code();
     set_error("%s: kernel launch failed", "bts_bbox_occupancy_eval");
     return BTS_E_LAUNCH;
   }

@@ -47,7 +47,7 @@ int transpose_launch(const float* src, float* dst, int N, int C, int H, int W, b
   dim3 grid((HW + 63) / 64, (C + 63) / 64, N);
   if (to_nhwc) transpose_kernel<true><<<grid, 256, 0, s>>>(src, dst, C, HW);
   else transpose_kernel<false><<<grid, 256, 0, s>>>(src, dst, C, HW);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // (N, 3, H, W) -> (N, H, W, 4) rgb0, x*scale + shift  (encode's images * .5 + .5, models_bts.py:82).  With a frame table (nv > 0) the
@@ -98,7 +98,7 @@ int pack_rgb_launch(const float* src, float* dst, int N, int H, int W, float sca
   FrameIds f;
   f.nv = 0, f.v = 0;
   pack_rgb_kernel<<<grid, 256, 0, s>>>(src, reinterpret_cast<float4*>(dst), HW, total, scale, shift, f);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // the ray of pixel (x, y) of a view: [c2w translation, R @ unproj(pixel), near, far]  (util.py:113-149, 244-273)
@@ -148,7 +148,7 @@ int gen_rays_launch(const float* poses, const float* projs, int V, int H, int W,
   const long total = (long)V * H * W;
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   gen_rays_kernel<<<grid, 256, 0, s>>>(poses, projs, V, H, W, zn, zf, norm_dir, reinterpret_cast<float4*>(rays));
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // patch_rays: PatchRaySampler.sample on device (ray_sampler.py:125-162).  Per sample P patches (view, y0, x0) of ph x pw pixels:
@@ -204,7 +204,7 @@ static int patch_rays_views_launch(const float* poses, const float* projs, const
   for (int j = 0; j < BTS_MAX_LOSS_VIEWS; ++j) m.ids[j] = j < n_ids ? ids[j] : 0;
   patch_rays_kernel<<<grid, 256, 0, s>>>(poses, projs, images, pv, py, px, n, v, c, H, W, P, ph, pw, zn, zf, norm_dir,
                                          reinterpret_cast<float4*>(rays), images ? gt : nullptr, m, gt_scale, gt_shift);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 int patch_rays_launch(const float* poses, const float* projs, const float* images, const int* pv, const int* py, const int* px, int n, int v,
@@ -229,7 +229,7 @@ int sample_coarse_launch(const float* rays, const float* u, long B, int K, int l
   const long total = B * K;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   sample_coarse_kernel<<<grid, 256, 0, s>>>(rays, u, B, K, lindisp, z);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // distance_to_z: z = depth * cam.z / |cam|,  cam = inv_K @ [gx, gy, 1]
@@ -260,7 +260,7 @@ int distance_to_z_launch(const float* depths, const float* invK, int N, int H, i
   const long total = (long)N * H * W;
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   distance_to_z_kernel<<<grid, 256, 0, s>>>(depths, invK, N, H, W, out);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -409,7 +409,7 @@ int handover_launch(const float* Ks, const float* poses, const float* images, co
   p.b_patch = (int)((ray_total + 255) / 256 < 1024 ? (ray_total + 255) / 256 : 1024);
   p.b_zero = n_zero ? (int)((zmax / 4 + 255) / 256 < 64 ? (zmax / 4 + 255) / 256 + 1 : 64) : 0;
   handover_kernel<<<p.b_cam + p.b_pack + p.b_patch + p.b_zero, 256, 0, s>>>(p);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // ---- the hand-over of an evaluation frame in ONE launch (bts_eval_frame_gt): cameras, the inverse intrinsics distance_to_z reads behind the
@@ -499,7 +499,7 @@ int eval_handover_launch(const float* Ks, const float* poses, const float* image
   p.b_rays = (int)((ray_total + 255) / 256 < 2048 ? (ray_total + 255) / 256 : 2048);
   p.b_gt = (int)((gt_items + 255) / 256 < 2048 ? (gt_items + 255) / 256 : 2048);
   eval_handover_kernel<<<p.b_cam + p.b_inv + p.b_pack + p.b_rays + p.b_gt, 256, 0, s>>>(p);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_t s) {
@@ -507,7 +507,7 @@ int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_
   if (dim == 3) invert_small_kernel<3><<<grid, 64, 0, s>>>(src, dst, N);
   else if (dim == 4) invert_small_kernel<4><<<grid, 64, 0, s>>>(src, dst, N);
   else return BTS_E_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // gen_rays with the near / far planes per view from a (V, 2) device array (bts_novel_views: gen_vid_transition.py:126-138 moves them
@@ -532,7 +532,7 @@ int gen_rays_nf_launch(const float* poses, const float* projs, const float* near
   const long total = (long)V * H * W;
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   gen_rays_nf_kernel<<<grid, 256, 0, s>>>(poses, projs, near_far, V, H, W, norm_dir, reinterpret_cast<float4*>(rays));
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 }  // namespace bts

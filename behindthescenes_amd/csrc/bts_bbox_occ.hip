@@ -190,7 +190,6 @@ __global__ __launch_bounds__(256) void bbox_metrics_kernel(const float* __restri
   }
 }
 
-static int launched() { return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH; }
 
 // v_offsets, f_offsets: HOST arrays of B + 1 entries (validated by the caller).  n_active: one int32 the active boxes are ADDED to, or NULL
 int bbox_bounds_launch(const float* vertices, const int* faces, const int* v_offsets, const int* f_offsets, int B, const float* to_key,
@@ -200,7 +199,7 @@ int bbox_bounds_launch(const float* vertices, const int* faces, const int* v_off
     BBoxOffsets offs;
     for (int k = 0; k <= nb; ++k) offs.v[k] = v_offsets[box0 + k], offs.f[k] = f_offsets[box0 + k];
     bbox_bounds_kernel<<<nb, 64, 0, s>>>(vertices, faces, offs, box0, to_key, proj, max_d, tables, n_faces, active, n_active);
-    if (int rc = launched()) return rc;
+    if (int rc = launch_code()) return rc;
   }
   return BTS_OK;
 }
@@ -209,13 +208,13 @@ int bbox_pseudo_depth_launch(const float* rays, int ph, int pw, const float* seg
                              const unsigned char* active, const float* semantic_id, int B, float* pseudo_depth, hipStream_t s) {
   const int R = ph * pw;
   if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pseudo_depth), (int)kPosInfBits, (size_t)R, s) != hipSuccess) {
-    (void)hipGetLastError();
+    (void)launch_code();
     return BTS_E_LAUNCH;
   }
   const float sh = (float)hs / (float)ph, sw = (float)ws / (float)pw;
   bbox_pseudo_depth_kernel<<<dim3((R + 255) / 256, (B + kChunk - 1) / kChunk), 256, 0, s>>>(rays, R, pw, seg, hs, ws, sh, sw, tables, n_faces, active,
                                                                                            semantic_id, B, reinterpret_cast<unsigned*>(pseudo_depth));
-  return launched();
+  return launch_code();
 }
 
 // counts: the six cells, ADDED to (the caller zeroes them)
@@ -224,7 +223,7 @@ int bbox_metrics_launch(const float* q_pts, int P, const float* sigma, const flo
                         unsigned char* masks, hipStream_t s) {
   bbox_metrics_kernel<<<(P + 255) / 256, 256, 0, s>>>(q_pts, P, sigma, pseudo, depth_z, H, W, proj, tables, n_faces, active, B, occ_threshold, counts,
                                                      masks);
-  return launched();
+  return launch_code();
 }
 
 }  // namespace bts

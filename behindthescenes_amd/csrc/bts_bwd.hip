@@ -60,7 +60,7 @@ int render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsR
     return BTS_E_UNSUPPORTED;
   }
   // the RE10K model at its own sample count (32 < K <= 48, exp_re10k.yaml: 48): four rays in three wave iterations (rowsb_kernel<PK>)
-  const bool pack48 = cfg->C == 32 && cfg->d_hidden == 32 && cfg->n_blocks == 1 && a->K > 32 && a->K <= 48 && a->rays_per_sample % 4 == 0;
+  const bool pack48 = Re10kShape::is(cfg->C, cfg->d_hidden, cfg->n_blocks) && a->K > 32 && a->K <= 48 && a->rays_per_sample % 4 == 0;
   if (pack48) bp.f.lpr = 48, bp.f.groups /= 4;
   const int grid = render_grid(bp.f);
   bp.f.chunk_log2 = render_chunk_log2(grid, bp.f.groups);

@@ -816,26 +816,17 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
 // ---------------------------------------------------------------------------------------------------------------
 template <int C, int HD, int NB>
 static int launch_rowsb(const BwdParams& bp, const RowsbOut& ro, int grid, hipStream_t s) {
-  constexpr int dyn = 4 * kGatherLdsPerWave;
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-    kern<<<grid, 256, dyn, s>>>(bp, ro);
-  };
-  if constexpr (NB == 1) {   // the 48-lane mode is built for the RE10K model (rowsb_packs_48 in bts_bwd.hip names the same condition)
-    if (bp.f.lpr == 48) {
-      if (bp.f.nv <= 1) go(rowsb_kernel<C, HD, NB, 1, true>);
-      else if (bp.f.nv <= 2) go(rowsb_kernel<C, HD, NB, 2, true>);
-      else if (bp.f.nv <= 4) go(rowsb_kernel<C, HD, NB, 4, true>);
-      else go(rowsb_kernel<C, HD, NB, 8, true>);
-      return launch_status();
-    }
-  }
-  if (bp.f.lpr != 64) return BTS_E_UNSUPPORTED;
-  if (bp.f.nv <= 1) go(rowsb_kernel<C, HD, NB, 1>);
-  else if (bp.f.nv <= 2) go(rowsb_kernel<C, HD, NB, 2>);
-  else if (bp.f.nv <= 4) go(rowsb_kernel<C, HD, NB, 4>);
-  else go(rowsb_kernel<C, HD, NB, 8>);
-  return launch_status();
+  return with_nvmax(bp.f.nv, [&](auto nvmax) {
+    auto go = [&](auto kern) {
+      launch_dyn_lds(kern, grid, 4 * kGatherLdsPerWave, s, bp, ro);
+      return launch_check(kBwdLaunchFailed);
+    };
+    // the 48-lane mode is built for the RE10K model alone (pack48 in bts_bwd.hip names the same shape)
+    if constexpr (std::is_same<Shape<C, HD, NB>, Re10kShape>::value)
+      if (bp.f.lpr == 48) return go(rowsb_kernel<C, HD, NB, nvmax(), true>);
+    if (bp.f.lpr != 64) return (int)BTS_E_UNSUPPORTED;
+    return go(rowsb_kernel<C, HD, NB, nvmax()>);
+  });
 }
 
 // bp.gs_ws: (n*Bp, K) floats; u0_ws: (n*Bp, K, HD) floats; p.groups / chunk_log2 / lpr set for one ray per wave iteration
@@ -846,10 +837,7 @@ int launch_bwd_blocks(const BwdParams& bp, float* u0_ws, int C, int HD, int NB, 
   ro.ticks = nullptr;
   if (const char* e = getenv("BTS_DBG_PTR")) ro.ticks = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
-  int rc = BTS_E_UNSUPPORTED;
-  if (C == 64 && HD == 64 && NB == 0) rc = launch_rowsb<64, 64, 0>(bp, ro, grid, s);
-  else if (C == 32 && HD == 32 && NB == 1) rc = launch_rowsb<32, 32, 1>(bp, ro, grid, s);
-  else if (C == 32 && HD == 32 && NB == 0) rc = launch_rowsb<32, 32, 0>(bp, ro, grid, s);
+  int rc = with_shape(C, HD, NB, [&](auto sh) { return launch_rowsb<sh.C, sh.HD, sh.NB>(bp, ro, grid, s); });
   // pass C, then pass B, on the caller's stream (side by side they measured slower: launch_rows in bts_bwd_rows.hip)
   const bool want_b = bp.d_proj || bp.d_empty_proj, want_c = bp.d_mlp != nullptr;
   if (rc == BTS_OK && want_c) rc = launch_dwpe_rows(bp.f, u0_ws, bp.d_mlp, bp.flush_ws, C, HD, NB, n, grid, s, bp.flush_clean);

@@ -1229,20 +1229,15 @@ static int launch_rows(const BwdParams& bp, int n, int grid, hipStream_t s) {
 #else
   constexpr int dyn = 0;
 #endif
-  auto go = [&](auto kern) {
-    if (dyn) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-    kern<<<grid, 256, dyn, s>>>(bp);
-  };
-  if (p.nv <= 1) go(rows_kernel<C, HD, 1>);
-  else if (p.nv <= 2) go(rows_kernel<C, HD, 2>);
-  else if (p.nv <= 4) go(rows_kernel<C, HD, 4>);
-  else go(rows_kernel<C, HD, 8>);
-  hipError_t e = hipGetLastError();
+  int rc = with_nvmax(p.nv, [&](auto nvmax) {
+    launch_dyn_lds(rows_kernel<C, HD, nvmax()>, grid, dyn, s, bp);
+    return launch_check(kBwdLaunchFailed);
+  });
   // Pass C and pass B one after the other on the caller's stream.  Pass C on a side queue next to pass B MEASURED SLOWER (round 6,
   // profiles/r06o: backward +7 % at exp_kitti_360.yaml, +6 % exp_kitti_raw.yaml, +4 % exp_re10k.yaml): pass C is a persistent grid that
   // takes two work-groups' worth of every CU the moment it starts, and the scatter blocks then queue for what is left.
   const bool want_b = bp.d_proj || bp.d_empty_proj, want_c = bp.d_mlp != nullptr;
-  if (e == hipSuccess && want_c) {
+  if (rc == BTS_OK && want_c) {
     DwpeParams dp;
     dp.f = p, dp.pmask_ws = bp.pmask_ws, dp.gs_ws = bp.gs_ws, dp.d_mlp = bp.d_mlp, dp.slots = bp.flush_ws, dp.rays = (long)n * p.Bp;
     const long wgs = (dp.rays + 3) / 4;
@@ -1251,9 +1246,9 @@ static int launch_rows(const BwdParams& bp, int n, int grid, hipStream_t s) {
     if (!bp.flush_clean) (void)hipMemsetAsync(bp.flush_ws, 0, sizeof(float) * kFlushSlots * kFlushRows * HD, s);
     kern<<<(int)(wgs < grid ? wgs : grid), 256, DwpeLds::TOTAL, s>>>(dp);   // grid = 2 work-groups per CU
     dwpe_reduce_kernel<C, HD><<<(kFlushRows * HD + 255) / 256, 256, 0, s>>>(bp.flush_ws, bp.d_mlp);
-    e = hipGetLastError();
+    rc = launch_check(kBwdLaunchFailed);
   }
-  if (e == hipSuccess && want_b) {
+  if (rc == BTS_OK && want_b) {
     const MlpLayout ml{C + kPeDim, HD, 0};
     ScatterMaskParams sp;
     sp.f = p, sp.mask_ws = bp.mask_ws, sp.u0_ws = nullptr, sp.gs_ws = bp.gs_ws, sp.d_proj = bp.d_proj, sp.d_empty_proj = bp.d_empty_proj;
@@ -1265,13 +1260,9 @@ static int launch_rows(const BwdParams& bp, int n, int grid, hipStream_t s) {
     const long units = (long)n * sp.groups_per_sample * (HD / 32);
     scatter_segments(sp, units, p.K);
     scatter_kernel<HD><<<(int)(units * sp.nseg), 64, 0, s>>>(sp);
-    e = hipGetLastError();
+    rc = launch_check(kBwdLaunchFailed);
   }
-  if (e != hipSuccess) {
-    set_error("%s: backward kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
+  return rc;
 }
 
 // segments of the K steps per ray group: as many waves as the chip holds AT ONCE -- eight per CU, 20 KB of LDS each -- and not one more
@@ -1308,7 +1299,7 @@ int launch_scatter_rows(const BwdParams& bp, const float* u0_ws, int HD, int n, 
   if (HD == 64) scatter_kernel<64, true><<<(int)(units * sp.nseg), 64, 0, s>>>(sp);
   else if (HD == 32) scatter_kernel<32, true><<<(int)(units * sp.nseg), 64, 0, s>>>(sp);
   else return BTS_E_UNSUPPORTED;
-  return launch_status();
+  return launch_check(kBwdLaunchFailed);
 }
 
 int launch_dwpe_rows(const FwdParams& p, const float* u0_ws, float* d_mlp, float* flush_ws, int C, int HD, int NB, int n, int grid, hipStream_t s,
@@ -1322,22 +1313,17 @@ int launch_dwpe_rows(const FwdParams& p, const float* u0_ws, float* d_mlp, float
   const long cap = HD == 32 ? (long)grid / 2 * 3 : grid;   // grid = 2 work-groups per CU; this kernel fits 3 at d_hidden 32
   const int g = (int)(wgs < cap ? wgs : cap);
   if (!flush_clean) (void)hipMemsetAsync(flush_ws, 0, sizeof(float) * kFlushSlots * kFlushRows * HD, s);
-  if (C == 64 && HD == 64) {
-    dwpe_rows_kernel<64, 64><<<g, 256, 0, s>>>(dp);
-    dwpe_reduce_kernel<64, 64><<<(kFlushRows * 64 + 255) / 256, 256, 0, s>>>(flush_ws, d_mlp);
-  } else if (C == 32 && HD == 32) {
-    dwpe_rows_kernel<32, 32><<<g, 256, 0, s>>>(dp);
-    dwpe_reduce_kernel<32, 32><<<(kFlushRows * 32 + 255) / 256, 256, 0, s>>>(flush_ws, d_mlp);
-  } else return BTS_E_UNSUPPORTED;
   (void)NB;
-  return launch_status();
+  return with_width(C, HD, [&](auto w) {
+    dwpe_rows_kernel<w.C, w.HD><<<g, 256, 0, s>>>(dp);
+    dwpe_reduce_kernel<w.C, w.HD><<<(kFlushRows * w.HD + 255) / 256, 256, 0, s>>>(flush_ws, d_mlp);
+    return launch_check(kBwdLaunchFailed);
+  });
 }
 
 // bp.gs_ws: (n*Bp, K) floats, bp.mask_ws: (n*Bp, HD/32, K) dwords, bp.pmask_ws: (n*Bp, HD) x 64 bits; p.groups / chunk_log2 / lpr set for one ray per wave iteration
 int launch_bwd_rows(const BwdParams& bp, int C, int HD, int n, int grid, hipStream_t s) {
-  if (C == 64 && HD == 64) return launch_rows<64, 64>(bp, n, grid, s);
-  if (C == 32 && HD == 32) return launch_rows<32, 32>(bp, n, grid, s);
-  return BTS_E_UNSUPPORTED;
+  return with_width(C, HD, [&](auto w) { return launch_rows<w.C, w.HD>(bp, n, grid, s); });
 }
 
 }  // namespace bts

@@ -603,12 +603,7 @@ int conv3x3_fwd_impl(const BtsConv3x3* c, hipStream_t s) {
     (void)hipFuncSetAttribute((const void*)conv_fwd_bf_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kConvBfLds);
     conv_fwd_bf_kernel<false><<<grid, 64 * kConvWaves, kConvBfLds, s>>>(p);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: convolution forward launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
+  return launch_check("%s: convolution forward launch failed (%ld)");
 }
 
 size_t conv3x3_bwd_workspace_impl(const BtsConv3x3* c) {
@@ -662,12 +657,7 @@ int conv3x3_bwd_impl(const BtsConv3x3* c, const float* g_y, void* workspace, siz
     conv_wgrad_bf_kernel<<<grid, 768, 0, s>>>(q);
     conv_wgrad_reduce_kernel<<<(kWgradPart + 255) / 256, 256, 0, s>>>(part, grid, d_weight, d_bias);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: convolution backward launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
+  return launch_check("%s: convolution backward launch failed (%ld)");
 }
 
 }  // namespace bts

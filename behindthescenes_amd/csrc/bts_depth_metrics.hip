@@ -345,7 +345,6 @@ __global__ __launch_bounds__(64) void depth_finish_kernel(DepthGeom g, float* __
   }
 }
 
-static int launched() { return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH; }
 static int n_blocks(int Hg, int Wg) { return (int)(((long)Hg * Wg + kPerBlock - 1) / kPerBlock); }
 
 // histograms | notes | partials of the metrics pass | partials of the moments pass, each per frame
@@ -373,25 +372,25 @@ int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t 
   const dim3 grid(g.nblk, a->B);
   if (a->mode == 1) {
     if (hipMemsetAsync(g.hist, 0, (size_t)a->B * kHistFrame * 4, s) != hipSuccess) {
-      (void)hipGetLastError();
+      (void)launch_code();
       return BTS_E_LAUNCH;
     }
     depth_hist_kernel<0><<<grid, kThreads, 0, s>>>(g);
-    if (int rc = launched()) return rc;
+    if (int rc = launch_code()) return rc;
     depth_hist_kernel<1><<<grid, kThreads, 0, s>>>(g);
-    if (int rc = launched()) return rc;
+    if (int rc = launch_code()) return rc;
     depth_hist_kernel<2><<<grid, kThreads, 0, s>>>(g);
-    if (int rc = launched()) return rc;
+    if (int rc = launch_code()) return rc;
   } else if (a->mode == 2) {
     depth_moments_kernel<<<grid, kThreads, 0, s>>>(g);
-    if (int rc = launched()) return rc;
+    if (int rc = launch_code()) return rc;
     depth_solve_kernel<<<a->B, 64, 0, s>>>(g);
-    if (int rc = launched()) return rc;
+    if (int rc = launch_code()) return rc;
   }
   depth_terms_kernel<<<grid, kThreads, 0, s>>>(g);
-  if (int rc = launched()) return rc;
+  if (int rc = launch_code()) return rc;
   depth_finish_kernel<<<a->B, 64, 0, s>>>(g, a->metrics, a->counts);
-  return launched();
+  return launch_code();
 }
 
 }  // namespace bts

@@ -831,50 +831,26 @@ __global__ __launch_bounds__(256, 2) void render_kernel(const FwdParams p) {
 // ---------------------------------------------------------------------------------------------------------------
 // launch dispatch (instantiated in bts_fwd.hip: launch_field<true, false>, launch_render<false>)
 // ---------------------------------------------------------------------------------------------------------------
-template <int C, int HD, int NB, bool QUERY, bool PROJ>
-static int launch_nv(const FwdParams& p, int grid, hipStream_t s) {
-  if (p.nv <= 1) field_kernel<C, HD, NB, 1, QUERY, PROJ><<<grid, 256, 0, s>>>(p);
-  else if (p.nv <= 2) field_kernel<C, HD, NB, 2, QUERY, PROJ><<<grid, 256, 0, s>>>(p);
-  else if (p.nv <= 4) field_kernel<C, HD, NB, 4, QUERY, PROJ><<<grid, 256, 0, s>>>(p);
-  else field_kernel<C, HD, NB, 8, QUERY, PROJ><<<grid, 256, 0, s>>>(p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
-}
-
-template <int C, int HD, int NB, bool PROJ>
-static int launch_render_nv(const FwdParams& p, int grid, hipStream_t s) {
-  if (p.nv <= 1) render_kernel<C, HD, NB, 1, PROJ><<<grid, 256, 0, s>>>(p);
-  else if (p.nv <= 2) render_kernel<C, HD, NB, 2, PROJ><<<grid, 256, 0, s>>>(p);
-  else if (p.nv <= 4) render_kernel<C, HD, NB, 4, PROJ><<<grid, 256, 0, s>>>(p);
-  else render_kernel<C, HD, NB, 8, PROJ><<<grid, 256, 0, s>>>(p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
-}
-
 template <bool PROJ>
 int launch_render(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s) {
-  if (C == 64 && HD == 64 && NB == 0) return launch_render_nv<64, 64, 0, PROJ>(p, grid, s);
-  if (C == 32 && HD == 32 && NB == 1) return launch_render_nv<32, 32, 1, PROJ>(p, grid, s);
-  if (C == 32 && HD == 32 && NB == 0) return launch_render_nv<32, 32, 0, PROJ>(p, grid, s);
-  set_error("%s: unsupported MLP shape C=%ld d_hidden=%ld n_blocks=%ld", "bts", C, HD, NB);
-  return BTS_E_UNSUPPORTED;
+  return with_shape(C, HD, NB, [&](auto sh) {
+    using S = decltype(sh);
+    return with_nvmax(p.nv, [&](auto nvmax) {
+      render_kernel<S::C, S::HD, S::NB, nvmax(), PROJ><<<grid, 256, 0, s>>>(p);
+      return launch_check();
+    });
+  });
 }
 
 template <bool QUERY, bool PROJ>
 int launch_field(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s) {
-  if (C == 64 && HD == 64 && NB == 0) return launch_nv<64, 64, 0, QUERY, PROJ>(p, grid, s);
-  if (C == 32 && HD == 32 && NB == 1) return launch_nv<32, 32, 1, QUERY, PROJ>(p, grid, s);
-  if (C == 32 && HD == 32 && NB == 0) return launch_nv<32, 32, 0, QUERY, PROJ>(p, grid, s);
-  set_error("%s: unsupported MLP shape C=%ld d_hidden=%ld n_blocks=%ld", "bts", C, HD, NB);
-  return BTS_E_UNSUPPORTED;
+  return with_shape(C, HD, NB, [&](auto sh) {
+    using S = decltype(sh);
+    return with_nvmax(p.nv, [&](auto nvmax) {
+      field_kernel<S::C, S::HD, S::NB, nvmax(), QUERY, PROJ><<<grid, 256, 0, s>>>(p);
+      return launch_check();
+    });
+  });
 }
 
 }  // namespace bts

@@ -171,18 +171,18 @@ int colorize_launch(const float* x, int B, int h, int w, int norm, int N, const 
   const int nb = frames_partials(n);
   if (norm) {
     frames_minmax_kernel<<<dim3(nb, B), kFramesThreads, 0, s>>>(x, n, partials);
-    if (hipGetLastError() != hipSuccess) return BTS_E_LAUNCH;
+    if (int rc = launch_code()) return rc;
   }
   colorize_kernel<<<dim3(frames_blocks(n), B), kFramesThreads, 0, s>>>(x, h, w, N, norm ? partials : nullptr, nb, lut, lut_u8, out,
                                                                        CanvasDev{canvas, Hc, Wc}, row0, col0);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 int pack_u8_launch(const float* x, long sb, long sy, long sx, long sc, int B, int h, int w, float scale, float shift, unsigned char* canvas,
                    int Hc, int Wc, int row0, int col0, hipStream_t s) {
   pack_u8_kernel<<<dim3(frames_blocks((long)h * w), B), kFramesThreads, 0, s>>>(x, sb, sy, sx, sc, h, w, scale, shift, CanvasDev{canvas, Hc, Wc},
                                                                                 row0, col0);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 // the max pre-pass (black_invalid only) and the finish kernel on a chunk's render
@@ -196,11 +196,11 @@ int novel_view_finish_launch(const BtsNovelViews* a, hipStream_t s) {
   q.img_row0 = a->canvas ? a->img_row0 : -1, q.img_col0 = a->img_col0, q.dep_row0 = a->canvas ? a->depth_row0 : -1, q.dep_col0 = a->depth_col0;
   if (a->black_invalid) {
     frames_minmax_kernel<<<dim3(q.nb, a->P), kFramesThreads, 0, s>>>(a->depth, n, a->frame_max);
-    if (hipGetLastError() != hipSuccess) return BTS_E_LAUNCH;
+    if (int rc = launch_code()) return rc;
     q.partials = a->frame_max;
   }
   novel_view_finish_kernel<<<dim3(frames_blocks(n), a->P), kFramesThreads, 0, s>>>(q);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 }  // namespace bts

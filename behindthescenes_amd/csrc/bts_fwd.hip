@@ -16,7 +16,8 @@ void set_error(const char* fmt, const char* a, long b, long c, long d) {
 const char* last_error() { return g_err; }
 
 bool shape_supported(int C, int HD, int NB) {
-  return (C == 64 && HD == 64 && NB == 0) || (C == 32 && HD == 32 && NB == 1) || (C == 32 && HD == 32 && NB == 0);
+  int rc;
+  return Shapes::shape(C, HD, NB, rc, [](auto) { return BTS_OK; });
 }
 
 // raw channels-last features (feat_nhwc, for callers that cannot pre-project): the compact lane = sample render kernel and the

@@ -1,9 +1,12 @@
 // Host functions of libbts_render.so that one translation unit defines and another calls: each is declared HERE and nowhere else,
 // with its default arguments.  Every .hip file that defines or calls one includes this header, so the compiler sees declaration and
 // definition together (a changed parameter is a compile error at the definition, not a link error -- or, for a default, nothing at all).
-// Behind them: the small inline helpers of the host layer.  No device code.
+// Behind them: the small inline helpers of the host layer and the kernel dispatch (the compiled shapes, the view-count rungs, the launch
+// check).  No device code.
 #pragma once
 #include "bts_common.h"
+
+#include <type_traits>
 
 namespace bts {
 
@@ -144,6 +147,80 @@ inline CamBlock split_cams(float* cams, int n, int nv) {
   c.K_r = c.w2c_enc + (long)n * 16;
   c.w2c_r = c.K_r + (long)n * nv * 9;
   return c;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// kernel dispatch: the compiled field shapes, the view-count rungs, the launch check
+// ---------------------------------------------------------------------------------------------------------------
+// The field shapes (C, d_hidden, n_blocks) the kernels are compiled for: THE list -- bts_supported (shape_supported) and every dispatch
+// read it, nothing else names a shape.
+template <int C_, int HD_, int NB_>
+struct Shape {
+  static constexpr int C = C_, HD = HD_, NB = NB_;
+  static bool is(int c, int hd, int nb) { return c == C && hd == HD && nb == NB; }
+};
+// what a (C, HD)-only dispatch is handed: a shape without its n_blocks
+template <int C_, int HD_>
+struct Width {
+  static constexpr int C = C_, HD = HD_;
+};
+template <class... S>
+struct ShapeList {
+  // rc = f(S{}) for the shape S that is (C, HD, NB) / rc = f(Width{}) for the first shape with these C and HD; false: there is none
+  template <class F>
+  static bool shape(int C, int HD, int NB, int& rc, F&& f) {
+    return ((S::is(C, HD, NB) && (rc = f(S{}), true)) || ...);
+  }
+  template <class F>
+  static bool width(int C, int HD, int& rc, F&& f) {
+    return ((C == S::C && HD == S::HD && (rc = f(Width<S::C, S::HD>{}), true)) || ...);
+  }
+};
+using Re10kShape = Shape<32, 32, 1>;   // exp_re10k.yaml: the one shape with a ResnetBlockFC, and with 48-lane modes
+using Shapes = ShapeList<Shape<64, 64, 0>, Re10kShape, Shape<32, 32, 0>>;
+
+// f(S{}) for the compiled shape S that is (C, HD, NB); no such shape: BTS_E_UNSUPPORTED and the text below.  (Every entry point rejects
+// such a shape with its own envelope message before anything gets here.)
+template <class F>
+int with_shape(int C, int HD, int NB, F&& f) {
+  int rc = BTS_E_UNSUPPORTED;
+  if (!Shapes::shape(C, HD, NB, rc, f)) set_error("%s: unsupported MLP shape C=%ld d_hidden=%ld n_blocks=%ld", "bts", C, HD, NB);
+  return rc;
+}
+// f(Width<C, HD>{}) where a compiled shape has these C and HD (the projection and the gate-bit passes do not depend on n_blocks),
+// BTS_E_UNSUPPORTED otherwise
+template <class F>
+int with_width(int C, int HD, F&& f) {
+  int rc = BTS_E_UNSUPPORTED;
+  (void)Shapes::width(C, HD, rc, f);
+  return rc;
+}
+
+// f(std::integral_constant<int, NVMAX>{}): the size of a kernel's per-view arrays for nv render views (nv <= BTS_MAX_VIEWS = 8)
+template <class F>
+int with_nvmax(int nv, F&& f) {
+  if (nv <= 1) return f(std::integral_constant<int, 1>{});
+  if (nv <= 2) return f(std::integral_constant<int, 2>{});
+  if (nv <= 4) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 8>{});
+}
+
+// The status of the launches issued so far, read ONCE (reading clears it): the only place csrc asks HIP for it.  A failure is
+// BTS_E_LAUNCH with set_error(fmt, who, code), who = the HIP error string unless the caller names itself; fmt = NULL leaves the message
+// to the caller (bts_api.hip's launched(rc, who))
+inline int launch_check(const char* fmt = "%s: kernel launch failed (%ld)", const char* who = nullptr) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return BTS_OK;
+  if (fmt) set_error(fmt, who ? who : hipGetErrorString(e), (long)e);
+  return BTS_E_LAUNCH;
+}
+inline int launch_code() { return launch_check(nullptr); }
+
+// kern<<<grid, 256, dyn, s>>>(args...) for a kernel whose dynamic LDS (dyn bytes) may exceed the 64 KB a launch gets without asking
+template <class K, class... A>
+void launch_dyn_lds(K kern, int grid, int dyn, hipStream_t s, const A&... args) {
+  if (dyn) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+  kern<<<grid, 256, dyn, s>>>(args...);
 }
 
 }  // namespace bts

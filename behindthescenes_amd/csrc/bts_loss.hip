@@ -252,12 +252,7 @@ int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s) {
   if (p.n_patches == 0) return BTS_OK;
   const int grid = (p.n_patches + 3) / 4;
   photometric_loss_kernel<<<grid, 256, 0, s>>>(p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: loss kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
+  return launch_check("%s: loss kernel launch failed (%ld)");
 }
 
 }  // namespace bts

@@ -470,12 +470,7 @@ int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream
   loss_tiled_pass1<<<grid, 256, 0, s>>>(p, (long)nt);
   loss_tiled_pass2<<<grid2, 64, 0, s>>>(p);
   if (p.g_rgb || p.g_depth) loss_tiled_pass3<<<grid, 256, 0, s>>>(p, (long)nt);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: tiled loss kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
+  return launch_check("%s: tiled loss kernel launch failed (%ld)");
 }
 
 }  // namespace bts

@@ -474,28 +474,7 @@ __global__ __launch_bounds__(kMcThreads) void mc_rows_kernel(const McParams mp) 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int mc_status(const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return BTS_OK;
-  set_error("%s: kernel launch failed (HIP error %ld)", who, (long)e);
-  return BTS_E_LAUNCH;
-}
-
-template <class F>
-static int mc_dispatch(int C, int HD, int NB, F&& go) {
-  if (C == 64 && HD == 64 && NB == 0) return go(std::integral_constant<int, 0>{});
-  if (C == 32 && HD == 32 && NB == 1) return go(std::integral_constant<int, 1>{});
-  if (C == 32 && HD == 32 && NB == 0) return go(std::integral_constant<int, 2>{});
-  return BTS_E_UNSUPPORTED;
-}
-template <int V>
-struct McShape;
-template <>
-struct McShape<0> { static constexpr int C = 64, HD = 64, NB = 0; };
-template <>
-struct McShape<1> { static constexpr int C = 32, HD = 32, NB = 1; };
-template <>
-struct McShape<2> { static constexpr int C = 32, HD = 32, NB = 0; };
+static int mc_status(const char* who) { return launch_check("%s: kernel launch failed (HIP error %ld)", who); }
 
 int mlp_color_render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s) {
   McParams mp;
@@ -514,8 +493,8 @@ int mlp_color_render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, 
     set_error("%s: too many rays in one call (%ld)", "bts_render_fwd_mlp_color", (long)cfg->n * p.Bp);
     return BTS_E_UNSUPPORTED;
   }
-  return mc_dispatch(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto v) {
-    using S = McShape<decltype(v)::value>;
+  return with_shape(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto sh) {
+    using S = decltype(sh);
     mc_render_kernel<S::C, S::HD, S::NB><<<(int)mp.n_groups, kMcThreads, 0, s>>>(mp);
     return mc_status("bts_render_fwd_mlp_color");
   });
@@ -533,8 +512,8 @@ int mlp_color_field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t,
     set_error("%s: too many points in one call (%ld)", "bts_field_query_mlp_color", pts);
     return BTS_E_UNSUPPORTED;
   }
-  return mc_dispatch(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto v) {
-    using S = McShape<decltype(v)::value>;
+  return with_shape(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto sh) {
+    using S = decltype(sh);
     mc_query_kernel<S::C, S::HD, S::NB><<<(int)blocks, kMcThreads, 0, s>>>(p);
     return mc_status("bts_field_query_mlp_color");
   });
@@ -576,8 +555,8 @@ int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, 
   // persistent grid of at most render_grid's size (the weight-gradient partials are flushed once per work-group).  How many reside per CU
   // is set by pass A's LDS and registers: one at d_hidden 64 (143 KB of LDS), one wave per SIMD at (32, 32, 1)
   const int grid = render_grid(p);
-  int rc = mc_dispatch(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto v) {
-    using S = McShape<decltype(v)::value>;
+  int rc = with_shape(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto sh) {
+    using S = decltype(sh);
     const long g_ = mp.n_groups < grid ? mp.n_groups : grid;
     mc_rows_kernel<S::C, S::HD, S::NB><<<(int)g_, kMcThreads, 0, s>>>(mp);
     return mc_status("bts_render_bwd_mlp_color");

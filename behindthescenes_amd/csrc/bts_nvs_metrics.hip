@@ -175,9 +175,9 @@ int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s) {
   g.r2 = a->data_range * a->data_range;
   g.part = reinterpret_cast<double*>(workspace);
   nvs_tiles_kernel<<<dim3(g.nblk, a->B), kNvsThreads, 0, s>>>(g);
-  if (hipGetLastError() != hipSuccess) return BTS_E_LAUNCH;
+  if (int rc = launch_code()) return rc;
   nvs_finish_kernel<<<a->B, 64, 0, s>>>(g, a->metrics);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 }  // namespace bts

@@ -240,7 +240,6 @@ static void slice_bounds(float y_lo, float y_hi, int y_res, LidarSliceBounds* yb
   for (int i = 0; i < y_res; ++i) yb->lo[i] = ys[i] - half, yb->hi[i] = ys[i] + half;
 }
 
-static int launched() { return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH; }
 
 size_t lidar_bins_bytes(int T, int y_res) {
   return ((size_t)y_res * T * kBins * 4 + 15) / 16 * 16 + (size_t)y_res * T * 8;
@@ -259,20 +258,20 @@ int lidar_slices_launch(const float* points, const int* offsets, int T, const fl
   const int n_bins = y_res * T * kBins, n_first = y_res * T;
   unsigned long long* first = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(bins_ws) + ((size_t)n_bins * 4 + 15) / 16 * 16);
   lidar_init_kernel<<<(n_bins + 255) / 256, 256, 0, s>>>(bins, first, n_bins, n_first);
-  if (int rc = launched()) return rc;
+  if (int rc = launch_code()) return rc;
   const int per_block = 256 * 8;
   lidar_bins_kernel<<<dim3((max_n + per_block - 1) / per_block, T), 256, 0, s>>>(reinterpret_cast<const float4*>(points), offs, velo_poses, borders, yb,
                                                                                y_res, max_dist, per_block, T, bins, first);
-  if (int rc = launched()) return rc;
+  if (int rc = launch_code()) return rc;
   lidar_table_kernel<<<y_res * T, 64, 0, s>>>(bins, first, borders, tables);
-  return launched();
+  return launch_code();
 }
 
 int lidar_occupancy_launch(const float* q_pts, int P, const float* tables, int y_res, int T, const float* world_to_velo, float min_dist,
                            unsigned char* is_occupied, unsigned char* is_visible, hipStream_t s) {
   const int dyn = T * kRows * 2 * 4;   // 92 672 B at T = 32
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(lidar_occupancy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess) {
-    (void)hipGetLastError();
+    (void)launch_code();
     return BTS_E_LAUNCH;
   }
   const int step = P / y_res, rest = P - y_res * step;
@@ -280,18 +279,18 @@ int lidar_occupancy_launch(const float* q_pts, int P, const float* tables, int y
   const float thresh = (float)((double)(T - 2) / (double)T);   // :122, compared in fp32 as torch compares a fp32 tensor with a Python scalar
   lidar_occupancy_kernel<<<dim3(gx > 0 ? gx : 1, y_res + 1), 256, dyn, s>>>(q_pts, P, tables, y_res, T, world_to_velo, min_dist, thresh, is_occupied,
                                                                            is_visible);
-  return launched();
+  return launch_code();
 }
 
 int occ_metrics_launch(const float* q_pts, int P, const float* sigma, const unsigned char* is_occupied, const unsigned char* is_visible,
                        const float* depth_z, int H, int W, const float* proj, const float* w2c, float occ_threshold, int* counts,
                        unsigned char* masks, hipStream_t s) {
   if (hipMemsetAsync(counts, 0, 6 * sizeof(int), s) != hipSuccess) {
-    (void)hipGetLastError();
+    (void)launch_code();
     return BTS_E_LAUNCH;
   }
   occ_metrics_kernel<<<(P + 255) / 256, 256, 0, s>>>(q_pts, P, sigma, is_occupied, is_visible, depth_z, H, W, proj, w2c, occ_threshold, counts, masks);
-  return launched();
+  return launch_code();
 }
 
 }  // namespace bts

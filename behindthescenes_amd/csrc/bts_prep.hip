@@ -576,11 +576,11 @@ static int run_fwd(const float* feat, const float* mlp, int N, int HW, float* pr
     compact_tiles_kernel<<<(int)((n_tiles + 255) / 256), 256, 0, s>>>(const_cast<unsigned char*>(tiles), (int)n_tiles, list, nullptr);
     if (feat_cl) project_kernel<C, HD, true><<<grid, 256, 0, s>>>(feat, mlp, proj, HW, tpi, (int)n_tiles, tiles, Wm, tw, list);
     else project_kernel<C, HD, false><<<grid, 256, 0, s>>>(feat, mlp, proj, HW, tpi, (int)n_tiles, tiles, Wm, tw, list);
-    return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+    return launch_code();
   }
   if (feat_cl) project_kernel<C, HD, true><<<grid, 256, 0, s>>>(feat, mlp, proj, HW, tpi, (int)n_tiles, tiles, Wm, tw);
   else project_kernel<C, HD, false><<<grid, 256, 0, s>>>(feat, mlp, proj, HW, tpi, (int)n_tiles, tiles, Wm, tw);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 template <int C, int HD>
@@ -591,7 +591,7 @@ static int run_bwd(const float* feat, const float* dproj, const float* mlp, int 
   const int nr = (dfeat && d_mlp) ? 2 : 4;
   const long want = (n_tiles + nr - 1) / nr, cap = 2L * device_cu_count();   // <= 2 work-groups per CU: the roles hold up to 256 VGPRs
   project_bwd_kernel<C, HD><<<(int)(want < cap ? want : cap), 256, 0, s>>>(feat, dproj, mlp, dfeat, d_mlp, HW, tiles, (int)n_tiles);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 template <int C, int HD>
@@ -611,18 +611,16 @@ static int run_bwd_tiles(const float* feat, float* dproj, unsigned char* tiles, 
     compact_tiles_kernel<<<(int)((n_tiles + 255) / 256), 256, 0, s>>>(tiles, (int)n_tiles, list, copy);
     if (feat_cl) project_bwd_tiles_kernel<C, HD, true, true><<<grid, 256, 0, s>>>(feat, dproj, tiles, mlp, dfeat, d_mlp, HW, tpi, (int)n_tiles, 1, Wm, tw, list, copy);
     else project_bwd_tiles_kernel<C, HD, false, true><<<grid, 256, 0, s>>>(feat, dproj, tiles, mlp, dfeat, d_mlp, HW, tpi, (int)n_tiles, 1, Wm, tw, list, copy);
-    return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+    return launch_code();
   }
   if (feat_cl) project_bwd_tiles_kernel<C, HD, true><<<grid, 256, 0, s>>>(feat, dproj, tiles, mlp, dfeat, d_mlp, HW, tpi, (int)n_tiles, clear, Wm, tw);
   else project_bwd_tiles_kernel<C, HD, false><<<grid, 256, 0, s>>>(feat, dproj, tiles, mlp, dfeat, d_mlp, HW, tpi, (int)n_tiles, clear, Wm, tw);
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 int project_features_impl(int C, int HD, const float* feat, const float* mlp, int N, int HW, float* proj, const unsigned char* tiles, hipStream_t s,
                           bool feat_cl, int Wm, void* list_ws, size_t list_ws_bytes) {
-  if (C == 64 && HD == 64) return run_fwd<64, 64>(feat, mlp, N, HW, proj, tiles, feat_cl, s, Wm, list_ws, list_ws_bytes);
-  if (C == 32 && HD == 32) return run_fwd<32, 32>(feat, mlp, N, HW, proj, tiles, feat_cl, s, Wm, list_ws, list_ws_bytes);
-  return BTS_E_UNSUPPORTED;
+  return with_width(C, HD, [&](auto w) { return run_fwd<w.C, w.HD>(feat, mlp, N, HW, proj, tiles, feat_cl, s, Wm, list_ws, list_ws_bytes); });
 }
 
 // ---- which tiles of the projected map will a render read?  One thread per sample: the render kernels' own depth (coarse_depth), point
@@ -666,21 +664,19 @@ int mark_tiles_impl(const float* rays, const float* z_samp, const float* jitter,
   const long want = (B + 3) / 4;   // one ray per wave iteration
   mark_tiles_kernel<<<(int)(want < 8192 ? want : 8192), 256, 0, s>>>(rays, z_samp, jitter, w2c_enc, K_enc, B, Bp, K, lindisp, H, W, fs, tpi, tiles,
                                                                      tile_cols(H >> fs, W >> fs, blocks));
-  return hipGetLastError() == hipSuccess ? BTS_OK : BTS_E_LAUNCH;
+  return launch_code();
 }
 
 int project_features_bwd_impl(int C, int HD, const float* feat, const float* dproj, const float* mlp, int N, int HW, float* dfeat,
                               float* d_mlp, hipStream_t s) {
-  if (C == 64 && HD == 64) return run_bwd<64, 64>(feat, dproj, mlp, N, HW, dfeat, d_mlp, s);
-  if (C == 32 && HD == 32) return run_bwd<32, 32>(feat, dproj, mlp, N, HW, dfeat, d_mlp, s);
-  return BTS_E_UNSUPPORTED;
+  return with_width(C, HD, [&](auto w) { return run_bwd<w.C, w.HD>(feat, dproj, mlp, N, HW, dfeat, d_mlp, s); });
 }
 
 int project_features_bwd_tiles_impl(int C, int HD, const float* feat, float* dproj, unsigned char* tiles, const float* mlp, int N, int HW, float* dfeat,
                                     float* d_mlp, int clear, hipStream_t s, bool feat_cl, int Wm, void* list_ws, size_t list_ws_bytes) {
-  if (C == 64 && HD == 64) return run_bwd_tiles<64, 64>(feat, dproj, tiles, mlp, N, HW, dfeat, d_mlp, clear, feat_cl, s, Wm, list_ws, list_ws_bytes);
-  if (C == 32 && HD == 32) return run_bwd_tiles<32, 32>(feat, dproj, tiles, mlp, N, HW, dfeat, d_mlp, clear, feat_cl, s, Wm, list_ws, list_ws_bytes);
-  return BTS_E_UNSUPPORTED;
+  return with_width(C, HD, [&](auto w) {
+    return run_bwd_tiles<w.C, w.HD>(feat, dproj, tiles, mlp, N, HW, dfeat, d_mlp, clear, feat_cl, s, Wm, list_ws, list_ws_bytes);
+  });
 }
 
 }  // namespace bts

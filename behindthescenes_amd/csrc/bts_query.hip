@@ -278,26 +278,6 @@ __global__ __launch_bounds__(256, 2) void query_kernel_p(const QueryParams qp) {
   }
 }
 
-template <int C, int HD, int NB>
-static int launch_query_nv(const QueryParams& qp, int grid, hipStream_t s) {
-  constexpr int dyn = 4 * kGatherLdsPerWave;
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-    kern<<<grid, 256, dyn, s>>>(qp);
-  };
-  const int nv = qp.f.only_density ? 0 : qp.f.nv;
-  if (nv <= 1) go(query_kernel_p<C, HD, NB, 1>);
-  else if (nv <= 2) go(query_kernel_p<C, HD, NB, 2>);
-  else if (nv <= 4) go(query_kernel_p<C, HD, NB, 4>);
-  else go(query_kernel_p<C, HD, NB, 8>);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
-}
-
 // plain query: cols = 0; profile: cols = columns per sample, col_len = Y, P = Y * cols
 int query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb, float* invalid,
                float* sigma, int cols, int col_len, float threshold, float* profile, hipStream_t s) {
@@ -314,12 +294,13 @@ int query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xy
   }
   const int grid = render_grid(qp.f);
   qp.f.chunk_log2 = render_chunk_log2(grid, qp.f.groups);
-  const int C = cfg->C, HD = cfg->d_hidden, NB = cfg->n_blocks;
-  if (C == 64 && HD == 64 && NB == 0) return launch_query_nv<64, 64, 0>(qp, grid, s);
-  if (C == 32 && HD == 32 && NB == 1) return launch_query_nv<32, 32, 1>(qp, grid, s);
-  if (C == 32 && HD == 32 && NB == 0) return launch_query_nv<32, 32, 0>(qp, grid, s);
-  set_error("%s: unsupported MLP shape C=%ld d_hidden=%ld n_blocks=%ld", "bts_field_query", C, HD, NB);
-  return BTS_E_UNSUPPORTED;
+  return with_shape(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto sh) {
+    using S = decltype(sh);
+    return with_nvmax(only_density ? 0 : qp.f.nv, [&](auto nvmax) {
+      launch_dyn_lds(query_kernel_p<S::C, S::HD, S::NB, nvmax()>, grid, 4 * kGatherLdsPerWave, s, qp);
+      return launch_check();
+    });
+  });
 }
 
 }  // namespace bts

@@ -911,28 +911,15 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
 }
 
 #ifndef BTS_NO_LAUNCH_GLUE
-static inline int launch_render_p_check() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: kernel launch failed (%ld)", hipGetErrorString(e), (long)e);
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
-}
-
 template <int C, int HD, int NB, int NVMAX, bool EPI>
 static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
 #ifdef BTS_GATHER_LDS
-  constexpr int dyn = 4 * kGatherLdsPerWave;
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-    kern<<<grid, 256, dyn, s>>>(p);
-  };
+  auto go = [&](auto kern) { launch_dyn_lds(kern, grid, 4 * kGatherLdsPerWave, s, p); };
   // the claimed tail (FwdParams::sched): the evaluation frame's one-ray kernels with two loops only
   if constexpr (!EPI && NB == 0 && NVMAX <= 2) {
     if (p.lpr == 64 && p.sched && p.dyn_first < p.groups) {
       go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true>);
-      return launch_render_p_check();
+      return launch_check();
     }
   }
   if (p.lpr == 64) go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI>);
@@ -941,24 +928,15 @@ static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
   if (p.lpr == 64) render_kernel_p<C, HD, NB, NVMAX, true, true, EPI><<<grid, 256, 0, s>>>(p);
   else render_kernel_p<C, HD, NB, NVMAX, false, true, EPI><<<grid, 256, 0, s>>>(p);
 #endif
-  return launch_render_p_check();
-}
-
-template <int C, int HD, int NB, bool EPI>
-static int launch_render_p_nv(const FwdParams& p, int grid, hipStream_t s) {
-  if (p.nv <= 1) return launch_render_p_one<C, HD, NB, 1, EPI>(p, grid, s);
-  if (p.nv <= 2) return launch_render_p_one<C, HD, NB, 2, EPI>(p, grid, s);
-  if (p.nv <= 4) return launch_render_p_one<C, HD, NB, 4, EPI>(p, grid, s);
-  return launch_render_p_one<C, HD, NB, 8, EPI>(p, grid, s);
+  return launch_check();
 }
 
 template <bool EPI>
 inline int launch_render_p(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s) {
-  if (C == 64 && HD == 64 && NB == 0) return launch_render_p_nv<64, 64, 0, EPI>(p, grid, s);
-  if (C == 32 && HD == 32 && NB == 1) return launch_render_p_nv<32, 32, 1, EPI>(p, grid, s);
-  if (C == 32 && HD == 32 && NB == 0) return launch_render_p_nv<32, 32, 0, EPI>(p, grid, s);
-  set_error("%s: unsupported MLP shape C=%ld d_hidden=%ld n_blocks=%ld", "bts", C, HD, NB);
-  return BTS_E_UNSUPPORTED;
+  return with_shape(C, HD, NB, [&](auto sh) {
+    using S = decltype(sh);
+    return with_nvmax(p.nv, [&](auto nvmax) { return launch_render_p_one<S::C, S::HD, S::NB, nvmax(), EPI>(p, grid, s); });
+  });
 }
 #endif  // BTS_NO_LAUNCH_GLUE
 

@@ -280,11 +280,7 @@ int train_step_fwd_impl(const BtsTrainStep* st, hipStream_t main_stream) {
   fin.n_scales = st->n_scales, fin.n_patches = n * st->P, fin.out = st->loss_vals;
   memcpy(fin.M, st->loss_matrix, sizeof(float) * 9 * 3 * st->n_scales);
   loss_finish_kernel<<<1, 256, 0, stream>>>(fin);
-  if (hipGetLastError() != hipSuccess) {
-    set_error("%s: loss reduction launch failed", "bts_train_step_fwd");
-    return BTS_E_LAUNCH;
-  }
-  return BTS_OK;
+  return launch_check("%s: loss reduction launch failed", "bts_train_step_fwd");
 }
 
 int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t main_stream) {
@@ -321,10 +317,7 @@ int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t
   }
   const long want = (sg.n_rgb + 255) / 256;
   scale_grads_kernel<<<dim3((unsigned)(want < 1024 ? want : 1024), (unsigned)st->n_scales), 256, 0, stream>>>(sg);
-  if (hipGetLastError() != hipSuccess) {
-    set_error("%s: gradient scaling launch failed", "bts_train_step_bwd");
-    return BTS_E_LAUNCH;
-  }
+  if (int rc = launch_check("%s: gradient scaling launch failed", "bts_train_step_bwd")) return rc;
   if (sq) {
     if (hipEventRecord(sq->fork, main_stream) != hipSuccess) return BTS_E_LAUNCH;
     for (int s = 1; s < st->n_scales; ++s)
@@ -371,10 +364,7 @@ int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t
   if (want_empty) {
     empty_grad_kernel<<<1, 256, 0, stream>>>(st->mlp_params, st->empty_feature, st->d_empty_proj, c.C, c.d_hidden, c.C + 3 + 6 * c.num_freqs, st->d_mlp_params,
                                              st->d_empty_feature);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("%s: empty-feature gradient launch failed", "bts_train_step_bwd");
-      return BTS_E_LAUNCH;
-    }
+    if (int rc = launch_check("%s: empty-feature gradient launch failed", "bts_train_step_bwd")) return rc;
   }
   return BTS_OK;
 }

@@ -18,8 +18,8 @@ def lib():
     return _lib.load()
 
 
-def _cfg(C_=64, H=32, W=96, nv=2, feat_shift=0, enc_view=-1):
-    cfg = native._spec_cfg(native.FieldSpec(C=C_, d_hidden=64, n_blocks=0), n=2, H=H, W=W, nv=nv, feat_shift=feat_shift)
+def _cfg(C_=64, H=32, W=96, nv=2, feat_shift=0, enc_view=-1, d_hidden=64, n_blocks=0):
+    cfg = native._spec_cfg(native.FieldSpec(C=C_, d_hidden=d_hidden, n_blocks=n_blocks), n=2, H=H, W=W, nv=nv, feat_shift=feat_shift)
     cfg.enc_render_view = enc_view
     return cfg
 
@@ -27,9 +27,14 @@ def _cfg(C_=64, H=32, W=96, nv=2, feat_shift=0, enc_view=-1):
 OK = _cfg()
 ODD = _cfg(C_=48)                               # outside the compiled envelope
 SHIFT = _cfg(H=36, W=100, feat_shift=3)         # H, W no multiples of 2^feat_shift
+# the compiled shapes (C, d_hidden, n_blocks); the odd shapes: C = 48 and two neighbours of the supported set, each one field away from a
+# compiled shape
+SHAPES = {(64, 64, 0), (32, 32, 1), (32, 32, 0)}
+ODD_SHAPES = {"C48": (48, 64, 0), "C64_blocks1": (64, 64, 1), "C32_hidden64": (32, 64, 0)}
+ODD_CFGS = {k: _cfg(C_=c, d_hidden=hd, n_blocks=nb) for k, (c, hd, nb) in ODD_SHAPES.items()}
 
 NULL_SIZE = "%s: NULL pointer or non-positive size"
-ENVELOPE = "%s: configuration outside the compiled envelope (C=48 d_hidden=64 n_blocks=0)"
+ENVELOPE = "%s: configuration outside the compiled envelope (C=%d d_hidden=%d n_blocks=%d)"
 BAD_SHIFT = "%s: feat_shift=3 needs 0 <= feat_shift <= 6 and H=36, W=100 multiples of 2^feat_shift"
 
 # entry -> (its arguments behind cfg with every pointer given and N = 1, index of N, index of a required pointer, index of `tiles` where the
@@ -51,7 +56,8 @@ def _projection_cases():
         yield f"{name}-null", name, [OK] + but(i_ptr, None), INVALID, NULL_SIZE % name
         yield f"{name}-null_cfg", name, [None] + args, INVALID, NULL_SIZE % name
         yield f"{name}-N0", name, [OK] + but(i_n, 0), INVALID, NULL_SIZE % name
-        yield f"{name}-C48", name, [ODD] + args, UNSUPPORTED, ENVELOPE % name
+        for odd, shape in ODD_SHAPES.items():
+            yield f"{name}-{odd}", name, [ODD_CFGS[odd]] + args, UNSUPPORTED, ENVELOPE % ((name,) + shape)
         yield f"{name}-shift", name, [SHIFT] + args, INVALID, BAD_SHIFT % name
         # a doubly wrong call reports the first check that fails: NULL / size, then the envelope, then feat_shift
         yield f"{name}-null_and_C48", name, [ODD] + but(i_ptr, None), INVALID, NULL_SIZE % name
@@ -124,8 +130,9 @@ def _render_cases():
         else:
             # the field checks come first and speak as "bts"
             yield f"{name}-null_cfg", name, [None, tens, args(base)] + call(None)[3:], INVALID, "bts: NULL cfg/tensors"
-            yield f"{name}-C48", name, call(args(base), cfg=ODD), UNSUPPORTED, \
-                "bts: configuration outside the compiled envelope (C=48 d_hidden=64 n_blocks=0; also needs num_freqs=6, nv<=8)"
+            for odd, shape in ODD_SHAPES.items():
+                yield f"{name}-{odd}", name, call(args(base), cfg=ODD_CFGS[odd]), UNSUPPORTED, \
+                    "bts: configuration outside the compiled envelope (C=%d d_hidden=%d n_blocks=%d; also needs num_freqs=6, nv<=8)" % shape
             yield f"{name}-shift", name, call(args(base), cfg=SHIFT), INVALID, BAD_SHIFT % "bts"
             if bwd:
                 yield f"{name}-no_proj", name, call(args(base), tens=_lib.BtsFieldTensors(**{**TENS, "proj_nhwc": None})), INVALID, null_msg % name
@@ -144,6 +151,13 @@ def test_workspace_sizes_in_the_messages_are_the_library_s(lib):
     a = _lib.BtsRenderArgs(**BWD_ARGS)
     assert lib.bts_render_bwd_workspace(C.byref(OK), C.byref(a)) == WS_PLAIN
     assert lib.bts_render_bwd_mlp_color_workspace(C.byref(_cfg(nv=1)), C.byref(a)) == WS_MC
+
+
+def test_bts_supported_answers_1_for_exactly_the_compiled_shapes(lib):
+    for c in (16, 32, 48, 64):
+        for hd in (32, 64):
+            for nb in (0, 1, 2):
+                assert lib.bts_supported(C.byref(_cfg(C_=c, d_hidden=hd, n_blocks=nb))) == (1 if (c, hd, nb) in SHAPES else 0), (c, hd, nb)
 
 
 @pytest.mark.parametrize("name,args,code,message", [c[1:] for c in CASES], ids=[c[0] for c in CASES])

@@ -87,6 +87,16 @@ class BtsEvalFrame(C.Structure):
     rgb_gt = None
     # likewise: the 256-word int32 device tensor of bts_eval_frame_sched's `sched` argument (None: the render's fixed ray lists alone)
     sched = None
+    # likewise: bts_eval_frame_prep's arguments as a dict -- params: the MLP's parameter tensors in the packed vector's order, packed / image:
+    # the float32 scratch tensors (image may be None) -- or None: the entry points that read mlp_params
+    prep = None
+
+
+BTS_MLP_MAX_TENSORS = 12
+
+
+class BtsMlpTensors(C.Structure):
+    _fields_ = [("tensor", C.c_void_p * BTS_MLP_MAX_TENSORS), ("n_tensors", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class BtsConv3x3(C.Structure):
@@ -180,6 +190,8 @@ SYMBOLS = {
     "bts_eval_frame": (C.c_int, [C.POINTER(BtsEvalFrame), _P]),
     "bts_eval_frame_gt": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P]),
     "bts_eval_frame_sched": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P, _P]),
+    "bts_mlp_image_floats": (C.c_int64, [C.POINTER(BtsFieldCfg)]),
+    "bts_eval_frame_prep": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P, C.POINTER(BtsMlpTensors), _P, _P, _P]),
     "bts_render_dyn_first": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "bts_conv3x3_fwd": (C.c_int, [C.POINTER(BtsConv3x3), _P]),
     "bts_conv3x3_bwd_workspace": (C.c_size_t, [C.POINTER(BtsConv3x3)]),

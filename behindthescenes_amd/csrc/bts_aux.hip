@@ -1,6 +1,8 @@
 // Small HBM-bound kernels at the edges of the render path: layout changes at the hand-off from the PyTorch encoder,
 // ray generation (util.py:113-149, 244-273), stratified depth sampling (nerf.py:103-123) and distance->z
 // (projection_operations.py:4-16).  All are coalesced streaming kernels; none does arithmetic worth an MFMA.
+#define BTS_NO_LAUNCH_GLUE   // (bts_render_kernel.h for the staged MLP's layout and routines only: eval_prep_kernel)
+#include "bts_render_kernel.h"
 #include "bts_host.h"
 #include <cstdint>
 
@@ -500,6 +502,108 @@ int eval_handover_launch(const float* Ks, const float* poses, const float* image
   p.b_gt = (int)((gt_items + 255) / 256 < 2048 ? (gt_items + 255) / 256 : 2048);
   eval_handover_kernel<<<p.b_cam + p.b_inv + p.b_pack + p.b_rays + p.b_gt, 256, 0, s>>>(p);
   return launch_code();
+}
+
+// ---- the projection and the MLP of an evaluation frame in ONE launch (bts_eval_frame_prep), behind the hand-over launch and in front of
+// the render.  The packed parameter vector was torch's `cat` of the parameter tensors, a dispatch of its own, and the staged MLP was
+// computed by each of the render's work-groups for itself; here both are the work of one work-group that runs under the projection.
+// Work-group ranges take the roles, and the roles do not communicate: no work-group waits for another.
+//   work-group 0 (of 8)     the MLP: the parameter tensors -> the packed vector (include/bts_render.h's layout: what `torch.cat` wrote),
+//                           then stage_weights / stage_weights_h on it into LDS as a render work-group does, and LDS -> `image`
+//                           (MlpImage: what the frame's render work-groups copy instead of staging; NULL: they stage from `packed`)
+//   the next b_proj         bts_project_body.h: bts_prep.hip's dense projection on the grid it would get alone; W_f is read from lin_in's
+//                           own weight tensor (the packed vector is written by this very launch)
+struct EvalPrepParams {
+  const float* feat;
+  float* proj;
+  int HW, tiles_per_img, n_tiles;
+  int b_proj;
+  const float* tensor[BTS_MLP_MAX_TENSORS];   // lin_in, the blocks' fc_0 / fc_1, lin_out: weight, bias
+  const float* empty;
+  float* packed;
+  float* image;
+};
+constexpr int kPrepHead = 8;   // work-groups in front of the projection's: the MLP's and seven that leave at once (one round of the XCDs)
+template <int C, int HD, int NB>
+__device__ __forceinline__ void eval_prep_mlp_body(float* lds, float* lds_packed, const EvalPrepParams& p) {
+  const MlpLayout ml{C + kPeDim, HD, NB};
+  // the packed vector, to global memory for the render (b_out; the staging of a launch without an image) and to LDS for the staging
+  // below: its strided 4-byte reads then cost LDS latency, not a trip to L2 each
+  auto put = [&](int t, int off, int count) {
+    const float* src = p.tensor[t];
+    for (int i = threadIdx.x; i < count; i += 256) {
+      const float v = src[i];
+      p.packed[off + i] = v, lds_packed[off + i] = v;
+    }
+  };
+  put(0, ml.w_in(), HD * (C + kPeDim)), put(1, ml.b_in(), HD);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    put(2 + 4 * b, ml.blk_w0(b), HD * HD), put(3 + 4 * b, ml.blk_b0(b), HD);
+    put(4 + 4 * b, ml.blk_w1(b), HD * HD), put(5 + 4 * b, ml.blk_b1(b), HD);
+  }
+  put(2 + 4 * NB, ml.w_out(), HD), put(3 + 4 * NB, ml.b_out(), 1);
+  __syncthreads();
+  if (!p.image) return;
+  stage_mlp<C, HD, NB>(lds, lds_packed, p.empty);
+  float4* dst = reinterpret_cast<float4*>(p.image);
+  const float4* src = reinterpret_cast<const float4*>(lds);
+  for (int i = threadIdx.x; i < MlpImage<C, HD, NB>::FLOATS / 4; i += 256) dst[i] = src[i];
+}
+// the projection role: bts_prep.hip's dense pass (no tile flags, no list, runs of 64 texels) on work-groups [kPrepHead, kPrepHead + n_blocks) of the launch
+template <int C, int HD, bool FEAT_CL>
+__device__ __forceinline__ void eval_prep_project_body(float* wl, const float* __restrict__ feat, const float* __restrict__ mlp, float* __restrict__ proj,
+                                                       int HW, int tiles_per_img, int n_tiles, int n_blocks) {
+  const unsigned char* tiles = nullptr;
+  const int* list = nullptr;
+  const int Wm = 0, tw = 0;
+#define BTS_PROJ_BLOCK ((int)blockIdx.x - kPrepHead)
+#define BTS_PROJ_BLOCKS n_blocks
+#include "bts_project_body.h"
+}
+template <int C, int HD, int NB, bool FEAT_CL>
+__global__ __launch_bounds__(256, 2) void eval_prep_kernel(const EvalPrepParams p) {
+  // one buffer, sized to the largest role: the MLP's image and its packed vector
+  constexpr int kPacked = (HD * (C + kPeDim) + HD + NB * (2 * HD * HD + 2 * HD) + HD + 1 + 3) & ~3;   // MlpLayout::total()
+  static_assert(MlpImage<C, HD, NB>::LDS_FLOATS + kPacked >= C * HD, "the projection's weights fit");
+  __shared__ __attribute__((aligned(16))) float lds[MlpImage<C, HD, NB>::LDS_FLOATS + kPacked];
+  // The MLP's one work-group is the launch's longest: it is dispatched FIRST and runs under the projection (as the last work-group it
+  // started when everything else had been handed out and ran on alone: profiles/r16a).  Work-groups 1 - 7 leave at once, so that
+  // projection work-group b is work-group 8 + b of the launch and runs on the XCD project_kernel's work-group b runs on (a launch's
+  // work-groups go round the XCDs): the render's waves find the rows of G in the L2 they found them in -- with the projection shifted
+  // by ONE work-group the render behind it took 2 % longer (profiles/r16a).
+  if (blockIdx.x < kPrepHead) {
+    if (blockIdx.x == 0) eval_prep_mlp_body<C, HD, NB>(lds, lds + MlpImage<C, HD, NB>::LDS_FLOATS, p);
+    return;
+  }
+  eval_prep_project_body<C, HD, FEAT_CL>(lds, p.feat, p.tensor[0], p.proj, p.HW, p.tiles_per_img, p.n_tiles, p.b_proj);
+}
+
+long mlp_image_floats(int C, int HD, int NB) {
+  int floats = 0;
+  (void)Shapes::shape(C, HD, NB, floats, [](auto sh) {
+    using S = decltype(sh);
+    return MlpImage<S::C, S::HD, S::NB>::FLOATS;
+  });
+  return floats;
+}
+
+int eval_prep_launch(int C, int HD, int NB, const float* feat, bool feat_cl, float* proj, const float* const* tensors, const float* empty, float* packed,
+                     float* image, int n, int HW, hipStream_t s) {
+  EvalPrepParams p;
+  p.feat = feat, p.proj = proj, p.HW = HW, p.tiles_per_img = (p.HW + 63) / 64, p.n_tiles = n * p.tiles_per_img;
+  // the dense projection's own grid (bts_prep.hip: run_fwd): a work-group per four tiles, at most four per CU
+  const long want = ((long)p.n_tiles + 3) / 4, cap = 4L * device_cu_count();
+  p.b_proj = (int)(want < cap ? want : cap);
+  for (int i = 0; i < BTS_MLP_MAX_TENSORS; ++i) p.tensor[i] = i < 4 + 4 * NB ? tensors[i] : nullptr;
+  p.empty = empty, p.packed = packed, p.image = image;
+  const int grid = kPrepHead + p.b_proj;
+  return with_shape(C, HD, NB, [&](auto sh) {
+    using S = decltype(sh);
+    if (feat_cl) eval_prep_kernel<S::C, S::HD, S::NB, true><<<grid, 256, 0, s>>>(p);
+    else eval_prep_kernel<S::C, S::HD, S::NB, false><<<grid, 256, 0, s>>>(p);
+    return launch_code();
+  });
 }
 
 int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_t s) {

@@ -279,6 +279,11 @@ __device__ __forceinline__ int tile_base(int t, int Wm, int tw) {
   return ty * 4 * Wm + (t - ty * tw) * 16;
 }
 __device__ __forceinline__ int tile_rs(int Wm, int tw) { return tw ? Wm - 16 : 0; }
+// texel (index inside its image) of slot i of the tile whose first texel is p0: bts_common.h, tile_rs
+__device__ __forceinline__ int tile_px(int p0, int i, int rs) { return p0 + i + (i >> 4) * rs; }
+// the same for a slot = cslot (wave-uniform, mostly a compile-time constant) + lslot (per lane, never carrying into bit 4 of the slot):
+// the row piece (cslot >> 4) stays a uniform -- the address is scalar base + lane offset + immediate instead of one VGPR per access
+__device__ __forceinline__ int tile_px_c(int p0, int cslot, int lslot, int rs) { return p0 + cslot + (cslot >> 4) * rs + lslot; }
 
 // depth code in [-1,1] (models_bts.py:157-171) of the projected point's depth (code_mode z) or distance (by_distance)
 __device__ __forceinline__ float depth_code(const Proj& pe, bool by_distance, bool inv_z, float inv_dmax, float inv_range, float d_min, float range) {

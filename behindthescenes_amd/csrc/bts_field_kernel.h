@@ -71,7 +71,12 @@ struct FwdParams {
     unsigned* sched;  // render: null = every group is on a wave's static list; else sched[32 x] counts XCD x's tickets for the groups
                       // [dyn_first, groups) (256 words, a cache line per counter, zero at launch: bts_eval_frame_sched)
   };
-  float* q_sigma;
+  // query -- or, in a render launch, the staged MLP as the evaluation frame's prep launch left it (bts_render_kernel.h: MlpImage); the
+  // same sharing of one slot as `sched` above
+  union {
+    float* q_sigma;
+    const float* mlp_image;  // render: null = every work-group stages the MLP itself from `mlp`
+  };
   int only_density;
   int tiles_per_sample;
   // lane = sample render kernel

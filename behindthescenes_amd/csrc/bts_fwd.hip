@@ -106,8 +106,10 @@ long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div) {
 
 int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s) { return render_fwd_sched_impl(cfg, t, a, nullptr, s); }
 
-int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s) {
+int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s,
+                          const float* mlp_image) {
   FwdParams p = make_params(cfg, t);
+  p.mlp_image = t->proj_nhwc ? mlp_image : nullptr;   // (the pipelined kernels' slot: render launches have no q_sigma)
   p.rays = a->rays, p.z_samp = a->z_samp;
   p.jitter = a->z_samp ? nullptr : a->jitter, p.z_out = a->z_samp ? nullptr : a->z_samp_out, p.lindisp = a->lindisp;
   p.Bp = a->rays_per_sample, p.K = a->K, p.hard_cap = a->hard_alpha_cap, p.white_bkgd = a->white_bkgd;

@@ -24,7 +24,9 @@ int render_grid(const FwdParams& p);
 int render_chunk_log2(int grid, long groups);
 long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div);
 int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
-int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s);
+// mlp_image: the staged MLP of bts_eval_frame_prep (bts_render_kernel.h: MlpImage) or NULL
+int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s,
+                          const float* mlp_image = nullptr);
 int field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
                      float* invalid, float* sigma, hipStream_t s);
 int occupancy_profile_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int Y, int cols, float threshold,
@@ -71,6 +73,10 @@ int patch_rays_launch(const float* poses, const float* projs, const float* image
                       int c, int H, int W, int P, int ph, int pw, float zn, float zf, int norm_dir, float* rays, float* gt, hipStream_t s);
 int sample_coarse_launch(const float* rays, const float* u, long B, int K, int lindisp, float* z, hipStream_t s);
 int distance_to_z_launch(const float* depths, const float* invK, int N, int H, int W, float* out, hipStream_t s);
+// the evaluation frame's prep launch (MLP | projection); mlp_image_floats: the size of its `image`, 0 = no such shape
+long mlp_image_floats(int C, int HD, int NB);
+int eval_prep_launch(int C, int HD, int NB, const float* feat, bool feat_cl, float* proj, const float* const* tensors, const float* empty, float* packed,
+                     float* image, int n, int HW, hipStream_t s);
 int invert_small_launch(const float* src, float* dst, int N, int dim, hipStream_t s);
 int handover_launch(const float* Ks, const float* poses, const float* images, const int* pv, const int* py, const int* px, int n, int v, int id_enc, int nv,
                     const int* ids_render, int n_loss, const int* ids_loss, int H, int W, int P, int ph, int pw, float z_near, float z_far, float scale,

@@ -12,12 +12,6 @@
 namespace bts {
 
 
-// texel (index inside its image) of slot i of the tile whose first texel is p0: bts_common.h, tile_rs
-__device__ __forceinline__ int tile_px(int p0, int i, int rs) { return p0 + i + (i >> 4) * rs; }
-// the same for a slot = cslot (wave-uniform, mostly a compile-time constant) + lslot (per lane, never carrying into bit 4 of the slot):
-// the row piece (cslot >> 4) stays a uniform -- the address is scalar base + lane offset + immediate instead of one VGPR per access
-__device__ __forceinline__ int tile_px_c(int p0, int cslot, int lslot, int rs) { return p0 + cslot + (cslot >> 4) * rs + lslot; }
-
 // ---- forward: one wave = 64 pixels x all Hd outputs.  D[pix][hid] = A[pix][c] . B[c][hid]:
 // A operand = F (lane l: pixel l&31, channel parity l>>5) read straight from the NCHW rows, B = w_in^T from LDS (k-major),
 // D rows (pixels) sit in registers, columns (hidden) across lanes -> every store is a 128-byte row segment of G.
@@ -27,101 +21,15 @@ __device__ __forceinline__ int tile_px_c(int p0, int cslot, int lslot, int rs) {
 // FEAT_CL: F is channels-last, (N, H, W, C) in memory (a torch tensor of shape (N, C, H, W) in channels_last format: what MIOpen's NHWC
 // kernels and bts_conv3x3_fwd produce): a lane reads ITS pixel's channels as float4 pieces -- k-step (q, e) pairs channel 8 q + e
 // (lane half 0) with 8 q + 4 + e (half 1) -- and a tile is 64 x C x 4 contiguous bytes instead of C row pieces of 256.
+// (the body is bts_project_body.h: the evaluation frame's prep launch includes it too)
 template <int C, int HD, bool FEAT_CL>
 __global__ __launch_bounds__(256, 2) void project_kernel(const float* __restrict__ feat, const float* __restrict__ mlp, float* __restrict__ proj,
                                                       int HW, int tiles_per_img, int n_tiles, const unsigned char* __restrict__ tiles, int Wm, int tw,
                                                       const int* __restrict__ list = nullptr) {
-  constexpr int HT = HD / 32;
-  constexpr int D_IN = C + kPeDim;
-  __shared__ float wl[C * HD];  // wl[c*HD + s] = w_in[hidden_of_storage(s)][c]: G comes out in its storage channel order
-  for (int i = threadIdx.x; i < C * HD; i += blockDim.x) {
-    const int c = i / HD, st = i % HD;
-    wl[i] = mlp[proj_hidden_of_storage(st) * D_IN + c];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int h = lane >> 5, col = lane & 31;
-  // `tiles` (bts_project_features_tiles): only the flagged tiles are computed -- a training step's samples read 38 % of them
-  // (exp_kitti_360.yaml's batch), the rest of the map is never looked at and stays as it is.  A tile's flag is fetched one tile ahead.
-  // `list` (bts_train_step_fwd, large maps): the flagged tiles as a compact list (compact_tiles_kernel), dealt round-robin -- every wave
-  // the same number of tiles to within one instead of a binomial share of the flags it happens to walk over
-  const int tile0 = blockIdx.x * 4 + wave, tstride = gridDim.x * 4;
-  const int n_work = list ? min(n_tiles, list[0]) : n_tiles;
-  int flag_n = list ? (tile0 < n_work ? list[4 + tile0] : 0) : ((tiles && tile0 < n_tiles) ? (int)tiles[tile0] : 1);
-  for (int it = tile0; it < n_work; it += tstride) {   // tile = 64 pixels of one image
-    const int fetched = __builtin_amdgcn_readfirstlane(flag_n);
-    flag_n = list ? (it + tstride < n_work ? list[4 + it + tstride] : 0) : ((tiles && it + tstride < n_tiles) ? (int)tiles[it + tstride] : 1);
-    if (!list && fetched == 0) continue;
-    const int tile = list ? fetched : it;
-    const int img = tile / tiles_per_img;
-    // slot i of the tile is texel p0 + i + (i >> 4) * rs of the image (bts_common.h: a 16 x 4 block, or 64 consecutive texels with rs = 0)
-    const int p0 = tile_base(tile - img * tiles_per_img, Wm, tw), rs = tile_rs(Wm, tw);
-    const int px0 = p0 + col + (col >> 4) * rs, px1 = p0 + 32 + col + ((32 + col) >> 4) * rs;   // this lane's texels of the two point tiles
-    const float* F = feat + (long)img * C * HW;
-    float* G = proj + (long)img * HW * HD;
-    f32x16 acc[2][HT];
-    if constexpr (FEAT_CL) {
-      const float4* F4 = reinterpret_cast<const float4*>(F);
-      const unsigned q0 = (unsigned)(min(px0, HW - 1) * (C / 4) + h), q1 = (unsigned)(min(px1, HW - 1) * (C / 4) + h);
-      float4 v0[C / 8], v1[C / 8];
-#pragma unroll
-      for (int q = 0; q < C / 8; ++q) v0[q] = F4[q0 + 2 * q], v1[q] = F4[q1 + 2 * q];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-        for (int ht = 0; ht < HT; ++ht) acc[pt][ht] = zero_acc();
-#pragma unroll
-      for (int q = 0; q < C / 8; ++q) {
-        const float* a0 = reinterpret_cast<const float*>(&v0[q]);
-        const float* a1 = reinterpret_cast<const float*>(&v1[q]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 8 * q + 4 * h + e;
-#pragma unroll
-          for (int ht = 0; ht < HT; ++ht) {
-            const float b = wl[c * HD + ht * 32 + col];
-            acc[0][ht] = mfma(a0[e], b, acc[0][ht]);
-            acc[1][ht] = mfma(a1[e], b, acc[1][ht]);
-          }
-        }
-      }
-    } else {
-    // wave-uniform base + 32-bit lane offset (one image's map is far below 4 GB): scalar-base loads, no 64-bit address per load
-    const unsigned o0 = (unsigned)(h * HW + min(px0, HW - 1)), o1 = (unsigned)(h * HW + min(px1, HW - 1));
-    float a0[C / 2], a1[C / 2];
-#pragma unroll
-    for (int s = 0; s < C / 2; ++s) {
-      const float* row = F + (long)(2 * s) * HW;   // uniform
-      a0[s] = row[o0], a1[s] = row[o1];
-    }
-    __builtin_amdgcn_sched_barrier(0);   // the scheduler otherwise sinks every load to its MFMA (two loads in flight, measured 2.9 TB/s)
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-      for (int ht = 0; ht < HT; ++ht) acc[pt][ht] = zero_acc();
-#pragma unroll
-    for (int s = 0; s < C / 2; ++s) {
-      const int c = 2 * s + h;
-#pragma unroll
-      for (int ht = 0; ht < HT; ++ht) {
-        const float b = wl[c * HD + ht * 32 + col];
-        acc[0][ht] = mfma(a0[s], b, acc[0][ht]);
-        acc[1][ht] = mfma(a1[s], b, acc[1][ht]);
-      }
-    }
-    }
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int pix = tile_px_c(p0, pt * 32 + mfma_row(q, 0), 4 * h, rs);   // mfma_row(q, h) = mfma_row(q, 0) + 4 h, (.. & 15) <= 11
-        if (pix < HW) {
-#pragma unroll
-          for (int ht = 0; ht < HT; ++ht) G[(unsigned)(pix * HD + ht * 32 + col)] = acc[pt][ht][q];
-        }
-      }
-  }
+  __shared__ float wl[C * HD];
+#define BTS_PROJ_BLOCK blockIdx.x
+#define BTS_PROJ_BLOCKS gridDim.x
+#include "bts_project_body.h"
 }
 
 // ---- backward: ONE kernel for both gradients, so that dG (the largest tensor of a training step: 503 MB at exp_kitti_360.yaml's

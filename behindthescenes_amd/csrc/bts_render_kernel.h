@@ -224,6 +224,27 @@ __device__ __forceinline__ void stage_weights_h(float* lh, const float* empty_pr
   for (int i = threadIdx.x; i < HD; i += blockDim.x) lh[LH::EMPTY + i] = empty_proj[i] * scale;
 }
 
+// The staged MLP of render_kernel_p as ONE block of floats: Lds<C, HD, NB, true> | pad to 16 bytes | LdsH<C, HD, NB>.  The evaluation frame's
+// prep launch (bts_aux.hip: eval_prep_kernel) runs stage_weights / stage_weights_h once and writes the block to global memory; the
+// frame's render launch copies it into LDS -- FLOATS / 4 coalesced 16-byte loads and one barrier per work-group instead of ~33 strided
+// 4-byte loads per thread, a 64-term FMA chain and five barriers, 512 times per frame.  The same bits by construction.
+template <int C, int HD, int NB>
+struct MlpImage {
+  static constexpr int LH_OFF = (Lds<C, HD, NB, true>::TOTAL + 3) & ~3;
+  static constexpr int FLOATS = (LH_OFF + LdsH<C, HD, NB>::TOTAL + 3) & ~3;
+  static constexpr int LDS_FLOATS = Lds<C, HD, NB, true>::TOTAL + LdsH<C, HD, NB>::TOTAL + 4;   // render_kernel_p's static array
+  static_assert(FLOATS <= LDS_FLOATS, "the image is copied into render_kernel_p's array as whole float4");
+};
+
+// stage the MLP of render_kernel_p (fp32 part and split-f16 part) into `lds` from the packed parameter vector; ends with a barrier
+template <int C, int HD, int NB>
+__device__ __forceinline__ void stage_mlp(float* lds, const float* mlp, const float* empty) {
+  stage_weights<C, HD, NB, true>(lds, mlp, empty);
+  __syncthreads();
+  stage_weights_h<C, HD, NB>(lds + MlpImage<C, HD, NB>::LH_OFF, lds + Lds<C, HD, NB, true>::EMPTY, mlp);
+  __syncthreads();
+}
+
 __device__ __forceinline__ void swap32u(unsigned& a, unsigned& b) {
   auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
   a = r[0], b = r[1];
@@ -719,7 +740,11 @@ using IterHead = IterHeadT<false>;
 // parameter, not a run-time test: the evaluation instantiations carry no trace of it (16 more spilled SGPRs otherwise).
 // DYN: the groups behind FwdParams::dyn_first are not on the waves' lists, they are claimed from the counter FwdParams::sched (below:
 // "Work distribution").  Built for the evaluation frame's kernels only; every other instantiation carries no trace of it.
-template <int C, int HD, int NB, int NVMAX, bool ONE_RAY, bool F16, bool EPI = false, bool DYN = false>
+// IMG: the preheader copies the staged MLP from FwdParams::mlp_image instead of staging it (MlpImage above).  A template parameter like
+// DYN, and for the same reason: the instantiations without it are, instruction for instruction, the kernels they were -- a run-time
+// test in the preheader re-colours the registers of the whole per-ray loop.  Built for the evaluation frame's kernels (no loss epilogue,
+// at most two render views); a launch with an image and no such instantiation stages in place.
+template <int C, int HD, int NB, int NVMAX, bool ONE_RAY, bool F16, bool EPI = false, bool DYN = false, bool IMG = false>
 __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParams p) {
   static_assert(F16, "lin_in runs on the f16 matrix pipe in split precision: the fp32-input-MFMA form of rounds 1 - 2 is gone (git history)");
   using L = Lds<C, HD, NB, true>;
@@ -728,12 +753,28 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   constexpr int NS = 4 * HT;
   __shared__ __attribute__((aligned(16))) float lds[L::TOTAL + (F16 ? LH::TOTAL + 4 : 0)];
   float* const lh = lds + ((L::TOTAL + 3) & ~3);  // 16-byte aligned: the f16 A operands are read as ds_read_b128
-  stage_weights<C, HD, NB, true>(lds, p.mlp, p.empty_feature);
-  __syncthreads();
-  if constexpr (F16) {
-    stage_weights_h<C, HD, NB>(lh, lds + L::EMPTY, p.mlp);
+#ifdef BTS_PROBE
+  const unsigned long long t_entry = __builtin_readcyclecounter();
+#endif
+  if constexpr (IMG) {
+    // the staged MLP ready-made (MlpImage: the prep launch of bts_eval_frame_prep ran the two routines below once for the frame)
+    const float4* src = reinterpret_cast<const float4*>(p.mlp_image);
+    float4* dst = reinterpret_cast<float4*>(lds);
+    for (int i = threadIdx.x; i < MlpImage<C, HD, NB>::FLOATS / 4; i += 256) dst[i] = src[i];
     __syncthreads();
+  } else {
+    stage_weights<C, HD, NB, true>(lds, p.mlp, p.empty_feature);
+    __syncthreads();
+    if constexpr (F16) {
+      stage_weights_h<C, HD, NB>(lh, lds + L::EMPTY, p.mlp);
+      __syncthreads();
+    }
   }
+#ifdef BTS_PROBE
+  // the preheader: kernel entry to the barrier behind the staged (or copied) MLP, per wave (tools/section_probe.py --lifetimes folds the
+  // waves of a work-group); 16 bits of cycles, saturated, above XCC_ID in the last counter word -- exact through the tools' float64 tables
+  const unsigned long long t_stage = __builtin_readcyclecounter() - t_entry;
+#endif
   // 2^S carried by the accumulators of the f16 path (1 on the fp32 path)
   const float scale = F16 ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lh[LH::SCALE]))) : 1.0f;
   const float inv_scale = F16 ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lh[LH::SCALE + 1]))) : 1.0f;
@@ -905,7 +946,7 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
 #pragma unroll
     for (int i = 0; i < 6; ++i) d[i] = t_acc[i];
     d[6] = __builtin_readcyclecounter() - t_begin;
-    d[7] = ((unsigned long long)xcc_id << 32) | hw_id;
+    d[7] = ((t_stage < 0xFFFFull ? t_stage : 0xFFFFull) << 36) | ((unsigned long long)xcc_id << 32) | hw_id;
   }
 #endif
 }
@@ -915,6 +956,20 @@ template <int C, int HD, int NB, int NVMAX, bool EPI>
 static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
 #ifdef BTS_GATHER_LDS
   auto go = [&](auto kern) { launch_dyn_lds(kern, grid, 4 * kGatherLdsPerWave, s, p); };
+  // the staged MLP ready-made (FwdParams::mlp_image): the evaluation frame's kernels, each form of them
+  if constexpr (!EPI && NVMAX <= 2) {
+    if (p.mlp_image) {
+      if constexpr (NB == 0) {
+        if (p.lpr == 64 && p.sched && p.dyn_first < p.groups) {
+          go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true, true>);
+          return launch_check();
+        }
+      }
+      if (p.lpr == 64) go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, false, true>);
+      else go(render_kernel_p<C, HD, NB, NVMAX, false, true, EPI, false, true>);
+      return launch_check();
+    }
+  }
   // the claimed tail (FwdParams::sched): the evaluation frame's one-ray kernels with two loops only
   if constexpr (!EPI && NB == 0 && NVMAX <= 2) {
     if (p.lpr == 64 && p.sched && p.dyn_first < p.groups) {

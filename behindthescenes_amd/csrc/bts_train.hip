@@ -369,14 +369,26 @@ int train_step_bwd_impl(const BtsTrainStep* st, const float* g_loss, hipStream_t
   return BTS_OK;
 }
 
-int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipStream_t stream) {
+// prep (bts_eval_frame_prep): the parameter tensors and the scratch of the launch that packs and stages the MLP under the projection;
+// NULL: the projection alone, on the caller's packed vector f->mlp_params
+struct EvalPrep {
+  const BtsMlpTensors* params;
+  float *packed, *image;
+};
+int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipStream_t stream, const EvalPrep* prep = nullptr) {
   const BtsFieldCfg& c = f->cfg;
   const int n = c.n, nv = c.nv;
   // cameras, inverse intrinsics (for distance_to_z behind the render), rgb0 packing, rays and rgb_gt: one launch (it also zeroes `sched`,
   // the render's ticket counter)
   int rc = eval_handover_launch(f->Ks, f->poses_c2w, f->images, n, f->v, f->id_encoder, nv, f->ids_render, c.H, c.W, f->z_near, f->z_far, f->norm_dir,
                                 f->img_scale, f->img_shift, f->cams, f->depth_z ? f->inv_K : nullptr, f->imgs_nhwc4, f->rays, rgb_gt, sched, stream);
-  if (!rc) rc = project_features_impl(c.C, c.d_hidden, f->feat_nchw, f->mlp_params, n, c.H * c.W, f->proj_nhwc, nullptr, stream, f->feat_channels_last != 0);
+  // the projection -- with `prep` on lin_in's own weight, and in the same launch the MLP: packed for the render, and staged once for all of
+  // its work-groups
+  if (!rc && prep)
+    rc = eval_prep_launch(c.C, c.d_hidden, c.n_blocks, f->feat_nchw, f->feat_channels_last != 0, f->proj_nhwc, prep->params->tensor,
+                          c.learn_empty ? f->empty_feature : nullptr, prep->packed, prep->image, n, c.H * c.W, stream);
+  else if (!rc)
+    rc = project_features_impl(c.C, c.d_hidden, f->feat_nchw, f->mlp_params, n, c.H * c.W, f->proj_nhwc, nullptr, stream, f->feat_channels_last != 0);
   if (rc) {
     set_error("%s: a hand-over kernel launch failed", "bts_eval_frame");
     return rc;
@@ -387,12 +399,12 @@ int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipSt
   memset(&t, 0, sizeof(t));
   const CamBlock cam = split_cams(f->cams, n, nv);
   t.proj_nhwc = f->proj_nhwc, t.K_enc = cam.K_enc, t.w2c_enc = cam.w2c_enc, t.imgs_nhwc4 = f->imgs_nhwc4, t.K_r = cam.K_r, t.w2c_r = cam.w2c_r;
-  t.empty_feature = c.learn_empty ? f->empty_feature : nullptr, t.mlp_params = f->mlp_params;
+  t.empty_feature = c.learn_empty ? f->empty_feature : nullptr, t.mlp_params = prep ? prep->packed : f->mlp_params;
   BtsRenderArgs a;
   memset(&a, 0, sizeof(a));
   a.rays_per_sample = f->v * c.H * c.W, a.K = f->K, a.hard_alpha_cap = f->hard_alpha_cap, a.rays = f->rays, a.jitter = f->jitter, a.lindisp = f->lindisp;
   a.rgb = f->rgb, a.depth = f->depth, a.weights = f->weights, a.alphas = f->alphas, a.invalid = f->invalid;
-  rc = render_fwd_sched_impl(&cfg, &t, &a, sched, stream);
+  rc = render_fwd_sched_impl(&cfg, &t, &a, sched, stream, prep ? prep->image : nullptr);
   if (rc) return rc;
   if (f->depth_z) {
     rc = distance_to_z_launch(f->depth, f->inv_K, n * f->v, c.H, c.W, f->depth_z, stream);
@@ -410,36 +422,70 @@ using namespace bts;
 
 extern "C" {
 
-int bts_eval_frame_sched(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, void* stream) {
+// the argument checks of the eval-frame entry points; packed: the caller hands f->mlp_params over (every entry but bts_eval_frame_prep)
+static int check_eval_frame(const BtsEvalFrame* f, const char* who, bool packed) {
   if (!f) {
-    set_error("%s: NULL frame", "bts_eval_frame");
+    set_error("%s: NULL frame", who);
     return BTS_E_INVALID;
   }
   const BtsFieldCfg& c = f->cfg;
   if (c.n <= 0 || c.H <= 0 || c.W <= 0 || f->v <= 0 || f->K <= 0 || c.nv < 0 || c.nv > BTS_MAX_VIEWS) {
-    set_error("%s: non-positive size or more than 8 render views (n=%ld, v=%ld, K=%ld)", "bts_eval_frame", c.n, f->v, f->K);
+    set_error("%s: non-positive size or more than 8 render views (n=%ld, v=%ld, K=%ld)", who, c.n, f->v, f->K);
     return BTS_E_INVALID;
   }
   if (!shape_supported(c.C, c.d_hidden, c.n_blocks) || c.num_freqs != kNumFreqs) {
-    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", "bts_eval_frame", c.C, c.d_hidden, c.n_blocks);
+    set_error("%s: configuration outside the compiled envelope (C=%ld d_hidden=%ld n_blocks=%ld)", who, c.C, c.d_hidden, c.n_blocks);
     return BTS_E_UNSUPPORTED;
   }
   bool ids_ok = f->id_encoder >= 0 && f->id_encoder < f->v;
   for (int j = 0; j < c.nv; ++j) ids_ok = ids_ok && f->ids_render[j] >= 0 && f->ids_render[j] < f->v;
   if (!ids_ok || c.enc_render_view < -1 || c.enc_render_view >= c.nv) {
-    set_error("%s: a frame id outside [0, v=%ld) or enc_render_view out of range", "bts_eval_frame", f->v);
+    set_error("%s: a frame id outside [0, v=%ld) or enc_render_view out of range", who, f->v);
     return BTS_E_INVALID;
   }
-  if (!f->images || !f->Ks || !f->poses_c2w || !f->feat_nchw || !f->mlp_params || !f->jitter || !f->cams || !f->proj_nhwc || !f->rays || !f->rgb ||
-      !f->depth || (c.nv > 0 && !f->imgs_nhwc4) || (f->depth_z && !f->inv_K) || (c.learn_empty && !f->empty_feature)) {
-    set_error("%s: NULL input / output / scratch pointer", "bts_eval_frame");
+  if (!f->images || !f->Ks || !f->poses_c2w || !f->feat_nchw || (packed && !f->mlp_params) || !f->jitter || !f->cams || !f->proj_nhwc || !f->rays ||
+      !f->rgb || !f->depth || (c.nv > 0 && !f->imgs_nhwc4) || (f->depth_z && !f->inv_K) || (c.learn_empty && !f->empty_feature)) {
+    set_error("%s: NULL input / output / scratch pointer", who);
     return BTS_E_INVALID;
   }
   if ((long)c.n * f->v * c.H * c.W > 0x7FF00000L) {
-    set_error("%s: too many rays in one call (%ld)", "bts_eval_frame", (long)c.n * f->v * c.H * c.W);
+    set_error("%s: too many rays in one call (%ld)", who, (long)c.n * f->v * c.H * c.W);
     return BTS_E_UNSUPPORTED;
   }
+  return BTS_OK;
+}
+
+int bts_eval_frame_sched(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, void* stream) {
+  if (int rc = check_eval_frame(f, "bts_eval_frame", true)) return rc;
   return eval_frame_impl(f, rgb_gt, sched, (hipStream_t)stream);
+}
+
+int64_t bts_mlp_image_floats(const BtsFieldCfg* cfg) { return cfg ? mlp_image_floats(cfg->C, cfg->d_hidden, cfg->n_blocks) : 0; }
+
+int bts_eval_frame_prep(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, const BtsMlpTensors* params, float* mlp_packed, float* mlp_image,
+                        void* stream) {
+  const char* who = "bts_eval_frame_prep";
+  if (int rc = check_eval_frame(f, who, false)) return rc;
+  if (!params || !mlp_packed) {
+    set_error("%s: NULL input / output / scratch pointer", who);
+    return BTS_E_INVALID;
+  }
+  const int want = 4 + 4 * f->cfg.n_blocks;
+  if (params->n_tensors != want || want > BTS_MLP_MAX_TENSORS) {
+    set_error("%s: n_tensors=%ld, the MLP has %ld parameter tensors (4 + 4 * n_blocks)", who, params->n_tensors, want);
+    return BTS_E_INVALID;
+  }
+  for (int i = 0; i < want; ++i)
+    if (!params->tensor[i]) {
+      set_error("%s: NULL input / output / scratch pointer", who);
+      return BTS_E_INVALID;
+    }
+  if ((reinterpret_cast<uintptr_t>(mlp_image) & 15) != 0) {
+    set_error("%s: mlp_image must be 16-byte aligned (the render's work-groups copy it with 16-byte loads)", who);
+    return BTS_E_INVALID;
+  }
+  const EvalPrep prep{params, mlp_packed, mlp_image};
+  return eval_frame_impl(f, rgb_gt, sched, (hipStream_t)stream, &prep);
 }
 
 int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream) { return bts_eval_frame_sched(f, rgb_gt, nullptr, stream); }

@@ -839,20 +839,56 @@ class Conv3x3Function(torch.autograd.Function):
         return d_x, d_w, d_b, None, None, None
 
 
+def mlp_tensor_sizes(cfg):
+    """Element counts of the density MLP's parameter tensors in the packed vector's order (include/bts_render.h): lin_in.weight, lin_in.bias,
+    per block fc_0.weight, fc_0.bias, fc_1.weight, fc_1.bias, then lin_out.weight, lin_out.bias."""
+    hd, d_in = int(cfg.d_hidden), int(cfg.C) + 3 + 6 * int(cfg.num_freqs)
+    return [hd * d_in, hd] + [hd * hd, hd, hd * hd, hd] * int(cfg.n_blocks) + [hd, 1]
+
+
+def mlp_image_floats(spec) -> int:
+    """Floats of bts_eval_frame_prep's ``mlp_image`` scratch for this field (the MLP as the render kernel stages it into LDS)."""
+    cfg = _spec_cfg(spec)
+    return int(_lib.load().bts_mlp_image_floats(C.byref(cfg)))
+
+
 def eval_frame(fr, stream, rgb_gt=None):
     """bts_eval_frame on a filled ``_lib.BtsEvalFrame`` (behindthescenes_amd.train_step.FusedEvalFrame builds it).  With ``rgb_gt`` -- a
     contiguous float32 (n, v, 3, H, W) tensor, given here or set as ``fr.rgb_gt`` -- bts_eval_frame_gt: the hand-over launch also writes
     ``images * img_scale + img_shift`` into it.  With ``fr.sched`` -- 256 int32 words on the device, the frame's own while it runs --
-    bts_eval_frame_sched: the render's waves claim the last part of the rays from its counters instead of walking fixed lists to the end."""
+    bts_eval_frame_sched: the render's waves claim the last part of the rays from its counters instead of walking fixed lists to the end.
+    With ``fr.prep`` -- ``dict(params=[the MLP's tensors], packed=scratch, image=scratch or None)`` -- bts_eval_frame_prep: the projection's
+    launch also reads the parameter tensors themselves, packs and stages them (``fr.mlp_params`` is not read), with or without ``sched`` and ``rgb_gt``."""
     if rgb_gt is None:
         rgb_gt = fr.rgb_gt
     sched = getattr(fr, "sched", None)
+    prep = getattr(fr, "prep", None)
     if rgb_gt is not None:
         c = fr.cfg
         _req(rgb_gt, "rgb_gt", (c.n, fr.v, 3, c.H, c.W))
     if sched is not None:
         if not sched.is_cuda or sched.dtype != torch.int32 or sched.numel() < 256 or not sched.is_contiguous():
             raise BtsNativeError("sched: 256 contiguous int32 words on the device expected")
+    if prep is not None:
+        lib = _lib.load()
+        sizes = mlp_tensor_sizes(fr.cfg)
+        params = list(prep["params"])
+        if len(params) != len(sizes) or len(params) > _lib.BTS_MLP_MAX_TENSORS:
+            raise BtsNativeError(f"prep: {len(sizes)} parameter tensors expected (lin_in, the blocks, lin_out: weight and bias), got {len(params)}")
+        mt = _lib.BtsMlpTensors()
+        mt.n_tensors = len(params)
+        for i, (t, want) in enumerate(zip(params, sizes)):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != want:
+                raise BtsNativeError(f"prep: parameter tensor {i} must be {want} contiguous float32 values on the device (got {tuple(t.shape)}, {t.dtype})")
+            mt.tensor[i] = t.data_ptr()
+        packed, image = prep["packed"], prep.get("image")
+        for name, t, want in (("packed", packed, sum(sizes)), ("image", image, int(lib.bts_mlp_image_floats(C.byref(fr.cfg))))):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < want or want <= 0):
+                raise BtsNativeError(f"prep: {name} must be {want} contiguous float32 values on the device")
+        _lib.check(lib.bts_eval_frame_prep(C.byref(fr), None if rgb_gt is None else _ptr(rgb_gt), None if sched is None else C.c_void_p(sched.data_ptr()),
+                                           C.byref(mt), _ptr(packed), None if image is None else _ptr(image), stream), "bts_eval_frame_prep")
+        return
+    if sched is not None:
         _lib.check(_lib.load().bts_eval_frame_sched(C.byref(fr), None if rgb_gt is None else _ptr(rgb_gt), C.c_void_p(sched.data_ptr()), stream), "bts_eval_frame_sched")
         return
     if rgb_gt is None:

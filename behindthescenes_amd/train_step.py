@@ -428,6 +428,13 @@ class FusedEvalFrame(torch.nn.Module):
         self._scratch = {}
         # the render launch's claimed tail (bts_eval_frame_sched; False: fixed ray lists to the end, bts_eval_frame_gt).  Same outputs.
         self.dynamic_tail = True
+        # the launch behind the hand-over is the prep launch (bts_eval_frame_prep: MLP | projection): it reads the MLP's parameter tensors
+        # themselves -- no packed() vector, no torch.cat -- and stages the MLP once for all of the render's work-groups under the
+        # projection; False: the projection alone on packed() (bts_eval_frame_sched / _gt).  Same outputs.
+        self.one_prep_launch = True
+        # ... and whether that launch also stages the MLP for the render's work-groups (False: it packs the parameters only, every render
+        # work-group stages for itself as without the prep launch).  Same outputs.
+        self.staged_mlp = True
 
     def why_not(self, images=None, ids_encoder=(0,), ids_render=(0,)):
         from .ray_sampler import ImageRaySampler
@@ -503,7 +510,10 @@ class FusedEvalFrame(torch.nn.Module):
         if sc is None:
             sc = self._scratch[key] = dict(cams=torch.empty(n * (25 + nv * 25), **f32), imgs=torch.empty((n, max(nv, 1), H, W, 4), **f32),
                                            proj=torch.empty((n, H, W, spec.d_hidden), **f32), inv_K=torch.empty((n, v, 3, 3), **f32),
-                                           sched=torch.zeros(256, device=dev, dtype=torch.int32))
+                                           sched=torch.zeros(256, device=dev, dtype=torch.int32),
+                                           # bts_eval_frame_prep's: the packed parameter vector and the MLP as the render stages it
+                                           mlp_packed=torch.empty(int(spec.mlp_param_count()), **f32),
+                                           mlp_image=torch.empty(int(native.mlp_image_floats(spec)), **f32))
         out = dict(rays=torch.empty((n, v * H * W, 8), **f32), rgb=torch.empty((n, v, H, W, nv, 3), **f32), depth=torch.empty((n, v, H, W), **f32),
                    depth_z=torch.empty((n, v, H, W), **f32) if to_z else None, weights=torch.empty((n, v, H, W, K), **f32) if want_weights else None,
                    alphas=torch.empty((n, v, H, W, K), **f32) if want_alphas else None, invalid=torch.empty((n, v, H, W, K, nv), **f32),
@@ -516,7 +526,19 @@ class FusedEvalFrame(torch.nn.Module):
         fr.K, fr.lindisp, fr.hard_alpha_cap, fr.norm_dir = K, int(bool(r.lindisp)), int(bool(r.hard_alpha_cap)), int(bool(smp.norm_dir))
         fr.z_near, fr.z_far, fr.img_scale, fr.img_shift = float(smp.z_near), float(smp.z_far), 0.5, 0.5
         fr.feat_channels_last = int(native.is_channels_last(feat))
-        params = net.mlp_coarse.packed().detach()
+        prep = None
+        if self.one_prep_launch:
+            # the parameters as they are NOW, by pointer: nothing is cached on their identity or version (the launch reads them every frame)
+            mlp = net.mlp_coarse
+            tensors = [mlp.lin_in.weight, mlp.lin_in.bias]
+            for blk in mlp.blocks:
+                tensors += [blk.fc_0.weight, blk.fc_0.bias, blk.fc_1.weight, blk.fc_1.bias]
+            tensors += [mlp.lin_out.weight, mlp.lin_out.bias]
+            tensors = [t.detach() if t.is_contiguous() and t.dtype == torch.float32 else t.detach().float().contiguous() for t in tensors]
+            prep = dict(params=tensors, packed=sc["mlp_packed"], image=sc["mlp_image"] if self.staged_mlp else None)
+            params = None
+        else:
+            params = net.mlp_coarse.packed().detach()
         empty = net.empty_feature.detach() if net.learn_empty else None
 
         def dp(t):
@@ -528,6 +550,7 @@ class FusedEvalFrame(torch.nn.Module):
             setattr(fr, k_, dp(out[k_]))
         fr.rgb_gt = out["rgb_gt"]          # (host-side attribute, no struct field: selects bts_eval_frame_gt in native.eval_frame)
         fr.sched = sc["sched"] if self.dynamic_tail else None      # (likewise: bts_eval_frame_sched)
+        fr.prep = prep                                              # (likewise: bts_eval_frame_prep)
         native.eval_frame(fr, native._stream(images))
         part = dict(rgb=out["rgb"], depth=out["depth_z"] if to_z else out["depth"], invalid=out["invalid"])
         if want_weights:

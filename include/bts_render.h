@@ -541,6 +541,27 @@ int bts_eval_frame(const BtsEvalFrame* f, void* stream);
  * with too few rays per wave for a tail take the fixed lists alone.  NULL: the fixed lists alone;
  * bts_eval_frame_gt(f, rgb_gt, stream) = bts_eval_frame_sched(f, rgb_gt, NULL, stream). */
 int bts_eval_frame_sched(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, void* stream);
+/* bts_eval_frame_prep (additive to ABI 9, the struct is unchanged): the same frame without a packed parameter vector from the caller: the
+ * launch behind the hand-over is eval_prep_kernel, the projection and the MLP (packed, and staged for the render) as work-group ranges of one dispatch.
+ *   params      the MLP's own tensors, device pointers to contiguous fp32: lin_in.weight, lin_in.bias, then per ResnetBlockFC fc_0.weight,
+ *               fc_0.bias, fc_1.weight, fc_1.bias, then lin_out.weight, lin_out.bias -- n_tensors = 4 + 4 * cfg.n_blocks.  Read by the
+ *               launch on the stream, every frame: weights changed in place between two frames are seen.  f->mlp_params is not read.
+ *   mlp_packed  scratch, bts_mlp_param_count(&f->cfg) floats: the launch writes the packed vector (the layout at the top of this header)
+ *               there and the render reads it
+ *   mlp_image   scratch, bts_mlp_image_floats(&f->cfg) floats on a 16-byte boundary, or NULL: the MLP as the render kernel stages it into LDS
+ *               (k-major fp32 rows, the split-f16 weights and their scale, the projected empty feature), computed once by the launch; the
+ *               render's work-groups copy it instead of staging it themselves, each for itself.  NULL: they stage from mlp_packed.
+ * Both scratch buffers belong to one frame at a time, like `sched`.  Every output is the same bits as bts_eval_frame_sched's: the frame
+ * is four dispatches as before, hand-over, prep, render, distance_to_z, and the caller's `torch.cat` of the parameters is gone. */
+#define BTS_MLP_MAX_TENSORS 12
+typedef struct BtsMlpTensors {
+  const float* tensor[BTS_MLP_MAX_TENSORS];
+  int32_t n_tensors;
+  int32_t reserved_;
+} BtsMlpTensors;
+int64_t bts_mlp_image_floats(const BtsFieldCfg* cfg);   /* 0: a shape outside the compiled envelope */
+int bts_eval_frame_prep(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, const BtsMlpTensors* params, float* mlp_packed, float* mlp_image,
+                        void* stream);
 /* The split that launch uses, on the host (no GPU): `grid` work-groups of four waves, `groups` rays -> the first claimed ray (= groups: no
  * tail), a multiple of 8 << *chunk_log2 (the XCD interleave's chunk, written when chunk_log2 is not NULL). */
 int64_t bts_render_dyn_first(int32_t grid, int64_t groups, int32_t* chunk_log2);

@@ -7,7 +7,8 @@ Ablations (BTS_ABLATE bits, probe build only): 1 no gather (register-gather buil
 the render kernel's shared-texel loop (one fetch of G per ray; wrong rows for view 1 -- what a single fetch would buy there).
     python tools/section_probe.py --lifetimes [--no-tail] [--out FILE]
 the flagship evaluation frame instead: per-wave lifetimes of its render launch over the chip, per XCD and per CU (the probe build stores
-XCC_ID and HW_ID next to the counters); --no-tail: fixed ray lists to the end; BTS_DYN_TAIL_DIV=d: a claimed tail of 1 / d of the rays."""
+XCC_ID and HW_ID next to the counters); --no-tail: fixed ray lists to the end; BTS_DYN_TAIL_DIV=d: a claimed tail of 1 / d of the rays.
+With them the launch's preheader per work-group: ticks from kernel entry to the barrier behind the staged MLP (the slowest of its waves)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -46,6 +47,25 @@ def lifetime_table(d, out=sys.stdout):
     return (life.max() - life.mean()) / life.max()
 
 
+def preheader_row(raw, frame_ms, out=sys.stdout):
+    """The preheader of every work-group that ran (the probe build keeps it, 16 bits saturated, above XCC_ID in d[7]): median and maximum
+    over the work-groups, in cycles of the counter the lifetimes are in and in microseconds.  Two conversions are printed: the device's
+    shader clock as the driver reports it, and the rate this very frame shows -- its longest wave's lifetime over the frame's event time,
+    which holds the other dispatches too, so that rate is a lower bound and the microseconds from it an upper one."""
+    ran = raw[:, :, 6].amax(dim=1) > 0
+    pre = ((raw[:, :, 7] >> 36) & 0xFFFF).amax(dim=1)[ran].double()
+    life = raw[:, :, 6].amax(dim=1)[ran].double()
+    import ctypes
+    khz = ctypes.c_int(0)
+    ctypes.CDLL("libamdhip64.so").hipDeviceGetAttribute(ctypes.byref(khz), 5, torch.cuda.current_device())   # hipDeviceAttributeClockRate
+    mhz = khz.value / 1e3 if khz.value > 0 else float("nan")
+    mhz_run = float(life.max()) / (frame_ms * 1e3)
+    print(f"preheader per work-group ({pre.numel()} work-groups): median {pre.median():.0f} cycles, max {pre.max():.0f} cycles"
+          f"{' (saturated)' if pre.max() >= 0xFFFF else ''}; at the reported {mhz:.0f} MHz: median {pre.median() / mhz:.2f} us, max {pre.max() / mhz:.2f} us; "
+          f"at the >= {mhz_run:.0f} MHz of this frame (longest wave {life.max():.0f} cycles in {frame_ms:.3f} ms): median <= {pre.median() / mhz_run:.2f} us, "
+          f"max <= {pre.max() / mhz_run:.2f} us", file=out)
+
+
 def eval_frame_lifetimes(argv):
     """python tools/section_probe.py --lifetimes [--no-tail] [--out FILE]: the flagship frame (bench.py's KITTI eval_depth workload through
     FusedEvalFrame) on the probe build; per-wave lifetimes of its render launch."""
@@ -78,11 +98,13 @@ def eval_frame_lifetimes(argv):
         e1.record()
         torch.cuda.synchronize()
         assert frame.last_path == "fused", frame.last_path
-        d = dbg.view(-1, 8).double().cpu()
+        raw = dbg.view(-1, 4, 8).cpu()
+        d = raw.view(-1, 8).double()
         d = d[d[:, 6] > 0]
         print(f"--- frame {rep}: {e0.elapsed_time(e1):.3f} ms (probe build, counters on), {V * H * W / d.shape[0]:.1f} rays per wave, "
               f"one ray = {d[:, 6].mean() * d.shape[0] / (V * H * W):.0f} ticks of wave time", file=out)
         gaps.append(float(lifetime_table(d, out)))
+        preheader_row(raw, e0.elapsed_time(e1), out)
     print("gap (max - mean) / max per frame: " + " ".join(f"{100 * g:.2f} %" for g in gaps), file=out)
 
 

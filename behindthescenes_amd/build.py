@@ -98,8 +98,7 @@ def build_library(force: bool = False, verbose: bool = False, probe: bool = Fals
 
 
 # differently scheduled builds of the product sources (tests/test_gpu_determinism.py re-runs parity against them)
-SCHEDULE_VARIANTS = {"o2": ["-O2"], "regionbarrier": ["-DBTS_REGION_BARRIER"], "gatherregs": ["-DBTS_GATHER_REGS"],
-                     "fetchearly": ["-DBTS_GL_FETCH_EARLY"],
+SCHEDULE_VARIANTS = {"o2": ["-O2"], "fetchearly": ["-DBTS_GL_FETCH_EARLY"],
                      # the render kernel without its second loop for rays whose samples share their texels (tests/test_gpu_shared_texels.py)
                      "nosharedtexels": ["-DBTS_NO_SHARED_TEXELS"],
                      # not a schedule: the list-driven projection passes at EVERY map size (tests/test_gpu_tile_list.py)

@@ -22,7 +22,6 @@
 //                              operand (lane = channel reads its channel of sample k: no transposition), encoding recomputed.
 // What torch.autograd would do for nerf.py:283-299 + models_bts.py:266-338 + resnetfc.py:53-62, 132-184 of the reference.
 #define BTS_NO_LAUNCH_GLUE
-#undef BTS_GATHER_REGS   // (the register-gather A/B build, variants/libbts_gatherregs.so, concerns the render kernels: the row passes of the backward exist in the LDS-gather form only)
 #include "bts_render_kernel.h"
 #include "bts_bwd.h"
 #include "bts_host.h"
@@ -30,10 +29,6 @@
 #include <type_traits>
 
 namespace bts {
-
-#ifndef BTS_GATHER_LDS
-#error "bts_bwd_blocks.hip is written against the LDS gather (the wave's gather ring doubles as its transposition tiles)"
-#endif
 
 // Weights of this pass in LDS next to the forward's f16 operands (LdsH): the encoding rows of lin_in in fp32 (k-major: the cold path's
 // A operand), w_out, the projected empty feature, and per block fc_1 / fc_0 TRANSPOSED as split-precision f16 A operands (the layout of
@@ -481,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void rowsb_kernel(const BwdParams bp, const
       if (__builtin_expect(!cold, 1)) {
         // the previous iteration's tile reads have returned (s_waitcnt at its end): the ring may be overwritten
         wave_lds_fence();
-        gl.tab[lane * 3 + 0] = (unsigned)tp.o00 * (HD * 4u), gl.tab[lane * 3 + 1] = (unsigned)tp.o01 * (HD * 4u), gl.tab[lane * 3 + 2] = (unsigned)tp.o10 * (HD * 4u);   // o11 = o10 + (o01 - o00)
+        gl_write_taps<HD>(gl, tp, lane);
         wave_lds_fence();
         gl_prologue<HD>(gl, rows, G, off_next);
       }

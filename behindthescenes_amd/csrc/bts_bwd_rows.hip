@@ -197,7 +197,6 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
   const int lane = threadIdx.x & 63;
   const int h0 = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef BTS_GATHER_LDS
   extern __shared__ __attribute__((aligned(128))) char gather_lds[];   // per wave: ring of 3 x 4 KB + 768 B tap table (render_kernel_p)
   GatherLds gl;
   {
@@ -212,7 +211,6 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) gl.rd[q] = (unsigned)(col * 128 + ((4 * h0 + q - (col >> 1)) & 7) * 16);
   }
-#endif
   const int nwg = gridDim.x;  // multiple of 8
   const int wg = xcd_remap(blockIdx.x, nwg);
   const int wg_per_xcd = nwg >> 3;
@@ -313,40 +311,29 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
     if (use_empty) tp.w00 = tp.w01 = tp.w10 = tp.w11 = 0.0f;
     tp.w00 *= scale, tp.w01 *= scale, tp.w10 *= scale, tp.w11 *= scale;
 
-    // ---------------- tap offsets / weights of both point tiles on every lane; the first two gather stages go out now: their latency
+    // ---------------- tap weights of both point tiles on every lane; the first three gather blocks go out now: their latency
     // runs under the compositing gradient below (a scan across the wave, exp / log / divide) instead of in front of the MFMA phase
-    int o[2][4];
     float wq[2][4];
     bool emp[2];
     {
       unsigned t0, t1;
-      bcast_tiles((unsigned)tp.o00, t0, t1), o[0][0] = (int)t0, o[1][0] = (int)t1;
-      bcast_tiles((unsigned)tp.o01, t0, t1), o[0][1] = (int)t0, o[1][1] = (int)t1;
-      bcast_tiles((unsigned)tp.o10, t0, t1), o[0][2] = (int)t0, o[1][2] = (int)t1;
-      bcast_tiles((unsigned)tp.o11, t0, t1), o[0][3] = (int)t0, o[1][3] = (int)t1;
       bcast_tiles(__float_as_uint(tp.w00), t0, t1), wq[0][0] = __uint_as_float(t0), wq[1][0] = __uint_as_float(t1);
       bcast_tiles(__float_as_uint(tp.w01), t0, t1), wq[0][1] = __uint_as_float(t0), wq[1][1] = __uint_as_float(t1);
       bcast_tiles(__float_as_uint(tp.w10), t0, t1), wq[0][2] = __uint_as_float(t0), wq[1][2] = __uint_as_float(t1);
       bcast_tiles(__float_as_uint(tp.w11), t0, t1), wq[0][3] = __uint_as_float(t0), wq[1][3] = __uint_as_float(t1);
       bcast_tiles(use_empty ? 1u : 0u, t0, t1), emp[0] = t0 != 0, emp[1] = t1 != 0;
     }
-#ifdef BTS_GATHER_LDS
     unsigned off_next[4];
     GRows rows;
     {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      gl.tab[lane * 3 + 0] = (unsigned)tp.o00 * (HD * 4u), gl.tab[lane * 3 + 1] = (unsigned)tp.o01 * (HD * 4u), gl.tab[lane * 3 + 2] = (unsigned)tp.o10 * (HD * 4u);   // o11 = o10 + (o01 - o00)
+      gl_write_taps<HD>(gl, tp, lane);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       gl_prologue<HD>(gl, rows, G, off_next);
     }
-#else
-    GBuf ba, bb;
-    stage_load<HD, 0>(ba, G, o, h);
-    stage_load<HD, 1>(bb, G, o, h);
-#endif
 
     BW_TICK(0)
     // ---------------- upstream gradient of this sample's weight: g_w = g_depth z + sum_j g_rgb_j . c_kj (+ g_weights_k)
@@ -427,19 +414,11 @@ __global__ __launch_bounds__(256, 2) void rows_kernel(const BwdParams bp) {
       __builtin_amdgcn_sched_barrier(0);
       int lane4 = lane * 4;
       asm volatile("" : "+v"(lane4));
-#ifdef BTS_GATHER_LDS
       region_seq_l<HD, 0>(acc, gl, rows, G, wq, off_next, lh + LH::W_F16 + lane4, LH::TERM_STRIDE, raw, v3, qb->f.freq_factor, bias);
       if constexpr (NS > kNumFreqs) {
         gl_consume<HD, 12>(acc, gl, rows, G, wq, off_next), gl_consume<HD, 13>(acc, gl, rows, G, wq, off_next);
         gl_consume<HD, 14>(acc, gl, rows, G, wq, off_next), gl_consume<HD, 15>(acc, gl, rows, G, wq, off_next);
       }
-#else
-      region_seq<HD, 0>(acc, ba, bb, G, o, wq, h, lh + LH::W_F16 + lane4, LH::TERM_STRIDE, raw, v3, qb->f.freq_factor, bias);
-      if constexpr (NS > kNumFreqs) {
-        stage_blend<HD, 6>(acc, ba, wq);
-        stage_blend<HD, 7>(acc, bb, wq);
-      }
-#endif
     }
     if (qb->f.learn_empty && __any(use_empty)) {
 #pragma unroll
@@ -1224,13 +1203,8 @@ static void scatter_segments(ScatterMaskParams& sp, long units, int K);
 template <int C, int HD>
 static int launch_rows(const BwdParams& bp, int n, int grid, hipStream_t s) {
   const FwdParams& p = bp.f;
-#ifdef BTS_GATHER_LDS
-  constexpr int dyn = 4 * kGatherLdsPerWave;
-#else
-  constexpr int dyn = 0;
-#endif
   int rc = with_nvmax(p.nv, [&](auto nvmax) {
-    launch_dyn_lds(rows_kernel<C, HD, nvmax()>, grid, dyn, s, bp);
+    launch_dyn_lds(rows_kernel<C, HD, nvmax()>, grid, 4 * kGatherLdsPerWave, s, bp);
     return launch_check(kBwdLaunchFailed);
   });
   // Pass C and pass B one after the other on the caller's stream.  Pass C on a side queue next to pass B MEASURED SLOWER (round 6,

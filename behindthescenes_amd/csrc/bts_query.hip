@@ -12,7 +12,6 @@
 // cumulative sum along y, count of levels whose running sum stays <= 8, / Y -- is a wave scan + a ballot in the same kernel and no
 // per-point tensor reaches HBM at all.
 #define BTS_NO_LAUNCH_GLUE
-#undef BTS_GATHER_REGS   // (the register-gather A/B build, variants/libbts_gatherregs.so, concerns the render kernels: the query kernel exist in the LDS-gather form only)
 #include "bts_render_kernel.h"
 #include "bts_host.h"
 

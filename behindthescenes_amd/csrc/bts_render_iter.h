@@ -122,12 +122,14 @@
       const bool use_empty = (ih.learn_empty != 0) & pe.invalid;
       const Taps tp_enc = tp;   // as grid_sample has them: a render view that IS the encoder view (FwdParams::enc_view) takes its colour taps from here
       if (use_empty) tp.w00 = tp.w01 = tp.w10 = tp.w11 = 0.0f;  // the empty feature is added after the blend
-      if constexpr (F16) tp.w00 *= scale, tp.w01 *= scale, tp.w10 *= scale, tp.w11 *= scale;  // exact: power of two
+      tp.w00 *= scale, tp.w01 *= scale, tp.w10 *= scale, tp.w11 *= scale;  // exact: power of two
 
       float col[NVMAX * 3];
       bool inv[NVMAX];
 
-      // ---------------- tap offsets / weights of both point tiles on every lane
+      // ---------------- tap weights of both point tiles on every lane.  (`o`, the offsets, is read by nothing -- they go through the tap
+      // table in LDS -- and costs no instruction, but without its four broadcasts hipcc numbers the tap weights' registers differently
+      // in the two-loop kernels: it leaves with the next change that moves those kernels' instruction streams anyway.)
       int o[2][4];
       float wq[2][4];
       bool emp[2];
@@ -151,10 +153,8 @@
                                             q->inv_range, q->d_min, q->range, q->freq_factor, q->learn_empty, b_out, px, py, pz);
       } else {
       BTS_TICK(0)
-      // ---------------- h = bilinear(G) + W_pe . PE + b: gather two stages ahead, blend between the octaves
+      // ---------------- h = bilinear(G) + W_pe . PE + b: gather three blocks ahead, blend between the octaves
       f32x16 acc[HT][2];
-#ifdef BTS_GATHER_LDS
-      static_assert(F16, "the LDS gather is wired into the f16 path only");
       unsigned off_next[4];
       GRows rows;
       if constexpr (SHARED) {
@@ -169,15 +169,7 @@
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         gl_prologue<HD>(gl, rows, G, off_next);
       }
-#else
-      GBuf ba, bb;
-      const bool nogather = BTS_ABL(1);
-      if (!nogather) {
-        stage_load<HD, 0>(ba, G, o, h);
-        stage_load<HD, 1>(bb, G, o, h);
-      }
-#endif
-      if constexpr (F16) {
+      {
         // bias row (times 2^S, fp32): the C operand of the first MFMA of every accumulator tile.  The raw inputs x, y, code ride in
         // the spare k rows of the f16 slices (|x|, |y| <= 2083 here -- beyond that the wave took the exact path above), so the
         // fp32-input MFMAs, which block the VALU for 64 cycles each, are gone from this path.
@@ -197,30 +189,18 @@
         __builtin_amdgcn_sched_barrier(0);
         int lane4 = lane * 4;
         asm volatile("" : "+v"(lane4));  // keep the A-operand reads inside the loop (see lane_off above)
-#ifdef BTS_GATHER_LDS
         region_seq_l<HD, 0, SHARED>(acc, gl, rows, G, wq, off_next, lh + LH::W_F16 + lane4, LH::TERM_STRIDE, raw, v3, ih.freq_factor, bias, h);
-        if constexpr (NS > kNumFreqs) {   // HD = 64: the blocks of stages 6 and 7
+        if constexpr (NS > kNumFreqs) {   // HD = 64: the last four blocks
           g_step<HD, 12, SHARED>(acc, gl, rows, G, wq, off_next, h), g_step<HD, 13, SHARED>(acc, gl, rows, G, wq, off_next, h);
           g_step<HD, 14, SHARED>(acc, gl, rows, G, wq, off_next, h), g_step<HD, 15, SHARED>(acc, gl, rows, G, wq, off_next, h);
         }
-#else
-        region_seq<HD, 0>(acc, ba, bb, G, o, wq, h, lh + LH::W_F16 + lane4, LH::TERM_STRIDE, raw, v3, q->freq_factor, bias, nosin, nomfma);
-#endif
       }
-#ifndef BTS_GATHER_LDS
-      if constexpr (NS > kNumFreqs) {  // HD = 64: stages 6 and 7 are still in the buffers
-        if (!nogather) {
-          stage_blend<HD, 6>(acc, ba, wq);
-          stage_blend<HD, 7>(acc, bb, wq);
-        }
-      }
-#endif
       if (q->learn_empty && __any(use_empty)) {
 #pragma unroll
         for (int ht = 0; ht < HT; ++ht)
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const float ev = F16 ? lh[LH::EMPTY + ht * 32 + mfma_row(q, 0) + 4 * h] : lds[L::EMPTY + ht * 32 + mfma_row(q, 0) + 4 * h];
+            const float ev = lh[LH::EMPTY + ht * 32 + mfma_row(q, 0) + 4 * h];
 #pragma unroll
             for (int pt = 0; pt < 2; ++pt) acc[ht][pt][q] += emp[pt] ? ev : 0.0f;
           }
@@ -238,20 +218,20 @@
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
             const int row = ot * 32 + mfma_row(q, 0) + 4 * h;
-            const float bias = F16 ? lh[LH::BIAS + b * 2 * HD + row] : base[HD * HD + row];
+            const float bias = lh[LH::BIAS + b * 2 * HD + row];
             net[ot][0][q] = bias, net[ot][1][q] = bias;
           }
-        if constexpr (F16 && HD == 32) hidden_layer_h(net, acc, lh + LH::W_BLK + (2 * b) * LH::BLK_LAYER_STRIDE + lane4b, LH::BLK_TERM_STRIDE, inv_scale);
+        if constexpr (HD == 32) hidden_layer_h(net, acc, lh + LH::W_BLK + (2 * b) * LH::BLK_LAYER_STRIDE + lane4b, LH::BLK_TERM_STRIDE, inv_scale);
         else hidden_layer<HD>(net, acc, base, lane);
 #pragma unroll
         for (int ot = 0; ot < HT; ++ot)
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
             const int row = ot * 32 + mfma_row(q, 0) + 4 * h;
-            const float bias = F16 ? lh[LH::BIAS + b * 2 * HD + HD + row] : base[2 * HD * HD + HD + row];
+            const float bias = lh[LH::BIAS + b * 2 * HD + HD + row];
             acc[ot][0][q] += bias, acc[ot][1][q] += bias;
           }
-        if constexpr (F16 && HD == 32) hidden_layer_h(acc, net, lh + LH::W_BLK + (2 * b + 1) * LH::BLK_LAYER_STRIDE + lane4b, LH::BLK_TERM_STRIDE, inv_scale);
+        if constexpr (HD == 32) hidden_layer_h(acc, net, lh + LH::W_BLK + (2 * b + 1) * LH::BLK_LAYER_STRIDE + lane4b, LH::BLK_TERM_STRIDE, inv_scale);
         else hidden_layer<HD>(acc, net, base + HD * HD + HD, lane);
       }
 
@@ -275,7 +255,7 @@
         p0 = pp[0], p1 = pp[1];
       }
       swap32(p0, p1);  // p0 = {tile0.lo, tile1.lo}, p1 = {tile0.hi, tile1.hi}: lane l now holds both halves of ITS sample
-      s_raw = F16 ? __builtin_fmaf(p0 + p1, inv_scale, b_out) : (p0 + p1) + b_out;
+      s_raw = __builtin_fmaf(p0 + p1, inv_scale, b_out);
       }
       float sigma = softplus(s_raw);
       if (q->empty_empty) sigma = pe.invalid ? 0.0f : sigma;

@@ -6,19 +6,13 @@
 //   * z of the NEXT ray is prefetched while the current ray is evaluated; with one ray per wave the ray itself is wave-uniform
 //     and lives in scalar registers (s_load);
 //   * colour taps (<= 2 views) are issued right after the geometry, they land during the MFMA phase;
-//   * the gather of G runs two stages ahead in two register buffers and is blended INTO the running accumulators between the
-//     positional-encoding octaves: stage s is blended after octave s while the MFMAs of the octave cover the latency of
-//     stage s+1 / s+2 and the blend's packed FMAs fill the matrix pipe's issue gaps (acc starts at 0; summation order only);
+//   * the gather of G runs three blocks ahead through a per-wave ring in LDS (GatherLds below) and is blended INTO the running
+//     accumulators between the positional-encoding octaves: the MFMAs of a region cover the latency of the blocks behind it and
+//     the blend's packed FMAs fill the matrix pipe's issue gaps (summation order only);
 //   * alpha compositing is a DPP scan (row_shr / row_bcast) instead of ds_bpermute shuffles.
 // Replaces: nerf.py:210-313, models_bts.py:138-338, resnetfc.py:132-184, code.py:30-42 of the reference.
 #pragma once
 #include "bts_field_kernel.h"
-
-// The gather of G goes through LDS (global_load_lds_dwordx4, see GatherLds below) unless the build says -DBTS_GATHER_REGS (the
-// round-1 form: two register buffers per lane; kept for A/B as variants/libbts_gatherregs.so)
-#if !defined(BTS_GATHER_REGS) && !defined(BTS_GATHER_LDS)
-#define BTS_GATHER_LDS
-#endif
 
 namespace bts {
 
@@ -99,33 +93,6 @@ __device__ __forceinline__ float seg_scan_add(float x, int lpr, int kl) {
   if (lpr >= 32) x += dpp_f<kDppBcast15, 0xA>(0.0f, x);
   if (lpr >= 64) x += dpp_f<kDppBcast31, 0xC>(0.0f, x);
   return x;
-}
-
-// gather stage S of the sequence over (point tile, hidden tile, tap pair)
-template <int HD, int S>
-struct GStage {
-  static constexpr int HT = HD / 32;
-  static constexpr int pt = S / (2 * HT), ht = (S / 2) % HT, tp2 = S % 2;
-};
-
-// 8 float4 of stage S: wave-uniform base (SGPR pair) + 32-bit per-lane byte offset (one sample's G is far below 4 GB), so that the
-// address is one v_lshl_add per row instead of 64-bit arithmetic
-template <int HD, int S>
-__device__ __forceinline__ void stage_load(GBuf& b, const float4* __restrict__ G, const int (&o)[2][4], int h) {
-  using St = GStage<HD, S>;
-  const char* base = reinterpret_cast<const char*>(G);
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const unsigned off = (unsigned)o[St::pt][2 * St::tp2 + t] * (unsigned)(HD * 4) + (unsigned)(St::ht * 128) + (unsigned)h * 64u;
-    const float4* row = reinterpret_cast<const float4*>(base + off);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) b.v[t][q] = row[q];
-  }
-}
-template <int HD, int S>
-__device__ __forceinline__ void stage_blend(f32x16 (&acc)[HD / 32][2], const GBuf& b, const float (&w)[2][4]) {
-  using St = GStage<HD, S>;
-  gblend<false>(acc[St::ht][St::pt], b, w[St::pt][2 * St::tp2], w[St::pt][2 * St::tp2 + 1]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -379,69 +346,6 @@ __device__ __forceinline__ void pe_advance(SinCos3& raw, SinCos3& pre, const Sin
   }
 }
 
-// Region R = octaves 2R (sines computed directly, one region ahead) and 2R+1 (by angle doubling), with gather stages 2R and 2R+1
-// blended behind the region's MFMAs and stages 2R+2, 2R+3 issued.  The regions are no longer fenced from each other: the scheduler
-// may pull the next region's trigonometry under this region's MFMAs (3 % faster, +3 spilled VGPRs).
-template <int HD, int R>
-__device__ __forceinline__ void region_seq_i(f32x16 (&acc)[HD / 32][2], GBuf& ba, GBuf& bb, const float4* __restrict__ G,
-                                             const int (&o)[2][4], const float (&wq)[2][4], int h, const float* wf, int term_stride,
-                                             SinCos3& raw, SinCos3& pre, const float (&v3)[3], float ff, const f32x16* bias, bool nosin = false,
-                                             bool nomfma = false) {
-  constexpr int HT = HD / 32;
-  constexpr int NS = 4 * HT;
-  if constexpr (R < 3) {
-    constexpr int NE = R == 0 ? 14 : (R == 1 ? 13 : 12);   // + raw x, y (region 0) / raw depth code (region 1) in the spare k rows
-    float e[NE];
-    if (nosin) {   // probe builds only: no trigonometry
-#pragma unroll
-      for (int i = 0; i < 12; ++i) e[i] = v3[i % 3] * ff;
-    } else {
-      float t[6];
-      pe_entries(t, raw, v3, ff);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) e[i] = t[i];
-      SinCos3 r1;
-      pe_second_octave<R>(r1, raw, pre);
-      pe_entries(t, r1, v3, ff * 2.0f);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) e[6 + i] = t[i];
-      pe_advance<R>(raw, pre, r1, v3, ff);
-    }
-    if constexpr (R == 0) e[12] = v3[0], e[13] = v3[1];
-    if constexpr (R == 1) e[12] = v3[2];
-    if (nomfma) {  // probe builds only: no split, no MFMAs
-#pragma unroll
-      for (int i = 0; i < NE; ++i) acc[0][0][i] += e[i];
-      if constexpr (R == 0) {
-#pragma unroll
-        for (int ht = 0; ht < HT; ++ht) acc[ht][0] += bias[ht], acc[ht][1] = bias[ht];
-      }
-    } else {
-      f16_region<HD, NE, R == 0>(acc, wf + R * HT * 256, term_stride, e, bias);
-    }
-    if constexpr (2 * R < NS) {
-      stage_blend<HD, 2 * R>(acc, ba, wq);
-      if constexpr (2 * R + 2 < NS) stage_load<HD, 2 * R + 2>(ba, G, o, h);
-      stage_blend<HD, 2 * R + 1>(acc, bb, wq);
-      if constexpr (2 * R + 3 < NS) stage_load<HD, 2 * R + 3>(bb, G, o, h);
-    }
-#ifdef BTS_REGION_BARRIER   // one scheduling region per encoding region: was needed against spills in r01c, costs 3 % now (r01g A/B)
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    region_seq_i<HD, R + 1>(acc, ba, bb, G, o, wq, h, wf, term_stride, raw, pre, v3, ff * 4.0f, bias, nosin, nomfma);
-  }
-}
-template <int HD, int R>
-__device__ __forceinline__ void region_seq(f32x16 (&acc)[HD / 32][2], GBuf& ba, GBuf& bb, const float4* __restrict__ G,
-                                           const int (&o)[2][4], const float (&wq)[2][4], int h, const float* wf, int term_stride,
-                                           SinCos3& raw, const float (&v3)[3], float ff, const f32x16* bias, bool nosin = false,
-                                           bool nomfma = false) {
-  static_assert(R == 0, "entered at region 0");
-  SinCos3 pre;
-  region_seq_i<HD, 0>(acc, ba, bb, G, o, wq, h, wf, term_stride, raw, pre, v3, ff, bias, nosin, nomfma);
-}
-
-#ifdef BTS_GATHER_LDS
 constexpr int kGatherLdsPerWave = 3 * 4096 + 768;
 // ---------------------------------------------------------------------------------------------------------------
 // The gather of G through LDS.
@@ -473,8 +377,14 @@ struct GatherLds {
   unsigned piece16x;    // ... in the ODD instructions (rows 8 .. 15, 24 .. 31): rotated by 4 more = piece16 ^ 64
   int m;                // L >> 3
 };
+// lane = sample writes its row of the tap table: byte offsets into G of three taps, o11 = o10 + (o01 - o00) (gl_offsets).  The caller
+// fences the wave's LDS traffic on both sides.
+template <int HD>
+__device__ __forceinline__ void gl_write_taps(const GatherLds& gl, const Taps& tp, int lane) {
+  gl.tab[lane * 3 + 0] = (unsigned)tp.o00 * (HD * 4u), gl.tab[lane * 3 + 1] = (unsigned)tp.o01 * (HD * 4u), gl.tab[lane * 3 + 2] = (unsigned)tp.o10 * (HD * 4u);
+}
 template <int HD, int T>
-struct GBlock {   // block T of a ray, in the order the stages are blended (GStage)
+struct GBlock {   // block T of a ray: tap T % 2 of tap pair (T / 2) % 2 of hidden tile ht of point tile pt, in the order they are blended
   static constexpr int HT = HD / 32;
   static constexpr int S = T / 2, pt = S / (2 * HT), ht = (S / 2) % HT, tap = 2 * (S % 2) + T % 2, slot = T % 3;
   static constexpr int NBLK = 8 * HT;
@@ -640,7 +550,9 @@ __device__ __forceinline__ void g_step(f32x16 (&acc)[HD / 32][2], const GatherLd
   else gl_consume<HD, T>(acc, c, r, G, w, off_next);
 }
 
-// region_seq with the gather through LDS: region R blends the blocks of stages 2R and 2R + 1 behind its MFMAs
+// Region R = octaves 2R (sines computed directly, one region ahead) and 2R + 1 (by angle doubling); the gather blocks 4R .. 4R + 3 are
+// blended behind the region's MFMAs.  The regions are not fenced from each other: the scheduler may pull the next region's
+// trigonometry under this region's MFMAs.
 template <int HD, int R, bool SH = false>
 __device__ __forceinline__ void region_seq_li(f32x16 (&acc)[HD / 32][2], const GatherLds& gl, GRows& rows, const float4* __restrict__ G,
                                               const float (&wq)[2][4], unsigned (&off_next)[4], const float* wf, int term_stride, SinCos3& raw,
@@ -684,8 +596,6 @@ __device__ __forceinline__ void region_seq_l(f32x16 (&acc)[HD / 32][2], const Ga
   SinCos3 pre;
   region_seq_li<HD, 0, SH>(acc, gl, rows, G, wq, off_next, wf, term_stride, raw, pre, v3, ff, bias, h);
 }
-#endif  // BTS_GATHER_LDS
-
 
 // Cold path: a wave in which some sample's encoding argument leaves the fast sincos range (|arg| > 1e5: points within millimetres
 // of the encoder's camera plane) evaluates that iteration with the compact lane = point routine (libm range reduction inside).
@@ -751,7 +661,7 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   using LH = LdsH<C, HD, NB>;
   constexpr int HT = HD / 32;
   constexpr int NS = 4 * HT;
-  __shared__ __attribute__((aligned(16))) float lds[L::TOTAL + (F16 ? LH::TOTAL + 4 : 0)];
+  __shared__ __attribute__((aligned(16))) float lds[L::TOTAL + LH::TOTAL + 4];
   float* const lh = lds + ((L::TOTAL + 3) & ~3);  // 16-byte aligned: the f16 A operands are read as ds_read_b128
 #ifdef BTS_PROBE
   const unsigned long long t_entry = __builtin_readcyclecounter();
@@ -765,24 +675,21 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   } else {
     stage_weights<C, HD, NB, true>(lds, p.mlp, p.empty_feature);
     __syncthreads();
-    if constexpr (F16) {
-      stage_weights_h<C, HD, NB>(lh, lds + L::EMPTY, p.mlp);
-      __syncthreads();
-    }
+    stage_weights_h<C, HD, NB>(lh, lds + L::EMPTY, p.mlp);
+    __syncthreads();
   }
 #ifdef BTS_PROBE
   // the preheader: kernel entry to the barrier behind the staged (or copied) MLP, per wave (tools/section_probe.py --lifetimes folds the
   // waves of a work-group); 16 bits of cycles, saturated, above XCC_ID in the last counter word -- exact through the tools' float64 tables
   const unsigned long long t_stage = __builtin_readcyclecounter() - t_entry;
 #endif
-  // 2^S carried by the accumulators of the f16 path (1 on the fp32 path)
-  const float scale = F16 ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lh[LH::SCALE]))) : 1.0f;
-  const float inv_scale = F16 ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lh[LH::SCALE + 1]))) : 1.0f;
+  // 2^S carried by the accumulators
+  const float scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lh[LH::SCALE])));
+  const float inv_scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lh[LH::SCALE + 1])));
 
   const int lane = threadIdx.x & 63;
   const int h0 = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef BTS_GATHER_LDS
   extern __shared__ __attribute__((aligned(128))) char gather_lds[];   // per wave: ring of 3 x 4 KB + 768 B tap table
   GatherLds gl;
   {
@@ -797,7 +704,6 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
 #pragma unroll
     for (int q = 0; q < 4; ++q) gl.rd[q] = (unsigned)(col * 128 + ((4 * h0 + q - (col >> 1)) & 7) * 16);
   }
-#endif
   const int nwg = gridDim.x;  // multiple of 8
   const int wg = xcd_remap(blockIdx.x, nwg);
   const int wg_per_xcd = nwg >> 3;
@@ -833,7 +739,6 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   const int Bp = p.Bp;
   const float b_out = as_const(p.mlp)[MlpLayout{C + kPeDim, HD, NB}.b_out()];
   const int lane_off0 = h0 * HD + (lane & 31);
-  const bool nomfma = BTS_ABL(4), nosin = BTS_ABL(2);
 
 #ifdef BTS_PROBE
   unsigned long long t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -908,7 +813,7 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   const float step0 = 1.0f / (float)p.K;                       // nerf.py:107
   const float base0 = coarse_base(p.K, min(kl, p.K - 1));      // linspace(0, 1 - step, K)[k] of this lane's sample (first chunk)
 
-  // Two loops (kTwoLoops: one ray per wave, LDS gather): the general one, and one for rays whose 64 samples hit the same four texels
+  // Two loops (kTwoLoops: one ray per wave): the general one, and one for rays whose 64 samples hit the same four texels
   // of G (every ray that starts at the encoder camera's centre: half of the eval frame) -- see gs_issue.  The test sits behind
   // make_taps and is wave-uniform: every lane's (o00, o01, o10) against lane 0's.  An iteration whose ray is of the other kind puts
   // back what it prefetched and leaves its loop WITHOUT advancing; the wave goes on in the other loop, which computes the ray's
@@ -916,7 +821,7 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   // bts_render_iter.h, included once per nest) instead of a branch in one body: the general loop keeps its registers and schedule.
   // Built where the second nest costs no spilled VGPR: no ResnetBlocks, at most two render views -- the evaluation kernels, whose
   // rays are the ones that start at the encoder camera.  -DBTS_NO_SHARED_TEXELS: the general loop alone, the kernels as they were.
-#if defined(BTS_GATHER_LDS) && !defined(BTS_NO_SHARED_TEXELS)
+#ifndef BTS_NO_SHARED_TEXELS
   constexpr bool kTwoLoops = ONE_RAY && !EPI && NB == 0 && NVMAX <= 2;
 #else
   constexpr bool kTwoLoops = false;
@@ -952,38 +857,27 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
 }
 
 #ifndef BTS_NO_LAUNCH_GLUE
+// One of up to six instantiations per (shape, NVMAX, EPI): ONE_RAY x {plain, IMG}, plus DYN (with and without IMG) for the evaluation
+// frame's one-ray kernels with two loops.  A launch that asks for a form its shape was not built in takes the next plainer one: a
+// staged image without an IMG kernel is staged in place, a claimed tail without a DYN kernel is walked as static lists.
 template <int C, int HD, int NB, int NVMAX, bool EPI>
 static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
-#ifdef BTS_GATHER_LDS
-  auto go = [&](auto kern) { launch_dyn_lds(kern, grid, 4 * kGatherLdsPerWave, s, p); };
-  // the staged MLP ready-made (FwdParams::mlp_image): the evaluation frame's kernels, each form of them
-  if constexpr (!EPI && NVMAX <= 2) {
-    if (p.mlp_image) {
-      if constexpr (NB == 0) {
-        if (p.lpr == 64 && p.sched && p.dyn_first < p.groups) {
-          go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true, true>);
-          return launch_check();
-        }
-      }
-      if (p.lpr == 64) go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, false, true>);
-      else go(render_kernel_p<C, HD, NB, NVMAX, false, true, EPI, false, true>);
-      return launch_check();
-    }
+  auto go = [&](auto kern) {
+    launch_dyn_lds(kern, grid, 4 * kGatherLdsPerWave, s, p);
+    return launch_check();
+  };
+  constexpr bool kImg = !EPI && NVMAX <= 2;   // built with the staged MLP ready-made (FwdParams::mlp_image)
+  constexpr bool kDyn = kImg && NB == 0;      // built with the claimed tail (FwdParams::sched); one ray per wave only
+  const bool one_ray = p.lpr == 64;
+  const bool dyn = kDyn && one_ray && p.sched && p.dyn_first < p.groups;
+  const bool img = kImg && p.mlp_image;
+  if constexpr (kDyn) {
+    if (dyn) return img ? go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true, true>) : go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true>);
   }
-  // the claimed tail (FwdParams::sched): the evaluation frame's one-ray kernels with two loops only
-  if constexpr (!EPI && NB == 0 && NVMAX <= 2) {
-    if (p.lpr == 64 && p.sched && p.dyn_first < p.groups) {
-      go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true>);
-      return launch_check();
-    }
+  if constexpr (kImg) {
+    if (img) return one_ray ? go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, false, true>) : go(render_kernel_p<C, HD, NB, NVMAX, false, true, EPI, false, true>);
   }
-  if (p.lpr == 64) go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI>);
-  else go(render_kernel_p<C, HD, NB, NVMAX, false, true, EPI>);
-#else
-  if (p.lpr == 64) render_kernel_p<C, HD, NB, NVMAX, true, true, EPI><<<grid, 256, 0, s>>>(p);
-  else render_kernel_p<C, HD, NB, NVMAX, false, true, EPI><<<grid, 256, 0, s>>>(p);
-#endif
-  return launch_check();
+  return one_ray ? go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI>) : go(render_kernel_p<C, HD, NB, NVMAX, false, true, EPI>);
 }
 
 template <bool EPI>

@@ -3,8 +3,10 @@
 Sections (s_memtime deltas accumulated per wave, averaged over waves, per ray iteration):
  0 geometry (ray/camera loads, projection, taps, colour issue, tile broadcast)   1 gather + encoding + MFMA
  2 lin_out + softplus   3 colour blend + compositing scan   4 per-sample stores   5 per-ray sums + stores
-Ablations (BTS_ABLATE bits, probe build only): 1 no gather (register-gather build), 2 no trigonometry, 4 no MFMAs, 64 every ray takes
-the render kernel's shared-texel loop (one fetch of G per ray; wrong rows for view 1 -- what a single fetch would buy there).
+Ablations (BTS_ABLATE bits, probe build only) the render loop reads: 8 no colour taps, 16 no per-sample stores, 32 lin_out as three adds, 64 every ray
+takes the shared-texel loop (one fetch of G per ray; wrong rows for view 1 -- what a single fetch would buy there), 128 the counters above.
+Bits 1 (no gather), 2 (no trigonometry) and 4 (no MFMAs) act in eval_point only -- the exact cold path and the raw-feature query --
+since the register gather, the one loop that read them, left the render kernel.
     python tools/section_probe.py --lifetimes [--no-tail] [--out FILE]
 the flagship evaluation frame instead: per-wave lifetimes of its render launch over the chip, per XCD and per CU (the probe build stores
 XCC_ID and HW_ID next to the counters); --no-tail: fixed ray lists to the end; BTS_DYN_TAIL_DIV=d: a claimed tail of 1 / d of the rays.
@@ -124,7 +126,7 @@ os.environ["BTS_DBG_PTR"] = str(dbg.data_ptr())
 half = rays.shape[0] // 2
 sets = {"both": (rays, z), "view0": (rays[:half].contiguous(), z[:half].contiguous()), "view1": (rays[half:].contiguous(), z[half:].contiguous())}
 for name, (r_, z_) in sets.items():
-    for extra in ((0, 2, 4, 1, 2 | 4 | 1, 64) if name != "both" else (0,)):
+    for extra in ((0, 64) if name != "both" else (0,)):
         os.environ["BTS_ABLATE"] = str(128 | extra)
         for _ in range(2):
             dbg.zero_()

@@ -54,6 +54,13 @@ class BtsLossArgs(C.Structure):
                [("scale_rgb", C.c_float), ("scale_eas", C.c_float)] + [(k, C.c_void_p) for k in ("invalid_wsum", "invalid_any")]
 
 
+class BtsPixelLossArgs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("rgb", "rgb_gt", "depth", "weights", "invalid", "invalid_wsum", "invalid_any", "rgb_samps", "out",
+                                          "thresholds", "kept", "g_rgb", "g_depth")] + [("B", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("n", "patch_h", "patch_w", "nv", "K", "criterion", "invalid_policy", "median_thresholding",
+                                         "edge_aware_smoothness", "reserved_")] + [("scale_rgb", C.c_float), ("scale_eas", C.c_float)]
+
+
 class BtsTrainScale(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("feat_nchw", "jitter", "rgb", "depth", "invalid_wsum", "invalid_any", "proj_nhwc", "sampled_tiles",
                                           "z_samp", "sigma_raw", "trans", "rgb_samps", "loss_parts", "g_rgb", "g_depth", "gs_rgb", "gs_depth",
@@ -182,6 +189,10 @@ SYMBOLS = {
     # the same loss for patches of any size (16 x 16 tiles, csrc/bts_loss_tiled.hip)
     "bts_photometric_loss_tiled_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "bts_photometric_loss_tiled": (C.c_int, [C.POINTER(BtsLossArgs), _P, C.c_size_t, _P]),
+    # the per-pixel criteria l1 / l2, median thresholding, the diverse flags (csrc/bts_loss_pixel.hip)
+    "bts_pixel_loss_workspace": (C.c_size_t, [C.c_int64, _I, _I, _I]),
+    "bts_pixel_loss": (C.c_int, [C.POINTER(BtsPixelLossArgs), _P, C.c_size_t, _P]),
+    "bts_loss_diverse_flags": (C.c_int, [_P, _P, _P, C.c_int64, _I, _I, _P, _P]),
     "bts_sample_coarse": (C.c_int, [_P, _P, C.c_int64, _I, _I, _P, _P]),
     "bts_distance_to_z": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
     "bts_invert_small": (C.c_int, [_P, _P, _I, _I, _P]),

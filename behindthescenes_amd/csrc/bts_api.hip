@@ -303,6 +303,54 @@ int bts_photometric_loss_tiled(const BtsLossArgs* a, void* workspace, size_t wor
   }
   return launched(photometric_loss_tiled_impl(a, workspace, (hipStream_t)stream), "bts_photometric_loss_tiled");
 }
+size_t bts_pixel_loss_workspace(int64_t B, int32_t n, int32_t patch_h, int32_t patch_w) { return pixel_loss_bytes((long)B, n, patch_h, patch_w); }
+int bts_pixel_loss(const BtsPixelLossArgs* a, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char who[] = "bts_pixel_loss";
+  if (!a || !a->rgb || !a->rgb_gt || !a->out || (a->edge_aware_smoothness && !a->depth)) {
+    set_error("%s: NULL required pointer (args, rgb, rgb_gt, out; depth with edge_aware_smoothness)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->B <= 0 || a->n <= 0 || a->patch_h <= 0 || a->patch_w <= 0 || a->nv <= 0) {
+    set_error("%s: non-positive size (B, n, patch_h, patch_w, nv)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->B > (1L << 29)) {
+    set_error("%s: %ld rays are more than 2^29", who, (long)a->B);
+    return BTS_E_INVALID;
+  }
+  if (a->B % ((long)a->n * a->patch_h * a->patch_w) != 0) {
+    set_error("%s: B = %ld rays are not a multiple of n * patch_h * patch_w = %ld", who, (long)a->B, (long)a->n * a->patch_h * a->patch_w);
+    return BTS_E_INVALID;
+  }
+  if (a->criterion != 1 && a->criterion != 2) {
+    set_error("%s: unknown criterion %ld (1 = l1, 2 = l2)", who, (long)a->criterion);
+    return BTS_E_INVALID;
+  }
+  if (a->invalid_policy < 0 || a->invalid_policy > 3) {
+    set_error("%s: unknown invalid_policy %ld", who, (long)a->invalid_policy);
+    return BTS_E_INVALID;
+  }
+  if (a->invalid_policy == 3 && !(a->rgb_samps && a->weights && a->invalid && a->K > 0)) {
+    set_error("%s: weight_guided_diverse needs rgb_samps, weights and invalid with K > 0", who);
+    return BTS_E_INVALID;
+  }
+  if ((a->invalid_policy == 1 && !a->invalid_any && !(a->invalid && a->K > 0)) ||
+      (a->invalid_policy == 2 && !a->invalid_wsum && !(a->invalid && a->weights && a->K > 0))) {
+    set_error("%s: invalid_policy %ld needs invalid_any / invalid_wsum, or invalid (and weights) with K > 0", who, (long)a->invalid_policy);
+    return BTS_E_INVALID;
+  }
+  const size_t need = pixel_loss_bytes((long)a->B, a->n, a->patch_h, a->patch_w);
+  if (!workspace || workspace_bytes < need) {
+    set_error("%s: workspace too small (%ld bytes needed, see bts_pixel_loss_workspace)", who, (long)need);
+    return BTS_E_INVALID;
+  }
+  return launched(pixel_loss_impl(a, workspace, (hipStream_t)stream), who);
+}
+int bts_loss_diverse_flags(const float* rgb_samps, const float* weights, const float* invalid, int64_t B, int32_t K, int32_t nv, float* flags,
+                           void* stream) {
+  BTS_CHECK_LAYOUT(rgb_samps && weights && invalid && flags && B > 0 && B <= (1L << 29) && K > 0 && nv > 0, "bts_loss_diverse_flags");
+  return launched(diverse_flags_launch(rgb_samps, weights, invalid, (long)B, K, nv, flags, (hipStream_t)stream), "bts_loss_diverse_flags");
+}
 int bts_sample_coarse(const float* rays, const float* u, int64_t B, int32_t K, int32_t lindisp, float* z_samp, void* stream) {
   BTS_CHECK_LAYOUT(rays && u && z_samp && B > 0 && K > 0, "bts_sample_coarse");
   return launched(sample_coarse_launch(rays, u, (long)B, K, lindisp, z_samp, (hipStream_t)stream), "bts_sample_coarse");

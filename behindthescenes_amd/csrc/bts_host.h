@@ -90,6 +90,10 @@ int eval_handover_launch(const float* Ks, const float* poses, const float* image
 int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s);
 size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv);
 int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s);
+// ---- bts_loss_pixel.hip: criteria l1 / l2, median thresholding, the diverse flags
+size_t pixel_loss_bytes(long B, int n, int ph, int pw);
+int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s);
+int diverse_flags_launch(const float* rgb_samps, const float* weights, const float* invalid, long B, int K, int nv, float* flags, hipStream_t s);
 
 // ---- bts_mlp_color.hip: MLP-predicted colour
 int mlp_color_render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);

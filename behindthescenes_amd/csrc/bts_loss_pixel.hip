@@ -1,0 +1,571 @@
+// bts_loss_pixel.hip -- the PER-PIXEL criteria of ReconstructionLoss (models/bts/model/loss.py:43-293): criterion l1 / l2, with or
+// without median thresholding, under any of the four invalid-ray policies (none, strict, weight_guided, weight_guided_diverse), plus the
+// edge-aware smoothness term of bts_loss_tiled.hip (read its header: the un-normalised edges, the patch's mean inverse depth m,
+// g_depth = s (u_p / m - S / (m^2 N)) d clamp / d depth, the closed-interval clamp gradient, sign(0) = 0).  Everything is memory-bound,
+// a few bytes per ray and pass: thread = ray, rows read as they lie.  Launches on one stream (a kernel boundary is the only hand-over
+// between work-groups):
+//   err          keep flag per ray (the policies of bts_loss_tiled.hip's ray_invalid in the same order of sums; diverse: diverse_flag
+//                below), e[ray, c] = min_v crit(rgb[ray, v, c] - gt[ray, c]) * keep -> workspace; per work-group the sum of e and the
+//                invalid rays; with median the histogram of bits 31..21 of e's bit pattern (e >= 0: pattern order = value order);
+//                without median the gradient, whose normaliser 1 / (3 B) is known up front
+//   hist<1>, <2> median only: bits 20..10 of the e that share the wanted 11 bits, then bits 9..0 of those that share 22 -- the exact radix
+//                selection of bts_depth_metrics.hip, per batch sample, rank (N - 1) / 2 = torch's LOWER median
+//   kept         median only: thr[sample] from the last histogram; per work-group the sum and the number of e <= thr (ties all kept)
+//   edges, patch smoothness in bts_loss_tiled.hip's geometry and order of sums: per ray the un-normalised edges and u_p, per 16 x 16 tile
+//                their sums; per patch m, S and S / m -- bit for bit that kernel's
+//   final        one work-group: the partials in index order -> out[4] = [rgb term, sum of the smoothness term, invalid rays, count],
+//                the kept count as an integer and the gradient's normaliser
+//   grad         median only: d rgb term / d rgb with 1 / count
+//   gdepth       g_depth
+// No float atomics: every sum is a fixed-order sum of partials (integer atomics build the histograms), reruns are bit-identical.
+// The gradient follows torch's amin: tied views share it EQUALLY; sign(0) = 0 for l1, 2 d for l2; no gradient flows through thr.
+// An e that is NaN or inf is outside the contract (nothing faults; the selection orders the pattern).
+#include <hip/hip_runtime.h>
+
+#include "bts_host.h"
+
+namespace bts {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kBins = 2048;
+constexpr int kTile = 16;                   // the smoothness passes' tile side
+constexpr int kHistSample = 3 * kBins;      // three radix passes per batch sample
+constexpr int kStateSample = 8;             // [0, 1] prefix and rank after pass 0's histogram, [4, 5] after pass 1's
+
+struct PixelParams {
+  const float* rgb;
+  const float* depth;
+  const float* weights;
+  const float* invalid;
+  const float* invalid_wsum;
+  const float* invalid_any;
+  const float* rgb_samps;
+  const float* rgb_gt;
+  float* out;                   // (4)
+  float* thresholds;            // (n) or NULL
+  long long* kept;              // (1) or NULL
+  float* g_rgb;
+  float* g_depth;
+  int n, ph, pw, nv, K, policy, crit, median, has_eas;
+  float s_rgb, s_eas;
+  long B, Bs;                   // rays, rays per batch sample
+  int blocks_per_sample;        // work-groups of 256 rays per sample
+  long n_blocks;
+  int area, tiles_x, tiles;     // 16 x 16 tiles per patch row, per patch (bts_loss_tiled.hip's)
+  long n_patches, n_tiles;
+  // workspace
+  float* e;                     // (B, 3)
+  unsigned char* keep;          // (B): 0 = invalid ray
+  unsigned* hist;               // (n, 3, 2048)
+  unsigned* state;              // (n, 8)
+  float* thr;                   // (n)
+  float* blk_sum;               // (n_blocks)
+  unsigned* blk_cnt;            // (n_blocks) kept values
+  unsigned* blk_inv;            // (n_blocks) invalid rays
+  float* u;                     // (B)
+  float2* tile_parts;           // (n_tiles): sum of un-normalised edges, sum of d
+  float4* patch_stats;          // (n_patches): m, S, S / m, 0
+  float* fin;                   // [0] = s_rgb / count
+};
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ float sign0(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+
+// weight_guided_diverse per (ray, view), loss.py:109-118: (sum_k invalid w > .9) | (mean_c std_k(rgb_samps) < .01); the unbiased std
+// (K - 1) in fp32, the mean first, then the squared deviations, k ascending; K == 1: 0 / 0 = NaN and the comparison is false
+__device__ __forceinline__ bool diverse_flag(const float* __restrict__ rgb_samps, const float* __restrict__ weights,
+                                             const float* __restrict__ invalid, long ray, int v, int nv, int K) {
+  float s = 0.0f;
+  for (int k = 0; k < K; ++k) s += invalid[(ray * K + k) * nv + v] * weights[ray * K + k];
+  float sd = 0.0f;
+  const long stride = (long)nv * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* x = rgb_samps + (ray * K * nv + v) * 3 + c;
+    float m = 0.0f;
+    for (int k = 0; k < K; ++k) m += x[k * stride];
+    m = m / (float)K;
+    float q = 0.0f;
+    for (int k = 0; k < K; ++k) {
+      const float d = x[k * stride] - m;
+      q += d * d;
+    }
+    sd += sqrtf(q / (float)(K - 1));
+  }
+  return (s > 0.9f) || (sd / 3.0f < 0.01f);
+}
+
+// invalid ray?  Policies 0-2: bts_loss_tiled.hip's ray_invalid (same order of sums, same comparisons); 3: every view's diverse flag
+__device__ __forceinline__ bool ray_invalid(const PixelParams& p, long ray) {
+  if (p.policy == 0) return false;
+  const int nv = p.nv, K = p.K;
+  bool all_v = true;
+  for (int v = 0; v < nv; ++v) {
+    if (p.policy == 3) {
+      all_v = all_v && diverse_flag(p.rgb_samps, p.weights, p.invalid, ray, v, nv, K);
+    } else if (p.policy == 2 && p.invalid_wsum) {
+      all_v = all_v && (p.invalid_wsum[ray * nv + v] > 0.9f);
+    } else if (p.policy == 1 && p.invalid_any) {
+      all_v = all_v && (p.invalid_any[ray * nv + v] > 0.5f);
+    } else if (p.policy == 2) {
+      float s = 0.0f;
+      for (int k = 0; k < K; ++k) s += p.invalid[(ray * K + k) * nv + v] * p.weights[ray * K + k];
+      all_v = all_v && (s > 0.9f);
+    } else {
+      bool any_k = false;
+      for (int k = 0; k < K; ++k) any_k = any_k || (p.invalid[(ray * K + k) * nv + v] > 0.5f);
+      all_v = all_v && any_k;
+    }
+  }
+  return all_v;
+}
+
+__device__ __forceinline__ float crit_of(int crit, float d) { return crit == 1 ? fabsf(d) : d * d; }
+
+// d (norm * sum of the kept e) / d rgb of one ray: per channel the views that attain the minimum share the gradient equally (amin)
+__device__ __forceinline__ void write_grad(const PixelParams& p, long ray, float keep, float thr, float norm) {
+  const int nv = p.nv;
+  const float* x = p.rgb + ray * nv * 3;
+  float* g = p.g_rgb + ray * nv * 3;
+  const float y[3] = {p.rgb_gt[ray * 3], p.rgb_gt[ray * 3 + 1], p.rgb_gt[ray * 3 + 2]};
+  float emin[3] = {0.0f, 0.0f, 0.0f};
+  for (int v = 0; v < nv; ++v)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float val = crit_of(p.crit, x[v * 3 + c] - y[c]);
+      emin[c] = v == 0 ? val : fminf(emin[c], val);
+    }
+  float ties[3] = {0.0f, 0.0f, 0.0f};
+  for (int v = 0; v < nv; ++v)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ties[c] += crit_of(p.crit, x[v * 3 + c] - y[c]) == emin[c] ? 1.0f : 0.0f;
+  float coef[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) coef[c] = (keep != 0.0f && emin[c] * keep <= thr) ? norm / ties[c] : 0.0f;
+  for (int v = 0; v < nv; ++v)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float d = x[v * 3 + c] - y[c];
+      const float dc = p.crit == 1 ? sign0(d) : 2.0f * d;
+      g[v * 3 + c] = crit_of(p.crit, d) == emin[c] ? coef[c] * dc : 0.0f;
+    }
+}
+
+// which sample and which ray a thread of the (sample, 256 rays) work-groups takes
+struct RayPos {
+  int sample;
+  long ray;
+  bool act;
+};
+__device__ __forceinline__ RayPos ray_pos(const PixelParams& p) {
+  RayPos r;
+  r.sample = (int)(blockIdx.x / p.blocks_per_sample);
+  const long in_sample = (long)(blockIdx.x - (unsigned)r.sample * p.blocks_per_sample) * kThreads + threadIdx.x;
+  r.act = in_sample < p.Bs;
+  r.ray = (long)r.sample * p.Bs + (r.act ? in_sample : 0);
+  return r;
+}
+
+// the work-group's sum: butterfly per wave, then the four waves in order; every thread gets it.  s_red: 4 words
+__device__ __forceinline__ float block_sum(float v, float* s_red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+__device__ __forceinline__ unsigned block_sum(unsigned v, unsigned* s_red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+
+// the work-group's non-zero bins into the sample's histogram
+__device__ __forceinline__ void flush_hist(const unsigned* s_hist, unsigned* dst) {
+  for (int i = threadIdx.x; i < kBins; i += kThreads) {
+    const unsigned c = s_hist[i];
+    if (c) atomicAdd(&dst[i], c);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void pixel_err_kernel(const PixelParams p) {
+  __shared__ unsigned s_hist[kBins];
+  __shared__ float s_f[4];
+  __shared__ unsigned s_u[4];
+  if (p.median) {
+    for (int i = threadIdx.x; i < kBins; i += kThreads) s_hist[i] = 0u;
+    __syncthreads();
+  }
+  const RayPos r = ray_pos(p);
+  float esum = 0.0f;
+  unsigned inv = 0u;
+  if (r.act) {
+    const long ray = r.ray;
+    const bool bad = ray_invalid(p, ray);
+    const float keep = bad ? 0.0f : 1.0f;
+    p.keep[ray] = bad ? 0 : 1;
+    inv = bad ? 1u : 0u;
+    const int nv = p.nv;
+    const float* x = p.rgb + ray * nv * 3;
+    const float y[3] = {p.rgb_gt[ray * 3], p.rgb_gt[ray * 3 + 1], p.rgb_gt[ray * 3 + 2]};
+    float emin[3] = {0.0f, 0.0f, 0.0f};
+    for (int v = 0; v < nv; ++v)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float val = crit_of(p.crit, x[v * 3 + c] - y[c]);
+        emin[c] = v == 0 ? val : fminf(emin[c], val);
+      }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float e = emin[c] * keep;
+      p.e[ray * 3 + c] = e;
+      esum += e;
+      if (p.median) atomicAdd(&s_hist[__float_as_uint(e) >> 21], 1u);
+    }
+    if (!p.median && p.g_rgb) write_grad(p, ray, keep, __uint_as_float(0x7F800000u), p.s_rgb / (float)(3 * p.B));
+  }
+  const float bs = block_sum(esum, s_f);
+  const unsigned bi = block_sum(inv, s_u);
+  if (threadIdx.x == 0) p.blk_sum[blockIdx.x] = bs, p.blk_cnt[blockIdx.x] = 0u, p.blk_inv[blockIdx.x] = bi;
+  if (p.median) flush_hist(s_hist, p.hist + (size_t)r.sample * kHistSample);     // (block_sum's barriers are behind the atomics)
+}
+
+// The bin of `hist` (2 048 bins) that holds the element of rank `rank` (0-based) and the rank inside that bin; median: rank = (total - 1) / 2
+// of the histogram's own total.  Every lane takes eight consecutive bins, the work-group scans the 256 sums (bts_depth_metrics.hip's
+// select_bin).  out: bin, rank inside; both 0 when rank >= total.  All 256 lanes call this; s_scan holds 256 words.
+__device__ void select_bin(const unsigned* __restrict__ hist, int median, unsigned rank, unsigned* s_scan, unsigned* out) {
+  const int t = threadIdx.x;
+  const uint4 lo = reinterpret_cast<const uint4*>(hist)[t * 2], hi = reinterpret_cast<const uint4*>(hist)[t * 2 + 1];
+  const unsigned h[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  unsigned local = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) local += h[k];
+  s_scan[t] = local;
+  __syncthreads();
+  for (int o = 1; o < kThreads; o <<= 1) {
+    const unsigned v = t >= o ? s_scan[t - o] : 0u;
+    __syncthreads();
+    s_scan[t] += v;
+    __syncthreads();
+  }
+  const unsigned total = s_scan[kThreads - 1], incl = s_scan[t], excl = incl - local;
+  if (median) rank = total ? (total - 1) / 2 : 0u;
+  if (t == 0 && rank >= total) out[0] = 0u, out[1] = 0u;
+  if (rank >= excl && rank < incl) {   // one lane, when rank < total
+    unsigned r = rank - excl, rem = 0u;
+    int bin = -1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (bin < 0) {
+        if (r < h[k]) bin = k, rem = r;
+        else r -= h[k];
+      }
+    }
+    out[0] = (unsigned)(t * 8 + bin), out[1] = rem;
+  }
+  __syncthreads();
+}
+
+// radix passes 1 and 2 of a sample's median.  What a work-group notes down (the prefix and the rank inside it) is read by the NEXT launch only
+template <int PASS>
+__global__ __launch_bounds__(kThreads) void pixel_hist_kernel(const PixelParams p) {
+  __shared__ unsigned s_hist[kBins];
+  __shared__ unsigned s_scan[kThreads];
+  __shared__ unsigned s_sel[2];
+  const RayPos r = ray_pos(p);
+  unsigned* hist_s = p.hist + (size_t)r.sample * kHistSample;
+  unsigned* state_s = p.state + (size_t)r.sample * kStateSample;
+  for (int i = threadIdx.x; i < kBins; i += kThreads) s_hist[i] = 0u;
+  unsigned want;
+  if (PASS == 1) {
+    select_bin(hist_s, 1, 0u, s_scan, s_sel);
+    want = s_sel[0];
+    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[0] = want, state_s[1] = s_sel[1];
+  } else {
+    select_bin(hist_s + kBins, 0, state_s[1], s_scan, s_sel);
+    want = (state_s[0] << 11) | s_sel[0];
+    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[4] = want, state_s[5] = s_sel[1];
+  }
+  __syncthreads();
+  if (r.act) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const unsigned key = __float_as_uint(p.e[r.ray * 3 + c]);
+      if (PASS == 1) {
+        if ((key >> 21) == want) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u);
+      } else {
+        if ((key >> 10) == want) atomicAdd(&s_hist[key & 1023u], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  flush_hist(s_hist, hist_s + PASS * kBins);
+}
+
+// thr[sample] = the value whose pattern is the 22-bit prefix and the last histogram's bin; the kept set e <= thr of this work-group's rays
+__global__ __launch_bounds__(kThreads) void pixel_kept_kernel(const PixelParams p) {
+  __shared__ unsigned s_scan[kThreads];
+  __shared__ unsigned s_sel[2];
+  __shared__ float s_f[4];
+  __shared__ unsigned s_u[4];
+  const RayPos r = ray_pos(p);
+  const unsigned* state_s = p.state + (size_t)r.sample * kStateSample;
+  select_bin(p.hist + (size_t)r.sample * kHistSample + 2 * kBins, 0, state_s[5], s_scan, s_sel);
+  const float thr = __uint_as_float((state_s[4] << 10) | s_sel[0]);
+  if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) {
+    p.thr[r.sample] = thr;
+    if (p.thresholds) p.thresholds[r.sample] = thr;
+  }
+  float sum = 0.0f;
+  unsigned cnt = 0u;
+  if (r.act) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float e = p.e[r.ray * 3 + c];
+      if (e <= thr) sum += e, cnt += 1u;
+    }
+  }
+  const float bs = block_sum(sum, s_f);
+  const unsigned bc = block_sum(cnt, s_u);
+  if (threadIdx.x == 0) p.blk_sum[blockIdx.x] = bs, p.blk_cnt[blockIdx.x] = bc;
+}
+
+// smoothness (loss.py:21-40, masked as in :252-254) on the un-normalised inverse depth: bts_loss_tiled.hip's pass 1 per pixel, the
+// neighbours read from memory.  The GEOMETRY is that kernel's too -- a work-group per 16 x 16 tile, thread = pixel, butterfly per wave,
+// the four waves in order, then (pixel_patch_kernel) its pass 2 -- so that m, S, the per-patch term and g_depth are the tiled kernel's bit
+// for bit (tests/test_gpu_loss_pixel.py)
+__global__ __launch_bounds__(kThreads) void pixel_edges_kernel(const PixelParams p) {
+  __shared__ float s_red[4][2];
+  const int tid = threadIdx.x;
+  const long patch = blockIdx.x / p.tiles;
+  const int r = (int)(blockIdx.x - patch * p.tiles);
+  const int ty = r / p.tiles_x;
+  const int py = ty * kTile + (tid >> 4), px = (r - ty * p.tiles_x) * kTile + (tid & 15);
+  float eas = 0.0f, d = 0.0f;
+  if (py < p.ph && px < p.pw) {
+    const int pw = p.pw, ph = p.ph;
+    const long ray = patch * p.area + (long)py * pw + px;
+    const float keep = (p.policy == 0 || p.keep[ray]) ? 1.0f : 0.0f;
+    d = 1.0f / fminf(fmaxf(p.depth[ray], 1e-3f), 80.0f);
+    const float* y = p.rgb_gt + ray * 3;
+    const bool has_r = px + 1 < pw, has_b = py + 1 < ph;
+    float wx = 0.0f, wy = 0.0f, ex = 0.0f, ey = 0.0f;
+    if (has_r) {
+      float idx = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) idx += fabsf(y[c] - y[3 + c]);
+      wx = expf(-(idx / 3.0f));
+      ex = d - 1.0f / fminf(fmaxf(p.depth[ray + 1], 1e-3f), 80.0f);
+    }
+    if (has_b) {
+      float idy = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) idy += fabsf(y[c] - y[3 * pw + c]);
+      wy = expf(-(idy / 3.0f));
+      ey = d - 1.0f / fminf(fmaxf(p.depth[ray + pw], 1e-3f), 80.0f);
+    }
+    eas = (fabsf(ex) * wx + fabsf(ey) * wy) * keep;
+    if (p.g_depth) {
+      // u_p: this pixel's own edges and the edges its left / upper neighbour owns
+      float u = sign0(ex) * wx * keep + sign0(ey) * wy * keep;
+      if (px > 0) {
+        float il = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) il += fabsf(y[c - 3] - y[c]);
+        const float kl = (p.policy == 0 || p.keep[ray - 1]) ? 1.0f : 0.0f;
+        u -= sign0(1.0f / fminf(fmaxf(p.depth[ray - 1], 1e-3f), 80.0f) - d) * expf(-(il / 3.0f)) * kl;
+      }
+      if (py > 0) {
+        float iu = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) iu += fabsf(y[c - 3 * pw] - y[c]);
+        const float ku = (p.policy == 0 || p.keep[ray - pw]) ? 1.0f : 0.0f;
+        u -= sign0(1.0f / fminf(fmaxf(p.depth[ray - pw], 1e-3f), 80.0f) - d) * expf(-(iu / 3.0f)) * ku;
+      }
+      p.u[ray] = u;
+    }
+  }
+  const float r0 = wave_sum(eas), r1 = wave_sum(d);
+  if ((tid & 63) == 0) s_red[tid >> 6][0] = r0, s_red[tid >> 6][1] = r1;
+  __syncthreads();
+  if (tid == 0)
+    p.tile_parts[blockIdx.x] = make_float2(((s_red[0][0] + s_red[1][0]) + s_red[2][0]) + s_red[3][0],
+                                           ((s_red[0][1] + s_red[1][1]) + s_red[2][1]) + s_red[3][1]);
+}
+
+// one wave per patch: lane l takes tiles l, l + 64, ... in order, then the butterfly (bts_loss_tiled.hip's pass 2)
+__global__ __launch_bounds__(64) void pixel_patch_kernel(const PixelParams p) {
+  const int lane = threadIdx.x;
+  for (long patch = blockIdx.x; patch < p.n_patches; patch += gridDim.x) {
+    const float2* cp = p.tile_parts + patch * p.tiles;
+    float a0 = 0.0f, a1 = 0.0f;
+    for (int t = lane; t < p.tiles; t += 64) {
+      const float2 q = cp[t];
+      a0 += q.x, a1 += q.y;
+    }
+    a0 = wave_sum(a0), a1 = wave_sum(a1);
+    if (lane == 0) {
+      const float m = a1 / (float)p.area;
+      p.patch_stats[patch] = make_float4(m, a0, a0 / m, 0.0f);
+    }
+  }
+}
+
+// one work-group: thread t takes partials t, t + 256, ... in order, then the waves' butterflies, then the four waves in order
+__global__ __launch_bounds__(kThreads) void pixel_final_kernel(const PixelParams p) {
+  __shared__ float s_f[4];
+  __shared__ double s_d[4];
+  __shared__ unsigned long long s_c[2][4];
+  float sum = 0.0f;
+  double eas = 0.0;      // the per-patch terms are added in fp64 and rounded once: the fp32 number nearest to their sum
+  unsigned long long cnt = 0ull, inv = 0ull;
+  for (long i = threadIdx.x; i < p.n_blocks; i += kThreads) sum += p.blk_sum[i], cnt += p.blk_cnt[i], inv += p.blk_inv[i];
+  if (p.has_eas)
+    for (long i = threadIdx.x; i < p.n_patches; i += kThreads) eas += p.patch_stats[i].z;
+  sum = block_sum(sum, s_f);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64), inv += __shfl_xor(inv, off, 64), eas += __shfl_xor(eas, off, 64);
+  if ((threadIdx.x & 63) == 0) s_c[0][threadIdx.x >> 6] = cnt, s_c[1][threadIdx.x >> 6] = inv, s_d[threadIdx.x >> 6] = eas;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long count = p.median ? s_c[0][0] + s_c[0][1] + s_c[0][2] + s_c[0][3] : 3ull * (unsigned long long)p.B;
+    const unsigned long long bad = s_c[1][0] + s_c[1][1] + s_c[1][2] + s_c[1][3];
+    p.out[0] = sum / (float)count;
+    p.out[1] = (float)(((s_d[0] + s_d[1]) + s_d[2]) + s_d[3]);
+    p.out[2] = (float)bad;
+    p.out[3] = (float)count;
+    if (p.kept) p.kept[0] = (long long)count;
+    p.fin[0] = p.s_rgb / (float)count;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void pixel_grad_kernel(const PixelParams p) {
+  const RayPos r = ray_pos(p);
+  if (r.act) write_grad(p, r.ray, p.keep[r.ray] ? 1.0f : 0.0f, p.thr[r.sample], p.fin[0]);
+}
+
+__global__ __launch_bounds__(kThreads) void pixel_gdepth_kernel(const PixelParams p) {
+  const long ray = blockIdx.x * (long)kThreads + threadIdx.x;
+  if (ray >= p.B) return;
+  float g = 0.0f;
+  if (p.has_eas) {
+    // dn_p = d_p / m, m = mean d:  d E / d d_j = u_j / m - (sum_p u_p d_p) / (m^2 N), and sum_p u_p d_p = the un-normalised edge sum
+    const float4 st = p.patch_stats[ray / p.area];
+    const float m = st.x, S = st.y;
+    const float dep = p.depth[ray];
+    const float dcl = fminf(fmaxf(dep, 1e-3f), 80.0f);
+    const float gd = p.u[ray] / m - S / (m * m * (float)p.area);
+    g = ((dep >= 1e-3f && dep <= 80.0f) ? -gd / (dcl * dcl) : 0.0f) * p.s_eas;
+  }
+  p.g_depth[ray] = g;
+}
+
+__global__ __launch_bounds__(kThreads) void diverse_flags_kernel(const float* __restrict__ rgb_samps, const float* __restrict__ weights,
+                                                                 const float* __restrict__ invalid, long B, int K, int nv,
+                                                                 float* __restrict__ flags) {
+  const long i = blockIdx.x * (long)kThreads + threadIdx.x;
+  if (i >= B * nv) return;
+  const long ray = i / nv;
+  flags[i] = diverse_flag(rgb_samps, weights, invalid, ray, (int)(i - ray * nv), nv, K) ? 1.0f : 0.0f;
+}
+
+constexpr size_t kAlign = 256;
+inline size_t up256(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
+
+struct Geom {
+  long Bs, n_blocks, n_patches, n_tiles;
+  int blocks_per_sample, area, tiles_x, tiles;
+};
+inline Geom geom_of(long B, int n, int ph, int pw) {
+  Geom g;
+  g.Bs = B / n;
+  g.blocks_per_sample = (int)((g.Bs + kThreads - 1) / kThreads);
+  g.n_blocks = (long)n * g.blocks_per_sample;
+  g.area = ph * pw;
+  g.n_patches = B / g.area;
+  g.tiles_x = (pw + kTile - 1) / kTile;
+  g.tiles = ((ph + kTile - 1) / kTile) * g.tiles_x;
+  g.n_tiles = g.n_patches * g.tiles;
+  return g;
+}
+
+}  // namespace
+
+// bytes of bts_pixel_loss's workspace: e, keep flags, histograms, selection state, thresholds, three partials per work-group, u, tile
+// partials, patch statistics, the final words
+size_t pixel_loss_bytes(long B, int n, int ph, int pw) {
+  if (B <= 0 || n <= 0 || ph <= 0 || pw <= 0 || (long)ph * pw > B) return 0;
+  const Geom g = geom_of(B, n, ph, pw);
+  return kAlign + up256((size_t)B * 3 * sizeof(float)) + up256((size_t)B) + up256((size_t)n * kHistSample * sizeof(unsigned)) +
+         up256((size_t)n * kStateSample * sizeof(unsigned)) + up256((size_t)n * sizeof(float)) + 3 * up256((size_t)g.n_blocks * sizeof(float)) +
+         up256((size_t)B * sizeof(float)) + up256((size_t)g.n_tiles * sizeof(float2)) + up256((size_t)g.n_patches * sizeof(float4)) +
+         up256(4 * sizeof(float));
+}
+
+int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s) {
+  PixelParams p;
+  p.rgb = a->rgb, p.depth = a->depth, p.weights = a->weights, p.invalid = a->invalid, p.invalid_wsum = a->invalid_wsum;
+  p.invalid_any = a->invalid_any, p.rgb_samps = a->rgb_samps, p.rgb_gt = a->rgb_gt;
+  p.out = a->out, p.thresholds = a->thresholds, p.kept = (long long*)a->kept, p.g_rgb = a->g_rgb, p.g_depth = a->g_depth;
+  p.n = a->n, p.ph = a->patch_h, p.pw = a->patch_w, p.nv = a->nv, p.K = a->K, p.policy = a->invalid_policy, p.crit = a->criterion;
+  p.median = a->median_thresholding ? 1 : 0, p.has_eas = a->edge_aware_smoothness ? 1 : 0;
+  p.s_rgb = a->scale_rgb, p.s_eas = a->scale_eas;
+  p.B = (long)a->B;
+  const Geom g = geom_of(p.B, p.n, p.ph, p.pw);
+  p.Bs = g.Bs, p.blocks_per_sample = g.blocks_per_sample, p.n_blocks = g.n_blocks, p.area = g.area, p.tiles_x = g.tiles_x, p.tiles = g.tiles;
+  p.n_patches = g.n_patches, p.n_tiles = g.n_tiles;
+  char* w = (char*)(((uintptr_t)workspace + kAlign - 1) & ~(uintptr_t)(kAlign - 1));
+  p.e = (float*)w, w += up256((size_t)p.B * 3 * sizeof(float));
+  p.keep = (unsigned char*)w, w += up256((size_t)p.B);
+  p.hist = (unsigned*)w, w += up256((size_t)p.n * kHistSample * sizeof(unsigned));
+  p.state = (unsigned*)w, w += up256((size_t)p.n * kStateSample * sizeof(unsigned));
+  p.thr = (float*)w, w += up256((size_t)p.n * sizeof(float));
+  p.blk_sum = (float*)w, w += up256((size_t)g.n_blocks * sizeof(float));
+  p.blk_cnt = (unsigned*)w, w += up256((size_t)g.n_blocks * sizeof(float));
+  p.blk_inv = (unsigned*)w, w += up256((size_t)g.n_blocks * sizeof(float));
+  p.u = (float*)w, w += up256((size_t)p.B * sizeof(float));
+  p.tile_parts = (float2*)w, w += up256((size_t)g.n_tiles * sizeof(float2));
+  p.patch_stats = (float4*)w, w += up256((size_t)g.n_patches * sizeof(float4));
+  p.fin = (float*)w;
+  const unsigned grid = (unsigned)g.n_blocks;
+  if (p.median && hipMemsetAsync(p.hist, 0, (size_t)p.n * kHistSample * sizeof(unsigned), s) != hipSuccess) {
+    set_error("%s: clearing the histograms failed", "bts_pixel_loss");
+    return BTS_E_LAUNCH;
+  }
+  pixel_err_kernel<<<grid, kThreads, 0, s>>>(p);
+  if (p.median) {
+    pixel_hist_kernel<1><<<grid, kThreads, 0, s>>>(p);
+    pixel_hist_kernel<2><<<grid, kThreads, 0, s>>>(p);
+    pixel_kept_kernel<<<grid, kThreads, 0, s>>>(p);
+  }
+  if (p.has_eas) {
+    pixel_edges_kernel<<<(unsigned)g.n_tiles, kThreads, 0, s>>>(p);
+    pixel_patch_kernel<<<(unsigned)(g.n_patches < 65536 ? g.n_patches : 65536), 64, 0, s>>>(p);
+  }
+  pixel_final_kernel<<<1, kThreads, 0, s>>>(p);
+  if (p.median && p.g_rgb) pixel_grad_kernel<<<grid, kThreads, 0, s>>>(p);
+  if (p.g_depth) pixel_gdepth_kernel<<<(unsigned)((p.B + kThreads - 1) / kThreads), kThreads, 0, s>>>(p);
+  return launch_check("%s: pixel loss kernel launch failed (%ld)");
+}
+
+int diverse_flags_launch(const float* rgb_samps, const float* weights, const float* invalid, long B, int K, int nv, float* flags,
+                         hipStream_t s) {
+  diverse_flags_kernel<<<(unsigned)((B * nv + kThreads - 1) / kThreads), kThreads, 0, s>>>(rgb_samps, weights, invalid, B, K, nv, flags);
+  return launch_check("%s: diverse flags kernel launch failed (%ld)");
+}
+
+}  // namespace bts

@@ -7,7 +7,10 @@ reference become one launch, one reduction and one device-to-host copy for the l
 pixels (every shipped config: ``patch_size: 8``) one wave takes one patch; above that -- the trainer's default ``patch_size = 16``,
 ``sample_mode: image``, and the validation loss, where ``ImageRaySampler.reconstruct`` hands over whole frames as ``(n, v, H, W, nv, 3)``
 -- the patch is cut into 16 x 16 tiles (``bts_photometric_loss_tiled``, csrc/bts_loss_tiled.hip: four launches, under ``no_grad``
-three); ``native.photometric_loss`` chooses.  The optional regularisers (depth /
+three); ``native.photometric_loss`` chooses.  With the config key ``native_pixel_loss: true`` the reference's other options run on
+HIP kernels too: criterion "l1" / "l2" with or without ``median_thresholding`` under any invalid policy (``bts_pixel_loss``,
+csrc/bts_loss_pixel.hip: ``native.pixel_loss``), and "l1+ssim" under ``weight_guided_diverse`` (``bts_loss_diverse_flags``, then the
+kernels above under the strict policy); "l1+ssim" with median thresholding and ``use_automasking`` stay refused.  The optional regularisers (depth /
 alpha / surfaceness / depth-smoothness / ray-entropy, all off in the shipped configs) are a few elementwise torch expressions on
 top.  Same constructor keys, same call signature, same ``(loss, loss_dict)`` result as the reference."""
 import math
@@ -40,6 +43,31 @@ class _PhotometricSums(torch.autograd.Function):
         d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
         d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
         return d_rgb, d_depth, None, None, None, None, None, None, None, None, None
+
+
+class _PixelTerms(torch.autograd.Function):
+    """(rgb term, sum of the smoothness term, number of invalid rays) of the per-pixel criteria l1 / l2 (``native.pixel_loss``); the rgb
+    term arrives normalised -- by 3 B, or with median thresholding by the kept count; differentiable w.r.t. rgb, depth."""
+
+    @staticmethod
+    def forward(ctx, rgb, depth, weights, invalid, rgb_samps, rgb_gt, n, ph, pw, criterion, policy, median, eas, invalid_wsum=None,
+                invalid_any=None):
+        ctx.set_materialize_grads(False)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out, _, _, g_rgb, g_depth = native.pixel_loss(rgb, depth if eas else None, weights, invalid, rgb_gt, n, ph, pw, criterion, policy, median,
+                                                      eas, 1.0, 1.0, need_grad=need, invalid_wsum=invalid_wsum, invalid_any=invalid_any,
+                                                      rgb_samps=rgb_samps)
+        ctx.save_for_backward(g_rgb, g_depth)
+        return out[:3]
+
+    @staticmethod
+    def backward(ctx, g):
+        g_rgb, g_depth = ctx.saved_tensors
+        if g is None:
+            return (None,) * 15
+        d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
+        d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
+        return (d_rgb, d_depth) + (None,) * 13
 
 
 def _flat(t, tail):
@@ -123,12 +151,26 @@ class ReconstructionLoss:
         self.alpha_reg_fraction = config.get("alpha_reg_fraction", 1 / 8)
         if self.alpha_reg_reduction not in ("ray", "slice"):
             raise ValueError(f"Unknown reduction for alpha regularization: {self.alpha_reg_reduction}")
+        self._flags = None    # (scale 0's `invalid`, its diverse flags) of the call in flight
         self._lin = {}    # (scales, rays per scale, fine present, lambdas[, device]) -> the (9 x 3 S) matrix of loss_matrix()
-        if self.criterion_str != "l1+ssim" or use_automasking or self.median_thresholding or self.invalid_policy == "weight_guided_diverse":
+        # opt-in (like native_mlp_color): criterion l1 / l2, median thresholding and weight_guided_diverse on bts_pixel_loss /
+        # bts_loss_diverse_flags (csrc/bts_loss_pixel.hip)
+        self.native_pixel_loss = bool(config.get("native_pixel_loss", False))
+        self.diverse = self.invalid_policy == "weight_guided_diverse"
+        self.pixel_criterion = self.criterion_str in ("l1", "l2")
+        got = (f"criterion={self.criterion_str}, invalid_policy={self.invalid_policy}, automasking={use_automasking}, "
+               f"median_thresholding={self.median_thresholding}")
+        if use_automasking:
+            raise NotImplementedError("use_automasking=True is not covered by the HIP loss (it needs a fourth colour channel through the render "
+                                      "kernels); got " + got)
+        if self.criterion_str == "l1+ssim" and self.median_thresholding:
+            raise NotImplementedError("criterion 'l1+ssim' with median_thresholding=True is not covered by the HIP loss (the SSIM gradient "
+                                      "couples neighbouring pixels: the mask would have to enter the tile kernel's coefficient gather); got " + got)
+        if (self.pixel_criterion or self.diverse) and not self.native_pixel_loss:
             raise NotImplementedError("the fused HIP loss covers criterion 'l1+ssim' with invalid_policy strict / weight_guided / none, "
-                                      "without automasking / median thresholding (every shipped config); got "
-                                      f"criterion={self.criterion_str}, invalid_policy={self.invalid_policy}, "
-                                      f"automasking={use_automasking}, median_thresholding={self.median_thresholding}")
+                                      "without automasking / median thresholding (every shipped config); criterion 'l1' / 'l2' (with or "
+                                      "without median_thresholding) and invalid_policy 'weight_guided_diverse' run on their own HIP kernels "
+                                      "with the config key `native_pixel_loss: true`; got " + got)
 
     @staticmethod
     def get_loss_metric_names():
@@ -142,6 +184,12 @@ class ReconstructionLoss:
         if c != 3:
             raise NotImplementedError("the fused HIP loss takes 3 colour channels")
         B = n * pc * h * w
+        if self.diverse:
+            # l1+ssim under weight_guided_diverse: the per-(ray, view) flags (bts_loss_diverse_flags) as `invalid_any` of the strict
+            # policy, whose all_v(flag > .5) is the diverse rule -- the shipped loss kernels serve it unchanged
+            sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
+                                          _flat(rgb_gt, (3,)).detach(), h, w, "strict", eas, None, self._diverse_flags(level0))
+            return sums, B
         if "weights" not in level0:     # lean training outputs: the renderer's epilogue reduced weights / invalid per ray and view
             sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
                                           _flat(rgb_gt, (3,)).detach(), h, w, self.invalid_policy, eas,
@@ -155,8 +203,52 @@ class ReconstructionLoss:
                                       _flat(rgb_gt, (3,)).detach(), h, w, self.invalid_policy, eas)
         return sums, B
 
+    def _diverse_inputs(self, level0):
+        """(rgb_samps (B, K, nv, 3), weights (B, K), invalid (B, K, nv)) of weight_guided_diverse, flat"""
+        missing = [k for k in ("rgb_samps", "weights", "invalid") if k not in level0]
+        if missing:
+            raise KeyError("invalid_policy weight_guided_diverse reads the per-sample `rgb_samps`, `weights` and `invalid`, which this render "
+                           f"dict does not carry (missing: {', '.join(missing)}): call the renderer with want_rgb_samps=True and "
+                           "want_weights=True and without lean_training_outputs (NeRFRenderer drops the per-sample tensors in that mode)")
+        K, nv = level0["invalid"].shape[-2:]
+        return (_flat(level0["rgb_samps"], (K, nv, 3)).detach(), _flat(level0["weights"], (K,)).detach(),
+                _flat(level0["invalid"], (K, nv)).detach())
+
+    def _diverse_flags(self, level0):
+        """(B, nv) 0 / 1 floats; one launch per render dict and call (every scale reads scale 0's)"""
+        if self._flags is None or self._flags[0] is not level0.get("invalid"):
+            self._flags = (level0.get("invalid"), native.loss_diverse_flags(*self._diverse_inputs(level0)))
+        return self._flags[1]
+
+    def _pixel(self, level, level0, rgb_gt, eas):
+        """-> (rgb term, sum of the smoothness term, number of invalid rays) as one (3,) tensor, number of rays: criterion l1 / l2"""
+        rgb = level["rgb"]                                   # (n, pc, h, w, nv, 3)
+        n, pc, h, w, nv, c = rgb.shape
+        if c != 3:
+            raise NotImplementedError("the HIP loss takes 3 colour channels")
+        B = n * pc * h * w
+        weights = invalid = samps = wsum = any_ = None
+        if self.diverse:
+            samps, weights, invalid = self._diverse_inputs(level0)
+        elif self.ignore_invalid and "weights" not in level0:     # lean training outputs
+            if self.invalid_policy == "weight_guided":
+                wsum = _flat(level0["invalid_wsum"], (nv,)).detach()
+            else:
+                any_ = _flat(level0["invalid_any"], (nv,)).detach()
+        elif self.ignore_invalid:
+            K = level0["weights"].shape[-1]
+            invalid = _flat(level0["invalid"], (K, nv)).detach()
+            weights = _flat(level0["weights"], (K,)).detach() if self.invalid_policy == "weight_guided" else None
+        terms = _PixelTerms.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, weights, invalid, samps,
+                                  _flat(rgb_gt, (3,)).detach(), n, h, w, self.criterion_str, self.invalid_policy, bool(self.median_thresholding),
+                                  eas, wsum, any_)
+        return terms, B
+
     def _photometric(self, level, level0, rgb_gt, eas):
         """-> (mean rgb term, mean smoothness term, invalid-ray ratio)"""
+        if self.pixel_criterion:
+            terms, B = self._pixel(level, level0, rgb_gt, eas)
+            return terms[0], terms[1] / B, terms[2] / B
         sums, B = self._sums(level, level0, rgb_gt, eas)
         return sums[0] / B, sums[1] / B, sums[2] / B
 
@@ -171,7 +263,7 @@ class ReconstructionLoss:
         3.7 ms exp_re10k.yaml step.  Returns None when the data needs the general path."""
         coarse_0, fine_0 = data["coarse"][0], data["fine"][0]
         S = len(data["coarse"])
-        mask_keys = ("weights", "invalid") if "weights" in coarse_0 else ("invalid_wsum", "invalid_any")
+        mask_keys = self._mask_keys(coarse_0)
         has_fine = []
         for coarse, fine in zip(data["coarse"], data["fine"]):
             if len(fine) > 0 and not (_same_view(fine["rgb"], coarse["rgb"]) and all(_same_view(fine_0[k], coarse_0[k]) for k in mask_keys)):
@@ -210,12 +302,22 @@ class ReconstructionLoss:
             return Md
         return M
 
+    def _mask_keys(self, coarse_0):
+        """the entries of scale 0's dict the invalid-ray policy reads (a fine dict that aliases them shares the coarse launch)"""
+        if self.diverse:
+            self._diverse_inputs(coarse_0)      # (a lean dict: the KeyError that says what to ask the renderer for)
+            return ("rgb_samps", "weights", "invalid")
+        return ("weights", "invalid") if "weights" in coarse_0 else ("invalid_wsum", "invalid_any")
+
     def __call__(self, data):
         with profiler.record_function("loss_computation"):       # loss.py:84
-            return self._call(data)
+            try:
+                return self._call(data)
+            finally:
+                self._flags = None
 
     def _call(self, data):
-        if not (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0 or self.lambda_depth_smoothness > 0
+        if not self.pixel_criterion and not (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0 or self.lambda_depth_smoothness > 0
                 or self.lambda_entropy > 0):
             res = self._call_photometric_only(data)
             if res is not None:
@@ -234,6 +336,8 @@ class ReconstructionLoss:
 
         def keep():   # 1 - invalid ray mask (n, pc, h, w) for the optional regularisers
             nonlocal keep_cache
+            if keep_cache is None and self.diverse:
+                keep_cache = 1 - torch.all(self._diverse_flags(coarse_0) > .5, dim=-1).reshape(coarse_0["depth"].shape).to(torch.float32)
             if keep_cache is None and "weights" not in coarse_0:    # lean training outputs
                 if self.invalid_policy == "strict":
                     bad = torch.all(coarse_0["invalid_any"] > .5, dim=-1)
@@ -261,7 +365,7 @@ class ReconstructionLoss:
                 m["inv"] = inv_ratio.detach()
             m["coarse"] = m["coarse"] + rgb_loss.detach() * self.lambda_coarse
             if len(fine) > 0:
-                mask_keys = ("weights", "invalid") if "weights" in coarse_0 else ("invalid_wsum", "invalid_any")
+                mask_keys = self._mask_keys(coarse_0)
                 if _same_view(fine["rgb"], coarse["rgb"]) and all(_same_view(fine_0[k], coarse_0[k]) for k in mask_keys):
                     # trainer.py:247-248 aliases fine = dict(coarse): reconstruct() then views the SAME storage once per dict, so the
                     # tensors are different Python objects over identical memory -- one launch serves both terms

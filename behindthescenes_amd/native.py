@@ -204,6 +204,77 @@ def photometric_loss_tiled(a, parts, g_rgb, g_depth, stream):
     return parts, g_rgb, g_depth
 
 
+PIXEL_CRITERIA = {"l1": 1, "l2": 2}
+PIXEL_POLICIES = {None: 0, "none": 0, "strict": 1, "weight_guided": 2, "weight_guided_diverse": 3}
+
+
+def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch_w: int, criterion: str, invalid_policy, median: bool,
+               eas: bool, scale_rgb: float = 1.0, scale_eas: float = 1.0, need_grad: bool = True, invalid_wsum=None, invalid_any=None,
+               rgb_samps=None):
+    """The per-pixel criteria "l1" / "l2" of the reference's loss, with or without median thresholding, under any of its four invalid-ray
+    policies, plus the edge-aware smoothness term (bts_pixel_loss, csrc/bts_loss_pixel.hip).  Flat layout of ``photometric_loss``:
+    rgb (B, nv*3), depth (B) | None, weights (B, K) | None, invalid (B, K, nv) | None, rgb_samps (B, K, nv, 3) | None, rgb_gt (B, 3);
+    ``n`` batch samples of B / n rays each, every sample a whole number of patch_h x patch_w patches.
+    -> out (4) = [rgb term, sum of the smoothness term, invalid rays, count], thresholds (n) | None, kept (1) int64 | None,
+    g_rgb (B, nv*3) | None = scale_rgb * d out[0] / d rgb, g_depth (B) | None = scale_eas * d out[1] / d depth."""
+    if criterion not in PIXEL_CRITERIA:
+        raise BtsNativeError(f"pixel_loss: criterion {criterion!r} is not one of {sorted(PIXEL_CRITERIA)}")
+    if invalid_policy not in PIXEL_POLICIES:
+        raise BtsNativeError(f"pixel_loss: unknown invalid_policy {invalid_policy!r}")
+    B = rgb_gt.shape[0]
+    if n <= 0 or patch_h <= 0 or patch_w <= 0 or B % (n * patch_h * patch_w):
+        raise BtsNativeError(f"{B} rays are not {n} samples of whole {patch_h}x{patch_w} patches")
+    nv = rgb.shape[-1] // 3
+    policy = PIXEL_POLICIES[invalid_policy]
+    _req(rgb, "rgb", (B, nv * 3)), _req(rgb_gt, "rgb_gt", (B, 3))
+    K = 0
+    sums = (policy == 2 and invalid_wsum is not None) or (policy == 1 and invalid_any is not None)
+    if sums:
+        _req(invalid_wsum if policy == 2 else invalid_any, "invalid_wsum / invalid_any", (B, nv))
+        weights = invalid = None
+    elif policy:
+        K = invalid.shape[1]
+        _req(invalid, "invalid", (B, K, nv))
+        if policy >= 2:
+            _req(weights, "weights", (B, K))
+        if policy == 3:
+            _req(rgb_samps, "rgb_samps", (B, K, nv, 3))
+    if eas:
+        _req(depth, "depth", (B,))
+    dev = rgb.device
+    out = torch.empty((4,), device=dev, dtype=torch.float32)
+    thresholds = torch.empty((n,), device=dev, dtype=torch.float32) if median else None
+    kept = torch.empty((1,), device=dev, dtype=torch.int64) if median else None
+    g_rgb = torch.empty_like(rgb) if need_grad else None
+    g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and eas) else None
+    a = _lib.BtsPixelLossArgs(rgb=rgb.data_ptr(), rgb_gt=rgb_gt.data_ptr(), depth=depth.data_ptr() if eas else None,
+                              weights=weights.data_ptr() if (weights is not None and policy >= 2) else None,
+                              invalid=invalid.data_ptr() if (invalid is not None and policy) else None,
+                              invalid_wsum=invalid_wsum.data_ptr() if (sums and policy == 2) else None,
+                              invalid_any=invalid_any.data_ptr() if (sums and policy == 1) else None,
+                              rgb_samps=rgb_samps.data_ptr() if policy == 3 else None, out=out.data_ptr(),
+                              thresholds=_ptr(thresholds), kept=_ptr(kept), g_rgb=_ptr(g_rgb), g_depth=_ptr(g_depth), B=B, n=n,
+                              patch_h=patch_h, patch_w=patch_w, nv=nv, K=K, criterion=PIXEL_CRITERIA[criterion], invalid_policy=policy,
+                              median_thresholding=int(bool(median)), edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
+                              scale_eas=scale_eas)
+    lib = _lib.load()
+    need = lib.bts_pixel_loss_workspace(B, n, patch_h, patch_w)
+    ws = torch.empty((max(int(need), 1),), device=dev, dtype=torch.uint8)
+    _lib.check(lib.bts_pixel_loss(C.byref(a), ws.data_ptr(), ws.numel(), _stream(rgb)), "bts_pixel_loss")
+    return out, thresholds, kept, g_rgb, g_depth
+
+
+def loss_diverse_flags(rgb_samps, weights, invalid):
+    """The per-(ray, view) flag of invalid_policy weight_guided_diverse as 0 / 1 floats (bts_loss_diverse_flags):
+    rgb_samps (B, K, nv, 3), weights (B, K), invalid (B, K, nv) -> (B, nv)."""
+    B, K, nv = invalid.shape
+    _req(invalid, "invalid", (B, K, nv)), _req(weights, "weights", (B, K)), _req(rgb_samps, "rgb_samps", (B, K, nv, 3))
+    flags = torch.empty((B, nv), device=invalid.device, dtype=torch.float32)
+    _lib.check(_lib.load().bts_loss_diverse_flags(_ptr(rgb_samps), _ptr(weights), _ptr(invalid), B, K, nv, _ptr(flags), _stream(invalid)),
+               "bts_loss_diverse_flags")
+    return flags
+
+
 def sample_coarse(rays: torch.Tensor, u: torch.Tensor, lindisp: bool) -> torch.Tensor:
     """rays (B,8), u (B,K) uniform jitter -> z_samp (B,K) (bts_sample_coarse)."""
     B, K = u.shape

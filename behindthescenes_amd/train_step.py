@@ -220,6 +220,11 @@ class FusedTrainStep(torch.nn.Module):
         if (crit.lambda_depth_reg > 0 or crit.lambda_alpha_reg > 0 or crit.lambda_surfaceness_reg > 0 or crit.lambda_depth_smoothness > 0
                 or crit.lambda_entropy > 0):
             return "an optional regulariser of the loss is on"
+        # the one-call step's loss pass is bts_photometric_loss: l1+ssim, no median thresholding, no diverse flags (native_pixel_loss)
+        if crit.criterion_str != "l1+ssim":
+            return f"criterion {crit.criterion_str} (the one-call training step computes l1+ssim only)"
+        if crit.median_thresholding:
+            return "median_thresholding"
         if crit.invalid_policy not in native.INVALID_POLICIES:
             return f"invalid_policy {crit.invalid_policy}"
         if smp.channels != 3 or smp.patch_size_x * smp.patch_size_y > 64:

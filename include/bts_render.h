@@ -302,6 +302,64 @@ int bts_photometric_loss(const BtsLossArgs* args, void* stream);
 size_t bts_photometric_loss_tiled_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv);
 int bts_photometric_loss_tiled(const BtsLossArgs* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The PER-PIXEL criteria of ReconstructionLoss (loss.py:43-293): criterion "l1" / "l2" (the reference's default), with or without
+ * median_thresholding, under invalid_policy none / strict / weight_guided / weight_guided_diverse, plus the edge-aware smoothness term
+ * of bts_photometric_loss_tiled (same formulas, its own passes: csrc/bts_loss_pixel.hip).  Rays in the flat layout of BtsLossArgs:
+ * B = n * (rays per batch sample), every sample a whole number of patch_h x patch_w patches (patch-major, then row, then column).
+ * The reference's quirks, kept on purpose:
+ *   - e[ray, c] = min_v crit(rgb[ray, v, c] - gt[ray, c]) * keep[ray]: the minimum over the views is taken PER CHANNEL (:154-155), three
+ *     channels of one pixel may pick three different views;
+ *   - median_thresholding (:163-167): per batch sample the threshold is torch's LOWER median, rank (N - 1) / 2 of the N = 3 B / n masked
+ *     values ascending -- invalid rays contribute zeros to that ranking, so a sample with more than half of its values masked has threshold 0
+ *     and keeps only zeros; the kept set is e <= thr, ties at the threshold are ALL kept; the term is (sum of kept) / count with ONE integer
+ *     count over all samples.  The selection is exact (radix on the bit pattern, 11 + 11 + 10 bits: thr is an element of e, bit for bit);
+ *   - weight_guided_diverse (:109-118): a (ray, view) is flagged when (sum_k invalid w > .9) | (mean_c std_k(rgb_samps) < .01), std the
+ *     unbiased one (K - 1) in fp32, mean first, then the squared deviations, k ascending; K == 1 gives NaN and the comparison is false;
+ *     a ray is invalid when every view is flagged;
+ *   - the gradient follows torch's amin: views tied at the minimum share it EQUALLY; sign(0) = 0 for l1, 2 d for l2; nothing flows
+ *     through the threshold; the smoothness mask is the same keep flag, its clamp gradient is over the closed interval.
+ * out (4) receives [rgb term = sum of kept e / count, sum over the rays of the smoothness term, number of invalid rays, count as a float]
+ * (count = 3 B without median); thresholds (n) and kept (1, the count as an integer) are optional and written with median only.
+ * g_rgb (B, nv, 3), when given, receives scale_rgb * d out[0] / d rgb; g_depth (B) scale_eas * d out[1] / d depth; with both NULL only
+ * the forward runs.  No float atomics: every sum is a fixed-order sum of per-work-group partials, reruns are bit-identical.
+ * `workspace`: at least bts_pixel_loss_workspace(B, n, patch_h, patch_w) bytes of device memory (about 18 bytes per ray and 24 KB per batch sample; any alignment;
+ * contents need not be initialised or kept).  BTS_E_INVALID with a bts_last_error text, nothing launched, for: a NULL required pointer
+ * (args, rgb, rgb_gt, out; depth with edge_aware_smoothness), a non-positive size, B not a multiple of n * patch_h * patch_w, more than
+ * 2^29 rays, an unknown criterion or invalid_policy, policy 1 / 2 without invalid_any / invalid_wsum or invalid (and weights) with K > 0,
+ * weight_guided_diverse without rgb_samps, weights or invalid, a workspace that is NULL or too small. */
+typedef struct {
+  const float* rgb;           /* (B, nv, 3) */
+  const float* rgb_gt;        /* (B, 3) */
+  const float* depth;         /* (B) or NULL without edge_aware_smoothness */
+  const float* weights;       /* (B, K)      policies 2, 3 */
+  const float* invalid;       /* (B, K, nv)  policies 1, 2, 3 */
+  const float* invalid_wsum;  /* (B, nv) or NULL: replaces weights / invalid for policy 2 */
+  const float* invalid_any;   /* (B, nv) or NULL: replaces invalid for policy 1 */
+  const float* rgb_samps;     /* (B, K, nv, 3)  policy 3 */
+  float* out;                 /* (4) */
+  float* thresholds;          /* (n) or NULL */
+  int64_t* kept;              /* (1) or NULL */
+  float* g_rgb;               /* (B, nv, 3) or NULL */
+  float* g_depth;             /* (B) or NULL */
+  int64_t B;
+  int32_t n, patch_h, patch_w, nv, K;
+  int32_t criterion;               /* 1 l1, 2 l2 */
+  int32_t invalid_policy;          /* 0 none, 1 strict, 2 weight_guided, 3 weight_guided_diverse */
+  int32_t median_thresholding;     /* 0 / 1 */
+  int32_t edge_aware_smoothness;   /* 0 / 1 */
+  int32_t reserved_;
+  float scale_rgb, scale_eas;
+} BtsPixelLossArgs;
+size_t bts_pixel_loss_workspace(int64_t B, int32_t n, int32_t patch_h, int32_t patch_w);
+int bts_pixel_loss(const BtsPixelLossArgs* args, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The per-(ray, view) flag of weight_guided_diverse (above) as 0 / 1 floats: rgb_samps (B, K, nv, 3), weights (B, K), invalid (B, K, nv)
+ * -> flags (B, nv).  Criterion "l1+ssim" with weight_guided_diverse needs no kernel of its own: these flags, handed to
+ * bts_photometric_loss / _tiled as invalid_any under the strict policy, give its all_v(flag > .5) -- the diverse rule.  BTS_E_INVALID for
+ * a NULL pointer or a non-positive size. */
+int bts_loss_diverse_flags(const float* rgb_samps, const float* weights, const float* invalid, int64_t B, int32_t K, int32_t nv, float* flags,
+                           void* stream);
+
 /* PatchRaySampler.sample (models/bts/model/ray_sampler.py:125-162) on device: for each of the n samples, P patches given by
  * (view, y0, x0) triples (int32, (n, P) each; the caller draws them -- the reference uses the CPU RNG) of ph x pw pixels.
  * poses_c2w (n, v, 4, 4), projs (n, v, 3, 3), images (n, v, c, H, W) or NULL -> rays (n, P*ph*pw, 8) and, with images,

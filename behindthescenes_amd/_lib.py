@@ -193,6 +193,12 @@ SYMBOLS = {
     "bts_pixel_loss_workspace": (C.c_size_t, [C.c_int64, _I, _I, _I]),
     "bts_pixel_loss": (C.c_int, [C.POINTER(BtsPixelLossArgs), _P, C.c_size_t, _P]),
     "bts_loss_diverse_flags": (C.c_int, [_P, _P, _P, C.c_int64, _I, _I, _P, _P]),
+    # auto-masking: the error map (csrc/bts_automask.hip) and the three loss entry points with the per-ray bound `thresh`
+    "bts_automask_errors": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, C.c_float, _P, _P, _P]),
+    "bts_photometric_loss_automask": (C.c_int, [C.POINTER(BtsLossArgs), _P, _P]),
+    "bts_photometric_loss_tiled_automask_workspace": (C.c_size_t, [_I, _I, _I, _I]),
+    "bts_photometric_loss_tiled_automask": (C.c_int, [C.POINTER(BtsLossArgs), _P, _P, C.c_size_t, _P]),
+    "bts_pixel_loss_automask": (C.c_int, [C.POINTER(BtsPixelLossArgs), _P, _P, C.c_size_t, _P]),
     "bts_sample_coarse": (C.c_int, [_P, _P, C.c_int64, _I, _I, _P, _P]),
     "bts_distance_to_z": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
     "bts_invert_small": (C.c_int, [_P, _P, _I, _I, _P]),

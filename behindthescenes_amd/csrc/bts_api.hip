@@ -269,43 +269,67 @@ int bts_patch_rays(const float* poses, const float* projs, const float* images, 
                                     rgb_gt, (hipStream_t)stream),
                   "bts_patch_rays");
 }
-int bts_photometric_loss(const BtsLossArgs* a, void* stream) {
+// bts_photometric_loss and its _automask form: one set of checks, one launch
+static int photometric_loss_entry(const BtsLossArgs* a, const float* thresh, void* stream, const char* who) {
   BTS_CHECK_LAYOUT(a && a->rgb && a->rgb_gt && a->parts && a->n_patches >= 0 && a->patch_h > 0 && a->patch_w > 0 &&
                        a->patch_h * a->patch_w <= 64 && a->nv > 0 && a->invalid_policy >= 0 && a->invalid_policy <= 2 &&
                        (a->invalid_policy != 1 || a->invalid_any || (a->invalid && a->K > 0)) &&
                        (a->invalid_policy != 2 || a->invalid_wsum || (a->invalid && a->weights && a->K > 0)) &&
                        (!a->edge_aware_smoothness || a->depth),
-                   "bts_photometric_loss");
-  return launched(photometric_loss_impl(a, (hipStream_t)stream), "bts_photometric_loss");
+                   who);
+  return launched(photometric_loss_impl(a, (hipStream_t)stream, thresh), who);
+}
+// thresh == NULL: BTS_E_INVALID before anything else of an _automask entry
+static int check_thresh(const float* thresh, const char* who) {
+  if (thresh) return BTS_OK;
+  set_error("%s: thresh is NULL (the per-ray bound, (B) floats; without one call the entry point without _automask)", who);
+  return BTS_E_INVALID;
+}
+int bts_photometric_loss(const BtsLossArgs* a, void* stream) { return photometric_loss_entry(a, nullptr, stream, "bts_photometric_loss"); }
+int bts_photometric_loss_automask(const BtsLossArgs* a, const float* thresh, void* stream) {
+  static const char who[] = "bts_photometric_loss_automask";
+  if (int rc = check_thresh(thresh, who)) return rc;
+  return photometric_loss_entry(a, thresh, stream, who);
 }
 size_t bts_photometric_loss_tiled_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv) {
   return loss_tiled_bytes(n_patches, patch_h, patch_w, nv);
 }
-int bts_photometric_loss_tiled(const BtsLossArgs* a, void* workspace, size_t workspace_bytes, void* stream) {
+size_t bts_photometric_loss_tiled_automask_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv) {
+  return loss_tiled_bytes(n_patches, patch_h, patch_w, nv, true);
+}
+static int photometric_loss_tiled_entry(const BtsLossArgs* a, const float* thresh, void* workspace, size_t workspace_bytes, void* stream,
+                                        const char* who) {
   BTS_CHECK_LAYOUT(a && a->rgb && a->rgb_gt && a->parts && a->n_patches >= 0 && a->patch_h > 0 && a->patch_w > 0 && a->nv > 0 &&
                        a->invalid_policy >= 0 && a->invalid_policy <= 2 && (!a->edge_aware_smoothness || a->depth),
-                   "bts_photometric_loss_tiled");
+                   who);
   if ((a->invalid_policy == 1 && !a->invalid_any && !(a->invalid && a->K > 0)) ||
       (a->invalid_policy == 2 && !a->invalid_wsum && !(a->invalid && a->weights && a->K > 0))) {
-    set_error("%s: invalid_policy %ld needs invalid_any / invalid_wsum, or invalid (and weights) with K > 0", "bts_photometric_loss_tiled",
-              (long)a->invalid_policy);
+    set_error("%s: invalid_policy %ld needs invalid_any / invalid_wsum, or invalid (and weights) with K > 0", who, (long)a->invalid_policy);
     return BTS_E_INVALID;
   }
   if ((long)a->n_patches * a->patch_h * a->patch_w > 2147483647L) {
-    set_error("%s: %ld patches of %ld x %ld pixels are more than 2^31 - 1 rays", "bts_photometric_loss_tiled", (long)a->n_patches, (long)a->patch_h,
-              (long)a->patch_w);
+    set_error("%s: %ld patches of %ld x %ld pixels are more than 2^31 - 1 rays", who, (long)a->n_patches, (long)a->patch_h, (long)a->patch_w);
     return BTS_E_INVALID;
   }
-  const size_t need = loss_tiled_bytes(a->n_patches, a->patch_h, a->patch_w, a->nv);
+  const size_t need = loss_tiled_bytes(a->n_patches, a->patch_h, a->patch_w, a->nv, thresh != nullptr);
   if (!workspace || workspace_bytes < need) {
-    set_error("%s: workspace too small (%ld bytes needed, see bts_photometric_loss_tiled_workspace)", "bts_photometric_loss_tiled", (long)need);
+    set_error(thresh ? "%s: workspace too small (%ld bytes needed, see bts_photometric_loss_tiled_automask_workspace)"
+                     : "%s: workspace too small (%ld bytes needed, see bts_photometric_loss_tiled_workspace)",
+              who, (long)need);
     return BTS_E_INVALID;
   }
-  return launched(photometric_loss_tiled_impl(a, workspace, (hipStream_t)stream), "bts_photometric_loss_tiled");
+  return launched(photometric_loss_tiled_impl(a, workspace, (hipStream_t)stream, thresh), who);
+}
+int bts_photometric_loss_tiled(const BtsLossArgs* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return photometric_loss_tiled_entry(a, nullptr, workspace, workspace_bytes, stream, "bts_photometric_loss_tiled");
+}
+int bts_photometric_loss_tiled_automask(const BtsLossArgs* a, const float* thresh, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char who[] = "bts_photometric_loss_tiled_automask";
+  if (int rc = check_thresh(thresh, who)) return rc;
+  return photometric_loss_tiled_entry(a, thresh, workspace, workspace_bytes, stream, who);
 }
 size_t bts_pixel_loss_workspace(int64_t B, int32_t n, int32_t patch_h, int32_t patch_w) { return pixel_loss_bytes((long)B, n, patch_h, patch_w); }
-int bts_pixel_loss(const BtsPixelLossArgs* a, void* workspace, size_t workspace_bytes, void* stream) {
-  static const char who[] = "bts_pixel_loss";
+static int pixel_loss_entry(const BtsPixelLossArgs* a, const float* thresh, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
   if (!a || !a->rgb || !a->rgb_gt || !a->out || (a->edge_aware_smoothness && !a->depth)) {
     set_error("%s: NULL required pointer (args, rgb, rgb_gt, out; depth with edge_aware_smoothness)", who);
     return BTS_E_INVALID;
@@ -344,7 +368,45 @@ int bts_pixel_loss(const BtsPixelLossArgs* a, void* workspace, size_t workspace_
     set_error("%s: workspace too small (%ld bytes needed, see bts_pixel_loss_workspace)", who, (long)need);
     return BTS_E_INVALID;
   }
-  return launched(pixel_loss_impl(a, workspace, (hipStream_t)stream), who);
+  return launched(pixel_loss_impl(a, workspace, (hipStream_t)stream, thresh), who);
+}
+int bts_pixel_loss(const BtsPixelLossArgs* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return pixel_loss_entry(a, nullptr, workspace, workspace_bytes, stream, "bts_pixel_loss");
+}
+int bts_pixel_loss_automask(const BtsPixelLossArgs* a, const float* thresh, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char who[] = "bts_pixel_loss_automask";
+  if (int rc = check_thresh(thresh, who)) return rc;
+  return pixel_loss_entry(a, thresh, workspace, workspace_bytes, stream, who);
+}
+int bts_automask_errors(const float* images, int32_t n, int32_t v, int32_t H, int32_t W, const int32_t* ids_loss, int32_t n_loss, float scale,
+                        float* errors, float* images4, void* stream) {
+  static const char who[] = "bts_automask_errors";
+  if (!images || !ids_loss) {
+    set_error("%s: NULL images or ids_loss", who);
+    return BTS_E_INVALID;
+  }
+  if (!errors && !images4) {
+    set_error("%s: both outputs (errors, images4) are NULL", who);
+    return BTS_E_INVALID;
+  }
+  if (n <= 0 || v <= 0 || H <= 0 || W <= 0) {
+    set_error("%s: non-positive size (n, v, H, W)", who);
+    return BTS_E_INVALID;
+  }
+  if (n_loss < 1 || n_loss > BTS_MAX_VIEWS) {
+    set_error("%s: %ld loss frames are outside [1, BTS_MAX_VIEWS = %ld]", who, (long)n_loss, (long)BTS_MAX_VIEWS);
+    return BTS_E_INVALID;
+  }
+  for (int j = 0; j < n_loss; ++j)
+    if (ids_loss[j] < 0 || ids_loss[j] >= v) {
+      set_error("%s: ids_loss[%ld] = %ld is outside [0, v = %ld)", who, (long)j, (long)ids_loss[j], (long)v);
+      return BTS_E_INVALID;
+    }
+  if (automask_tiles(n, H, W) > 2147483647L) {
+    set_error("%s: %ld frames of %ld x %ld pixels are more than 2^31 - 1 tiles", who, (long)n, (long)H, (long)W);
+    return BTS_E_INVALID;
+  }
+  return launched(automask_errors_launch(images, n, v, H, W, ids_loss, n_loss, scale, errors, images4, (hipStream_t)stream), who);
 }
 int bts_loss_diverse_flags(const float* rgb_samps, const float* weights, const float* invalid, int64_t B, int32_t K, int32_t nv, float* flags,
                            void* stream) {

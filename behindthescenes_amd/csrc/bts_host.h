@@ -87,12 +87,17 @@ int eval_handover_launch(const float* Ks, const float* poses, const float* image
                          float* rgb_gt, unsigned* sched, hipStream_t s);
 
 // ---- bts_loss.hip (patches of at most 64 pixels), bts_loss_tiled.hip (patches of any size)
-int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s);
-size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv);
-int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s);
+// thresh (B) or NULL: the automasking bound on every pixel's error -- a compile-time variant of the kernels, the forms without it are untouched
+int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s, const float* thresh = nullptr);
+size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv, bool with_thresh = false);
+int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s, const float* thresh = nullptr);
 // ---- bts_loss_pixel.hip: criteria l1 / l2, median thresholding, the diverse flags
 size_t pixel_loss_bytes(long B, int n, int ph, int pw);
-int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s);
+int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, const float* thresh = nullptr);
+// ---- bts_automask.hip: the error map of use_automasking
+long automask_tiles(int n, int H, int W);
+int automask_errors_launch(const float* images, int n, int v, int H, int W, const int* ids_loss, int L, float scale, float* errors,
+                           float* images4, hipStream_t s);
 int diverse_flags_launch(const float* rgb_samps, const float* weights, const float* invalid, long B, int K, int nv, float* flags, hipStream_t s);
 
 // ---- bts_mlp_color.hip: MLP-predicted colour

@@ -33,6 +33,15 @@ struct LossParams {
   float s_rgb, s_eas;    // d loss / d (sum rgb term), d loss / d (sum smoothness term)
   int has_eas;
 };
+// ... with the automasking bound (loss.py:157-158): e <- min(min_v e_v, thresh) before the keep factor; the gradient of torch's binary
+// min -- full below the bound, none above, HALF on a tie -- multiplies the pixel's upstream gradient, so a bound pixel hands no SSIM
+// coefficients to its neighbours.  A type of its own: the kernel without the bound keeps its arguments and its code
+struct LossParamsThr : LossParams {
+  const float* thresh;   // (B)
+};
+
+// d min(e, t) / d e as torch.min(a, b) forms it
+__device__ __forceinline__ float min_grad_factor(float e, float t) { return e < t ? 1.0f : (e > t ? 0.0f : 0.5f); }
 
 constexpr int kPlane = 208;  // floats per LDS plane: (ph + 2) * (pw + 2) <= 3 * 66
 
@@ -68,7 +77,9 @@ struct SsimStats {
   float mu_x, gxx, gxy;
 };
 
-__global__ __launch_bounds__(256) void photometric_loss_kernel(const LossParams p) {
+template <class P>
+__global__ __launch_bounds__(256) void photometric_loss_kernel(const P p) {
+  constexpr bool kThr = std::is_same<P, LossParamsThr>::value;
   // per wave: Y planes (3 channels), X plane, products X^2 and XY, and three coefficient planes for the backward gather
   __shared__ float lds[4][9][kPlane];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -156,8 +167,13 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const LossParams 
     const float e = 0.85f * (ss / 3.0f) + 0.15f * (l1 / 3.0f);
     if (v == 0 || e < e_min) e_min = e, v_star = v;
   }
+  float up = keep * p.s_rgb;             // d loss / d e_{v*}(this pixel)
+  if constexpr (kThr) {
+    const float t = act ? p.thresh[ray] : 0.0f;
+    up = up * min_grad_factor(e_min, t);
+    e_min = fminf(e_min, t);
+  }
   const float L = e_min * keep;          // policy none: keep = 1 on every pixel
-  const float up = keep * p.s_rgb;       // d loss / d e_{v*}(this pixel)
 
   // ---- pass 2: gradient with respect to the rendered colours
   if (p.g_rgb) {
@@ -242,8 +258,8 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const LossParams 
   }
 }
 
-int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s) {
-  LossParams p;
+int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s, const float* thresh) {
+  LossParamsThr p;
   p.rgb = a->rgb, p.depth = a->depth, p.weights = a->weights, p.invalid = a->invalid, p.rgb_gt = a->rgb_gt;
   p.invalid_wsum = a->invalid_wsum, p.invalid_any = a->invalid_any;
   p.parts = a->parts, p.g_rgb = a->g_rgb, p.g_depth = a->g_depth;
@@ -251,7 +267,11 @@ int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s) {
   p.s_rgb = a->scale_rgb, p.s_eas = a->scale_eas, p.has_eas = a->edge_aware_smoothness;
   if (p.n_patches == 0) return BTS_OK;
   const int grid = (p.n_patches + 3) / 4;
-  photometric_loss_kernel<<<grid, 256, 0, s>>>(p);
+  p.thresh = thresh;
+  if (thresh)
+    photometric_loss_kernel<LossParamsThr><<<grid, 256, 0, s>>>(p);
+  else
+    photometric_loss_kernel<LossParams><<<grid, 256, 0, s>>>(static_cast<const LossParams&>(p));
   return launch_check("%s: loss kernel launch failed (%ld)");
 }
 

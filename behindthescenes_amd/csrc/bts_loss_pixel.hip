@@ -69,6 +69,13 @@ struct PixelParams {
   float4* patch_stats;          // (n_patches): m, S, S / m, 0
   float* fin;                   // [0] = s_rgb / count
 };
+// ... with the automasking bound (loss.py:157-158): e[ray, c] = min(min_v crit, thresh[ray]) * keep -- the ray's ONE bound against each of
+// its three channels, before the keep factor and before the median ranking; the gradient of torch's binary min (full below the bound,
+// none above, HALF on a tie) multiplies the channel's share.  A type of its own: the kernels without the bound keep their arguments
+// and their code
+struct PixelParamsThr : PixelParams {
+  const float* thresh;          // (B)
+};
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -135,7 +142,9 @@ __device__ __forceinline__ bool ray_invalid(const PixelParams& p, long ray) {
 __device__ __forceinline__ float crit_of(int crit, float d) { return crit == 1 ? fabsf(d) : d * d; }
 
 // d (norm * sum of the kept e) / d rgb of one ray: per channel the views that attain the minimum share the gradient equally (amin)
-__device__ __forceinline__ void write_grad(const PixelParams& p, long ray, float keep, float thr, float norm) {
+template <class P>
+__device__ __forceinline__ void write_grad(const P& p, long ray, float keep, float thr, float norm) {
+  constexpr bool kThr = std::is_same<P, PixelParamsThr>::value;
   const int nv = p.nv;
   const float* x = p.rgb + ray * nv * 3;
   float* g = p.g_rgb + ray * nv * 3;
@@ -152,8 +161,17 @@ __device__ __forceinline__ void write_grad(const PixelParams& p, long ray, float
 #pragma unroll
     for (int c = 0; c < 3; ++c) ties[c] += crit_of(p.crit, x[v * 3 + c] - y[c]) == emin[c] ? 1.0f : 0.0f;
   float coef[3];
+  if constexpr (kThr) {
+    const float t = p.thresh[ray];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) coef[c] = (keep != 0.0f && emin[c] * keep <= thr) ? norm / ties[c] : 0.0f;
+    for (int c = 0; c < 3; ++c) {
+      const float f = emin[c] < t ? 1.0f : (emin[c] > t ? 0.0f : 0.5f);      // torch.min(e, thresh): a tie splits the gradient
+      coef[c] = (keep != 0.0f && fminf(emin[c], t) * keep <= thr) ? norm / ties[c] * f : 0.0f;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) coef[c] = (keep != 0.0f && emin[c] * keep <= thr) ? norm / ties[c] : 0.0f;
+  }
   for (int v = 0; v < nv; ++v)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -202,7 +220,9 @@ __device__ __forceinline__ void flush_hist(const unsigned* s_hist, unsigned* dst
   }
 }
 
-__global__ __launch_bounds__(kThreads) void pixel_err_kernel(const PixelParams p) {
+template <class P>
+__global__ __launch_bounds__(kThreads) void pixel_err_kernel(const P p) {
+  constexpr bool kThr = std::is_same<P, PixelParamsThr>::value;
   __shared__ unsigned s_hist[kBins];
   __shared__ float s_f[4];
   __shared__ unsigned s_u[4];
@@ -231,7 +251,9 @@ __global__ __launch_bounds__(kThreads) void pixel_err_kernel(const PixelParams p
       }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float e = emin[c] * keep;
+      float e = emin[c];
+      if constexpr (kThr) e = fminf(e, p.thresh[ray]);
+      e = e * keep;
       p.e[ray * 3 + c] = e;
       esum += e;
       if (p.median) atomicAdd(&s_hist[__float_as_uint(e) >> 21], 1u);
@@ -453,7 +475,8 @@ __global__ __launch_bounds__(kThreads) void pixel_final_kernel(const PixelParams
   }
 }
 
-__global__ __launch_bounds__(kThreads) void pixel_grad_kernel(const PixelParams p) {
+template <class P>
+__global__ __launch_bounds__(kThreads) void pixel_grad_kernel(const P p) {
   const RayPos r = ray_pos(p);
   if (r.act) write_grad(p, r.ray, p.keep[r.ray] ? 1.0f : 0.0f, p.thr[r.sample], p.fin[0]);
 }
@@ -516,8 +539,10 @@ size_t pixel_loss_bytes(long B, int n, int ph, int pw) {
          up256(4 * sizeof(float));
 }
 
-int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s) {
-  PixelParams p;
+int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, const float* thresh) {
+  PixelParamsThr pt;
+  pt.thresh = thresh;
+  PixelParams& p = pt;
   p.rgb = a->rgb, p.depth = a->depth, p.weights = a->weights, p.invalid = a->invalid, p.invalid_wsum = a->invalid_wsum;
   p.invalid_any = a->invalid_any, p.rgb_samps = a->rgb_samps, p.rgb_gt = a->rgb_gt;
   p.out = a->out, p.thresholds = a->thresholds, p.kept = (long long*)a->kept, p.g_rgb = a->g_rgb, p.g_depth = a->g_depth;
@@ -546,7 +571,10 @@ int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s) {
     set_error("%s: clearing the histograms failed", "bts_pixel_loss");
     return BTS_E_LAUNCH;
   }
-  pixel_err_kernel<<<grid, kThreads, 0, s>>>(p);
+  if (thresh)
+    pixel_err_kernel<PixelParamsThr><<<grid, kThreads, 0, s>>>(pt);
+  else
+    pixel_err_kernel<PixelParams><<<grid, kThreads, 0, s>>>(p);
   if (p.median) {
     pixel_hist_kernel<1><<<grid, kThreads, 0, s>>>(p);
     pixel_hist_kernel<2><<<grid, kThreads, 0, s>>>(p);
@@ -557,7 +585,12 @@ int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s) {
     pixel_patch_kernel<<<(unsigned)(g.n_patches < 65536 ? g.n_patches : 65536), 64, 0, s>>>(p);
   }
   pixel_final_kernel<<<1, kThreads, 0, s>>>(p);
-  if (p.median && p.g_rgb) pixel_grad_kernel<<<grid, kThreads, 0, s>>>(p);
+  if (p.median && p.g_rgb) {
+    if (thresh)
+      pixel_grad_kernel<PixelParamsThr><<<grid, kThreads, 0, s>>>(pt);
+    else
+      pixel_grad_kernel<PixelParams><<<grid, kThreads, 0, s>>>(p);
+  }
   if (p.g_depth) pixel_gdepth_kernel<<<(unsigned)((p.B + kThreads - 1) / kThreads), kThreads, 0, s>>>(p);
   return launch_check("%s: pixel loss kernel launch failed (%ld)");
 }

@@ -59,6 +59,14 @@ struct TiledParams {
   unsigned char* keep;     // (B): 0 = invalid ray
   int vec4;                // weights / invalid rows can be read as float4 (nv == 1, K % 4 == 0, 16-byte aligned bases)
 };
+// ... with the automasking bound (bts_loss.hip: LossParamsThr): pass 1 bounds e and scales the pixel's upstream gradient by the factor
+// of torch's binary min (1, 0 or -- on a tie -- .5), which therefore sits in the coefficients BEFORE the neighbours gather them in pass 3;
+// the factor itself goes to the workspace for pass 3's L1 term.  A type of its own: the kernels without the bound keep their arguments
+// and their code
+struct TiledParamsThr : TiledParams {
+  const float* thresh;     // (B)
+  float* fthr;             // workspace (B): d min(e, thresh) / d e
+};
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -167,7 +175,9 @@ __global__ __launch_bounds__(256) void loss_tiled_keep(const TiledParams p) {
   for (long ray = blockIdx.x * 256L + threadIdx.x; ray < p.B; ray += gridDim.x * 256L) p.keep[ray] = ray_invalid(p, ray) ? 0 : 1;
 }
 
-__global__ __launch_bounds__(256) void loss_tiled_pass1(const TiledParams p, const long n_tiles) {
+template <class P>
+__global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_tiles) {
+  constexpr bool kThr = std::is_same<P, TiledParamsThr>::value;
   __shared__ float sY[3][kHalo], sX[3][kHalo], sD[kHalo], sK[kHalo];
   __shared__ float sRed[4][4];
   const int tid = threadIdx.x;
@@ -246,8 +256,15 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const TiledParams p, con
       for (int c = 0; c < 3; ++c) b_x[c] = x[c], b_mu[c] = mu[c], b_gxx[c] = gxx[c], b_gxy[c] = gxy[c];
     }
   }
+  float up = keep * p.s_rgb;             // d loss / d e_{v*}(this pixel)
+  if constexpr (kThr) {
+    const float t = act ? p.thresh[ray] : 0.0f;
+    const float f = e_min < t ? 1.0f : (e_min > t ? 0.0f : 0.5f);      // torch.min(e, thresh): a tie splits the gradient
+    up = up * f;
+    e_min = fminf(e_min, t);
+    if (p.g_rgb && act) p.fthr[ray] = f;
+  }
   const float L = e_min * keep;
-  const float up = keep * p.s_rgb;       // d loss / d e_{v*}(this pixel)
 
   // ---- the SSIM backward coefficients of v* (gathered by the neighbours in pass 3)
   if (p.g_rgb && act) {
@@ -350,7 +367,9 @@ __global__ __launch_bounds__(64) void loss_tiled_pass2(const TiledParams p) {
   }
 }
 
-__global__ __launch_bounds__(256) void loss_tiled_pass3(const TiledParams p, const long n_tiles) {
+template <class P>
+__global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_tiles) {
+  constexpr bool kThr = std::is_same<P, TiledParamsThr>::value;
   __shared__ float sC[9][kHalo];
   __shared__ int sV[kHalo];
   const int tid = threadIdx.x;
@@ -389,6 +408,8 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const TiledParams p, con
 #pragma unroll
       for (int c = 0; c < 3; ++c) vq[r * 3 + c] = sV[ctr + (r - 1) * kLd + (c - 1)];
     const float y[3] = {p.rgb_gt[ray * 3], p.rgb_gt[ray * 3 + 1], p.rgb_gt[ray * 3 + 2]};
+    float up_c = p.s_rgb;                 // the centre's upstream gradient when it is kept
+    if constexpr (kThr) up_c = up_c * p.fthr[ray];
     for (int v = 0; v < nv; ++v) {
       unsigned m = 0;
 #pragma unroll
@@ -405,7 +426,7 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const TiledParams p, con
         const float t_mu = gauss9_masked(sC[c * 3 + 0], ctr, m), t_xx = gauss9_masked(sC[c * 3 + 1], ctr, m),
                     t_xy = gauss9_masked(sC[c * 3 + 2], ctr, m);
         // the L1 term's gradient: a centre with v* >= 0 is kept, so its upstream gradient is s_rgb
-        const float g_l1 = (m & 16u) ? p.s_rgb * (0.15f / 3.0f) * sign0(x - y[c]) : 0.0f;
+        const float g_l1 = (m & 16u) ? up_c * (0.15f / 3.0f) * sign0(x - y[c]) : 0.0f;
         dst[c] = t_mu + 2.0f * x * t_xx + y[c] * t_xy + g_l1;
       }
     }
@@ -433,17 +454,17 @@ inline long tiles_of(int ph, int pw) { return (long)((ph + kTile - 1) / kTile) *
 }  // namespace
 
 // bytes of bts_photometric_loss_tiled's workspace: tile partials, patch statistics, v*, nine coefficient planes, u, keep flags
-size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv) {
+size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv, bool with_thresh) {
   if (n_patches < 0 || ph <= 0 || pw <= 0 || nv <= 0) return 0;
   const size_t B = (size_t)n_patches * (size_t)ph * (size_t)pw;
   const size_t nt = (size_t)n_patches * (size_t)tiles_of(ph, pw);
   return kAlign + up256(nt * sizeof(float4)) + up256((size_t)n_patches * sizeof(float4)) + up256(B * sizeof(int)) + up256(B * 9 * sizeof(float)) +
-         up256(B * sizeof(float)) + up256(B);
+         up256(B * sizeof(float)) + up256(B) + (with_thresh ? up256(B * sizeof(float)) : 0);
 }
 
-int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s) {
+int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s, const float* thresh) {
   if (a->n_patches == 0) return BTS_OK;
-  TiledParams p;
+  TiledParamsThr p;
   p.rgb = a->rgb, p.depth = a->depth, p.weights = a->weights, p.invalid = a->invalid, p.rgb_gt = a->rgb_gt;
   p.invalid_wsum = a->invalid_wsum, p.invalid_any = a->invalid_any;
   p.parts = a->parts, p.g_rgb = a->g_rgb, p.g_depth = a->g_depth;
@@ -459,17 +480,27 @@ int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream
   p.vstar = (int*)w, w += up256((size_t)p.B * sizeof(int));
   p.coef = (float*)w, w += up256((size_t)p.B * 9 * sizeof(float));
   p.u = (float*)w, w += up256((size_t)p.B * sizeof(float));
-  p.keep = (unsigned char*)w;
+  p.keep = (unsigned char*)w, w += up256((size_t)p.B);
+  p.thresh = thresh, p.fthr = thresh ? (float*)w : nullptr;
+  const TiledParams& base = p;
   p.vec4 = p.nv == 1 && p.K > 0 && (p.K & 3) == 0 && ((uintptr_t)p.invalid & 15) == 0 && ((uintptr_t)p.weights & 15) == 0;
   const unsigned grid = (unsigned)((long)nt < kMaxGrid ? (long)nt : kMaxGrid);
   const unsigned grid2 = (unsigned)(p.n_patches < kMaxGrid ? (long)p.n_patches : kMaxGrid);
   if (p.policy != 0) {
     const long kb = (p.B + 255) / 256;
-    loss_tiled_keep<<<(unsigned)(kb < kMaxGrid ? kb : kMaxGrid), 256, 0, s>>>(p);
+    loss_tiled_keep<<<(unsigned)(kb < kMaxGrid ? kb : kMaxGrid), 256, 0, s>>>(base);
   }
-  loss_tiled_pass1<<<grid, 256, 0, s>>>(p, (long)nt);
-  loss_tiled_pass2<<<grid2, 64, 0, s>>>(p);
-  if (p.g_rgb || p.g_depth) loss_tiled_pass3<<<grid, 256, 0, s>>>(p, (long)nt);
+  if (thresh)
+    loss_tiled_pass1<TiledParamsThr><<<grid, 256, 0, s>>>(p, (long)nt);
+  else
+    loss_tiled_pass1<TiledParams><<<grid, 256, 0, s>>>(base, (long)nt);
+  loss_tiled_pass2<<<grid2, 64, 0, s>>>(base);
+  if (p.g_rgb || p.g_depth) {
+    if (thresh)
+      loss_tiled_pass3<TiledParamsThr><<<grid, 256, 0, s>>>(p, (long)nt);
+    else
+      loss_tiled_pass3<TiledParams><<<grid, 256, 0, s>>>(base, (long)nt);
+  }
   return launch_check("%s: tiled loss kernel launch failed (%ld)");
 }
 

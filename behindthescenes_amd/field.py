@@ -165,6 +165,10 @@ class BTSNet(nn.Module):
             ids_render = list(range(images.shape[1]))
         n, nv_enc, c, h, w = images_encoder.shape
         if self.torch_mode:
+            if colours is not None and colours.shape[2] == 4:
+                raise NotImplementedError("a 4-channel images_alt (automasking: the error map as the frames' fourth channel) is served by the HIP "
+                                          "render path only; the torch-composed modes (sample_color=False without native_mlp_color, combine_ids / "
+                                          "several encoder views) sample every channel of grid_c_imgs and would render the map as a colour")
             return self._encode_torch_mode(images, Ks, poses_w2c, images_encoder, Ks_encoder, poses_w2c_encoder, ids_encoder, ids_render, colours,
                                            combine_ids)
 
@@ -199,7 +203,10 @@ class BTSNet(nn.Module):
         native.check_supported(self.spec, nv)
         if nv and not self.spec.mlp_color:   # (predicted colours read no frames)
             scale, shift = (0.5, 0.5) if self._grid_c_raw else (1.0, 0.0)   # x * .5 + .5 inside the packing kernel (mul, then add)
-            self._imgs_nhwc4 = native.pack_rgb(src.detach().float().contiguous(), scale, shift)
+            # automasking: images_alt carries the error map as a fourth channel (automask.automask_images); the renderer samples the three
+            # colours -- grid_c_imgs keeps all four, as the reference's does
+            rgb_src = src[:, :, :3] if (colours is not None and src.shape[2] == 4) else src
+            self._imgs_nhwc4 = native.pack_rgb(rgb_src.detach().float().contiguous(), scale, shift)
             self._K_r = self.grid_c_Ks.detach().float().contiguous()
             self._w2c_r = self.grid_c_poses_w2c.detach().float().contiguous()
         else:

@@ -10,7 +10,12 @@ pixels (every shipped config: ``patch_size: 8``) one wave takes one patch; above
 three); ``native.photometric_loss`` chooses.  With the config key ``native_pixel_loss: true`` the reference's other options run on
 HIP kernels too: criterion "l1" / "l2" with or without ``median_thresholding`` under any invalid policy (``bts_pixel_loss``,
 csrc/bts_loss_pixel.hip: ``native.pixel_loss``), and "l1+ssim" under ``weight_guided_diverse`` (``bts_loss_diverse_flags``, then the
-kernels above under the strict policy); "l1+ssim" with median thresholding and ``use_automasking`` stay refused.  The optional regularisers (depth /
+kernels above under the strict policy); "l1+ssim" with median thresholding stays refused.  With ``native_automask: true``
+``use_automasking=True`` runs on the same kernels' ``_automask`` entry points: ``rgb_gt`` then carries the error map of
+``automask.automask_images`` as a fourth channel, which bounds every pixel's error (``min(e, thresh)`` after the minimum over the views,
+before the invalid-ray mask and the median ranking; torch's binary-min gradient, a tie taking half).  The reference renders that fourth
+channel as well and cuts it off first thing; its gradient is exactly 0, so the render kernels keep their three channels and the rendered
+``rgb`` arrives with 3.  The optional regularisers (depth /
 alpha / surfaceness / depth-smoothness / ray-entropy, all off in the shipped configs) are a few elementwise torch expressions on
 top.  Same constructor keys, same call signature, same ``(loss, loss_dict)`` result as the reference."""
 import math
@@ -26,11 +31,11 @@ class _PhotometricSums(torch.autograd.Function):
     """(sum of the rgb term, sum of the smoothness term, number of invalid rays) over all patches; differentiable w.r.t. rgb, depth."""
 
     @staticmethod
-    def forward(ctx, rgb, depth, weights, invalid, rgb_gt, ph, pw, policy, eas, invalid_wsum=None, invalid_any=None):
+    def forward(ctx, rgb, depth, weights, invalid, rgb_gt, ph, pw, policy, eas, invalid_wsum=None, invalid_any=None, thresh=None):
         ctx.set_materialize_grads(False)
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         parts, g_rgb, g_depth = native.photometric_loss(rgb, depth if eas else None, weights, invalid, rgb_gt, ph, pw, policy, eas, 1.0, 1.0,
-                                                        need_grad=need, invalid_wsum=invalid_wsum, invalid_any=invalid_any)
+                                                        need_grad=need, invalid_wsum=invalid_wsum, invalid_any=invalid_any, thresh=thresh)
         ctx.save_for_backward(g_rgb, g_depth)
         ctx.had_depth = depth is not None
         return parts.sum(0)[:3]
@@ -39,10 +44,10 @@ class _PhotometricSums(torch.autograd.Function):
     def backward(ctx, g):
         g_rgb, g_depth = ctx.saved_tensors
         if g is None:
-            return (None,) * 11
+            return (None,) * 12
         d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
         d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
-        return d_rgb, d_depth, None, None, None, None, None, None, None, None, None
+        return d_rgb, d_depth, None, None, None, None, None, None, None, None, None, None
 
 
 class _PixelTerms(torch.autograd.Function):
@@ -51,12 +56,12 @@ class _PixelTerms(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb, depth, weights, invalid, rgb_samps, rgb_gt, n, ph, pw, criterion, policy, median, eas, invalid_wsum=None,
-                invalid_any=None):
+                invalid_any=None, thresh=None):
         ctx.set_materialize_grads(False)
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         out, _, _, g_rgb, g_depth = native.pixel_loss(rgb, depth if eas else None, weights, invalid, rgb_gt, n, ph, pw, criterion, policy, median,
                                                       eas, 1.0, 1.0, need_grad=need, invalid_wsum=invalid_wsum, invalid_any=invalid_any,
-                                                      rgb_samps=rgb_samps)
+                                                      rgb_samps=rgb_samps, thresh=thresh)
         ctx.save_for_backward(g_rgb, g_depth)
         return out[:3]
 
@@ -64,10 +69,10 @@ class _PixelTerms(torch.autograd.Function):
     def backward(ctx, g):
         g_rgb, g_depth = ctx.saved_tensors
         if g is None:
-            return (None,) * 15
+            return (None,) * 16
         d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
         d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
-        return (d_rgb, d_depth) + (None,) * 13
+        return (d_rgb, d_depth) + (None,) * 14
 
 
 def _flat(t, tail):
@@ -160,9 +165,12 @@ class ReconstructionLoss:
         self.pixel_criterion = self.criterion_str in ("l1", "l2")
         got = (f"criterion={self.criterion_str}, invalid_policy={self.invalid_policy}, automasking={use_automasking}, "
                f"median_thresholding={self.median_thresholding}")
-        if use_automasking:
-            raise NotImplementedError("use_automasking=True is not covered by the HIP loss (it needs a fourth colour channel through the render "
-                                      "kernels); got " + got)
+        # opt-in: use_automasking on the loss kernels' _automask entry points (rgb_gt's fourth channel bounds every pixel's error)
+        self.native_automask = bool(config.get("native_automask", False))
+        if use_automasking and not self.native_automask:
+            raise NotImplementedError("use_automasking=True runs on the HIP loss kernels' threshold variants with the config key "
+                                      "`native_automask: true` (rgb_gt then carries automask.automask_images' error map as a fourth "
+                                      "channel; the rendered rgb keeps 3); got " + got)
         if self.criterion_str == "l1+ssim" and self.median_thresholding:
             raise NotImplementedError("criterion 'l1+ssim' with median_thresholding=True is not covered by the HIP loss (the SSIM gradient "
                                       "couples neighbouring pixels: the mask would have to enter the tile kernel's coefficient gather); got " + got)
@@ -176,9 +184,20 @@ class ReconstructionLoss:
     def get_loss_metric_names():
         return ["loss", "loss_rgb_coarse", "loss_rgb_fine", "loss_ray_entropy", "loss_depth_reg"]
 
-    def _sums(self, level, level0, rgb_gt, eas):
+    def _split_gt(self, rgb_gt):
+        """-> (colours (B, 3), threshold (B) | None): with automasking the fourth channel of rgb_gt is the per-ray bound (loss.py:139-143)"""
+        if not self.use_automasking:
+            return _flat(rgb_gt, (3,)).detach(), None
+        if rgb_gt.shape[-1] != 4:
+            raise ValueError(f"use_automasking=True reads the error map as rgb_gt's fourth channel (automask.automask_images, a sampler "
+                             f"with channels=4); got rgb_gt with {rgb_gt.shape[-1]} channels")
+        return _flat(rgb_gt[..., :3], (3,)).detach(), _flat(rgb_gt[..., 3], ()).detach()
+
+    def _sums(self, level, level0, gt, eas):
         """-> ((sum of the rgb term, sum of the smoothness term, number of invalid rays) as one (3,) tensor, number of rays) of one set
-        of renderer outputs in patch layout."""
+        of renderer outputs in patch layout.  gt: _split_gt's pair."""
+        rgb_gt, thresh = gt
+        bound = () if thresh is None else (thresh,)          # (the autograd function's last argument, only with automasking)
         rgb = level["rgb"]                                   # (n, pc, h, w, nv, 3)
         n, pc, h, w, nv, c = rgb.shape
         if c != 3:
@@ -188,19 +207,19 @@ class ReconstructionLoss:
             # l1+ssim under weight_guided_diverse: the per-(ray, view) flags (bts_loss_diverse_flags) as `invalid_any` of the strict
             # policy, whose all_v(flag > .5) is the diverse rule -- the shipped loss kernels serve it unchanged
             sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
-                                          _flat(rgb_gt, (3,)).detach(), h, w, "strict", eas, None, self._diverse_flags(level0))
+                                          rgb_gt, h, w, "strict", eas, None, self._diverse_flags(level0), *bound)
             return sums, B
         if "weights" not in level0:     # lean training outputs: the renderer's epilogue reduced weights / invalid per ray and view
             sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
-                                          _flat(rgb_gt, (3,)).detach(), h, w, self.invalid_policy, eas,
+                                          rgb_gt, h, w, self.invalid_policy, eas,
                                           _flat(level0["invalid_wsum"], (nv,)).detach() if self.invalid_policy == "weight_guided" else None,
-                                          _flat(level0["invalid_any"], (nv,)).detach() if self.invalid_policy == "strict" else None)
+                                          _flat(level0["invalid_any"], (nv,)).detach() if self.invalid_policy == "strict" else None, *bound)
             return sums, B
         K = level0["weights"].shape[-1]
         sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None,
                                       _flat(level0["weights"], (K,)).detach() if self.invalid_policy == "weight_guided" else None,
                                       _flat(level0["invalid"], (K, nv)).detach() if self.ignore_invalid else None,
-                                      _flat(rgb_gt, (3,)).detach(), h, w, self.invalid_policy, eas)
+                                      rgb_gt, h, w, self.invalid_policy, eas, *((None, None) + bound if bound else ()))
         return sums, B
 
     def _diverse_inputs(self, level0):
@@ -220,8 +239,9 @@ class ReconstructionLoss:
             self._flags = (level0.get("invalid"), native.loss_diverse_flags(*self._diverse_inputs(level0)))
         return self._flags[1]
 
-    def _pixel(self, level, level0, rgb_gt, eas):
+    def _pixel(self, level, level0, gt, eas):
         """-> (rgb term, sum of the smoothness term, number of invalid rays) as one (3,) tensor, number of rays: criterion l1 / l2"""
+        rgb_gt, thresh = gt
         rgb = level["rgb"]                                   # (n, pc, h, w, nv, 3)
         n, pc, h, w, nv, c = rgb.shape
         if c != 3:
@@ -240,16 +260,16 @@ class ReconstructionLoss:
             invalid = _flat(level0["invalid"], (K, nv)).detach()
             weights = _flat(level0["weights"], (K,)).detach() if self.invalid_policy == "weight_guided" else None
         terms = _PixelTerms.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, weights, invalid, samps,
-                                  _flat(rgb_gt, (3,)).detach(), n, h, w, self.criterion_str, self.invalid_policy, bool(self.median_thresholding),
-                                  eas, wsum, any_)
+                                  rgb_gt, n, h, w, self.criterion_str, self.invalid_policy, bool(self.median_thresholding),
+                                  eas, wsum, any_, *(() if thresh is None else (thresh,)))
         return terms, B
 
-    def _photometric(self, level, level0, rgb_gt, eas):
+    def _photometric(self, level, level0, gt, eas):
         """-> (mean rgb term, mean smoothness term, invalid-ray ratio)"""
         if self.pixel_criterion:
-            terms, B = self._pixel(level, level0, rgb_gt, eas)
+            terms, B = self._pixel(level, level0, gt, eas)
             return terms[0], terms[1] / B, terms[2] / B
-        sums, B = self._sums(level, level0, rgb_gt, eas)
+        sums, B = self._sums(level, level0, gt, eas)
         return sums[0] / B, sums[1] / B, sums[2] / B
 
     _KEYS = ["loss_rgb_coarse", "loss_rgb_fine", "loss_ray_entropy", "loss_depth_reg", "loss_alpha_reg", "loss_eas",
@@ -270,7 +290,8 @@ class ReconstructionLoss:
                 return None
             has_fine.append(len(fine) > 0)
         eas_on = self.lambda_edge_aware_smoothness > 0
-        sums, Bs = zip(*(self._sums(c, coarse_0, data["rgb_gt"], eas_on) for c in data["coarse"]))
+        gt = self._split_gt(data["rgb_gt"])       # (two tiny copies with automasking: rays, not pixels)
+        sums, Bs = zip(*(self._sums(c, coarse_0, gt, eas_on) for c in data["coarse"]))
         st = torch.stack(sums).reshape(-1)                      # (3 S): rgb, eas, invalid count per scale
         M = self.loss_matrix(S, Bs, tuple(has_fine), st.device)
         loss = torch.dot(M[8], st)
@@ -331,6 +352,7 @@ class ReconstructionLoss:
                            "per-sample tensors in that mode)")
         zero = torch.zeros((), device=dev)
         loss = zero
+        gt = self._split_gt(data["rgb_gt"])
         m = dict(coarse=zero, fine=zero, depth_reg=zero, alpha_reg=zero, surf=zero, eas=zero, dsmooth=zero, inv=zero)
         keep_cache = None
 
@@ -360,7 +382,7 @@ class ReconstructionLoss:
         for scale in range(n_scales):
             coarse, fine = data["coarse"][scale], data["fine"][scale]
             eas_on = self.lambda_edge_aware_smoothness > 0
-            rgb_loss, eas, inv_ratio = self._photometric(coarse, coarse_0, data["rgb_gt"], eas_on)
+            rgb_loss, eas, inv_ratio = self._photometric(coarse, coarse_0, gt, eas_on)
             if scale == 0:
                 m["inv"] = inv_ratio.detach()
             m["coarse"] = m["coarse"] + rgb_loss.detach() * self.lambda_coarse
@@ -371,7 +393,7 @@ class ReconstructionLoss:
                     # tensors are different Python objects over identical memory -- one launch serves both terms
                     fine_loss = rgb_loss
                 else:
-                    fine_loss, _, _ = self._photometric(fine, fine_0, data["rgb_gt"], False)
+                    fine_loss, _, _ = self._photometric(fine, fine_0, gt, False)
                 m["fine"] = m["fine"] + fine_loss.detach() * self.lambda_fine
                 rgb_loss = rgb_loss * self.lambda_coarse + fine_loss * self.lambda_fine
             loss = loss + rgb_loss

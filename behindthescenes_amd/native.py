@@ -149,10 +149,11 @@ WAVE_PATCH_PIXELS = 64      # bts_photometric_loss: one wave per patch, lane = p
 
 
 def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w: int, invalid_policy, eas: bool,
-                     scale_rgb: float, scale_eas: float, need_grad: bool = True, invalid_wsum=None, invalid_any=None):
+                     scale_rgb: float, scale_eas: float, need_grad: bool = True, invalid_wsum=None, invalid_any=None, thresh=None):
     """Patch-ordered renderer outputs -> per-patch partial sums and the loss gradients (bts_photometric_loss for patches of up to 64
     pixels, bts_photometric_loss_tiled above that: any (patch_h, patch_w), whole frames included).
-    rgb (B, nv*3), depth (B) | None, weights (B, K) | None, invalid (B, K, nv) | None, rgb_gt (B, 3)
+    rgb (B, nv*3), depth (B) | None, weights (B, K) | None, invalid (B, K, nv) | None, rgb_gt (B, 3), thresh (B) | None: the
+    automasking bound on every pixel's error (the _automask entry points)
     -> parts (B / (ph*pw), 4), g_rgb (B, nv*3) | None, g_depth (B) | None."""
     B = rgb_gt.shape[0]
     area = patch_h * patch_w
@@ -174,6 +175,8 @@ def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w
             _req(weights, "weights", (B, K))
     if eas:
         _req(depth, "depth", (B,))
+    if thresh is not None:
+        _req(thresh, "thresh", (B,))
     dev = rgb.device
     parts = torch.empty((B // area, 4), device=dev, dtype=torch.float32)
     g_rgb = torch.empty_like(rgb) if need_grad else None
@@ -188,16 +191,25 @@ def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w
                          invalid_any=invalid_any.data_ptr() if (sums and policy == 1) else None)
     if area > WAVE_PATCH_PIXELS:
         # larger patches and whole frames: 16 x 16 tiles of each patch (bts_photometric_loss_tiled)
-        return photometric_loss_tiled(a, parts, g_rgb, g_depth, _stream(rgb))
+        return photometric_loss_tiled(a, parts, g_rgb, g_depth, _stream(rgb), thresh)
+    if thresh is not None:
+        _lib.check(_lib.load().bts_photometric_loss_automask(C.byref(a), _ptr(thresh), _stream(rgb)), "bts_photometric_loss_automask")
+        return parts, g_rgb, g_depth
     _lib.check(_lib.load().bts_photometric_loss(C.byref(a), _stream(rgb)), "bts_photometric_loss")
     return parts, g_rgb, g_depth
 
 
-def photometric_loss_tiled(a, parts, g_rgb, g_depth, stream):
+def photometric_loss_tiled(a, parts, g_rgb, g_depth, stream, thresh=None):
     """bts_photometric_loss_tiled on a filled BtsLossArgs: any patch size, with a scratch workspace from torch's allocator (the library
     allocates nothing).  ``native.photometric_loss`` routes patches of more than 64 pixels here; tests call it directly to cross-check the
     two kernels on small patches."""
     lib = _lib.load()
+    if thresh is not None:      # the same passes with the automasking bound (one more float per ray of workspace)
+        need = lib.bts_photometric_loss_tiled_automask_workspace(a.n_patches, a.patch_h, a.patch_w, a.nv)
+        ws = torch.empty((max(int(need), 1),), device=parts.device, dtype=torch.uint8)
+        _lib.check(lib.bts_photometric_loss_tiled_automask(C.byref(a), _ptr(thresh), ws.data_ptr(), ws.numel(), stream),
+                   "bts_photometric_loss_tiled_automask")
+        return parts, g_rgb, g_depth
     need = lib.bts_photometric_loss_tiled_workspace(a.n_patches, a.patch_h, a.patch_w, a.nv)
     ws = torch.empty((max(int(need), 1),), device=parts.device, dtype=torch.uint8)
     _lib.check(lib.bts_photometric_loss_tiled(C.byref(a), ws.data_ptr(), ws.numel(), stream), "bts_photometric_loss_tiled")
@@ -210,11 +222,12 @@ PIXEL_POLICIES = {None: 0, "none": 0, "strict": 1, "weight_guided": 2, "weight_g
 
 def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch_w: int, criterion: str, invalid_policy, median: bool,
                eas: bool, scale_rgb: float = 1.0, scale_eas: float = 1.0, need_grad: bool = True, invalid_wsum=None, invalid_any=None,
-               rgb_samps=None):
+               rgb_samps=None, thresh=None):
     """The per-pixel criteria "l1" / "l2" of the reference's loss, with or without median thresholding, under any of its four invalid-ray
     policies, plus the edge-aware smoothness term (bts_pixel_loss, csrc/bts_loss_pixel.hip).  Flat layout of ``photometric_loss``:
     rgb (B, nv*3), depth (B) | None, weights (B, K) | None, invalid (B, K, nv) | None, rgb_samps (B, K, nv, 3) | None, rgb_gt (B, 3);
-    ``n`` batch samples of B / n rays each, every sample a whole number of patch_h x patch_w patches.
+    ``n`` batch samples of B / n rays each, every sample a whole number of patch_h x patch_w patches.  thresh (B) | None: the automasking
+    bound, one per ray, applied to each of its three channels before the keep factor and the median ranking (bts_pixel_loss_automask).
     -> out (4) = [rgb term, sum of the smoothness term, invalid rays, count], thresholds (n) | None, kept (1) int64 | None,
     g_rgb (B, nv*3) | None = scale_rgb * d out[0] / d rgb, g_depth (B) | None = scale_eas * d out[1] / d depth."""
     if criterion not in PIXEL_CRITERIA:
@@ -241,6 +254,8 @@ def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch
             _req(rgb_samps, "rgb_samps", (B, K, nv, 3))
     if eas:
         _req(depth, "depth", (B,))
+    if thresh is not None:
+        _req(thresh, "thresh", (B,))
     dev = rgb.device
     out = torch.empty((4,), device=dev, dtype=torch.float32)
     thresholds = torch.empty((n,), device=dev, dtype=torch.float32) if median else None
@@ -260,8 +275,28 @@ def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch
     lib = _lib.load()
     need = lib.bts_pixel_loss_workspace(B, n, patch_h, patch_w)
     ws = torch.empty((max(int(need), 1),), device=dev, dtype=torch.uint8)
-    _lib.check(lib.bts_pixel_loss(C.byref(a), ws.data_ptr(), ws.numel(), _stream(rgb)), "bts_pixel_loss")
+    if thresh is not None:
+        _lib.check(lib.bts_pixel_loss_automask(C.byref(a), _ptr(thresh), ws.data_ptr(), ws.numel(), _stream(rgb)), "bts_pixel_loss_automask")
+    else:
+        _lib.check(lib.bts_pixel_loss(C.byref(a), ws.data_ptr(), ws.numel(), _stream(rgb)), "bts_pixel_loss")
     return out, thresholds, kept, g_rgb, g_depth
+
+
+def automask_errors(images: torch.Tensor, ids_loss, scale: float = 0.5, want_errors: bool = True, want_images4: bool = False):
+    """The error map of use_automasking (trainer.py:203-206; bts_automask_errors, csrc/bts_automask.hip): images (n, v, 3, H, W), the
+    processed frames in [0, 1]; ids_loss: 1 .. BTS_MAX_VIEWS frame indices in [0, v) -> errors (n, v, H, W) | None, images4
+    (n, v, 4, H, W) | None (the frames with the map as their fourth plane), one launch."""
+    _req(images, "images")
+    if images.dim() != 5 or images.shape[2] != 3:
+        raise BtsNativeError(f"images: expected (n, v, 3, H, W), got {tuple(images.shape)}")
+    n, v, _, H, W = images.shape
+    ids = [int(i) for i in ids_loss]
+    arr = (C.c_int32 * max(len(ids), 1))(*ids)
+    errors = torch.empty((n, v, H, W), device=images.device, dtype=torch.float32) if want_errors else None
+    images4 = torch.empty((n, v, 4, H, W), device=images.device, dtype=torch.float32) if want_images4 else None
+    _lib.check(_lib.load().bts_automask_errors(_ptr(images), n, v, H, W, arr, len(ids), scale, _ptr(errors), _ptr(images4), _stream(images)),
+               "bts_automask_errors")
+    return errors, images4
 
 
 def loss_diverse_flags(rgb_samps, weights, invalid):

@@ -35,7 +35,11 @@ class RaySampler:
 
     @staticmethod
     def _reshape_all(render_dict, lead, channels, rgb_gt_shape=None):
-        """Shared body of the three reconstruct() variants: view every per-ray tensor as lead + (...)."""
+        """Shared body of the three reconstruct() variants: view every per-ray tensor as lead + (...).  channels == 4 (automasking: the
+        error map rides as the ground truth's fourth channel) reshapes ``rgb_gt`` with 4 and the RENDERED ``rgb`` / ``rgb_samps`` with 3:
+        the kernels only ever render three channels per view -- the reference's fourth rendered channel is cut off first thing in its
+        loss and receives no gradient, so it is not produced (a documented divergence: include/bts_render.h)."""
+        gt_channels, channels = channels, (3 if channels == 4 else channels)
         for key in ("coarse", "fine"):
             part = render_dict[key]
             n = part["rgb"].shape[0]
@@ -61,7 +65,7 @@ class RaySampler:
             render_dict[key] = part
         if "rgb_gt" in render_dict and render_dict["rgb_gt"] is not None:
             g = render_dict["rgb_gt"]
-            render_dict["rgb_gt"] = g.view(g.shape[0], *lead, channels)
+            render_dict["rgb_gt"] = g.view(g.shape[0], *lead, gt_channels)
         return render_dict
 
 

@@ -225,6 +225,8 @@ class FusedTrainStep(torch.nn.Module):
             return f"criterion {crit.criterion_str} (the one-call training step computes l1+ssim only)"
         if crit.median_thresholding:
             return "median_thresholding"
+        if crit.use_automasking:
+            return "use_automasking (the one-call training step's loss pass has no per-pixel bound; the entries compute the error map)"
         if crit.invalid_policy not in native.INVALID_POLICIES:
             return f"invalid_policy {crit.invalid_policy}"
         if smp.channels != 3 or smp.patch_size_x * smp.patch_size_y > 64:
@@ -250,6 +252,9 @@ class FusedTrainStep(torch.nn.Module):
     def _entries(self, images, projs, poses, ids_encoder, ids_render, ids_loss):
         net, smp = self.wrapped.net, self.sampler
         images_ip = images * .5 + .5
+        if getattr(self.criterion, "use_automasking", False):      # trainer.py:201-206: the error map as the frames' fourth channel
+            from .automask import automask_images
+            images_ip = automask_images(images_ip, ids_loss, len(ids_render))
         net.encode(images, projs, poses, ids_encoder=ids_encoder, ids_render=ids_render, images_alt=images_ip)
         all_rays, all_rgb_gt = smp.sample(native_take(images_ip, ids_loss), native_take(poses, ids_loss), native_take(projs, ids_loss))
         data = dict(coarse=[], fine=[])

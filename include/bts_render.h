@@ -360,6 +360,43 @@ int bts_pixel_loss(const BtsPixelLossArgs* args, void* workspace, size_t workspa
 int bts_loss_diverse_flags(const float* rgb_samps, const float* weights, const float* invalid, int64_t B, int32_t K, int32_t nv, float* flags,
                            void* stream);
 
+/* Auto-masking (use_automasking, trainer.py:201-206 and loss.py:139-143, 157-158, 174-175).  The trainer forms, per frame, the mean
+ * l1+ssim error of that frame against the loss frames and carries it as a FOURTH ground-truth channel; the loss bounds every pixel's
+ * error by it.  Two pieces:
+ *
+ * bts_automask_errors: images (n, v, 3, H, W) fp32, the PROCESSED frames in [0, 1]; ids_loss: n_loss HOST int32 values, 1 <= n_loss <=
+ * BTS_MAX_VIEWS, each in [0, v), any order, repeats allowed.  With x = scale * frame f and y_j = scale * frame ids_loss[j]:
+ *   err[n, f, p] = (1 / n_loss) sum_j ( .85 mean_c ssim(x, y_j)[c, p] + .15 mean_c |x - y_j|[c, p] )
+ * ssim as in bts_photometric_loss (3 x 3 Gaussian window, ZERO padding at the frame border, clamp(1 - n / d, 0, 1) / 2, C1 = 1e-4, C2 =
+ * 9e-4 unscaled), plain fp32.  errors (n, v, H, W) and / or images4 (n, v, 4, H, W) = the input planes copied plus the map as plane 3
+ * (the trainer's torch.cat, written by the same launch); at least one of them non-NULL.  One launch, no atomics, reruns bit-identical
+ * (csrc/bts_automask.hip).  Quirks of the reference that are reproduced ON PURPOSE:
+ *   - the frames, already in [0, 1], are multiplied by `scale` = .5 a second time (C1 / C2 are not scaled with them);
+ *   - the partner frames are the LOSS frames although trainer.py calls them render_imgs; its .view only works when
+ *     len(ids_loss) == len(ids_render);
+ *   - the mean over j includes a frame's comparison with itself when f is one of ids_loss (that term is ~ 0).
+ * BTS_E_INVALID, nothing launched, for: a NULL images / ids_loss, both outputs NULL, a non-positive size, n_loss outside
+ * [1, BTS_MAX_VIEWS], an id outside [0, v), more than 2^31 - 1 tiles.
+ *
+ * bts_photometric_loss_automask / _tiled_automask / bts_pixel_loss_automask: the three loss entry points above with the per-ray threshold
+ * thresh (B) = the fourth channel of rgb_gt.  Every check of the base entry point applies; thresh == NULL is BTS_E_INVALID.  Semantics:
+ *   - e <- min(e, thresh) AFTER the minimum over the views, BEFORE the invalid-ray keep factor and before bts_pixel_loss' median ranking;
+ *     for l1 / l2 the ray's one threshold is compared with each of its three channels, for l1+ssim with the pixel's single error;
+ *   - the gradient is torch's binary min: full where e < thresh, zero where e > thresh, HALF where they are equal; nothing flows into
+ *     thresh; under SSIM a bound pixel's factor multiplies its own backward coefficients before the neighbours gather them;
+ *   - thresh = +inf gives the base entry point's results bit for bit.
+ * The tiled form's workspace is bts_photometric_loss_tiled_automask_workspace bytes (the base's plus one float per ray).
+ * DIVERGENCE from the reference, on purpose: the reference renders the fourth channel too and cuts it off first thing in the loss
+ * (rgb_coarse[..., :-1]; its gradient is exactly 0) -- these kernels only ever render and read three channels per view.  One visible
+ * consequence: under weight_guided_diverse the reference's diversity test (mean over the channels of std_k(rgb_samps)) would average
+ * in the rendered map channel as a fourth; here it is the mean over the three colours, as without automasking. */
+int bts_automask_errors(const float* images, int32_t n, int32_t v, int32_t H, int32_t W, const int32_t* ids_loss, int32_t n_loss, float scale,
+                        float* errors, float* images4, void* stream);
+int bts_photometric_loss_automask(const BtsLossArgs* args, const float* thresh, void* stream);
+size_t bts_photometric_loss_tiled_automask_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv);
+int bts_photometric_loss_tiled_automask(const BtsLossArgs* args, const float* thresh, void* workspace, size_t workspace_bytes, void* stream);
+int bts_pixel_loss_automask(const BtsPixelLossArgs* args, const float* thresh, void* workspace, size_t workspace_bytes, void* stream);
+
 /* PatchRaySampler.sample (models/bts/model/ray_sampler.py:125-162) on device: for each of the n samples, P patches given by
  * (view, y0, x0) triples (int32, (n, P) each; the caller draws them -- the reference uses the CPU RNG) of ph x pw pixels.
  * poses_c2w (n, v, 4, 4), projs (n, v, 3, 3), images (n, v, c, H, W) or NULL -> rays (n, P*ph*pw, 8) and, with images,

@@ -297,16 +297,21 @@ size_t bts_photometric_loss_tiled_workspace(int32_t n_patches, int32_t patch_h, 
 size_t bts_photometric_loss_tiled_automask_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv) {
   return loss_tiled_bytes(n_patches, patch_h, patch_w, nv, true);
 }
+// policies strict / weight_guided (BtsLossArgs, BtsPixelLossArgs): the renderer's per-ray reduction or the per-sample rows it stands for
+static int check_policy_inputs(int policy, const float* invalid_any, const float* invalid_wsum, const float* invalid, const float* weights, int K,
+                               const char* who) {
+  if ((policy == 1 && !invalid_any && !(invalid && K > 0)) || (policy == 2 && !invalid_wsum && !(invalid && weights && K > 0))) {
+    set_error("%s: invalid_policy %ld needs invalid_any / invalid_wsum, or invalid (and weights) with K > 0", who, (long)policy);
+    return BTS_E_INVALID;
+  }
+  return BTS_OK;
+}
 static int photometric_loss_tiled_entry(const BtsLossArgs* a, const float* thresh, void* workspace, size_t workspace_bytes, void* stream,
                                         const char* who) {
   BTS_CHECK_LAYOUT(a && a->rgb && a->rgb_gt && a->parts && a->n_patches >= 0 && a->patch_h > 0 && a->patch_w > 0 && a->nv > 0 &&
                        a->invalid_policy >= 0 && a->invalid_policy <= 2 && (!a->edge_aware_smoothness || a->depth),
                    who);
-  if ((a->invalid_policy == 1 && !a->invalid_any && !(a->invalid && a->K > 0)) ||
-      (a->invalid_policy == 2 && !a->invalid_wsum && !(a->invalid && a->weights && a->K > 0))) {
-    set_error("%s: invalid_policy %ld needs invalid_any / invalid_wsum, or invalid (and weights) with K > 0", who, (long)a->invalid_policy);
-    return BTS_E_INVALID;
-  }
+  if (int rc = check_policy_inputs(a->invalid_policy, a->invalid_any, a->invalid_wsum, a->invalid, a->weights, a->K, who)) return rc;
   if ((long)a->n_patches * a->patch_h * a->patch_w > 2147483647L) {
     set_error("%s: %ld patches of %ld x %ld pixels are more than 2^31 - 1 rays", who, (long)a->n_patches, (long)a->patch_h, (long)a->patch_w);
     return BTS_E_INVALID;
@@ -358,11 +363,7 @@ static int pixel_loss_entry(const BtsPixelLossArgs* a, const float* thresh, void
     set_error("%s: weight_guided_diverse needs rgb_samps, weights and invalid with K > 0", who);
     return BTS_E_INVALID;
   }
-  if ((a->invalid_policy == 1 && !a->invalid_any && !(a->invalid && a->K > 0)) ||
-      (a->invalid_policy == 2 && !a->invalid_wsum && !(a->invalid && a->weights && a->K > 0))) {
-    set_error("%s: invalid_policy %ld needs invalid_any / invalid_wsum, or invalid (and weights) with K > 0", who, (long)a->invalid_policy);
-    return BTS_E_INVALID;
-  }
+  if (int rc = check_policy_inputs(a->invalid_policy, a->invalid_any, a->invalid_wsum, a->invalid, a->weights, a->K, who)) return rc;
   const size_t need = pixel_loss_bytes((long)a->B, a->n, a->patch_h, a->patch_w);
   if (!workspace || workspace_bytes < need) {
     set_error("%s: workspace too small (%ld bytes needed, see bts_pixel_loss_workspace)", who, (long)need);

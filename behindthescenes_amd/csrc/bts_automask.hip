@@ -3,8 +3,9 @@
 // as a fourth plane behind the frame's three colour planes.  The reference spends about twenty torch ops on (n v L, 3, H + 2, W + 2)
 // tensors on it; here one launch reads every input plane and writes every output plane once.
 //   err[n, f, p] = (1 / L) sum_j ( .85 mean_c ssim(x_f, y_j)[c, p] + .15 mean_c |x_f - y_j|[c, p] ),  x = scale * frame
-// with the SSIM of bts_loss.hip (read its header: 3 x 3 Gaussian window, ZERO padding at the frame border, clamp(1 - n / d, 0, 1) / 2,
-// c1 = 1e-4, c2 = 9e-4), plain fp32; the windowed sums weigh one operand first and accumulate with fused multiply-adds (weigh9 / dot9).
+// with the SSIM of bts_loss.hip (bts_loss_device.h: the 3 x 3 Gaussian window and ssim_term = clamp(1 - n / d, 0, 1) / 2 with c1 = 1e-4,
+// c2 = 9e-4; ZERO padding at the frame border), plain fp32; the windowed sums are this file's own: they weigh one operand first and
+// accumulate with fused multiply-adds (weigh9 / dot9).
 // One work-group of 256 threads per (batch element, 8 x 32 tile), thread = pixel (a wave takes two rows of 32 consecutive floats: whole
 // 128-byte lines).  The L partner tiles are staged once, scaled, with their one-pixel halo in LDS; every thread forms mu_y and G * y^2 of
 // its pixel for the L x 3 (partner, channel) pairs once and keeps them in registers.  Then the work-group walks the v frames of its
@@ -14,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bts_host.h"
+#include "bts_loss_device.h"
 
 namespace bts {
 
@@ -34,8 +36,6 @@ struct AutomaskParams {
   int ids[BTS_MAX_VIEWS];
 };
 
-constexpr float kGa = 0.0947f, kGb = 0.1183f, kGc = 0.1478f;   // layers.py:92-101 window
-
 // the 3 x 3 neighbourhood of `ctr` in a zero-bordered plane, row-major, times `scale`
 __device__ __forceinline__ void load9(const float* pl, int ctr, float scale, float* q) {
 #pragma unroll
@@ -43,7 +43,7 @@ __device__ __forceinline__ void load9(const float* pl, int ctr, float scale, flo
 #pragma unroll
     for (int c = 0; c < 3; ++c) q[r * 3 + c] = scale * pl[ctr + (r - 1) * kLd + (c - 1)];
 }
-// The window applied once: qw[k] = G[k] * q[k].  Every windowed sum of this kernel is then a row-major sum of qw (the mean) or a chain of
+// The window (bts_loss_device.h: kGa, kGb, kGc) applied once: qw[k] = G[k] * q[k].  Every windowed sum of this kernel is then a row-major sum of qw (the mean) or a chain of
 // nine fused multiply-adds of qw with a second neighbourhood (G * q^2, G * qp): a third of the instructions of weighting every product
 // on its own, and one rounding per term instead of two
 __device__ __forceinline__ void weigh9(const float* q, float* qw) {
@@ -120,7 +120,6 @@ __global__ __launch_bounds__(256) void automask_kernel(const AutomaskParams p) {
       }
     }
 
-  constexpr float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
   for (int f = 0; f < v; ++f) {
     if (f) __syncthreads();      // the previous frame's readers are done with sX
     const float* src = frames + (long)f * 3 * HW;
@@ -141,18 +140,13 @@ __global__ __launch_bounds__(256) void automask_kernel(const AutomaskParams p) {
       load9(sX[c], ctr, p.scale, x);
       weigh9(x, xw);
       const float mu_x = sum9(xw), gxx = dot9(xw, x);
-      const float mxx = mu_x * mu_x, sx = gxx - mxx;
 #pragma unroll
       for (int j = 0; j < LMAX; ++j) {
         if (j < L) {
           float y[9];
           load9(sY[j][c], ctr, 1.0f, y);
           const float gxy = dot9(xw, y);
-          const float myy = mu_y[j][c] * mu_y[j][c], mxy = mu_x * mu_y[j][c];
-          const float sy = gyy[j][c] - myy, sxy = gxy - mxy;
-          const float nn = (2.0f * mxy + c1) * (2.0f * sxy + c2);
-          const float dd = (mxx + myy + c1) * (sx + sy + c2);
-          ss[j] += fminf(fmaxf(1.0f - nn / dd, 0.0f), 1.0f) / 2.0f;
+          ss[j] += ssim_term(mu_x, gxx, gxy, mu_y[j][c], gyy[j][c]);
           l1[j] += fabsf(x[4] - yc[j][c]);
         }
       }

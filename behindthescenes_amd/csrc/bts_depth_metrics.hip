@@ -24,6 +24,7 @@
 // rank-deficient system (fewer than two distinct predictions under the mask: the coefficients are not finite here, LAPACK returns the
 // minimum-norm solution).  N = 0 gives a NaN row and zero counts.
 #include "bts_host.h"
+#include "bts_loss_device.h"
 
 namespace bts {
 
@@ -80,45 +81,6 @@ __device__ __forceinline__ int wave_sum(int v) {
   return v;
 }
 
-// The bin of `hist` (2 048 bins) that holds the element of rank `rank` (0-based; median != 0: rank = (total - 1) / 2), the rank inside
-// that bin and the total.  Every lane takes eight consecutive bins, the work-group scans the 256 sums.  out: bin, rank inside, total;
-// bin = rank = 0 when rank >= total.  All 256 lanes call this; s_scan holds 256 words.
-__device__ void select_bin(const unsigned* __restrict__ hist, int median, unsigned rank, unsigned* s_scan, unsigned* out) {
-  const int t = threadIdx.x;
-  const uint4 lo = reinterpret_cast<const uint4*>(hist)[t * 2], hi = reinterpret_cast<const uint4*>(hist)[t * 2 + 1];
-  const unsigned h[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  unsigned local = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) local += h[k];
-  s_scan[t] = local;
-  __syncthreads();
-  for (int o = 1; o < kThreads; o <<= 1) {
-    const unsigned v = t >= o ? s_scan[t - o] : 0u;
-    __syncthreads();
-    s_scan[t] += v;
-    __syncthreads();
-  }
-  const unsigned total = s_scan[kThreads - 1], incl = s_scan[t], excl = incl - local;
-  if (median) rank = total ? (total - 1) / 2 : 0u;
-  if (t == 0) {
-    out[2] = total;
-    if (rank >= total) out[0] = 0u, out[1] = 0u;
-  }
-  if (rank >= excl && rank < incl) {   // one lane, when rank < total
-    unsigned r = rank - excl, rem = 0u;
-    int bin = -1;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (bin < 0) {
-        if (r < h[k]) bin = k, rem = r;
-        else r -= h[k];
-      }
-    }
-    out[0] = (unsigned)(t * 8 + bin), out[1] = rem;
-  }
-  __syncthreads();
-}
-
 // One radix pass of the two medians (:104-105).  PASS 0: bits 31..21 of every key under gt > 0.  PASS 1: bits 20..10 of the keys whose
 // upper 11 bits are the bin of the wanted rank in pass 0's histogram.  PASS 2: bits 9..0 of the keys that share 22 bits.
 // state words of a frame: [0..4] prefix_gt, rank_gt, prefix_pred, rank_pred, N after pass 0's histogram; [8..12] the same after pass 1's.
@@ -135,15 +97,15 @@ __global__ __launch_bounds__(kThreads) void depth_hist_kernel(DepthGeom g) {
   for (int i = threadIdx.x; i < 2 * kBinsRadix; i += kThreads) s_hist[i] = 0u;
   unsigned want_g = 0u, want_p = 0u;
   if (PASS == 1) {
-    select_bin(hist_f, 1, 0u, s_scan, s_sel[0]);
-    select_bin(hist_f + kBinsRadix, 1, 0u, s_scan, s_sel[1]);
+    select_bin<true>(hist_f, 1, 0u, s_scan, s_sel[0]);
+    select_bin<true>(hist_f + kBinsRadix, 1, 0u, s_scan, s_sel[1]);
     want_g = s_sel[0][0], want_p = s_sel[1][0];
     if (blockIdx.x == 0 && threadIdx.x == 0)
       state_f[0] = want_g, state_f[1] = s_sel[0][1], state_f[2] = want_p, state_f[3] = s_sel[1][1], state_f[4] = s_sel[0][2];
   } else if (PASS == 2) {
     const unsigned pg = state_f[0], rg = state_f[1], pp = state_f[2], rp = state_f[3], n = state_f[4];
-    select_bin(hist_f + 2 * kBinsRadix, 0, rg, s_scan, s_sel[0]);
-    select_bin(hist_f + 3 * kBinsRadix, 0, rp, s_scan, s_sel[1]);
+    select_bin<true>(hist_f + 2 * kBinsRadix, 0, rg, s_scan, s_sel[0]);
+    select_bin<true>(hist_f + 3 * kBinsRadix, 0, rp, s_scan, s_sel[1]);
     want_g = (pg << 11) | s_sel[0][0], want_p = (pp << 11) | s_sel[1][0];
     if (blockIdx.x == 0 && threadIdx.x == 0)
       state_f[8] = want_g, state_f[9] = s_sel[0][1], state_f[10] = want_p, state_f[11] = s_sel[1][1], state_f[12] = n;
@@ -271,8 +233,8 @@ __global__ __launch_bounds__(kThreads) void depth_terms_kernel(DepthGeom g) {
   float x0 = 1.0f, x1 = 0.0f;
   if (g.mode == 1) {
     const unsigned pg = state_f[8], rg = state_f[9], pp = state_f[10], rp = state_f[11], n = state_f[12];
-    select_bin(g.hist + (size_t)f * kHistFrame + 4 * kBinsRadix, 0, rg, s_scan, s_sel[0]);
-    select_bin(g.hist + (size_t)f * kHistFrame + 5 * kBinsRadix, 0, rp, s_scan, s_sel[1]);
+    select_bin<true>(g.hist + (size_t)f * kHistFrame + 4 * kBinsRadix, 0, rg, s_scan, s_sel[0]);
+    select_bin<true>(g.hist + (size_t)f * kHistFrame + 5 * kBinsRadix, 0, rp, s_scan, s_sel[1]);
     const float med_g = depth_unkey((pg << 10) | s_sel[0][0]), med_p = depth_unkey((pp << 10) | s_sel[1][0]);
     x0 = n ? med_g / med_p : __uint_as_float(0x7FC00000u);   // the median of an empty selection
     if (blockIdx.x == 0 && threadIdx.x == 0) state_f[16] = __float_as_uint(x0), state_f[17] = __float_as_uint(0.0f);

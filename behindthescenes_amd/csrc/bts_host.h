@@ -145,6 +145,27 @@ int novel_view_finish_launch(const BtsNovelViews* a, hipStream_t s);
 // ---------------------------------------------------------------------------------------------------------------
 inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+// A workspace's layout, written ONCE as a sequence of take<T>(count) calls: run over Carver(nullptr) it counts the bytes, run over
+// Carver(workspace) it hands out the pointers.  Every buffer starts on a 256-byte boundary behind the (rounded-up) workspace pointer;
+// bytes() includes the 256 that rounding may cost
+constexpr size_t kAlign = 256;
+inline size_t up256(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
+class Carver {
+ public:
+  explicit Carver(void* workspace) : base_(reinterpret_cast<char*>(up256((size_t)(uintptr_t)workspace))) {}
+  template <class T>
+  T* take(size_t count) {
+    T* p = base_ ? reinterpret_cast<T*>(base_ + off_) : nullptr;
+    off_ += up256(count * sizeof(T));
+    return p;
+  }
+  size_t bytes() const { return kAlign + off_; }
+
+ private:
+  char* base_;
+  size_t off_ = 0;
+};
+
 // tiles (64 texels each, either geometry: bts_common.h) of the map of an H x W frame at feat_shift fs
 inline long map_tiles(int H, int W, int fs) { return ((long)(H >> fs) * (W >> fs) + 63) / 64; }
 

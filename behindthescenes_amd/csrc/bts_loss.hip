@@ -11,12 +11,14 @@
 // Backward of the SSIM term: every pixel q turns its upstream gradient into three coefficients (of d mu_x, d G*x^2, d G*xy);
 // pixel p then gathers them from its neighbours:  g_x[p] = sum_q G(q-p) (c_mu(q) + 2 x_p c_xx(q) + y_p c_xy(q)).
 // 3x3 neighbourhoods go through zero-bordered LDS planes private to the wave (LDS operations of one wave execute in order: no barrier).
+// The window, the SSIM term with its coefficients, the inverse depth and the depth gradient are bts_loss_device.h's, shared with
+// bts_loss_tiled.hip; the smoothness edges stay here: they work on the NORMALISED dn = d / m through lane exchanges.
 #include <hip/hip_runtime.h>
 
 #include "bts_host.h"
+#include "bts_loss_device.h"
 
 namespace bts {
-
 
 struct LossParams {
   const float* rgb;      // (B, nv, 3)
@@ -40,16 +42,7 @@ struct LossParamsThr : LossParams {
   const float* thresh;   // (B)
 };
 
-// d min(e, t) / d e as torch.min(a, b) forms it
-__device__ __forceinline__ float min_grad_factor(float e, float t) { return e < t ? 1.0f : (e > t ? 0.0f : 0.5f); }
-
 constexpr int kPlane = 208;  // floats per LDS plane: (ph + 2) * (pw + 2) <= 3 * 66
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Lanes of a wave exchange pixels through LDS planes.  The hardware executes a wave's LDS instructions in order, but the COMPILER
 // sees one thread storing to plane[ctr] and loading plane[ctr +- 1]: provably different addresses, so it may hoist the loads above
@@ -58,19 +51,6 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Gaussian-weighted sum of the 3x3 neighbourhood of `centre` in a zero-bordered plane (layers.py:92-101 window)
-__device__ __forceinline__ float gauss9(const float* pl, int centre, int ld) {
-  constexpr float a = 0.0947f, b = 0.1183f, c = 0.1478f;
-  const float* r0 = pl + centre - ld;
-  const float* r1 = pl + centre;
-  const float* r2 = pl + centre + ld;
-  float s = a * r0[-1];
-  s += b * r0[0], s += a * r0[1];
-  s += b * r1[-1], s += c * r1[0], s += b * r1[1];
-  s += a * r2[-1], s += b * r2[0], s += a * r2[1];
-  return s;
 }
 
 struct SsimStats {
@@ -95,7 +75,8 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const P p) {
   const int ctr = (ly + 1) * ld + lx + 1;
   const long ray = (long)patch * area + (act ? lane : 0);
 
-  // ---- invalid ray?  (loss.py:100-118)
+  // ---- invalid ray?  (loss.py:100-118)  bts_loss_device.h's ray_invalid<false, false>, written out: called as a function its loop over
+  // the views is laid out before it is inlined, and this kernel's instructions change (five spellings tried, tools/asm_compare.py)
   bool invalid = false;
   if (p.policy != 0) {
     bool all_v = true;
@@ -135,7 +116,6 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const P p) {
     wave_lds_fence();
   }
 
-  constexpr float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
   // statistics of (view v, channel c) at this pixel; planes 3 / 4 / 5 hold x, x^2, x*y
   auto stats = [&](float x, int c) {
     if (act) pl[3][ctr] = x, pl[4][ctr] = x * x, pl[5][ctr] = x * y[c];
@@ -157,11 +137,7 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const P p) {
     for (int c = 0; c < 3; ++c) {
       const float x = act ? p.rgb[(ray * nv + v) * 3 + c] : 0.0f;
       const SsimStats s = stats(x, c);
-      const float mxx = s.mu_x * s.mu_x, myy = mu_y[c] * mu_y[c], mxy = s.mu_x * mu_y[c];
-      const float sx = s.gxx - mxx, sy = gyy[c] - myy, sxy = s.gxy - mxy;
-      const float nn = (2.0f * mxy + c1) * (2.0f * sxy + c2);
-      const float dd = (mxx + myy + c1) * (sx + sy + c2);
-      ss += fminf(fmaxf(1.0f - nn / dd, 0.0f), 1.0f) / 2.0f;
+      ss += ssim_term(s.mu_x, s.gxx, s.gxy, mu_y[c], gyy[c]);
       l1 += fabsf(x - y[c]);
     }
     const float e = 0.85f * (ss / 3.0f) + 0.15f * (l1 / 3.0f);
@@ -182,27 +158,13 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const P p) {
       for (int c = 0; c < 3; ++c) {
         const float x = act ? p.rgb[(ray * nv + v) * 3 + c] : 0.0f;
         const SsimStats s = stats(x, c);
-        float k_mu = 0.0f, k_xx = 0.0f, k_xy = 0.0f, g_l1 = 0.0f;
+        SsimCoef k = {0.0f, 0.0f, 0.0f};
+        float g_l1 = 0.0f;
         if (act && v == v_star && up != 0.0f) {
-          const float mxx = s.mu_x * s.mu_x, myy = mu_y[c] * mu_y[c], mxy = s.mu_x * mu_y[c];
-          const float sx = s.gxx - mxx, sy = gyy[c] - myy, sxy = s.gxy - mxy;
-          const float A1 = 2.0f * mxy + c1, A2 = 2.0f * sxy + c2, B1 = mxx + myy + c1, B2 = sx + sy + c2;
-          const float nn = A1 * A2, dd = B1 * B2;
-          const float t = 1.0f - nn / dd;
-          if (t >= 0.0f && t <= 1.0f) {   // torch.clamp passes the gradient on the closed interval
-            // d(ssim) = -1/2 d(n/d);  d(n/d) = dn/d - n dd/d^2
-            const float gs = up * (0.85f / 3.0f) * (-0.5f);
-            const float dn_mu = 2.0f * mu_y[c] * (A2 - A1), dn_xy = 2.0f * A1;
-            const float dd_mu = 2.0f * s.mu_x * (B2 - B1), dd_xx = B1;
-            const float inv_d = 1.0f / dd, n_d2 = nn * inv_d * inv_d;
-            k_mu = gs * (dn_mu * inv_d - n_d2 * dd_mu);
-            k_xy = gs * (dn_xy * inv_d);
-            k_xx = gs * (-n_d2 * dd_xx);
-          }
-          const float df = x - y[c];
-          g_l1 = up * (0.15f / 3.0f) * (df > 0.0f ? 1.0f : (df < 0.0f ? -1.0f : 0.0f));
+          k = ssim_coef(s.mu_x, s.gxx, s.gxy, mu_y[c], gyy[c], up);
+          g_l1 = up * (0.15f / 3.0f) * sign0(x - y[c]);
         }
-        if (act) pl[6][ctr] = k_mu, pl[7][ctr] = k_xx, pl[8][ctr] = k_xy;
+        if (act) pl[6][ctr] = k.k_mu, pl[7][ctr] = k.k_xx, pl[8][ctr] = k.k_xy;
         wave_lds_fence();
         const float t_mu = gauss9(pl[6], ctr, ld), t_xx = gauss9(pl[7], ctr, ld), t_xy = gauss9(pl[8], ctr, ld);
         wave_lds_fence();
@@ -215,8 +177,8 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const P p) {
   float eas = 0.0f;
   if (p.has_eas) {
     const float dep = act ? p.depth[ray] : 1.0f;
-    const float dcl = fminf(fmaxf(dep, 1e-3f), 80.0f);
-    const float d = act ? 1.0f / dcl : 0.0f;
+    const float d_any = inv_depth(dep);      // (in front of the select: inside its arm the compiler schedules the kernel differently)
+    const float d = act ? d_any : 0.0f;
     const float m = wave_sum(d) / (float)area;
     const float dn = d / m;
     const float keep_e = keep;
@@ -234,18 +196,16 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(const P p) {
     eas = (fabsf(ex) * wx + fabsf(ey) * wy) * keep_e;
     if (p.g_depth) {
       // u_p = d (sum eas) / d dn_p: this pixel's own edges and the edges of its left / upper neighbour
-      const float sgx = (ex > 0.0f ? 1.0f : (ex < 0.0f ? -1.0f : 0.0f)) * wx * keep_e;
-      const float sgy = (ey > 0.0f ? 1.0f : (ey < 0.0f ? -1.0f : 0.0f)) * wy * keep_e;
+      const float sgx = sign0(ex) * wx * keep_e;
+      const float sgy = sign0(ey) * wy * keep_e;
       const float from_l = __shfl_up(sgx, 1, 64), from_u = __shfl_up(sgy, pw, 64);
       float u = sgx + sgy;
       if (act && lx > 0) u -= from_l;
       if (act && ly > 0) u -= from_u;
       if (!act) u = 0.0f;
-      // dn_p = d_p / m, m = mean d:  d/d d_j = u_j / m - (sum_p u_p d_p) / (m^2 N)
-      const float sud = wave_sum(u * d);
-      const float gd = u / m - sud / (m * m * (float)area);
-      const float g_dep = (dep >= 1e-3f && dep <= 80.0f) ? -gd / (dcl * dcl) : 0.0f;
-      if (act) p.g_depth[ray] = g_dep * p.s_eas;
+      const float sud = wave_sum(u * d);      // sum_p u_p d_p
+      const float g_dep = depth_grad(u, m, sud, area, dep, p.s_eas);
+      if (act) p.g_depth[ray] = g_dep;
     }
   } else if (p.g_depth && act) {
     p.g_depth[ray] = 0.0f;

@@ -1,15 +1,16 @@
 // bts_loss_pixel.hip -- the PER-PIXEL criteria of ReconstructionLoss (models/bts/model/loss.py:43-293): criterion l1 / l2, with or
 // without median thresholding, under any of the four invalid-ray policies (none, strict, weight_guided, weight_guided_diverse), plus the
-// edge-aware smoothness term of bts_loss_tiled.hip (read its header: the un-normalised edges, the patch's mean inverse depth m,
-// g_depth = s (u_p / m - S / (m^2 N)) d clamp / d depth, the closed-interval clamp gradient, sign(0) = 0).  Everything is memory-bound,
+// edge-aware smoothness term of bts_loss_tiled.hip (its header has the scheme: the un-normalised edges, the patch's mean inverse depth
+// m; the arithmetic both files call is bts_loss_device.h's: inv_depth, edge_term, edge_u_own, depth_grad with the closed-interval clamp
+// gradient, sign(0) = 0).  Everything is memory-bound,
 // a few bytes per ray and pass: thread = ray, rows read as they lie.  Launches on one stream (a kernel boundary is the only hand-over
 // between work-groups):
-//   err          keep flag per ray (the policies of bts_loss_tiled.hip's ray_invalid in the same order of sums; diverse: diverse_flag
-//                below), e[ray, c] = min_v crit(rgb[ray, v, c] - gt[ray, c]) * keep -> workspace; per work-group the sum of e and the
+//   err          keep flag per ray (bts_loss_device.h's ray_invalid, with the diverse policy and its diverse_flag),
+//                e[ray, c] = min_v crit(rgb[ray, v, c] - gt[ray, c]) * keep -> workspace; per work-group the sum of e and the
 //                invalid rays; with median the histogram of bits 31..21 of e's bit pattern (e >= 0: pattern order = value order);
 //                without median the gradient, whose normaliser 1 / (3 B) is known up front
 //   hist<1>, <2> median only: bits 20..10 of the e that share the wanted 11 bits, then bits 9..0 of those that share 22 -- the exact radix
-//                selection of bts_depth_metrics.hip, per batch sample, rank (N - 1) / 2 = torch's LOWER median
+//                selection bts_depth_metrics.hip runs (bts_loss_device.h: select_bin), per batch sample, rank (N - 1) / 2 = torch's LOWER median
 //   kept         median only: thr[sample] from the last histogram; per work-group the sum and the number of e <= thr (ties all kept)
 //   edges, patch smoothness in bts_loss_tiled.hip's geometry and order of sums: per ray the un-normalised edges and u_p, per 16 x 16 tile
 //                their sums; per patch m, S and S / m -- bit for bit that kernel's
@@ -23,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bts_host.h"
+#include "bts_loss_device.h"
 
 namespace bts {
 
@@ -30,7 +32,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kBins = 2048;
-constexpr int kTile = 16;                   // the smoothness passes' tile side
 constexpr int kHistSample = 3 * kBins;      // three radix passes per batch sample
 constexpr int kStateSample = 8;             // [0, 1] prefix and rank after pass 0's histogram, [4, 5] after pass 1's
 
@@ -77,68 +78,6 @@ struct PixelParamsThr : PixelParams {
   const float* thresh;          // (B)
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ float sign0(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
-
-// weight_guided_diverse per (ray, view), loss.py:109-118: (sum_k invalid w > .9) | (mean_c std_k(rgb_samps) < .01); the unbiased std
-// (K - 1) in fp32, the mean first, then the squared deviations, k ascending; K == 1: 0 / 0 = NaN and the comparison is false
-__device__ __forceinline__ bool diverse_flag(const float* __restrict__ rgb_samps, const float* __restrict__ weights,
-                                             const float* __restrict__ invalid, long ray, int v, int nv, int K) {
-  float s = 0.0f;
-  for (int k = 0; k < K; ++k) s += invalid[(ray * K + k) * nv + v] * weights[ray * K + k];
-  float sd = 0.0f;
-  const long stride = (long)nv * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float* x = rgb_samps + (ray * K * nv + v) * 3 + c;
-    float m = 0.0f;
-    for (int k = 0; k < K; ++k) m += x[k * stride];
-    m = m / (float)K;
-    float q = 0.0f;
-    for (int k = 0; k < K; ++k) {
-      const float d = x[k * stride] - m;
-      q += d * d;
-    }
-    sd += sqrtf(q / (float)(K - 1));
-  }
-  return (s > 0.9f) || (sd / 3.0f < 0.01f);
-}
-
-// invalid ray?  Policies 0-2: bts_loss_tiled.hip's ray_invalid (same order of sums, same comparisons); 3: every view's diverse flag
-__device__ __forceinline__ bool ray_invalid(const PixelParams& p, long ray) {
-  if (p.policy == 0) return false;
-  const int nv = p.nv, K = p.K;
-  bool all_v = true;
-  for (int v = 0; v < nv; ++v) {
-    if (p.policy == 3) {
-      all_v = all_v && diverse_flag(p.rgb_samps, p.weights, p.invalid, ray, v, nv, K);
-    } else if (p.policy == 2 && p.invalid_wsum) {
-      all_v = all_v && (p.invalid_wsum[ray * nv + v] > 0.9f);
-    } else if (p.policy == 1 && p.invalid_any) {
-      all_v = all_v && (p.invalid_any[ray * nv + v] > 0.5f);
-    } else if (p.policy == 2) {
-      float s = 0.0f;
-      for (int k = 0; k < K; ++k) s += p.invalid[(ray * K + k) * nv + v] * p.weights[ray * K + k];
-      all_v = all_v && (s > 0.9f);
-    } else {
-      bool any_k = false;
-      for (int k = 0; k < K; ++k) any_k = any_k || (p.invalid[(ray * K + k) * nv + v] > 0.5f);
-      all_v = all_v && any_k;
-    }
-  }
-  return all_v;
-}
-
 __device__ __forceinline__ float crit_of(int crit, float d) { return crit == 1 ? fabsf(d) : d * d; }
 
 // d (norm * sum of the kept e) / d rgb of one ray: per channel the views that attain the minimum share the gradient equally (amin)
@@ -165,7 +104,7 @@ __device__ __forceinline__ void write_grad(const P& p, long ray, float keep, flo
     const float t = p.thresh[ray];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float f = emin[c] < t ? 1.0f : (emin[c] > t ? 0.0f : 0.5f);      // torch.min(e, thresh): a tie splits the gradient
+      const float f = min_grad_factor(emin[c], t);
       coef[c] = (keep != 0.0f && fminf(emin[c], t) * keep <= thr) ? norm / ties[c] * f : 0.0f;
     }
   } else {
@@ -235,7 +174,7 @@ __global__ __launch_bounds__(kThreads) void pixel_err_kernel(const P p) {
   unsigned inv = 0u;
   if (r.act) {
     const long ray = r.ray;
-    const bool bad = ray_invalid(p, ray);
+    const bool bad = ray_invalid<false, true>(p, ray);
     const float keep = bad ? 0.0f : 1.0f;
     p.keep[ray] = bad ? 0 : 1;
     inv = bad ? 1u : 0u;
@@ -266,42 +205,6 @@ __global__ __launch_bounds__(kThreads) void pixel_err_kernel(const P p) {
   if (p.median) flush_hist(s_hist, p.hist + (size_t)r.sample * kHistSample);     // (block_sum's barriers are behind the atomics)
 }
 
-// The bin of `hist` (2 048 bins) that holds the element of rank `rank` (0-based) and the rank inside that bin; median: rank = (total - 1) / 2
-// of the histogram's own total.  Every lane takes eight consecutive bins, the work-group scans the 256 sums (bts_depth_metrics.hip's
-// select_bin).  out: bin, rank inside; both 0 when rank >= total.  All 256 lanes call this; s_scan holds 256 words.
-__device__ void select_bin(const unsigned* __restrict__ hist, int median, unsigned rank, unsigned* s_scan, unsigned* out) {
-  const int t = threadIdx.x;
-  const uint4 lo = reinterpret_cast<const uint4*>(hist)[t * 2], hi = reinterpret_cast<const uint4*>(hist)[t * 2 + 1];
-  const unsigned h[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  unsigned local = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) local += h[k];
-  s_scan[t] = local;
-  __syncthreads();
-  for (int o = 1; o < kThreads; o <<= 1) {
-    const unsigned v = t >= o ? s_scan[t - o] : 0u;
-    __syncthreads();
-    s_scan[t] += v;
-    __syncthreads();
-  }
-  const unsigned total = s_scan[kThreads - 1], incl = s_scan[t], excl = incl - local;
-  if (median) rank = total ? (total - 1) / 2 : 0u;
-  if (t == 0 && rank >= total) out[0] = 0u, out[1] = 0u;
-  if (rank >= excl && rank < incl) {   // one lane, when rank < total
-    unsigned r = rank - excl, rem = 0u;
-    int bin = -1;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (bin < 0) {
-        if (r < h[k]) bin = k, rem = r;
-        else r -= h[k];
-      }
-    }
-    out[0] = (unsigned)(t * 8 + bin), out[1] = rem;
-  }
-  __syncthreads();
-}
-
 // radix passes 1 and 2 of a sample's median.  What a work-group notes down (the prefix and the rank inside it) is read by the NEXT launch only
 template <int PASS>
 __global__ __launch_bounds__(kThreads) void pixel_hist_kernel(const PixelParams p) {
@@ -314,11 +217,11 @@ __global__ __launch_bounds__(kThreads) void pixel_hist_kernel(const PixelParams 
   for (int i = threadIdx.x; i < kBins; i += kThreads) s_hist[i] = 0u;
   unsigned want;
   if (PASS == 1) {
-    select_bin(hist_s, 1, 0u, s_scan, s_sel);
+    select_bin<false>(hist_s, 1, 0u, s_scan, s_sel);
     want = s_sel[0];
     if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[0] = want, state_s[1] = s_sel[1];
   } else {
-    select_bin(hist_s + kBins, 0, state_s[1], s_scan, s_sel);
+    select_bin<false>(hist_s + kBins, 0, state_s[1], s_scan, s_sel);
     want = (state_s[0] << 11) | s_sel[0];
     if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[4] = want, state_s[5] = s_sel[1];
   }
@@ -346,7 +249,7 @@ __global__ __launch_bounds__(kThreads) void pixel_kept_kernel(const PixelParams 
   __shared__ unsigned s_u[4];
   const RayPos r = ray_pos(p);
   const unsigned* state_s = p.state + (size_t)r.sample * kStateSample;
-  select_bin(p.hist + (size_t)r.sample * kHistSample + 2 * kBins, 0, state_s[5], s_scan, s_sel);
+  select_bin<false>(p.hist + (size_t)r.sample * kHistSample + 2 * kBins, 0, state_s[5], s_scan, s_sel);
   const float thr = __uint_as_float((state_s[4] << 10) | s_sel[0]);
   if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) {
     p.thr[r.sample] = thr;
@@ -369,7 +272,8 @@ __global__ __launch_bounds__(kThreads) void pixel_kept_kernel(const PixelParams 
 // smoothness (loss.py:21-40, masked as in :252-254) on the un-normalised inverse depth: bts_loss_tiled.hip's pass 1 per pixel, the
 // neighbours read from memory.  The GEOMETRY is that kernel's too -- a work-group per 16 x 16 tile, thread = pixel, butterfly per wave,
 // the four waves in order, then (pixel_patch_kernel) its pass 2 -- so that m, S, the per-patch term and g_depth are the tiled kernel's bit
-// for bit (tests/test_gpu_loss_pixel.py)
+// for bit (tests/test_gpu_loss_pixel.py).  The edges' sum and u_p's own part are bts_loss_device.h's; the weights and the left / upper
+// neighbours' part stay written out: behind a function their loads come in another order and the kernel's instructions change
 __global__ __launch_bounds__(kThreads) void pixel_edges_kernel(const PixelParams p) {
   __shared__ float s_red[4][2];
   const int tid = threadIdx.x;
@@ -382,7 +286,7 @@ __global__ __launch_bounds__(kThreads) void pixel_edges_kernel(const PixelParams
     const int pw = p.pw, ph = p.ph;
     const long ray = patch * p.area + (long)py * pw + px;
     const float keep = (p.policy == 0 || p.keep[ray]) ? 1.0f : 0.0f;
-    d = 1.0f / fminf(fmaxf(p.depth[ray], 1e-3f), 80.0f);
+    d = inv_depth(p.depth[ray]);
     const float* y = p.rgb_gt + ray * 3;
     const bool has_r = px + 1 < pw, has_b = py + 1 < ph;
     float wx = 0.0f, wy = 0.0f, ex = 0.0f, ey = 0.0f;
@@ -391,32 +295,32 @@ __global__ __launch_bounds__(kThreads) void pixel_edges_kernel(const PixelParams
 #pragma unroll
       for (int c = 0; c < 3; ++c) idx += fabsf(y[c] - y[3 + c]);
       wx = expf(-(idx / 3.0f));
-      ex = d - 1.0f / fminf(fmaxf(p.depth[ray + 1], 1e-3f), 80.0f);
+      ex = d - inv_depth(p.depth[ray + 1]);
     }
     if (has_b) {
       float idy = 0.0f;
 #pragma unroll
       for (int c = 0; c < 3; ++c) idy += fabsf(y[c] - y[3 * pw + c]);
       wy = expf(-(idy / 3.0f));
-      ey = d - 1.0f / fminf(fmaxf(p.depth[ray + pw], 1e-3f), 80.0f);
+      ey = d - inv_depth(p.depth[ray + pw]);
     }
-    eas = (fabsf(ex) * wx + fabsf(ey) * wy) * keep;
+    eas = edge_term(ex, ey, wx, wy, keep);
     if (p.g_depth) {
       // u_p: this pixel's own edges and the edges its left / upper neighbour owns
-      float u = sign0(ex) * wx * keep + sign0(ey) * wy * keep;
+      float u = edge_u_own(ex, ey, wx, wy, keep);
       if (px > 0) {
         float il = 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) il += fabsf(y[c - 3] - y[c]);
         const float kl = (p.policy == 0 || p.keep[ray - 1]) ? 1.0f : 0.0f;
-        u -= sign0(1.0f / fminf(fmaxf(p.depth[ray - 1], 1e-3f), 80.0f) - d) * expf(-(il / 3.0f)) * kl;
+        u -= sign0(inv_depth(p.depth[ray - 1]) - d) * expf(-(il / 3.0f)) * kl;
       }
       if (py > 0) {
         float iu = 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) iu += fabsf(y[c - 3 * pw] - y[c]);
         const float ku = (p.policy == 0 || p.keep[ray - pw]) ? 1.0f : 0.0f;
-        u -= sign0(1.0f / fminf(fmaxf(p.depth[ray - pw], 1e-3f), 80.0f) - d) * expf(-(iu / 3.0f)) * ku;
+        u -= sign0(inv_depth(p.depth[ray - pw]) - d) * expf(-(iu / 3.0f)) * ku;
       }
       p.u[ray] = u;
     }
@@ -429,7 +333,8 @@ __global__ __launch_bounds__(kThreads) void pixel_edges_kernel(const PixelParams
                                            ((s_red[0][1] + s_red[1][1]) + s_red[2][1]) + s_red[3][1]);
 }
 
-// one wave per patch: lane l takes tiles l, l + 64, ... in order, then the butterfly (bts_loss_tiled.hip's pass 2)
+// one wave per patch: lane l takes tiles l, l + 64, ... in order, then the butterfly (bts_loss_tiled.hip's pass 2, written out in both:
+// as a shared function the loop is laid out on its own before it is inlined, which moves both kernels' instruction streams)
 __global__ __launch_bounds__(64) void pixel_patch_kernel(const PixelParams p) {
   const int lane = threadIdx.x;
   for (long patch = blockIdx.x; patch < p.n_patches; patch += gridDim.x) {
@@ -486,13 +391,10 @@ __global__ __launch_bounds__(kThreads) void pixel_gdepth_kernel(const PixelParam
   if (ray >= p.B) return;
   float g = 0.0f;
   if (p.has_eas) {
-    // dn_p = d_p / m, m = mean d:  d E / d d_j = u_j / m - (sum_p u_p d_p) / (m^2 N), and sum_p u_p d_p = the un-normalised edge sum
-    const float4 st = p.patch_stats[ray / p.area];
-    const float m = st.x, S = st.y;
+    const float u = p.u[ray];
+    const float4 st = p.patch_stats[ray / p.area];      // m, S = sum_p u_p d_p = the un-normalised edge sum
     const float dep = p.depth[ray];
-    const float dcl = fminf(fmaxf(dep, 1e-3f), 80.0f);
-    const float gd = p.u[ray] / m - S / (m * m * (float)p.area);
-    g = ((dep >= 1e-3f && dep <= 80.0f) ? -gd / (dcl * dcl) : 0.0f) * p.s_eas;
+    g = depth_grad(u, st.x, st.y, p.area, dep, p.s_eas);
   }
   p.g_depth[ray] = g;
 }
@@ -505,9 +407,6 @@ __global__ __launch_bounds__(kThreads) void diverse_flags_kernel(const float* __
   const long ray = i / nv;
   flags[i] = diverse_flag(rgb_samps, weights, invalid, ray, (int)(i - ray * nv), nv, K) ? 1.0f : 0.0f;
 }
-
-constexpr size_t kAlign = 256;
-inline size_t up256(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
 
 struct Geom {
   long Bs, n_blocks, n_patches, n_tiles;
@@ -526,17 +425,31 @@ inline Geom geom_of(long B, int n, int ph, int pw) {
   return g;
 }
 
+// THE layout of bts_pixel_loss's workspace: e, keep flags, histograms, selection state, thresholds, three partials per work-group, u,
+// tile partials, patch statistics, the final words
+inline void pixel_layout(Carver& w, PixelParams& p, size_t B, size_t n, const Geom& g) {
+  p.e = w.take<float>(B * 3);
+  p.keep = w.take<unsigned char>(B);
+  p.hist = w.take<unsigned>(n * kHistSample);
+  p.state = w.take<unsigned>(n * kStateSample);
+  p.thr = w.take<float>(n);
+  p.blk_sum = w.take<float>((size_t)g.n_blocks);
+  p.blk_cnt = w.take<unsigned>((size_t)g.n_blocks);
+  p.blk_inv = w.take<unsigned>((size_t)g.n_blocks);
+  p.u = w.take<float>(B);
+  p.tile_parts = w.take<float2>((size_t)g.n_tiles);
+  p.patch_stats = w.take<float4>((size_t)g.n_patches);
+  p.fin = w.take<float>(4);
+}
+
 }  // namespace
 
-// bytes of bts_pixel_loss's workspace: e, keep flags, histograms, selection state, thresholds, three partials per work-group, u, tile
-// partials, patch statistics, the final words
 size_t pixel_loss_bytes(long B, int n, int ph, int pw) {
   if (B <= 0 || n <= 0 || ph <= 0 || pw <= 0 || (long)ph * pw > B) return 0;
-  const Geom g = geom_of(B, n, ph, pw);
-  return kAlign + up256((size_t)B * 3 * sizeof(float)) + up256((size_t)B) + up256((size_t)n * kHistSample * sizeof(unsigned)) +
-         up256((size_t)n * kStateSample * sizeof(unsigned)) + up256((size_t)n * sizeof(float)) + 3 * up256((size_t)g.n_blocks * sizeof(float)) +
-         up256((size_t)B * sizeof(float)) + up256((size_t)g.n_tiles * sizeof(float2)) + up256((size_t)g.n_patches * sizeof(float4)) +
-         up256(4 * sizeof(float));
+  Carver count(nullptr);
+  PixelParams p;
+  pixel_layout(count, p, (size_t)B, (size_t)n, geom_of(B, n, ph, pw));
+  return count.bytes();
 }
 
 int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, const float* thresh) {
@@ -553,19 +466,8 @@ int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, c
   const Geom g = geom_of(p.B, p.n, p.ph, p.pw);
   p.Bs = g.Bs, p.blocks_per_sample = g.blocks_per_sample, p.n_blocks = g.n_blocks, p.area = g.area, p.tiles_x = g.tiles_x, p.tiles = g.tiles;
   p.n_patches = g.n_patches, p.n_tiles = g.n_tiles;
-  char* w = (char*)(((uintptr_t)workspace + kAlign - 1) & ~(uintptr_t)(kAlign - 1));
-  p.e = (float*)w, w += up256((size_t)p.B * 3 * sizeof(float));
-  p.keep = (unsigned char*)w, w += up256((size_t)p.B);
-  p.hist = (unsigned*)w, w += up256((size_t)p.n * kHistSample * sizeof(unsigned));
-  p.state = (unsigned*)w, w += up256((size_t)p.n * kStateSample * sizeof(unsigned));
-  p.thr = (float*)w, w += up256((size_t)p.n * sizeof(float));
-  p.blk_sum = (float*)w, w += up256((size_t)g.n_blocks * sizeof(float));
-  p.blk_cnt = (unsigned*)w, w += up256((size_t)g.n_blocks * sizeof(float));
-  p.blk_inv = (unsigned*)w, w += up256((size_t)g.n_blocks * sizeof(float));
-  p.u = (float*)w, w += up256((size_t)p.B * sizeof(float));
-  p.tile_parts = (float2*)w, w += up256((size_t)g.n_tiles * sizeof(float2));
-  p.patch_stats = (float4*)w, w += up256((size_t)g.n_patches * sizeof(float4));
-  p.fin = (float*)w;
+  Carver carve(workspace);
+  pixel_layout(carve, p, (size_t)p.B, (size_t)p.n, g);
   const unsigned grid = (unsigned)g.n_blocks;
   if (p.median && hipMemsetAsync(p.hist, 0, (size_t)p.n * kHistSample * sizeof(unsigned), s) != hipSuccess) {
     set_error("%s: clearing the histograms failed", "bts_pixel_loss");

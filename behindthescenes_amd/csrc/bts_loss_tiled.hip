@@ -1,10 +1,11 @@
 // bts_loss_tiled.hip -- the photometric loss of bts_loss.hip for patches of ANY size (the trainer's default 16 x 16 patch, sample_mode
 // "image", the validation loss on whole 192 x 640 frames): a patch is cut into 16 x 16 tiles, one work-group of 256 threads per tile,
-// thread = pixel.  The arithmetic per pixel is that of bts_loss.hip (read its header: formulas, closed-interval clamp gradient,
-// sign(0) = 0); what is new is that 3x3 neighbourhoods cross tile borders and that the smoothness term needs the PATCH's mean inverse
+// thread = pixel.  The arithmetic per pixel is that of bts_loss.hip, through the functions both call (bts_loss_device.h: the SSIM term
+// and its backward coefficients with the closed-interval clamp gradient, sign(0) = 0, the depth gradient; bts_loss.hip's header has the
+// formulas); what is new is that 3x3 neighbourhoods cross tile borders and that the smoothness term needs the PATCH's mean inverse
 // depth.  Up to four launches on one stream (a kernel boundary is the only hand-over between work-groups; no float atomics, every sum
 // is a fixed-order sum of partials, reruns are bit-identical):
-//   keep, per ray      the invalid-ray policy once per ray (thread = ray, the samples in bts_loss.hip's order; 16-byte loads of the
+//   keep, per ray      the invalid-ray policy once per ray (thread = ray; bts_loss_device.h's ray_invalid with 16-byte loads of the
 //                      weights / invalid rows when nv = 1 and K is a multiple of 4: the validation frame) -> one byte per ray; not
 //                      launched with policy none
 //   pass 1, per tile   stages ground truth, that keep flag and d = 1 / clamp(depth) of the 18 x 18 halo in LDS, then one view's colours at a
@@ -24,13 +25,13 @@
 #include <hip/hip_runtime.h>
 
 #include "bts_host.h"
+#include "bts_loss_device.h"
 
 namespace bts {
 
-
 namespace {
 
-constexpr int kTile = 16;              // interior pixels per tile side (256 threads, thread = pixel)
+// (kTile = 16, bts_loss_device.h: interior pixels per tile side -- 256 threads, thread = pixel)
 constexpr int kLd = kTile + 2;         // row length of a plane with its one-pixel halo
 constexpr int kHalo = kLd * kLd;       // 324
 
@@ -68,25 +69,7 @@ struct TiledParamsThr : TiledParams {
   float* fthr;             // workspace (B): d min(e, thresh) / d e
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-constexpr float kGa = 0.0947f, kGb = 0.1183f, kGc = 0.1478f;   // layers.py:92-101 window
-
-// Gaussian-weighted sums over the 3x3 neighbourhood of `ctr` in zero-bordered planes, in bts_loss.hip's order of additions
-__device__ __forceinline__ float gauss9(const float* pl, int ctr) {
-  const float* r0 = pl + ctr - kLd;
-  const float* r1 = pl + ctr;
-  const float* r2 = pl + ctr + kLd;
-  float s = kGa * r0[-1];
-  s += kGb * r0[0], s += kGa * r0[1];
-  s += kGb * r1[-1], s += kGc * r1[0], s += kGb * r1[1];
-  s += kGa * r2[-1], s += kGb * r2[0], s += kGa * r2[1];
-  return s;
-}
+// gauss9 (bts_loss_device.h) of the product of two planes, in its order of additions
 __device__ __forceinline__ float gauss9_prod(const float* pa, const float* pb, int ctr) {
   const float* a0 = pa + ctr - kLd;
   const float* a1 = pa + ctr;
@@ -112,49 +95,6 @@ __device__ __forceinline__ float gauss9_masked(const float* pl, int ctr, unsigne
   return s;
 }
 
-__device__ __forceinline__ float sign0(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
-
-// invalid ray?  (loss.py:100-118; bts_loss.hip)
-__device__ __forceinline__ bool ray_invalid(const TiledParams& p, long ray) {
-  if (p.policy == 0) return false;
-  const int nv = p.nv, K = p.K;
-  if (p.vec4 && !(p.policy == 2 ? p.invalid_wsum : p.invalid_any)) {      // one view: the rows of K floats as 16-byte loads, same order of sums
-    const float4* i4 = reinterpret_cast<const float4*>(p.invalid + ray * K);
-    if (p.policy == 2) {
-      const float4* w4 = reinterpret_cast<const float4*>(p.weights + ray * K);
-      float s = 0.0f;
-      for (int k = 0; k < K / 4; ++k) {
-        const float4 i = i4[k], w = w4[k];
-        s += i.x * w.x, s += i.y * w.y, s += i.z * w.z, s += i.w * w.w;
-      }
-      return s > 0.9f;
-    }
-    bool any_k = false;
-    for (int k = 0; k < K / 4; ++k) {
-      const float4 i = i4[k];
-      any_k = any_k || (i.x > 0.5f) || (i.y > 0.5f) || (i.z > 0.5f) || (i.w > 0.5f);
-    }
-    return any_k;
-  }
-  bool all_v = true;
-  for (int v = 0; v < nv; ++v) {
-    if (p.policy == 2 && p.invalid_wsum) {
-      all_v = all_v && (p.invalid_wsum[ray * nv + v] > 0.9f);
-    } else if (p.policy == 1 && p.invalid_any) {
-      all_v = all_v && (p.invalid_any[ray * nv + v] > 0.5f);
-    } else if (p.policy == 2) {
-      float s = 0.0f;
-      for (int k = 0; k < K; ++k) s += p.invalid[(ray * K + k) * nv + v] * p.weights[ray * K + k];
-      all_v = all_v && (s > 0.9f);
-    } else {
-      bool any_k = false;
-      for (int k = 0; k < K; ++k) any_k = any_k || (p.invalid[(ray * K + k) * nv + v] > 0.5f);
-      all_v = all_v && any_k;
-    }
-  }
-  return all_v;
-}
-
 // which tile of which patch a work-group takes (1-D grid over n_patches x tiles; beyond kMaxGrid work-groups each takes several)
 constexpr long kMaxGrid = 1L << 20;
 struct TilePos {
@@ -172,7 +112,7 @@ __device__ __forceinline__ TilePos tile_pos(const TiledParams& p, long blk) {
 }
 
 __global__ __launch_bounds__(256) void loss_tiled_keep(const TiledParams p) {
-  for (long ray = blockIdx.x * 256L + threadIdx.x; ray < p.B; ray += gridDim.x * 256L) p.keep[ray] = ray_invalid(p, ray) ? 0 : 1;
+  for (long ray = blockIdx.x * 256L + threadIdx.x; ray < p.B; ray += gridDim.x * 256L) p.keep[ray] = ray_invalid<true, false>(p, ray) ? 0 : 1;
 }
 
 template <class P>
@@ -195,7 +135,7 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
       const long ray = tp.base + (long)py * pw + px;
       y0 = p.rgb_gt[ray * 3], y1 = p.rgb_gt[ray * 3 + 1], y2 = p.rgb_gt[ray * 3 + 2];
       k = (p.policy == 0 || p.keep[ray]) ? 1.0f : 0.0f;
-      if (p.has_eas) d = 1.0f / fminf(fmaxf(p.depth[ray], 1e-3f), 80.0f);
+      if (p.has_eas) d = inv_depth(p.depth[ray]);
     }
     sY[0][i] = y0, sY[1][i] = y1, sY[2][i] = y2, sD[i] = d, sK[i] = k;
   }
@@ -212,11 +152,10 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     y[c] = sY[c][ctr];
-    mu_y[c] = gauss9(sY[c], ctr);
+    mu_y[c] = gauss9(sY[c], ctr, kLd);
     gyy[c] = gauss9_prod(sY[c], sY[c], ctr);
   }
 
-  constexpr float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
   // ---- e_v, the minimum over the views (loss.py:152-153); the statistics of v* stay in registers for the coefficients
   float e_min = 0.0f;
   int v_star = 0;
@@ -239,14 +178,10 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       x[c] = sX[c][ctr];
-      mu[c] = gauss9(sX[c], ctr);
+      mu[c] = gauss9(sX[c], ctr, kLd);
       gxx[c] = gauss9_prod(sX[c], sX[c], ctr);
       gxy[c] = gauss9_prod(sX[c], sY[c], ctr);
-      const float mxx = mu[c] * mu[c], myy = mu_y[c] * mu_y[c], mxy = mu[c] * mu_y[c];
-      const float sx = gxx[c] - mxx, sy = gyy[c] - myy, sxy = gxy[c] - mxy;
-      const float nn = (2.0f * mxy + c1) * (2.0f * sxy + c2);
-      const float dd = (mxx + myy + c1) * (sx + sy + c2);
-      ss += fminf(fmaxf(1.0f - nn / dd, 0.0f), 1.0f) / 2.0f;
+      ss += ssim_term(mu[c], gxx[c], gxy[c], mu_y[c], gyy[c]);
       l1 += fabsf(x[c] - y[c]);
     }
     const float e = 0.85f * (ss / 3.0f) + 0.15f * (l1 / 3.0f);
@@ -259,7 +194,7 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
   float up = keep * p.s_rgb;             // d loss / d e_{v*}(this pixel)
   if constexpr (kThr) {
     const float t = act ? p.thresh[ray] : 0.0f;
-    const float f = e_min < t ? 1.0f : (e_min > t ? 0.0f : 0.5f);      // torch.min(e, thresh): a tie splits the gradient
+    const float f = min_grad_factor(e_min, t);
     up = up * f;
     e_min = fminf(e_min, t);
     if (p.g_rgb && act) p.fthr[ray] = f;
@@ -272,26 +207,10 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
     p.vstar[ray] = live ? v_star : -1;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float k_mu = 0.0f, k_xx = 0.0f, k_xy = 0.0f;
-      if (live) {
-        const float mxx = b_mu[c] * b_mu[c], myy = mu_y[c] * mu_y[c], mxy = b_mu[c] * mu_y[c];
-        const float sx = b_gxx[c] - mxx, sy = gyy[c] - myy, sxy = b_gxy[c] - mxy;
-        const float A1 = 2.0f * mxy + c1, A2 = 2.0f * sxy + c2, B1 = mxx + myy + c1, B2 = sx + sy + c2;
-        const float nn = A1 * A2, dd = B1 * B2;
-        const float t = 1.0f - nn / dd;
-        if (t >= 0.0f && t <= 1.0f) {   // torch.clamp passes the gradient on the closed interval
-          const float gs = up * (0.85f / 3.0f) * (-0.5f);
-          const float dn_mu = 2.0f * mu_y[c] * (A2 - A1), dn_xy = 2.0f * A1;
-          const float dd_mu = 2.0f * b_mu[c] * (B2 - B1), dd_xx = B1;
-          const float inv_d = 1.0f / dd, n_d2 = nn * inv_d * inv_d;
-          k_mu = gs * (dn_mu * inv_d - n_d2 * dd_mu);
-          k_xy = gs * (dn_xy * inv_d);
-          k_xx = gs * (-n_d2 * dd_xx);
-        }
-      }
-      p.coef[(long)(c * 3 + 0) * p.B + ray] = k_mu;
-      p.coef[(long)(c * 3 + 1) * p.B + ray] = k_xx;
-      p.coef[(long)(c * 3 + 2) * p.B + ray] = k_xy;
+      const SsimCoef k = live ? ssim_coef(b_mu[c], b_gxx[c], b_gxy[c], mu_y[c], gyy[c], up) : SsimCoef{0.0f, 0.0f, 0.0f};
+      p.coef[(long)(c * 3 + 0) * p.B + ray] = k.k_mu;
+      p.coef[(long)(c * 3 + 1) * p.B + ray] = k.k_xx;
+      p.coef[(long)(c * 3 + 2) * p.B + ray] = k.k_xy;
     }
   }
 
@@ -308,10 +227,11 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
     }
     const float wx = has_r ? expf(-(idx / 3.0f)) : 0.0f, wy = has_b ? expf(-(idy / 3.0f)) : 0.0f;
     const float ex = d - sD[ctr + 1], ey = d - sD[ctr + kLd];
-    eas = (fabsf(ex) * wx + fabsf(ey) * wy) * keep;
+    eas = edge_term(ex, ey, wx, wy, keep);
     if (p.g_depth) {
-      // u_p: this pixel's own edges and the edges its left / upper neighbour owns
-      float u = sign0(ex) * wx * keep + sign0(ey) * wy * keep;
+      // u_p: this pixel's own edges and the edges its left / upper neighbour owns (those, like the weights above, are also
+      // pixel_edges_kernel's; written out in both: behind a function the neighbours' loads come in another order)
+      float u = edge_u_own(ex, ey, wx, wy, keep);
       if (px > 0) {
         float il = 0.0f;
 #pragma unroll
@@ -344,7 +264,7 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
   }
 }
 
-// one wave per patch
+// one wave per patch (the reduction is also pixel_patch_kernel's, bts_loss_pixel.hip: written out in both, see there)
 __global__ __launch_bounds__(64) void loss_tiled_pass2(const TiledParams p) {
   const int lane = threadIdx.x;
   for (long patch = blockIdx.x; patch < p.n_patches; patch += gridDim.x) {
@@ -434,32 +354,38 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_
   if (p.g_depth) {
     float g = 0.0f;
     if (p.has_eas) {
-      // dn_p = d_p / m, m = mean d:  d E / d d_j = u_j / m - (sum_p u_p d_p) / (m^2 N), and sum_p u_p d_p = the un-normalised edge sum
-      const float4 st = p.patch_stats[tp.patch];
-      const float m = st.x, S = st.y;
+      const float u = p.u[ray];
+      const float4 st = p.patch_stats[tp.patch];      // m, S = sum_p u_p d_p = the un-normalised edge sum
       const float dep = p.depth[ray];
-      const float dcl = fminf(fmaxf(dep, 1e-3f), 80.0f);
-      const float gd = p.u[ray] / m - S / (m * m * (float)((long)ph * pw));
-      g = ((dep >= 1e-3f && dep <= 80.0f) ? -gd / (dcl * dcl) : 0.0f) * p.s_eas;
+      g = depth_grad(u, st.x, st.y, (long)ph * pw, dep, p.s_eas);
     }
     p.g_depth[ray] = g;
   }
   }
 }
 
-constexpr size_t kAlign = 256;
-inline size_t up256(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
 inline long tiles_of(int ph, int pw) { return (long)((ph + kTile - 1) / kTile) * ((pw + kTile - 1) / kTile); }
+
+// THE layout of bts_photometric_loss_tiled's workspace: tile partials, patch statistics, v*, nine coefficient planes, u, keep flags and,
+// with the automasking bound, its gradient factors
+inline void tiled_layout(Carver& w, TiledParamsThr& p, size_t n_patches, size_t n_tiles, size_t B, bool with_thresh) {
+  p.tile_parts = w.take<float4>(n_tiles);
+  p.patch_stats = w.take<float4>(n_patches);
+  p.vstar = w.take<int>(B);
+  p.coef = w.take<float>(B * 9);
+  p.u = w.take<float>(B);
+  p.keep = w.take<unsigned char>(B);
+  p.fthr = with_thresh ? w.take<float>(B) : nullptr;
+}
 
 }  // namespace
 
-// bytes of bts_photometric_loss_tiled's workspace: tile partials, patch statistics, v*, nine coefficient planes, u, keep flags
 size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv, bool with_thresh) {
   if (n_patches < 0 || ph <= 0 || pw <= 0 || nv <= 0) return 0;
-  const size_t B = (size_t)n_patches * (size_t)ph * (size_t)pw;
-  const size_t nt = (size_t)n_patches * (size_t)tiles_of(ph, pw);
-  return kAlign + up256(nt * sizeof(float4)) + up256((size_t)n_patches * sizeof(float4)) + up256(B * sizeof(int)) + up256(B * 9 * sizeof(float)) +
-         up256(B * sizeof(float)) + up256(B) + (with_thresh ? up256(B * sizeof(float)) : 0);
+  Carver count(nullptr);
+  TiledParamsThr p;
+  tiled_layout(count, p, (size_t)n_patches, (size_t)n_patches * (size_t)tiles_of(ph, pw), (size_t)n_patches * (size_t)ph * (size_t)pw, with_thresh);
+  return count.bytes();
 }
 
 int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s, const float* thresh) {
@@ -474,14 +400,9 @@ int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream
   p.tiles = (int)tiles_of(p.ph, p.pw);
   p.B = (long)p.n_patches * p.ph * p.pw;
   const size_t nt = (size_t)p.n_patches * (size_t)p.tiles;
-  char* w = (char*)(((uintptr_t)workspace + kAlign - 1) & ~(uintptr_t)(kAlign - 1));
-  p.tile_parts = (float4*)w, w += up256(nt * sizeof(float4));
-  p.patch_stats = (float4*)w, w += up256((size_t)p.n_patches * sizeof(float4));
-  p.vstar = (int*)w, w += up256((size_t)p.B * sizeof(int));
-  p.coef = (float*)w, w += up256((size_t)p.B * 9 * sizeof(float));
-  p.u = (float*)w, w += up256((size_t)p.B * sizeof(float));
-  p.keep = (unsigned char*)w, w += up256((size_t)p.B);
-  p.thresh = thresh, p.fthr = thresh ? (float*)w : nullptr;
+  Carver carve(workspace);
+  tiled_layout(carve, p, (size_t)p.n_patches, nt, (size_t)p.B, thresh != nullptr);
+  p.thresh = thresh;
   const TiledParams& base = p;
   p.vec4 = p.nv == 1 && p.K > 0 && (p.K & 3) == 0 && ((uintptr_t)p.invalid & 15) == 0 && ((uintptr_t)p.weights & 15) == 0;
   const unsigned grid = (unsigned)((long)nt < kMaxGrid ? (long)nt : kMaxGrid);

@@ -135,6 +135,23 @@ def test_backward_workspace_is_what_the_passes_hand_each_other(lib):
     assert ws(kitti, 1, 3, 5) == a16((3 * 5 * 3 + 1) * 4 + 3 * 128 * 4) + slots(64)
 
 
+def test_loss_workspace_sizes_are_the_recorded_ones(lib):
+    """bts_photometric_loss_tiled[_automask]_workspace and bts_pixel_loss_workspace count the bytes with the layout function that
+    carves the pointers (csrc/bts_host.h: Carver).  The literals were printed by the library of the commit before that function
+    existed, where size and carving were two hand-kept lists: (n_patches, ph, pw, nv) on both sides of a 16 x 16 tile boundary and of
+    the 256-byte rounding, the pixel form with B = n_patches * ph * pw rays in n = 1 and 2 batch samples."""
+    recorded = {(1, 1, 1, 1): (1792, 2048, 27648, 51456),
+                (3, 8, 8, 2): (9472, 10240, 30208, 54784),
+                (2, 16, 16, 1): (23808, 25856, 35584, 60160),
+                (2, 17, 33, 4): (51712, 56320, 46336, 70912),
+                (1, 192, 640, 1): (5537792, 6029312, 2124800, 2149376)}
+    for (n_patches, ph, pw, nv), (tiled, tiled_automask, pixel_n1, pixel_n2) in recorded.items():
+        assert lib.bts_photometric_loss_tiled_workspace(n_patches, ph, pw, nv) == tiled
+        assert lib.bts_photometric_loss_tiled_automask_workspace(n_patches, ph, pw, nv) == tiled_automask
+        assert lib.bts_pixel_loss_workspace(n_patches * ph * pw, 1, ph, pw) == pixel_n1
+        assert lib.bts_pixel_loss_workspace(n_patches * ph * pw, 2, ph, pw) == pixel_n2
+
+
 def test_errors_are_codes_with_messages_never_exceptions(lib):
     assert lib.bts_render_fwd(None, None, None, None) == -1                       # BTS_E_INVALID
     assert b"NULL" in lib.bts_last_error()

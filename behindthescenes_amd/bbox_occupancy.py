@@ -10,8 +10,9 @@ import ctypes as C
 import torch
 
 from . import _lib, native
+from ._evalcommon import FusedOccupancy, occupancy_ratios, proj3 as _proj3
 from ._lib import BtsNativeError
-from .native import _ptr, _req, _stream
+from .native import _addr, _ptr, _req, _req_as, _stream
 
 M_MAX = _lib.BTS_BBOX_MAX_FACES
 # the ids KITTI-360's label table puts in category `flat`: road, sidewalk, parking, rail track (evaluator_3dbb.py:201)
@@ -59,17 +60,10 @@ def _req_boxes(vertices, faces, semantic_id, v_off, f_off, what):
     if B <= 0 or len(f_off) != B + 1:
         raise BtsNativeError(f"{what}: no boxes (none given, or every box is of a skipped category)")
     _req(vertices, "vertices", (v_off[B], 3))
-    if not isinstance(faces, torch.Tensor) or not faces.is_cuda or faces.dtype != torch.int32 or not faces.is_contiguous() \
-            or tuple(faces.shape) != (f_off[B], 3):
-        raise BtsNativeError(f"faces: expected a contiguous int32 GPU tensor of shape {(f_off[B], 3)}")
+    _req_as(faces, "faces", torch.int32, (f_off[B], 3))
     if semantic_id is not None:
         _req(semantic_id, "semantic_id", (B,))
     return B
-
-
-def _proj3(proj):
-    _req(proj, "proj")
-    return _req(proj.reshape(proj.shape[-2:])[:3, :3].contiguous(), "proj", (3, 3))
 
 
 def bbox_tables(vertices, faces, v_offsets, f_offsets, pose, proj, max_d=20):
@@ -97,9 +91,7 @@ def pseudo_depth(rays, grid, seg, tables, n_faces, active, semantic_id):
     seg = _req(seg.reshape(seg.shape[-2:]), "seg")
     B = tables.shape[0]
     _req(tables, "tables", (B, M_MAX, 5)), _req(semantic_id, "semantic_id", (B,))
-    if n_faces.dtype != torch.int32 or active.dtype != torch.uint8 or not n_faces.is_cuda or not active.is_cuda \
-            or tuple(n_faces.shape) != (B,) or tuple(active.shape) != (B,):
-        raise BtsNativeError("pseudo_depth: n_faces must be (B) int32 and active (B) uint8 on the GPU, as bbox_tables returns them")
+    _req_as(n_faces, "n_faces", torch.int32, (B,)), _req_as(active, "active", torch.uint8, (B,))      # as bbox_tables returns them
     out = torch.empty((ph, pw), device=rays.device, dtype=torch.float32)
     _lib.check(_lib.load().bts_bbox_pseudo_depth(_ptr(rays), ph, pw, _ptr(seg), seg.shape[0], seg.shape[1], _ptr(tables), _ptr(n_faces),
                                                  _ptr(active), _ptr(semantic_id), B, _ptr(out), _stream(rays)), "bts_bbox_pseudo_depth")
@@ -107,30 +99,12 @@ def pseudo_depth(rays, grid, seg, tables, n_faces, active, semantic_id):
 
 
 def metrics_from_counts(counts):
-    """The nine metrics of evaluator_3dbb.py:288-299 from the six cell counts of bts_bbox_occupancy_eval
-    ([V&P, V&!P, !V&O&P, !V&O&!P, !V&!O&P, !V&!O&!P]; a seventh entry is ignored) -- the ratios of lidar_occupancy.metrics_from_counts
-    under this evaluator's names.  Types as in the reference: Python floats where it calls .item(), 0-dim fp32 tensors (here on the CPU)
-    elsewhere; a mean over an empty selection is NaN, as torch's mean of an empty tensor."""
-    c = [int(v) for v in counts][:6]
-
-    def ratio(num, den):
-        return torch.tensor(float(num), dtype=torch.float32) / torch.tensor(float(den), dtype=torch.float32)
-
-    n = sum(c)
-    return {
-        "o_acc": ratio(c[1] + c[2] + c[5], n).item(),
-        "o_rec": ratio(c[2], c[2] + c[3]).item(),
-        "o_prec": ratio(c[2], c[0] + c[2] + c[4]).item(),
-        "no_nv_acc": ratio(c[2] + c[5], c[2] + c[3] + c[4] + c[5]).item(),
-        "no_nv_rec": ratio(c[5], c[4] + c[5]),
-        "no_nv_prec": ratio(c[5], c[3] + c[5]),
-        "no_nv_r": ratio(c[4] + c[5], n).item(),
-        "t_no_nv": float(c[4] + c[5]),
-        "t_no_nop_nv": torch.tensor(float(c[5]), dtype=torch.float32),
-    }
+    """The nine metrics of evaluator_3dbb.py:288-299 from the six cell counts of bts_bbox_occupancy_eval (a seventh entry is ignored):
+    _evalcommon.occupancy_ratios -- the ratios of lidar_occupancy.metrics_from_counts -- under this evaluator's names."""
+    return dict(zip(METRIC_KEYS, occupancy_ratios(counts)))
 
 
-class FusedBBoxOccupancyEval:
+class FusedBBoxOccupancyEval(FusedOccupancy):
     """BTSWrapper.forward of evaluator_3dbb.py around the render (:201-241, :253-299) in one library call.
 
         ev = FusedBBoxOccupancyEval(net)                   # an ENCODED behindthescenes_amd.BTSNet
@@ -143,25 +117,13 @@ class FusedBBoxOccupancyEval:
     the encoder view (projs[0, 0], poses[0, 0]).  Raises BtsNativeError when no box is active (the reference fails there too, :227)."""
 
     def __init__(self, net, x_range=(-4, 4), y_range=(0, 1), z_range=(20, 3), ppm=5, ppm_y=4, occ_threshold=0.5):
-        self.net = net
         self.occ_threshold, self.max_d = occ_threshold, z_range[0]
         grid, (self.xd, self.yd, self.zd) = get_pts(x_range, y_range, z_range, ppm, ppm_y)
-        self._q_cpu = grid.reshape(-1, 3).contiguous()
-        self._q = None
-
-    def q_pts(self, dev):
-        if self._q is None or self._q.device != dev:
-            self._q = self._q_cpu.to(dev)
-        return self._q
+        super().__init__(net, grid)
 
     def __call__(self, bboxes, seg, rays, grid, pred_depth_z, proj, pose, q_pts=None, want_masks=False, want_sigma=False,
                  want_pseudo_depth=False):
-        ft = self.net.native_field()
-        if ft.mlp_color:
-            raise BtsNativeError("FusedBBoxOccupancyEval: not available for MLP-predicted colour (sample_color=False)")
-        if ft.n != 1:
-            raise BtsNativeError(f"FusedBBoxOccupancyEval: the evaluator queries one encoded sample, this field holds {ft.n}")
-        native._check_partial(ft, None, None, "FusedBBoxOccupancyEval")
+        ft = self._field()
         vertices, faces, semantic_id, v_off, f_off = bboxes if isinstance(bboxes, tuple) else pack_bboxes(bboxes)
         B = _req_boxes(vertices, faces, semantic_id, v_off, f_off, "FusedBBoxOccupancyEval")
         dev = vertices.device
@@ -170,46 +132,22 @@ class FusedBBoxOccupancyEval:
         rays = _req(rays.reshape(-1, 8), "rays", (ph * pw, 8))
         _req(seg, "seg")
         seg = _req(seg.reshape(seg.shape[-2:]), "seg")
-        _req(pred_depth_z, "pred_depth_z")
-        depth = _req(pred_depth_z.reshape(pred_depth_z.shape[-2:]), "pred_depth_z", (ph, pw))
-        q = self.q_pts(dev) if q_pts is None else q_pts
-        _req(q, "q_pts")
-        if q.dim() != 2 or q.shape[1] != 3:
-            raise BtsNativeError(f"q_pts: expected (P, 3), got {tuple(q.shape)}")
+        q = self._query(dev, q_pts)
+        depth, K, pose = self._camera(pred_depth_z, proj, pose, (ph, pw))
         P = q.shape[0]
-        K = _proj3(proj)
-        _req(pose, "pose")
-        pose = _req(pose.reshape(4, 4), "pose", (4, 4))
-        lib = _lib.load()
-        counts = torch.empty(7, device=dev, dtype=torch.int32)
-        masks = torch.empty((3, P), device=dev, dtype=torch.uint8) if want_masks else None
-        sigma = torch.empty(P, device=dev, dtype=torch.float32) if want_sigma else None
+        counts, masks, sigma = self._outputs(dev, P, 7, want_masks, want_sigma)
         pseudo = torch.empty((ph, pw), device=dev, dtype=torch.float32) if want_pseudo_depth else None
-        ws_bytes = lib.bts_bbox_occupancy_eval_workspace(P, B, ph, pw)
-        ws = torch.empty(max(ws_bytes, 16) // 4, device=dev, dtype=torch.float32)
-        mlp = self.net.mlp_coarse.packed().detach()
-        cfg, tens = ft.cfg(), ft.tensors(mlp)
-
-        def dp(t):
-            return None if t is None else t.data_ptr()
         args = _lib.BtsBBoxOccupancyEval(q_pts=q.data_ptr(), P=P, B=B, ph=ph, pw=pw, hs=seg.shape[0], ws=seg.shape[1], vertices=vertices.data_ptr(),
                                          faces=faces.data_ptr(), v_offsets=C.cast(v_off, C.c_void_p).value,
                                          f_offsets=C.cast(f_off, C.c_void_p).value, semantic_id=semantic_id.data_ptr(), rays=rays.data_ptr(),
                                          seg=seg.data_ptr(), max_d=float(self.max_d), occ_threshold=float(self.occ_threshold),
                                          pred_depth_z=depth.data_ptr(), proj=K.data_ptr(), cam_pose=pose.data_ptr(), counts=counts.data_ptr(),
-                                         masks=dp(masks), sigma=dp(sigma), pseudo_depth=dp(pseudo), tables=None)
-        with torch.no_grad():
-            _lib.check(lib.bts_bbox_occupancy_eval(C.byref(cfg), C.byref(tens), C.byref(args), _ptr(ws), ws_bytes, _stream(q)),
-                       "bts_bbox_occupancy_eval")
+                                         masks=_addr(masks), sigma=_addr(sigma), pseudo_depth=_addr(pseudo), tables=None)
+        self._launch("bts_bbox_occupancy_eval", ft, q, _lib.load().bts_bbox_occupancy_eval_workspace(P, B, ph, pw), args)
         host = counts.tolist()   # the ONE device-to-host copy
         if host[6] == 0:
             raise BtsNativeError(f"FusedBBoxOccupancyEval: none of the {B} boxes is in the frustum (no vertex within max_d = {self.max_d})")
-        out = metrics_from_counts(host)
-        out["counts"] = host
-        if want_masks:
-            out["is_occupied_pred"], out["is_occupied"], out["is_visible"] = (m.view(torch.bool) for m in masks)
-        if want_sigma:
-            out["sigma"] = sigma
+        out = self._result(metrics_from_counts(host), host, masks, sigma)
         if want_pseudo_depth:
             out["pseudo_depth"] = pseudo
         return out

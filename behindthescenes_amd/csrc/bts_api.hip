@@ -568,11 +568,12 @@ int bts_lidar_occupancy(const float* q_pts, int32_t P, const float* tables, int3
                   "bts_lidar_occupancy");
 }
 
-// workspace of bts_occupancy_eval: bins + keys | tables | world_to_velo (T, 16) | camera w2c (16) | is_occupied (P) | is_visible (P) | sigma (P)
+// workspace of bts_occupancy_eval: bts_occ.hip's occ_eval_layout
 size_t bts_occupancy_eval_workspace(int32_t P, int32_t T, int32_t y_res) {
   if (P <= 0 || T <= 0 || y_res <= 0 || T > BTS_LIDAR_MAX_CLOUDS || y_res > BTS_LIDAR_MAX_SLICES) return 0;
-  return align16(lidar_bins_bytes(T, y_res)) + align16((size_t)y_res * T * 362 * 2 * 4) + (size_t)(T + 1) * 64 + 2 * align16((size_t)P) +
-         align16((size_t)P * 4);
+  Carver count(nullptr);
+  occ_eval_layout(count, P, T, y_res);
+  return count.bytes();
 }
 
 int bts_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsOccupancyEval* a, void* workspace, size_t workspace_bytes,
@@ -594,26 +595,17 @@ int bts_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const B
   }
   const int P = a->P, T = a->T, y_res = a->y_res;
   hipStream_t s = (hipStream_t)stream;
-  char* w = reinterpret_cast<char*>(workspace);
-  void* bins = w;
-  w += align16(lidar_bins_bytes(T, y_res));
-  float* tables = a->tables ? a->tables : reinterpret_cast<float*>(w);
-  w += align16((size_t)y_res * T * 362 * 2 * 4);
-  float* w2v = reinterpret_cast<float*>(w);
-  float* w2c = w2v + (size_t)T * 16;
-  w += (size_t)(T + 1) * 64;
-  uint8_t* is_occ = reinterpret_cast<uint8_t*>(w);
-  w += align16((size_t)P);
-  uint8_t* is_vis = reinterpret_cast<uint8_t*>(w);
-  w += align16((size_t)P);
-  float* sigma = a->sigma ? a->sigma : reinterpret_cast<float*>(w);
+  Carver carve(workspace);
+  const OccEvalWs w = occ_eval_layout(carve, P, T, y_res);
+  float* tables = a->tables ? a->tables : w.tables;
+  float* sigma = a->sigma ? a->sigma : w.sigma;
 
   if (int rc = field_query_impl(cfg, t, a->q_pts, P, 1, nullptr, nullptr, sigma, s)) return rc;
-  int rc = invert_small_launch(a->velo_poses, w2v, T, 4, s);
-  if (!rc) rc = invert_small_launch(a->cam_pose, w2c, 1, 4, s);
-  if (!rc) rc = lidar_slices_launch(a->points, a->offsets, T, a->velo_poses, a->borders361, a->y_lo, a->y_hi, y_res, a->max_dist, bins, tables, s);
-  if (!rc) rc = lidar_occupancy_launch(a->q_pts, P, tables, y_res, T, w2v, a->min_dist, is_occ, is_vis, s);
-  if (!rc) rc = occ_metrics_launch(a->q_pts, P, sigma, is_occ, is_vis, a->pred_depth_z, a->H, a->W, a->proj, w2c, a->occ_threshold, a->counts, a->masks, s);
+  int rc = invert_small_launch(a->velo_poses, w.w2v, T, 4, s);
+  if (!rc) rc = invert_small_launch(a->cam_pose, w.w2c, 1, 4, s);
+  if (!rc) rc = lidar_slices_launch(a->points, a->offsets, T, a->velo_poses, a->borders361, a->y_lo, a->y_hi, y_res, a->max_dist, w.bins, tables, s);
+  if (!rc) rc = lidar_occupancy_launch(a->q_pts, P, tables, y_res, T, w.w2v, a->min_dist, w.is_occ, w.is_vis, s);
+  if (!rc) rc = occ_metrics_launch(a->q_pts, P, sigma, w.is_occ, w.is_vis, a->pred_depth_z, a->H, a->W, a->proj, w.w2c, a->occ_threshold, a->counts, a->masks, s);
   if (rc) set_error("%s: kernel launch failed", "bts_occupancy_eval");
   return rc;
 }
@@ -747,11 +739,12 @@ int bts_bbox_pseudo_depth(const float* rays, int32_t ph, int32_t pw, const float
                   "bts_bbox_pseudo_depth");
 }
 
-// workspace of bts_bbox_occupancy_eval: to_keyframe (16) | tables (B, 32, 5) | n_faces (B) | active (B) | pseudo depth (ph, pw) | sigma (P)
+// workspace of bts_bbox_occupancy_eval: bts_bbox_occ.hip's bbox_eval_layout
 size_t bts_bbox_occupancy_eval_workspace(int32_t P, int32_t B, int32_t ph, int32_t pw) {
   if (P <= 0 || B <= 0 || B > BTS_BBOX_MAX_BOXES || !bbox_grid_ok(ph, pw, 1, 1)) return 0;
-  return 64 + align16((size_t)B * BTS_BBOX_MAX_FACES * 5 * 4) + align16((size_t)B * 4) + align16((size_t)B) + align16((size_t)ph * pw * 4) +
-         align16((size_t)P * 4);
+  Carver count(nullptr);
+  bbox_eval_layout(count, P, B, ph, pw);
+  return count.bytes();
 }
 
 int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsBBoxOccupancyEval* a, void* workspace,
@@ -777,18 +770,11 @@ int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, co
   }
   const int P = a->P, B = a->B;
   hipStream_t s = (hipStream_t)stream;
-  char* w = reinterpret_cast<char*>(workspace);
-  float* to_key = reinterpret_cast<float*>(w);
-  w += 64;
-  float* tables = a->tables ? a->tables : reinterpret_cast<float*>(w);
-  w += align16((size_t)B * BTS_BBOX_MAX_FACES * 5 * 4);
-  int32_t* n_faces = reinterpret_cast<int32_t*>(w);
-  w += align16((size_t)B * 4);
-  uint8_t* active = reinterpret_cast<uint8_t*>(w);
-  w += align16((size_t)B);
-  float* pseudo = a->pseudo_depth ? a->pseudo_depth : reinterpret_cast<float*>(w);
-  w += align16((size_t)a->ph * a->pw * 4);
-  float* sigma = a->sigma ? a->sigma : reinterpret_cast<float*>(w);
+  Carver carve(workspace);
+  const BBoxEvalWs w = bbox_eval_layout(carve, P, B, a->ph, a->pw);
+  float* tables = a->tables ? a->tables : w.tables;
+  float* pseudo = a->pseudo_depth ? a->pseudo_depth : w.pseudo;
+  float* sigma = a->sigma ? a->sigma : w.sigma;
 
   if (int rc = field_query_impl(cfg, t, a->q_pts, P, 1, nullptr, nullptr, sigma, s)) return rc;
   if (hipMemsetAsync(a->counts, 0, 7 * sizeof(int32_t), s) != hipSuccess) {
@@ -796,11 +782,11 @@ int bts_bbox_occupancy_eval(const BtsFieldCfg* cfg, const BtsFieldTensors* t, co
     set_error("%s: kernel launch failed", "bts_bbox_occupancy_eval");
     return BTS_E_LAUNCH;
   }
-  int rc = invert_small_launch(a->cam_pose, to_key, 1, 4, s);
-  if (!rc) rc = bbox_bounds_launch(a->vertices, a->faces, a->v_offsets, a->f_offsets, B, to_key, a->proj, a->max_d, tables, n_faces, active,
+  int rc = invert_small_launch(a->cam_pose, w.to_key, 1, 4, s);
+  if (!rc) rc = bbox_bounds_launch(a->vertices, a->faces, a->v_offsets, a->f_offsets, B, w.to_key, a->proj, a->max_d, tables, w.n_faces, w.active,
                                    a->counts + 6, s);
-  if (!rc) rc = bbox_pseudo_depth_launch(a->rays, a->ph, a->pw, a->seg, a->hs, a->ws, tables, n_faces, active, a->semantic_id, B, pseudo, s);
-  if (!rc) rc = bbox_metrics_launch(a->q_pts, P, sigma, pseudo, a->pred_depth_z, a->ph, a->pw, a->proj, tables, n_faces, active, B,
+  if (!rc) rc = bbox_pseudo_depth_launch(a->rays, a->ph, a->pw, a->seg, a->hs, a->ws, tables, w.n_faces, w.active, a->semantic_id, B, pseudo, s);
+  if (!rc) rc = bbox_metrics_launch(a->q_pts, P, sigma, pseudo, a->pred_depth_z, a->ph, a->pw, a->proj, tables, w.n_faces, w.active, B,
                                     a->occ_threshold, a->counts, a->masks, s);
   if (rc) set_error("%s: kernel launch failed", "bts_bbox_occupancy_eval");
   return rc;

@@ -4,6 +4,7 @@
 // into the six counters of occ_metrics_kernel.  No matrix pipe, no inline assembly; the only reductions are an int32 add and a
 // bit-pattern minimum of positive floats, so reruns are bit-identical.
 #include "bts_host.h"
+#include "bts_eval_device.h"
 
 namespace bts {
 
@@ -143,8 +144,8 @@ __global__ __launch_bounds__(256) void bbox_pseudo_depth_kernel(const float* __r
 
 // BTSWrapper.forward :257-299 per query point (key frame): project_into_cam (:146-150), the nearest look-up in the pseudo depth and in
 // the predicted z-depth (:259-260), V = dist <= gt | dist <= pred (:261), O = in_bbox of any active box & !V (:264-275),
-// P = sigma > threshold (:286), and the cell of (V, O, P) in occ_metrics_kernel's order, counted with a wave ballot and one atomic per
-// wave and cell.  masks (3, P): P, O, V as bytes, when given.
+// P = sigma > threshold (:286), and the cell of (V, O, P) in bts_eval_device.h's order, counted by its count_cells.  masks (3, P): P, O, V
+// as bytes, when given.
 __global__ __launch_bounds__(256) void bbox_metrics_kernel(const float* __restrict__ q_pts, int P, const float* __restrict__ sigma,
                                                            const float* __restrict__ pseudo, const float* __restrict__ depth_z, int H, int W,
                                                            const float* __restrict__ proj, const float* __restrict__ tables,
@@ -175,6 +176,7 @@ __global__ __launch_bounds__(256) void bbox_metrics_kernel(const float* __restri
     const bool V = (dist <= pseudo[texel]) | (dist <= depth_z[texel]);   // a ray no box stops has +inf pseudo depth: visible
     const bool O = inside & !V;
     const bool Pm = sigma[i] > occ_threshold;
+    // the twin of occ_metrics_kernel's lines (bts_occ.hip): as a function of bts_eval_device.h they change both kernels' instructions
     cell = V ? (Pm ? 0 : 1) : (O ? (Pm ? 2 : 3) : (Pm ? 4 : 5));
     if (masks) {
       masks[i] = Pm ? 1 : 0;
@@ -182,14 +184,20 @@ __global__ __launch_bounds__(256) void bbox_metrics_kernel(const float* __restri
       masks[2L * P + i] = V ? 1 : 0;
     }
   }
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    const unsigned long long b = __ballot(cell == c);
-    if (lane == 0 && b) atomicAdd(&counts[c], __popcll(b));
-  }
+  count_cells(cell, counts);
 }
 
+// THE layout of bts_bbox_occupancy_eval's workspace.  tables, pseudo and sigma keep their slots when the caller brings buffers of its own
+BBoxEvalWs bbox_eval_layout(Carver& w, int P, int B, int ph, int pw) {
+  BBoxEvalWs o;
+  o.to_key = w.take<float>(16);
+  o.tables = w.take<float>((size_t)B * kFaces * 5);
+  o.n_faces = w.take<int>((size_t)B);
+  o.active = w.take<unsigned char>((size_t)B);
+  o.pseudo = w.take<float>((size_t)ph * pw);
+  o.sigma = w.take<float>((size_t)P);
+  return o;
+}
 
 // v_offsets, f_offsets: HOST arrays of B + 1 entries (validated by the caller).  n_active: one int32 the active boxes are ADDED to, or NULL
 int bbox_bounds_launch(const float* vertices, const int* faces, const int* v_offsets, const int* f_offsets, int B, const float* to_key,

@@ -56,6 +56,14 @@ __device__ __forceinline__ f32x16 zero_acc() {
 // F.interpolate(mode="nearest")'s source index (upsample_nearest2d): scale = (float)in / (float)out in fp32, the identity when in == out
 __device__ __forceinline__ int nearest_src(int dst, float scale, int in) { return min((int)floorf((float)dst * scale), in - 1); }
 
+// monotone map float -> uint32 (the order of the keys is the order of the floats: an integer minimum or a radix selection over the
+// keys is one over the floats) and back
+__device__ __forceinline__ unsigned float_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float float_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
 // F.grid_sample(mode="nearest", padding_mode="border", align_corners=True) on an (H, W) map at the normalised (gx, gy): unnormalise,
 // clip, round half to even -> the texel's index y * W + x
 __device__ __forceinline__ long nearest_border_texel(float gx, float gy, int H, int W) {

@@ -24,6 +24,7 @@
 // rank-deficient system (fewer than two distinct predictions under the mask: the coefficients are not finite here, LAPACK returns the
 // minimum-norm solution).  N = 0 gives a NaN row and zero counts.
 #include "bts_host.h"
+#include "bts_eval_device.h"
 #include "bts_loss_device.h"
 
 namespace bts {
@@ -46,13 +47,6 @@ struct DepthGeom {
   double* mom;        // (B, nblk, 8)  the moments pass
 };
 
-// monotone map float -> uint32 (the order of the keys is the order of the floats) and back
-__device__ __forceinline__ unsigned depth_key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float depth_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
 // (upsample_nearest2d's source index of :101 is bts_common.h's nearest_src)
 __device__ __forceinline__ float pred_at(const DepthGeom& g, const float* pred_f, int i) {
   const int y = i / g.Wg, x = i - y * g.Wg;
@@ -68,17 +62,6 @@ __device__ __forceinline__ void load_gt4(const float* gt_f, int i0, int n_px, in
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = i0 + k < n_px ? gt_f[i0 + k] : 0.0f;
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
 }
 
 // One radix pass of the two medians (:104-105).  PASS 0: bits 31..21 of every key under gt > 0.  PASS 1: bits 20..10 of the keys whose
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void depth_hist_kernel(DepthGeom g) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (v[k] > 0.0f) {
-        const unsigned kg = depth_key(v[k]), kp = depth_key(pred_at(g, pred_f, i0 + k));
+        const unsigned kg = float_key(v[k]), kp = float_key(pred_at(g, pred_f, i0 + k));
         if (PASS == 0) {
           atomicAdd(&s_hist[kg >> 21], 1u);
           atomicAdd(&s_hist[kBinsRadix + (kp >> 21)], 1u);
@@ -148,9 +131,9 @@ __device__ void store_partial(double (&s)[4], int (&c)[5], double* slot) {
   __shared__ int s_c[kThreads / 64][5];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] = wave_sum(s[k]);
+  for (int k = 0; k < 4; ++k) s[k] = lane0_sum(s[k]);
 #pragma unroll
-  for (int k = 0; k < 5; ++k) c[k] = wave_sum(c[k]);
+  for (int k = 0; k < 5; ++k) c[k] = lane0_sum(c[k]);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) s_d[wave][k] = s[k];
@@ -235,7 +218,7 @@ __global__ __launch_bounds__(kThreads) void depth_terms_kernel(DepthGeom g) {
     const unsigned pg = state_f[8], rg = state_f[9], pp = state_f[10], rp = state_f[11], n = state_f[12];
     select_bin<true>(g.hist + (size_t)f * kHistFrame + 4 * kBinsRadix, 0, rg, s_scan, s_sel[0]);
     select_bin<true>(g.hist + (size_t)f * kHistFrame + 5 * kBinsRadix, 0, rp, s_scan, s_sel[1]);
-    const float med_g = depth_unkey((pg << 10) | s_sel[0][0]), med_p = depth_unkey((pp << 10) | s_sel[1][0]);
+    const float med_g = float_unkey((pg << 10) | s_sel[0][0]), med_p = float_unkey((pp << 10) | s_sel[1][0]);
     x0 = n ? med_g / med_p : __uint_as_float(0x7FC00000u);   // the median of an empty selection
     if (blockIdx.x == 0 && threadIdx.x == 0) state_f[16] = __float_as_uint(x0), state_f[17] = __float_as_uint(0.0f);
   } else if (g.mode == 2) {
@@ -309,10 +292,19 @@ __global__ __launch_bounds__(64) void depth_finish_kernel(DepthGeom g, float* __
 
 static int n_blocks(int Hg, int Wg) { return (int)(((long)Hg * Wg + kPerBlock - 1) / kPerBlock); }
 
-// histograms | notes | partials of the metrics pass | partials of the moments pass, each per frame
+// THE layout of bts_depth_metrics' workspace: histograms | notes | partials of the metrics pass | partials of the moments pass, each per frame
+static void depth_layout(Carver& w, DepthGeom& g, size_t B, size_t nblk) {
+  g.hist = w.take<unsigned>(B * kHistFrame);
+  g.state = w.take<unsigned>(B * kStateFrame);
+  g.part = w.take<double>(B * nblk * kSlotDoubles);
+  g.mom = w.take<double>(B * nblk * kSlotDoubles);
+}
+
 size_t depth_metrics_bytes(int B, int Hg, int Wg) {
-  const size_t slots = (size_t)B * n_blocks(Hg, Wg) * kSlotDoubles * sizeof(double);
-  return align16((size_t)B * kHistFrame * 4) + align16((size_t)B * kStateFrame * 4) + 2 * align16(slots);
+  Carver count(nullptr);
+  DepthGeom g;
+  depth_layout(count, g, (size_t)B, (size_t)n_blocks(Hg, Wg));
+  return count.bytes();
 }
 
 int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t s) {
@@ -323,14 +315,8 @@ int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t 
   g.vec = ((uintptr_t)a->gt & 15) == 0 && (a->B == 1 || (g.n_px & 3) == 0);
   g.sh = (float)a->H / (float)a->Hg, g.sw = (float)a->W / (float)a->Wg;
   g.clamp_lo = a->clamp_lo, g.clamp_hi = a->clamp_hi;
-  char* w = reinterpret_cast<char*>(workspace);
-  const size_t slots = align16((size_t)a->B * g.nblk * kSlotDoubles * sizeof(double));
-  g.hist = reinterpret_cast<unsigned*>(w);
-  w += align16((size_t)a->B * kHistFrame * 4);
-  g.state = reinterpret_cast<unsigned*>(w);
-  w += align16((size_t)a->B * kStateFrame * 4);
-  g.part = reinterpret_cast<double*>(w);
-  g.mom = reinterpret_cast<double*>(w + slots);
+  Carver carve(workspace);
+  depth_layout(carve, g, (size_t)a->B, (size_t)g.nblk);
   const dim3 grid(g.nblk, a->B);
   if (a->mode == 1) {
     if (hipMemsetAsync(g.hist, 0, (size_t)a->B * kHistFrame * 4, s) != hipSuccess) {

@@ -15,6 +15,7 @@
 // Plain fp32 with correctly rounded division (__fdiv_rn), no contraction, no reciprocal approximations: the panels are compared byte
 // for byte with numpy / torch on the host.  Quirks of the reference that are reproduced ON PURPOSE are listed in include/bts_render.h.
 #include "bts_host.h"
+#include "bts_eval_device.h"
 
 namespace bts {
 
@@ -60,10 +61,8 @@ __global__ __launch_bounds__(kFramesThreads) void frames_minmax_kernel(const flo
     if (v != v) bad = 1.0f;
     else lo = fminf(lo, v), hi = fmaxf(hi, v);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_down(lo, o)), hi = fmaxf(hi, __shfl_down(hi, o)), bad = fmaxf(bad, __shfl_down(bad, o));
-  }
+  const MinMaxBad m = lane0_minmax(lo, hi, bad);
+  lo = m.lo, hi = m.hi, bad = m.bad;
   if ((t & 63) == 0) s_lo[t >> 6] = lo, s_hi[t >> 6] = hi, s_nan[t >> 6] = bad;
   __syncthreads();
   if (t == 0) {
@@ -79,10 +78,9 @@ __device__ __forceinline__ void fold_minmax(const float* __restrict__ partials, 
     const int l = threadIdx.x;
     const float* p = partials + ((size_t)b * kFramesPartials + l) * 3;
     float lo = l < nb ? p[0] : __int_as_float(0x7F800000), hi = l < nb ? p[1] : __int_as_float(0xFF800000), bad = l < nb ? p[2] : 0.0f;
+    // (the steps of lane0_minmax, written out: called as that function this fold changes colorize_kernel's instructions)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo = fminf(lo, __shfl_down(lo, o)), hi = fmaxf(hi, __shfl_down(hi, o)), bad = fmaxf(bad, __shfl_down(bad, o));
-    }
+    for (int o = 32; o > 0; o >>= 1) minmax_step(lo, hi, bad, o);
     if (l == 0) {
       const float nan = __int_as_float(0x7FC00000);
       s_mm[0] = bad != 0.0f ? nan : lo, s_mm[1] = bad != 0.0f ? nan : hi;

@@ -108,8 +108,22 @@ size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs*
 int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
                               hipStream_t s);
 
-// ---- bts_occ.hip: LiDAR occupancy evaluation
+// ---- bts_occ.hip: LiDAR occupancy evaluation.  *_layout: the ONE statement of a workspace's layout, run over a Carver (below) once to
+// count the bytes and once to hand out the pointers
+class Carver;
+struct LidarBins {
+  unsigned* bins;
+  unsigned long long* first;
+};
+LidarBins lidar_bins_layout(Carver& w, int T, int y_res);
 size_t lidar_bins_bytes(int T, int y_res);
+struct OccEvalWs {
+  char* bins;   // lidar_bins_layout's
+  float *tables, *w2v, *w2c;
+  unsigned char *is_occ, *is_vis;
+  float* sigma;
+};
+OccEvalWs occ_eval_layout(Carver& w, int P, int T, int y_res);
 int lidar_slices_launch(const float* points, const int* offsets, int T, const float* velo_poses, const float* borders, float y_lo, float y_hi,
                         int y_res, float max_dist, void* bins_ws, float* tables, hipStream_t s);
 int lidar_occupancy_launch(const float* q_pts, int P, const float* tables, int y_res, int T, const float* world_to_velo, float min_dist,
@@ -125,6 +139,13 @@ size_t nvs_metrics_bytes(int B, int He, int We);
 int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s);
 
 // ---- bts_bbox_occ.hip: 3D-bounding-box occupancy evaluation
+struct BBoxEvalWs {
+  float *to_key, *tables;
+  int* n_faces;
+  unsigned char* active;
+  float *pseudo, *sigma;
+};
+BBoxEvalWs bbox_eval_layout(Carver& w, int P, int B, int ph, int pw);
 int bbox_bounds_launch(const float* vertices, const int* faces, const int* v_offsets, const int* f_offsets, int B, const float* to_key,
                        const float* proj, float max_d, float* tables, int* n_faces, unsigned char* active, int* n_active, hipStream_t s);
 int bbox_pseudo_depth_launch(const float* rays, int ph, int pw, const float* seg, int hs, int ws, const float* tables, const int* n_faces,

@@ -1,7 +1,8 @@
 // bts_loss_device.h -- the rules the loss kernels share, each written ONCE: bts_loss.hip (one wave per patch of at most 64 pixels),
 // bts_loss_tiled.hip (16 x 16 tiles of patches of any size), bts_loss_pixel.hip (per-pixel criteria), bts_automask.hip (the error map)
 // and, for the rank selection, bts_depth_metrics.hip include it.  "Bit for bit the other kernel's result" means: both call the function
-// below.  Device code only, every function inlined into its kernel (select_bin: left to the compiler, as before).
+// below.  Device code only, every function inlined into its kernel (select_bin: left to the compiler, as before).  The evaluation
+// kernels' shared rules are bts_eval_device.h's; its lane-0 __shfl_down sums are NOT the wave_sum below (every lane holds that one).
 //   - wave sums, sign(0) = 0, the gradient factor of torch's binary min
 //   - the invalid-ray rule (loss.py:100-118) for every policy, over the kernel's parameter struct
 //   - the 3 x 3 Gaussian window of SSIM (layers.py:92-101), the per-channel SSIM term and its three backward coefficients

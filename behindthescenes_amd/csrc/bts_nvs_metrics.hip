@@ -16,13 +16,14 @@
 // All arithmetic is fp64 from the fp32 inputs, as skimage's (before 0.19 `multichannel=True` images were promoted to float64), with
 // no contraction.  Quirks of the reference that are reproduced ON PURPOSE:
 //   - F.interpolate's nearest source index is min((int)floorf(dst * scale), in - 1) with scale = (float)in / (float)out in fp32
-//     (:154-155), not the exact rational -- the index bts_depth_metrics.hip documents, restated here;
+//     (:154-155), not the exact rational -- bts_common.h's nearest_src, the index bts_depth_metrics.hip documents;
 //   - the crop box is the host's: ceil(0.05 * h), floor(0.95 * h) evaluated on Python floats (:158-161);
 //   - cov_norm = 49 / 48: the sample covariance of skimage's default use_sample_covariance=True;
 //   - the mean of S runs over the interior only (skimage crops (win_size - 1) // 2 = 3 pixels from every side), so the filter's
 //     reflect border never reaches the result and no border mode exists here.
 // Outside the contract: NaN or inf in either image (nothing faults, the row is unspecified).
 #include "bts_host.h"
+#include "bts_eval_device.h"
 
 namespace bts {
 
@@ -45,15 +46,6 @@ struct NvsGeom {
   double* part;               // (B, nblk, 4)
 };
 
-// upsample_nearest2d's source index (:154-155), as in bts_depth_metrics.hip
-__device__ __forceinline__ int nvs_nearest_src(int dst, float scale, int in) { return min((int)floorf((float)dst * scale), in - 1); }
-
-__device__ __forceinline__ double nvs_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(kNvsThreads) void nvs_tiles_kernel(NvsGeom g) {
   __shared__ double s_x[kHaloY][kHaloXP], s_y[kHaloY][kHaloXP];
   __shared__ double s_row[5][kHaloY][kRowXP];
@@ -73,7 +65,7 @@ __global__ __launch_bounds__(kNvsThreads) void nvs_tiles_kernel(NvsGeom g) {
       const int cy = cy0 + r, cx = cx0 + q;
       double x = 0.0, y = 0.0;
       if (cy < g.h && cx < g.w) {
-        const long long sy = nvs_nearest_src(g.y0 + cy, g.sh, g.H), sx = nvs_nearest_src(g.x0 + cx, g.sw, g.W);
+        const long long sy = nearest_src(g.y0 + cy, g.sh, g.H), sx = nearest_src(g.x0 + cx, g.sw, g.W);
         x = (double)pred_f[sy * g.pred_sy + sx * g.pred_sx + c * g.pred_sc];
         y = (double)gt_f[sy * g.gt_sy + sx * g.gt_sx + c * g.gt_sc];
         if (r < own_y && q < own_x) {
@@ -117,7 +109,7 @@ __global__ __launch_bounds__(kNvsThreads) void nvs_tiles_kernel(NvsGeom g) {
   }
   const int lane = t & 63, wave = t >> 6;
 #pragma unroll
-  for (int k = 0; k < kNvsSlot; ++k) acc[k] = nvs_wave_sum(acc[k]);
+  for (int k = 0; k < kNvsSlot; ++k) acc[k] = lane0_sum(acc[k]);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < kNvsSlot; ++k) s_part[wave][k] = acc[k];
@@ -156,10 +148,16 @@ __global__ __launch_bounds__(64) void nvs_finish_kernel(NvsGeom g, double* __res
 
 static int nvs_tiles(int n, int tile) { return n > kWin - 1 ? (n - (kWin - 1) + tile - 1) / tile : 1; }
 
-// the partials of the largest crop eval_resolution admits
+// THE layout of bts_nvs_metrics' workspace: the partials of the largest crop eval_resolution admits
+static void nvs_layout(Carver& w, NvsGeom& g, size_t B, int He, int We) {
+  g.part = w.take<double>(B * nvs_tiles(He, kTileY) * nvs_tiles(We, kTileX) * kNvsSlot);
+}
+
 size_t nvs_metrics_bytes(int B, int He, int We) {
-  const size_t b = (size_t)B * nvs_tiles(He, kTileY) * nvs_tiles(We, kTileX) * kNvsSlot * sizeof(double);
-  return (b + 15) / 16 * 16;
+  Carver count(nullptr);
+  NvsGeom g;
+  nvs_layout(count, g, (size_t)B, He, We);
+  return count.bytes();
 }
 
 int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s) {
@@ -173,7 +171,8 @@ int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s) {
   g.sh = (float)a->H / (float)a->He, g.sw = (float)a->W / (float)a->We;
   g.c1 = (0.01 * a->data_range) * (0.01 * a->data_range), g.c2 = (0.03 * a->data_range) * (0.03 * a->data_range);
   g.r2 = a->data_range * a->data_range;
-  g.part = reinterpret_cast<double*>(workspace);
+  Carver carve(workspace);
+  nvs_layout(carve, g, (size_t)a->B, a->He, a->We);
   nvs_tiles_kernel<<<dim3(g.nblk, a->B), kNvsThreads, 0, s>>>(g);
   if (int rc = launch_code()) return rc;
   nvs_finish_kernel<<<a->B, 64, 0, s>>>(g, a->metrics);

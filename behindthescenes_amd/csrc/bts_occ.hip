@@ -3,6 +3,7 @@
 // point up in the tables of its slice, classify the points into six counters.  No matrix pipe, no inline assembly; every reduction is
 // an integer / bit-pattern atomic, so reruns are bit-identical.
 #include "bts_host.h"
+#include "bts_eval_device.h"
 
 namespace bts {
 
@@ -17,12 +18,6 @@ struct LidarOffsets {
 struct LidarSliceBounds {
   float lo[BTS_LIDAR_MAX_SLICES], hi[BTS_LIDAR_MAX_SLICES];
 };
-
-// monotone map float -> uint32 (the order of the floats is the order of the results)
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __global__ __launch_bounds__(256) void lidar_init_kernel(unsigned* __restrict__ bins, unsigned long long* __restrict__ first, int n_bins,
                                                          int n_first) {
@@ -75,7 +70,7 @@ __global__ __launch_bounds__(256) void lidar_bins_kernel(const float4* __restric
     }
     const int bin = lo - 1;   // -1: below border_0; 360: at or above border_360 -- in no bin
     const unsigned dbits = __float_as_uint(dist);
-    const unsigned long long key = ((unsigned long long)ordered_bits(angle) << 32) | dbits;
+    const unsigned long long key = ((unsigned long long)float_key(angle) << 32) | dbits;
     for (int s = 0; s < y_res; ++s) {
       if (far || (yw >= yb.lo[s] && yw <= yb.hi[s])) {
         if (bin >= 0 && bin < kBins) atomicMin(&s_bins[s * kBins + bin], dbits);
@@ -185,9 +180,8 @@ __global__ __launch_bounds__(256) void lidar_occupancy_kernel(const float* __res
 
 // BTSWrapper.forward :296-298 + :308 + :314-330 per query point: predicted visibility (project_into_cam :163-168, a nearest,
 // border-clamped, align_corners=True look-up in the predicted z-depth map, dist <= pred_dist), predicted occupancy sigma > threshold,
-// V = is_visible | is_visible_pred, O = is_occupied & !V, and the cell of (V, O, P) among
-//   0: V & P   1: V & !P   2: !V & O & P   3: !V & O & !P   4: !V & !O & P   5: !V & !O & !P
-// counted with a wave ballot, one atomic per wave and cell.  masks (3, P): P, O, V as bytes, when given.
+// V = is_visible | is_visible_pred, O = is_occupied & !V, and the cell of (V, O, P) in bts_eval_device.h's order, counted by its
+// count_cells.  masks (3, P): P, O, V as bytes, when given.
 __global__ __launch_bounds__(256) void occ_metrics_kernel(const float* __restrict__ q_pts, int P, const float* __restrict__ sigma,
                                                           const unsigned char* __restrict__ is_occupied, const unsigned char* __restrict__ is_visible,
                                                           const float* __restrict__ depth_z, int H, int W, const float* __restrict__ proj,
@@ -212,6 +206,7 @@ __global__ __launch_bounds__(256) void occ_metrics_kernel(const float* __restric
     const bool Pm = sigma[i] > occ_threshold;
     const bool V = (is_visible[i] != 0) | vis_pred;
     const bool O = (is_occupied[i] != 0) & !V;
+    // the twin of bbox_metrics_kernel's lines (bts_bbox_occ.hip): as a function of bts_eval_device.h they change both kernels' instructions
     cell = V ? (Pm ? 0 : 1) : (O ? (Pm ? 2 : 3) : (Pm ? 4 : 5));
     if (masks) {
       masks[i] = Pm ? 1 : 0;
@@ -219,12 +214,7 @@ __global__ __launch_bounds__(256) void occ_metrics_kernel(const float* __restric
       masks[2L * P + i] = V ? 1 : 0;
     }
   }
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    const unsigned long long b = __ballot(cell == c);
-    if (lane == 0 && b) atomicAdd(&counts[c], __popcll(b));
-  }
+  count_cells(cell, counts);
 }
 
 // torch.linspace(lo, hi, y_res) in fp32 (:59) and the slice bounds of :67-72
@@ -241,8 +231,32 @@ static void slice_bounds(float y_lo, float y_hi, int y_res, LidarSliceBounds* yb
 }
 
 
+// THE layout of bts_lidar_slices' workspace: the per-bin minima (y_res, T, 360) and the smallest-angle keys (y_res, T)
+LidarBins lidar_bins_layout(Carver& w, int T, int y_res) {
+  LidarBins b;
+  b.bins = w.take<unsigned>((size_t)y_res * T * kBins);
+  b.first = w.take<unsigned long long>((size_t)y_res * T);
+  return b;
+}
+
 size_t lidar_bins_bytes(int T, int y_res) {
-  return ((size_t)y_res * T * kBins * 4 + 15) / 16 * 16 + (size_t)y_res * T * 8;
+  Carver count(nullptr);
+  lidar_bins_layout(count, T, y_res);
+  return count.bytes();
+}
+
+// THE layout of bts_occupancy_eval's workspace.  tables and sigma keep their slots when the caller brings buffers of its own, so the
+// size does not depend on which outputs were asked for
+OccEvalWs occ_eval_layout(Carver& w, int P, int T, int y_res) {
+  OccEvalWs o;
+  o.bins = w.take<char>(lidar_bins_bytes(T, y_res));
+  o.tables = w.take<float>((size_t)y_res * T * kRows * 2);
+  o.w2v = w.take<float>((size_t)T * 16);
+  o.w2c = w.take<float>(16);
+  o.is_occ = w.take<unsigned char>((size_t)P);
+  o.is_vis = w.take<unsigned char>((size_t)P);
+  o.sigma = w.take<float>((size_t)P);
+  return o;
 }
 
 // offsets: HOST array of T + 1 point offsets (validated by the caller)
@@ -254,16 +268,16 @@ int lidar_slices_launch(const float* points, const int* offsets, int T, const fl
   for (int t = 0; t < T; ++t) max_n = offsets[t + 1] - offsets[t] > max_n ? offsets[t + 1] - offsets[t] : max_n;
   LidarSliceBounds yb;
   slice_bounds(y_lo, y_hi, y_res, &yb);
-  unsigned* bins = reinterpret_cast<unsigned*>(bins_ws);
+  Carver carve(bins_ws);
+  const LidarBins b = lidar_bins_layout(carve, T, y_res);
   const int n_bins = y_res * T * kBins, n_first = y_res * T;
-  unsigned long long* first = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(bins_ws) + ((size_t)n_bins * 4 + 15) / 16 * 16);
-  lidar_init_kernel<<<(n_bins + 255) / 256, 256, 0, s>>>(bins, first, n_bins, n_first);
+  lidar_init_kernel<<<(n_bins + 255) / 256, 256, 0, s>>>(b.bins, b.first, n_bins, n_first);
   if (int rc = launch_code()) return rc;
   const int per_block = 256 * 8;
   lidar_bins_kernel<<<dim3((max_n + per_block - 1) / per_block, T), 256, 0, s>>>(reinterpret_cast<const float4*>(points), offs, velo_poses, borders, yb,
-                                                                               y_res, max_dist, per_block, T, bins, first);
+                                                                               y_res, max_dist, per_block, T, b.bins, b.first);
   if (int rc = launch_code()) return rc;
-  lidar_table_kernel<<<y_res * T, 64, 0, s>>>(bins, first, borders, tables);
+  lidar_table_kernel<<<y_res * T, 64, 0, s>>>(b.bins, b.first, borders, tables);
   return launch_code();
 }
 

@@ -12,6 +12,7 @@ There is no torch fallback: CPU tensors are rejected, as everywhere else in this
 import torch
 
 from . import _lib, native
+from ._evalcommon import MetricRows
 from ._lib import BtsNativeError
 from .train_step import FusedEvalFrame
 
@@ -38,7 +39,7 @@ def compute_depth_metrics(depth_pred, depth_gt, depth_scaling=None):
     return _as_dict(row)
 
 
-class FusedDepthEval:
+class FusedDepthEval(MetricRows):
     """An eval_depth frame that ends in one row of metrics on the device.
 
         ev = FusedDepthEval(wrapped, sampler, depth_scaling="median")
@@ -54,28 +55,16 @@ class FusedDepthEval:
     def __init__(self, wrapped, sampler, depth_scaling=None, capacity=4096):
         if depth_scaling not in native.DEPTH_SCALING_MODES:
             raise BtsNativeError(f"depth_scaling: expected None, 'median' or 'l2', got {depth_scaling!r}")
-        if int(capacity) <= 0:
-            raise BtsNativeError(f"capacity: a positive number of frames expected, got {capacity}")
+        super().__init__(_lib.BTS_DEPTH_METRICS_ROW, torch.float32, capacity, "FusedDepthEval")
         self.eval_frame = FusedEvalFrame(wrapped, sampler)
-        self.depth_scaling, self.capacity = depth_scaling, int(capacity)
-        self.rows = None
-        self.n_frames = 0
-
-    def reset(self):
-        if self.rows is not None:
-            self.rows.zero_()
-        self.n_frames = 0
+        self.depth_scaling = depth_scaling
 
     def update(self, depth_pred, depth_gt):
         """The metrics of one frame from a z-depth the caller already holds (``depth_pred (1, 1, H, W)``): the next row of the buffer."""
-        if self.n_frames >= self.capacity:
-            raise BtsNativeError(f"FusedDepthEval: {self.capacity} frames are stored; compute() / reset() first or construct with a larger capacity")
+        self.full()
         pred, gt = _frame(depth_pred, "depth_pred"), _frame(depth_gt, "depth_gt")
         native._req(pred, "depth_pred"), native._req(gt, "depth_gt")
-        if self.rows is None or self.rows.device != pred.device:
-            self.rows = torch.zeros((self.capacity, _lib.BTS_DEPTH_METRICS_ROW), device=pred.device, dtype=torch.float32)
-            self.n_frames = 0
-        row = self.rows[self.n_frames:self.n_frames + 1]
+        row = self.next_row(pred.device)
         native.depth_metrics(pred, gt, self.depth_scaling, out=row)
         self.n_frames += 1
         return row[0]
@@ -84,8 +73,7 @@ class FusedDepthEval:
         """``kwargs`` go to ``FusedEvalFrame.forward`` (ids_encoder, ids_render, jitter, ...); the depth must be the z-depth (to_z)."""
         if not kwargs.get("to_z", True):
             raise BtsNativeError("FusedDepthEval: the metrics are defined on the z-depth (to_z=True)")
-        if self.n_frames >= self.capacity:      # before the render, not after it
-            raise BtsNativeError(f"FusedDepthEval: {self.capacity} frames are stored; compute() / reset() first or construct with a larger capacity")
+        self.full()      # before the render, not after it
         native._req(_frame(depth_gt, "depth_gt"), "depth_gt")
         data = self.eval_frame(images, projs, poses, **kwargs)
         depth = data["fine"][0]["depth"]                 # (n, v, H, W); the reference takes [:, :1] of batch 1 (evaluator.py:99)
@@ -99,7 +87,4 @@ class FusedDepthEval:
     def compute(self):
         if self.n_frames == 0:
             raise BtsNativeError("FusedDepthEval.compute: no frame has been evaluated")
-        host = self.rows[:self.n_frames, :len(METRIC_KEYS)].cpu().double()      # the ONE device-to-host copy
-        keep = ~torch.isnan(host)
-        sums, n = torch.where(keep, host, torch.zeros_like(host)).sum(dim=0), keep.sum(dim=0)
-        return {k: (sums[i].item() / int(n[i]) if int(n[i]) else float("nan")) for i, k in enumerate(METRIC_KEYS)}
+        return self.means(METRIC_KEYS)      # the ONE device-to-host copy

@@ -13,8 +13,9 @@ import math
 import torch
 
 from . import _lib, native
+from ._evalcommon import FusedOccupancy, occupancy_ratios
 from ._lib import BtsNativeError
-from .native import _ptr, _req, _stream
+from .native import _addr, _ptr, _req, _scratch, _stream
 
 N_BINS = 360
 METRIC_KEYS = ("o_acc", "o_rec", "o_prec", "ie_acc", "ie_rec", "ie_prec", "ie_r", "t_ie", "t_no_nop_nv")
@@ -67,8 +68,7 @@ def lidar_tables(point_clouds, velo_poses, y_range, y_res, max_dist):
     lib = _lib.load()
     dev = points.device
     y_res = int(y_res)
-    ws_bytes = lib.bts_lidar_slices_workspace(T, y_res)
-    ws = torch.empty(max(ws_bytes, 16) // 4, device=dev, dtype=torch.float32)
+    ws = _scratch(dev, lib.bts_lidar_slices_workspace(T, y_res))
     tables = torch.empty((max(y_res, 0), T, N_BINS + 2, 2), device=dev, dtype=torch.float32)
     _lib.check(lib.bts_lidar_slices(_ptr(points), offsets, T, _ptr(poses), _ptr(_borders(dev)), float(y_range[0]), float(y_range[-1]), y_res,
                                     float(max_dist), _ptr(ws), _ptr(tables), _stream(points)), "bts_lidar_slices")
@@ -121,29 +121,12 @@ def check_occupancy(pts, slices, velo_poses, min_dist=3):
 
 
 def metrics_from_counts(counts):
-    """The nine metrics of evaluator_lidar.py:319-340 from the six cell counts of bts_occupancy_eval
-    ([V&P, V&!P, !V&O&P, !V&O&!P, !V&!O&P, !V&!O&!P]).  Types as in the reference: Python floats where it calls .item(), 0-dim fp32
-    tensors (here on the CPU) elsewhere; a mean over an empty selection is NaN, as torch's mean of an empty tensor."""
-    c = [int(v) for v in counts]
-
-    def ratio(num, den):
-        return torch.tensor(float(num), dtype=torch.float32) / torch.tensor(float(den), dtype=torch.float32)
-
-    n = sum(c)
-    return {
-        "o_acc": ratio(c[1] + c[2] + c[5], n).item(),
-        "o_rec": ratio(c[2], c[2] + c[3]).item(),
-        "o_prec": ratio(c[2], c[0] + c[2] + c[4]).item(),
-        "ie_acc": ratio(c[2] + c[5], c[2] + c[3] + c[4] + c[5]).item(),
-        "ie_rec": ratio(c[5], c[4] + c[5]),
-        "ie_prec": ratio(c[5], c[3] + c[5]),
-        "ie_r": ratio(c[4] + c[5], n).item(),
-        "t_ie": float(c[4] + c[5]),
-        "t_no_nop_nv": torch.tensor(float(c[5]), dtype=torch.float32),
-    }
+    """The nine metrics of evaluator_lidar.py:319-340 from the six cell counts of bts_occupancy_eval: _evalcommon.occupancy_ratios under
+    this evaluator's names."""
+    return dict(zip(METRIC_KEYS, occupancy_ratios(counts)))
 
 
-class FusedOccupancyEval:
+class FusedOccupancyEval(FusedOccupancy):
     """BTSWrapper.forward of evaluator_lidar.py after the render (:292-340) in one library call.
 
         ev = FusedOccupancyEval(net)                       # an ENCODED behindthescenes_amd.BTSNet
@@ -155,65 +138,29 @@ class FusedOccupancyEval:
 
     def __init__(self, net, x_range=(-4, 4), y_range=(0, .75), z_range=(20, 4), ppm=10, ppm_y=4, y_res=1, min_dist=3, occ_threshold=0.5,
                  max_dist=None):
-        self.net = net
         self.y_range, self.min_dist, self.occ_threshold = y_range, min_dist, occ_threshold
         self.max_dist = (z_range[0] ** 2 + x_range[0] ** 2) ** .5 if max_dist is None else max_dist
         grid, (self.xd, self.yd, self.zd) = get_pts(x_range, y_range, z_range, ppm, ppm_y, y_res)
-        self._q_cpu = grid.reshape(-1, 3).contiguous()
-        self._q = None
-
-    def q_pts(self, dev):
-        if self._q is None or self._q.device != dev:
-            self._q = self._q_cpu.to(dev)
-        return self._q
+        super().__init__(net, grid)
 
     def __call__(self, point_clouds, velo_poses, pred_depth_z, proj, pose, q_pts=None, want_masks=False, want_sigma=False, want_tables=False):
-        ft = self.net.native_field()
-        if ft.mlp_color:
-            raise BtsNativeError("FusedOccupancyEval: not available for MLP-predicted colour (sample_color=False)")
-        if ft.n != 1:
-            raise BtsNativeError(f"FusedOccupancyEval: the evaluator queries one encoded sample, this field holds {ft.n}")
-        native._check_partial(ft, None, None, "FusedOccupancyEval")
+        ft = self._field()
         points, offsets, poses, T = _pack_clouds(point_clouds, velo_poses)
         dev = points.device
-        q = self.q_pts(dev) if q_pts is None else q_pts
-        _req(q, "q_pts")
-        if q.dim() != 2 or q.shape[1] != 3:
-            raise BtsNativeError(f"q_pts: expected (P, 3), got {tuple(q.shape)}")
-        P = q.shape[0]
-        depth = _req(pred_depth_z.reshape(pred_depth_z.shape[-2:]) if isinstance(pred_depth_z, torch.Tensor) else pred_depth_z, "pred_depth_z")
-        H, W = depth.shape
-        _req(proj, "proj"), _req(pose, "pose")
-        K = _req(proj.reshape(proj.shape[-2:])[:3, :3].contiguous(), "proj", (3, 3))
-        pose = _req(pose.reshape(4, 4), "pose", (4, 4))
-        y_res = int(self.yd)
-        lib = _lib.load()
-        counts = torch.empty(6, device=dev, dtype=torch.int32)
-        masks = torch.empty((3, P), device=dev, dtype=torch.uint8) if want_masks else None
-        sigma = torch.empty(P, device=dev, dtype=torch.float32) if want_sigma else None
+        q = self._query(dev, q_pts)
+        depth, K, pose = self._camera(pred_depth_z, proj, pose)
+        P, (H, W), y_res = q.shape[0], depth.shape, int(self.yd)
+        counts, masks, sigma = self._outputs(dev, P, 6, want_masks, want_sigma)
         tables = torch.empty((y_res, T, N_BINS + 2, 2), device=dev, dtype=torch.float32) if want_tables else None
-        ws_bytes = lib.bts_occupancy_eval_workspace(P, T, y_res)
-        ws = torch.empty(max(ws_bytes, 16) // 4, device=dev, dtype=torch.float32)
-        mlp = self.net.mlp_coarse.packed().detach()
-        cfg, tens = ft.cfg(), ft.tensors(mlp)
-
-        def dp(t):
-            return None if t is None else t.data_ptr()
         args = _lib.BtsOccupancyEval(q_pts=q.data_ptr(), P=P, T=T, y_res=y_res, H=H, W=W, reserved_=0, points=points.data_ptr(),
                                      offsets=C.cast(offsets, C.c_void_p).value, velo_poses=poses.data_ptr(), borders361=_borders(dev).data_ptr(),
                                      y_lo=float(self.y_range[0]), y_hi=float(self.y_range[-1]), max_dist=float(self.max_dist),
                                      min_dist=float(self.min_dist), occ_threshold=float(self.occ_threshold), reserved2_=0,
                                      pred_depth_z=depth.data_ptr(), proj=K.data_ptr(), cam_pose=pose.data_ptr(), counts=counts.data_ptr(),
-                                     masks=dp(masks), sigma=dp(sigma), tables=dp(tables))
-        with torch.no_grad():
-            _lib.check(lib.bts_occupancy_eval(C.byref(cfg), C.byref(tens), C.byref(args), _ptr(ws), ws_bytes, _stream(q)), "bts_occupancy_eval")
+                                     masks=_addr(masks), sigma=_addr(sigma), tables=_addr(tables))
+        self._launch("bts_occupancy_eval", ft, q, _lib.load().bts_occupancy_eval_workspace(P, T, y_res), args)
         host = counts.tolist()   # the ONE device-to-host copy
-        out = metrics_from_counts(host)
-        out["counts"] = host
-        if want_masks:
-            out["is_occupied_pred"], out["is_occupied"], out["is_visible"] = (m.view(torch.bool) for m in masks)
-        if want_sigma:
-            out["sigma"] = sigma
+        out = self._result(metrics_from_counts(host), host, masks, sigma)
         if want_tables:
             out["tables"] = tables
         return out

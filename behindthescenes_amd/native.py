@@ -58,18 +58,40 @@ def _stream(t: torch.Tensor):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def _req(t: torch.Tensor, name: str, shape=None):
+def _addr(t: Optional[torch.Tensor]):
+    """the device address for a pointer field of an argument struct (None: NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def _req_as(t, name: str, dtype, shape=None, contiguous=True):
+    """THE tensor check: a GPU tensor of ``dtype``, contiguous (unless the entry point reads strides), of ``shape`` when given"""
     if not isinstance(t, torch.Tensor):
         raise BtsNativeError(f"{name}: expected a tensor")
     if not t.is_cuda:
         raise BtsNativeError(f"{name}: must live on the GPU (got {t.device}); the HIP renderer has no CPU path")
-    if t.dtype != torch.float32:
-        raise BtsNativeError(f"{name}: must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
+    if t.dtype != dtype:
+        raise BtsNativeError(f"{name}: must be {str(dtype).split('.')[-1]} (got {t.dtype})")
+    if contiguous and not t.is_contiguous():
         raise BtsNativeError(f"{name}: must be contiguous")
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise BtsNativeError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     return t
+
+
+def _req(t, name: str, shape=None):
+    return _req_as(t, name, torch.float32, shape)
+
+
+def _req_tiles(tiles, n_tiles, dev, whose):
+    """the tile flags of a projected map (a ValueError, as ever)"""
+    if tiles.dtype != torch.uint8 or not tiles.is_contiguous() or tiles.numel() != n_tiles or tiles.device != dev:
+        raise ValueError(f"tiles: expected a contiguous uint8 tensor of (N, proj_tile_count) on {whose} device")
+
+
+def _scratch(dev, n_bytes):
+    """Fresh scratch of at least 16 bytes from torch's allocator (the library allocates nothing); it goes back to the caching allocator
+    with the call.  (_workspace below is the kept per-stream buffer of the entry points that run every step.)"""
+    return torch.empty(max(int(n_bytes), 16), device=dev, dtype=torch.uint8)
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -131,8 +153,7 @@ def patch_rays(poses_c2w, projs, images, patch_v, patch_y, patch_x, ph: int, pw:
     if not isinstance(images, tuple) and ((ph > H) or (pw > W)):
         raise BtsNativeError(f"patch {ph}x{pw} does not fit a {H}x{W} frame")
     for t, nme in ((patch_v, "patch_v"), (patch_y, "patch_y"), (patch_x, "patch_x")):
-        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n, P):
-            raise BtsNativeError(f"{nme}: expected a contiguous int32 device tensor of shape {(n, P)}")
+        _req_as(t, nme, torch.int32, (n, P))
     dev = poses_c2w.device
     rays = torch.empty((n, P * ph * pw, 8), device=dev, dtype=torch.float32)
     gt = torch.empty((n, P * ph * pw, c), device=dev, dtype=torch.float32) if images is not None else None
@@ -181,14 +202,12 @@ def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w
     parts = torch.empty((B // area, 4), device=dev, dtype=torch.float32)
     g_rgb = torch.empty_like(rgb) if need_grad else None
     g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and depth is not None) else None
-    a = _lib.BtsLossArgs(rgb=rgb.data_ptr(), depth=None if depth is None else depth.data_ptr(),
-                         weights=None if (weights is None or policy != 2) else weights.data_ptr(),
-                         invalid=None if (invalid is None or not policy) else invalid.data_ptr(), rgb_gt=rgb_gt.data_ptr(),
-                         parts=parts.data_ptr(), g_rgb=None if g_rgb is None else g_rgb.data_ptr(),
-                         g_depth=None if g_depth is None else g_depth.data_ptr(), n_patches=B // area, patch_h=patch_h, patch_w=patch_w,
+    a = _lib.BtsLossArgs(rgb=rgb.data_ptr(), depth=_addr(depth), weights=_addr(weights if policy == 2 else None),
+                         invalid=_addr(invalid if policy else None), rgb_gt=rgb_gt.data_ptr(), parts=parts.data_ptr(), g_rgb=_addr(g_rgb),
+                         g_depth=_addr(g_depth), n_patches=B // area, patch_h=patch_h, patch_w=patch_w,
                          nv=nv, K=K, invalid_policy=policy, edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
-                         scale_eas=scale_eas, invalid_wsum=invalid_wsum.data_ptr() if (sums and policy == 2) else None,
-                         invalid_any=invalid_any.data_ptr() if (sums and policy == 1) else None)
+                         scale_eas=scale_eas, invalid_wsum=_addr(invalid_wsum if (sums and policy == 2) else None),
+                         invalid_any=_addr(invalid_any if (sums and policy == 1) else None))
     if area > WAVE_PATCH_PIXELS:
         # larger patches and whole frames: 16 x 16 tiles of each patch (bts_photometric_loss_tiled)
         return photometric_loss_tiled(a, parts, g_rgb, g_depth, _stream(rgb), thresh)
@@ -205,13 +224,11 @@ def photometric_loss_tiled(a, parts, g_rgb, g_depth, stream, thresh=None):
     two kernels on small patches."""
     lib = _lib.load()
     if thresh is not None:      # the same passes with the automasking bound (one more float per ray of workspace)
-        need = lib.bts_photometric_loss_tiled_automask_workspace(a.n_patches, a.patch_h, a.patch_w, a.nv)
-        ws = torch.empty((max(int(need), 1),), device=parts.device, dtype=torch.uint8)
+        ws = _scratch(parts.device, lib.bts_photometric_loss_tiled_automask_workspace(a.n_patches, a.patch_h, a.patch_w, a.nv))
         _lib.check(lib.bts_photometric_loss_tiled_automask(C.byref(a), _ptr(thresh), ws.data_ptr(), ws.numel(), stream),
                    "bts_photometric_loss_tiled_automask")
         return parts, g_rgb, g_depth
-    need = lib.bts_photometric_loss_tiled_workspace(a.n_patches, a.patch_h, a.patch_w, a.nv)
-    ws = torch.empty((max(int(need), 1),), device=parts.device, dtype=torch.uint8)
+    ws = _scratch(parts.device, lib.bts_photometric_loss_tiled_workspace(a.n_patches, a.patch_h, a.patch_w, a.nv))
     _lib.check(lib.bts_photometric_loss_tiled(C.byref(a), ws.data_ptr(), ws.numel(), stream), "bts_photometric_loss_tiled")
     return parts, g_rgb, g_depth
 
@@ -262,19 +279,17 @@ def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch
     kept = torch.empty((1,), device=dev, dtype=torch.int64) if median else None
     g_rgb = torch.empty_like(rgb) if need_grad else None
     g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and eas) else None
-    a = _lib.BtsPixelLossArgs(rgb=rgb.data_ptr(), rgb_gt=rgb_gt.data_ptr(), depth=depth.data_ptr() if eas else None,
-                              weights=weights.data_ptr() if (weights is not None and policy >= 2) else None,
-                              invalid=invalid.data_ptr() if (invalid is not None and policy) else None,
-                              invalid_wsum=invalid_wsum.data_ptr() if (sums and policy == 2) else None,
-                              invalid_any=invalid_any.data_ptr() if (sums and policy == 1) else None,
-                              rgb_samps=rgb_samps.data_ptr() if policy == 3 else None, out=out.data_ptr(),
-                              thresholds=_ptr(thresholds), kept=_ptr(kept), g_rgb=_ptr(g_rgb), g_depth=_ptr(g_depth), B=B, n=n,
+    a = _lib.BtsPixelLossArgs(rgb=rgb.data_ptr(), rgb_gt=rgb_gt.data_ptr(), depth=_addr(depth if eas else None),
+                              weights=_addr(weights if policy >= 2 else None), invalid=_addr(invalid if policy else None),
+                              invalid_wsum=_addr(invalid_wsum if (sums and policy == 2) else None),
+                              invalid_any=_addr(invalid_any if (sums and policy == 1) else None),
+                              rgb_samps=_addr(rgb_samps if policy == 3 else None), out=out.data_ptr(),
+                              thresholds=_addr(thresholds), kept=_addr(kept), g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), B=B, n=n,
                               patch_h=patch_h, patch_w=patch_w, nv=nv, K=K, criterion=PIXEL_CRITERIA[criterion], invalid_policy=policy,
                               median_thresholding=int(bool(median)), edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
                               scale_eas=scale_eas)
     lib = _lib.load()
-    need = lib.bts_pixel_loss_workspace(B, n, patch_h, patch_w)
-    ws = torch.empty((max(int(need), 1),), device=dev, dtype=torch.uint8)
+    ws = _scratch(dev, lib.bts_pixel_loss_workspace(B, n, patch_h, patch_w))
     if thresh is not None:
         _lib.check(lib.bts_pixel_loss_automask(C.byref(a), _ptr(thresh), ws.data_ptr(), ws.numel(), _stream(rgb)), "bts_pixel_loss_automask")
     else:
@@ -391,8 +406,7 @@ def project_features(spec: FieldSpec, feat_nchw: torch.Tensor, mlp_params: torch
     out = torch.empty((N, H, W, spec.d_hidden), device=feat_nchw.device, dtype=torch.float32)
     cfg = _spec_cfg(spec, N, H, W)
     if tiles is not None:
-        if tiles.dtype != torch.uint8 or not tiles.is_contiguous() or tiles.numel() != N * proj_tile_count(spec, H, W) or tiles.device != out.device:
-            raise ValueError("tiles: expected a contiguous uint8 tensor of (N, proj_tile_count) on the map's device")
+        _req_tiles(tiles, N * proj_tile_count(spec, H, W), out.device, "the map's")
     if cl:
         _lib.check(_lib.load().bts_project_features_cl(C.byref(cfg), _ptr(feat_nchw), _ptr(mlp_params), N, _ptr(tiles), _ptr(out), _stream(out)),
                    "bts_project_features_cl")
@@ -413,8 +427,8 @@ def mark_sampled_tiles(spec: FieldSpec, n: int, H: int, W: int, feat_shift: int,
     _req(rays, "rays", (src.shape[0], 8)), _req(src, "z_samp / jitter"), _req(K_enc, "K_enc", (n, 3, 3)), _req(w2c_enc, "w2c_enc", (n, 4, 4))
     cfg = _spec_cfg(spec, n, H, W, feat_shift=feat_shift)
     tiles = torch.zeros((n, proj_tile_count(spec, H >> feat_shift, W >> feat_shift)), device=rays.device, dtype=torch.uint8)
-    args = BtsRenderArgs(rays_per_sample=rays.shape[0] // n, K=src.shape[1], rays=rays.data_ptr(), z_samp=None if z_samp is None else z_samp.data_ptr(),
-                         jitter=None if z_samp is not None else jitter.data_ptr(), lindisp=int(bool(lindisp)), reserved_=0)
+    args = BtsRenderArgs(rays_per_sample=rays.shape[0] // n, K=src.shape[1], rays=rays.data_ptr(), z_samp=_addr(z_samp),
+                         jitter=_addr(jitter if z_samp is None else None), lindisp=int(bool(lindisp)), reserved_=0)
     _lib.check(_lib.load().bts_mark_sampled_tiles(C.byref(cfg), _ptr(K_enc), _ptr(w2c_enc), C.byref(args), _ptr(tiles), _stream(rays)),
                "bts_mark_sampled_tiles")
     return tiles
@@ -437,8 +451,7 @@ def project_features_bwd(spec: FieldSpec, feat_nchw, d_proj, mlp_params, need_fe
     cfg = _spec_cfg(spec, N, H, W)
     lib = _lib.load()
     if tiles is not None:
-        if tiles.dtype != torch.uint8 or not tiles.is_contiguous() or tiles.numel() != N * proj_tile_count(spec, H, W) or tiles.device != d_proj.device:
-            raise ValueError("tiles: expected a contiguous uint8 tensor of (N, proj_tile_count) on d_proj's device")
+        _req_tiles(tiles, N * proj_tile_count(spec, H, W), d_proj.device, "d_proj's")
     if cl:
         _lib.check(lib.bts_project_features_bwd_cl(C.byref(cfg), _ptr(feat_nchw), _ptr(d_proj), _ptr(tiles), _ptr(mlp_params), N, _ptr(d_feat),
                                                    _ptr(d_mlp), 1 if (clear_after and tiles is not None) else 0, _stream(d_proj)),
@@ -526,11 +539,9 @@ class FieldTensors:
         return _spec_cfg(self.spec, self.n, self.H, self.W, self.nv if nv is None else nv, self.feat_shift, self.enc_view)
 
     def tensors(self, mlp_params: torch.Tensor) -> BtsFieldTensors:
-        def dp(t):
-            return None if t is None else t.data_ptr()
-        return BtsFieldTensors(feat_nhwc=dp(self.feat_nhwc), proj_nhwc=dp(self.proj_nhwc), K_enc=dp(self.K_enc), w2c_enc=dp(self.w2c_enc),
-                               imgs_nhwc4=dp(self.imgs_nhwc4), K_r=dp(self.K_r), w2c_r=dp(self.w2c_r),
-                               empty_feature=dp(self.empty_feature), mlp_params=mlp_params.data_ptr())
+        return BtsFieldTensors(feat_nhwc=_addr(self.feat_nhwc), proj_nhwc=_addr(self.proj_nhwc), K_enc=_addr(self.K_enc), w2c_enc=_addr(self.w2c_enc),
+                               imgs_nhwc4=_addr(self.imgs_nhwc4), K_r=_addr(self.K_r), w2c_r=_addr(self.w2c_r),
+                               empty_feature=_addr(self.empty_feature), mlp_params=mlp_params.data_ptr())
 
 
 def check_supported(spec: FieldSpec, nv: int = 1):
@@ -551,11 +562,9 @@ def _render_args(ft: FieldTensors, rays, z_samp, hard_alpha_cap, white_bkgd, out
     if sigma_noise is not None:
         _req(sigma_noise, "sigma_noise", (rays.shape[0], K))
     return BtsRenderArgs(rays_per_sample=rays.shape[0] // ft.n, K=K, hard_alpha_cap=int(hard_alpha_cap),
-                         white_bkgd=int(white_bkgd), rays=rays.data_ptr(), z_samp=None if z_samp is None else z_samp.data_ptr(),
-                         sigma_noise=None if sigma_noise is None else sigma_noise.data_ptr(),
-                         jitter=None if jitter is None else jitter.data_ptr(), lindisp=int(bool(lindisp)), reserved_=0,
-                         z_samp_out=None if outs.get("z_samp") is None else outs["z_samp"].data_ptr(),
-                         **{k: (None if outs.get(k) is None else outs[k].data_ptr()) for k in _OUT_KEYS})
+                         white_bkgd=int(white_bkgd), rays=rays.data_ptr(), z_samp=_addr(z_samp), sigma_noise=_addr(sigma_noise),
+                         jitter=_addr(jitter), lindisp=int(bool(lindisp)), reserved_=0, z_samp_out=_addr(outs.get("z_samp")),
+                         **{k: _addr(outs.get(k)) for k in _OUT_KEYS})
 
 
 def render_fwd(ft: FieldTensors, mlp_params: torch.Tensor, rays: torch.Tensor, z_samp: torch.Tensor, *, hard_alpha_cap: bool,
@@ -638,11 +647,8 @@ def render_bwd(ft: FieldTensors, mlp_params, rays, z_samp, sigma_raw, trans, *, 
     if rgb_samps is not None:
         _req(rgb_samps, "rgb_samps", (B, K, ft.nv * 3))
     args = _render_args(ft, rays, z_samp, hard_alpha_cap, white_bkgd, dict(sigma_raw=sigma_raw, trans=trans, rgb_samps=rgb_samps), sigma_noise)
-
-    def dp(t):
-        return None if t is None else t.data_ptr()
-    grads = BtsRenderGrads(g_rgb=dp(g_rgb), g_depth=dp(g_depth), g_weights=dp(g_weights), g_alphas=dp(g_alphas),
-                           d_proj_nhwc=dp(d_proj), d_mlp_params=dp(d_mlp), d_empty_proj=dp(d_empty), d_proj_tiles=dp(tiles))
+    grads = BtsRenderGrads(g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), g_weights=_addr(g_weights), g_alphas=_addr(g_alphas),
+                           d_proj_nhwc=_addr(d_proj), d_mlp_params=_addr(d_mlp), d_empty_proj=_addr(d_empty), d_proj_tiles=_addr(tiles))
     lib = _lib.load()
     if ft.mlp_color:
         ws_bytes = lib.bts_render_bwd_mlp_color_workspace(C.byref(cfg), C.byref(args))
@@ -750,13 +756,13 @@ def depth_metrics(pred: torch.Tensor, gt: torch.Tensor, depth_scaling=None, clam
         out = torch.empty((B, _lib.BTS_DEPTH_METRICS_ROW), device=pred.device, dtype=torch.float32)
     else:
         _req(out, "out", (B, _lib.BTS_DEPTH_METRICS_ROW))
-    if counts is not None and (not counts.is_cuda or counts.dtype != torch.int32 or not counts.is_contiguous() or tuple(counts.shape) != (B, 5)):
-        raise BtsNativeError("counts: expected a contiguous (B, 5) int32 tensor on the GPU")
+    if counts is not None:
+        _req_as(counts, "counts", torch.int32, (B, 5))
     lib = _lib.load()
     ws_bytes = int(lib.bts_depth_metrics_workspace(B, Hg, Wg, mode))
     ws = _workspace(pred.device, max(ws_bytes, 16))
     args = _lib.BtsDepthMetrics(pred=pred.data_ptr(), H=H, W=W, gt=gt.data_ptr(), Hg=Hg, Wg=Wg, B=B, mode=mode, clamp_lo=float(clamp[0]),
-                                clamp_hi=float(clamp[1]), metrics=out.data_ptr(), counts=None if counts is None else counts.data_ptr())
+                                clamp_hi=float(clamp[1]), metrics=out.data_ptr(), counts=_addr(counts))
     _lib.check(lib.bts_depth_metrics(C.byref(args), _ptr(ws), ws_bytes, _stream(pred)), "bts_depth_metrics")
     return out
 
@@ -773,13 +779,7 @@ def nvs_metrics(pred: torch.Tensor, gt: torch.Tensor, eval_resolution, out=None)
     (B, 8) float64: ssim psnr mse ssim_c0 ssim_c1 ssim_c2 n_interior n_crop -- the image half of compute_nvs_metrics of
     models/bts/evaluator_nvs.py:141-178 per frame (bts_nvs_metrics): nearest resize to ``eval_resolution``, the 5 % crop, skimage's
     SSIM (7 x 7 uniform window, fp64) and PSNR.  ``out``: the caller's (B, 8) float64 buffer.  Nothing is copied and nothing synchronises."""
-    for t, name in ((pred, "rgb_pred"), (gt, "rgb_gt")):
-        if not isinstance(t, torch.Tensor):
-            raise BtsNativeError(f"{name}: expected a tensor")
-        if not t.is_cuda:
-            raise BtsNativeError(f"{name}: must live on the GPU (got {t.device}); the HIP renderer has no CPU path")
-        if t.dtype != torch.float32:
-            raise BtsNativeError(f"{name}: must be float32 (got {t.dtype})")
+    _req_as(pred, "rgb_pred", torch.float32, contiguous=False), _req_as(gt, "rgb_gt", torch.float32, contiguous=False)
     if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape != gt.shape:
         raise BtsNativeError(f"nvs_metrics: expected two (B, H, W, 3) views of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
     if pred.device != gt.device:
@@ -791,9 +791,8 @@ def nvs_metrics(pred: torch.Tensor, gt: torch.Tensor, eval_resolution, out=None)
     y0, y1, x0, x1 = nvs_crop_box((He, We))
     if out is None:
         out = torch.empty((B, _lib.BTS_NVS_METRICS_ROW), device=pred.device, dtype=torch.float64)
-    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64 or not out.is_contiguous() or \
-            tuple(out.shape) != (B, _lib.BTS_NVS_METRICS_ROW) or out.device != pred.device:
-        raise BtsNativeError(f"out: expected a contiguous ({B}, {_lib.BTS_NVS_METRICS_ROW}) float64 tensor on {pred.device}")
+    elif _req_as(out, "out", torch.float64, (B, _lib.BTS_NVS_METRICS_ROW)).device != pred.device:
+        raise BtsNativeError(f"out on {out.device}, rgb_pred on {pred.device}")
     lib = _lib.load()
     ws_bytes = int(lib.bts_nvs_metrics_workspace(B, He, We))
     ws = _workspace(pred.device, max(ws_bytes, 16))
@@ -808,18 +807,6 @@ def nvs_metrics(pred: torch.Tensor, gt: torch.Tensor, eval_resolution, out=None)
 # --------------------------------------------------------------------------------------------------------------
 # novel-view frames and colour-mapped depth (csrc/bts_frames.hip; the host mirrors live in novel_views.py)
 # --------------------------------------------------------------------------------------------------------------
-def _req_as(t, name, dtype, shape=None):
-    if not isinstance(t, torch.Tensor):
-        raise BtsNativeError(f"{name}: expected a tensor")
-    if not t.is_cuda:
-        raise BtsNativeError(f"{name}: must live on the GPU (got {t.device}); the HIP renderer has no CPU path")
-    if t.dtype != dtype or not t.is_contiguous():
-        raise BtsNativeError(f"{name}: must be a contiguous {dtype} tensor (got {t.dtype})")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise BtsNativeError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t
-
-
 def _req_canvas(canvas, B, h, w, row0, col0, what):
     if not isinstance(canvas, torch.Tensor) or canvas.dim() != 4 or canvas.shape[0] != B or canvas.shape[3] != 3:
         raise BtsNativeError(f"canvas: a ({B}, Hc, Wc, 3) uint8 tensor expected")
@@ -860,8 +847,7 @@ def colorize(x: torch.Tensor, N: int, lut_f64=None, lut_u8=None, norm: bool = Fa
 def pack_u8(x: torch.Tensor, canvas: torch.Tensor, row0: int = 0, col0: int = 0, scale: float = 1.0, shift: float = 0.0):
     """x (B, h, w, 3) float32 VIEW of any strides (a permuted channel-planar image) -> uint8 of x * scale + shift into ``canvas``
     (B, Hc, Wc, 3) at (row0, col0) (bts_pack_u8)."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
-        raise BtsNativeError("x: a float32 tensor on the GPU expected; the HIP renderer has no CPU path")
+    _req_as(x, "x", torch.float32, contiguous=False)
     if x.dim() != 4 or x.shape[-1] != 3 or x.numel() == 0:
         raise BtsNativeError(f"x: a non-empty (B, h, w, 3) view expected, got {tuple(x.shape)}")
     B, h, w, _ = (int(s) for s in x.shape)
@@ -887,7 +873,7 @@ def novel_views(ft: Optional["FieldTensors"], mlp_params, a: "_lib.BtsNovelViews
 # --------------------------------------------------------------------------------------------------------------
 def _conv_struct(x, weight, bias, y, N, H, W, up2, elu, out_nchw):
     return _lib.BtsConv3x3(N=N, H=H, W=W, C=x.shape[-1], up2=int(up2), elu=int(elu), out_nchw=int(out_nchw), reserved_=0, x=x.data_ptr(),
-                           weight=weight.data_ptr(), bias=None if bias is None else bias.data_ptr(), y=None if y is None else y.data_ptr())
+                           weight=weight.data_ptr(), bias=_addr(bias), y=_addr(y))
 
 
 def conv3x3_fwd(x, weight, bias, up2=False, elu=False, out_nchw=False):
@@ -972,7 +958,7 @@ def eval_frame(fr, stream, rgb_gt=None):
     if rgb_gt is not None:
         c = fr.cfg
         _req(rgb_gt, "rgb_gt", (c.n, fr.v, 3, c.H, c.W))
-    if sched is not None:
+    if sched is not None:      # (this and the prep checks run once per FRAME: one inline expression each, not a call per tensor)
         if not sched.is_cuda or sched.dtype != torch.int32 or sched.numel() < 256 or not sched.is_contiguous():
             raise BtsNativeError("sched: 256 contiguous int32 words on the device expected")
     if prep is not None:
@@ -991,11 +977,10 @@ def eval_frame(fr, stream, rgb_gt=None):
         for name, t, want in (("packed", packed, sum(sizes)), ("image", image, int(lib.bts_mlp_image_floats(C.byref(fr.cfg))))):
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < want or want <= 0):
                 raise BtsNativeError(f"prep: {name} must be {want} contiguous float32 values on the device")
-        _lib.check(lib.bts_eval_frame_prep(C.byref(fr), None if rgb_gt is None else _ptr(rgb_gt), None if sched is None else C.c_void_p(sched.data_ptr()),
-                                           C.byref(mt), _ptr(packed), None if image is None else _ptr(image), stream), "bts_eval_frame_prep")
+        _lib.check(lib.bts_eval_frame_prep(C.byref(fr), _ptr(rgb_gt), _ptr(sched), C.byref(mt), _ptr(packed), _ptr(image), stream), "bts_eval_frame_prep")
         return
     if sched is not None:
-        _lib.check(_lib.load().bts_eval_frame_sched(C.byref(fr), None if rgb_gt is None else _ptr(rgb_gt), C.c_void_p(sched.data_ptr()), stream), "bts_eval_frame_sched")
+        _lib.check(_lib.load().bts_eval_frame_sched(C.byref(fr), _ptr(rgb_gt), _ptr(sched), stream), "bts_eval_frame_sched")
         return
     if rgb_gt is None:
         _lib.check(_lib.load().bts_eval_frame(C.byref(fr), stream), "bts_eval_frame")
@@ -1010,7 +995,7 @@ def train_step_fwd(st, stream):
 
 def train_step_bwd(st, g_loss, stream):
     """bts_train_step_bwd: ``g_loss`` a 0-dim float32 device tensor (the upstream gradient of the loss) or None (= 1)."""
-    _lib.check(_lib.load().bts_train_step_bwd(C.byref(st), None if g_loss is None else C.c_void_p(g_loss.data_ptr()), stream), "bts_train_step_bwd")
+    _lib.check(_lib.load().bts_train_step_bwd(C.byref(st), _ptr(g_loss), stream), "bts_train_step_bwd")
 
 
 # --------------------------------------------------------------------------------------------------------------

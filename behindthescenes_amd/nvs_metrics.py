@@ -14,6 +14,7 @@ There is no torch fallback: CPU tensors are rejected, as everywhere else in this
 import torch
 
 from . import _lib, native
+from ._evalcommon import MetricRows, nan_skipping_means
 from ._lib import BtsNativeError
 from .depth_metrics import METRIC_KEYS as DEPTH_METRIC_KEYS, FusedDepthEval
 from .train_step import FusedEvalFrame
@@ -56,7 +57,7 @@ def compute_nvs_metrics(rgb_pred, rgb_gt, eval_resolution):
     return _as_dict(native.nvs_metrics(pred, gt, _resolution(eval_resolution))[0])
 
 
-class FusedNVSEval:
+class FusedNVSEval(MetricRows):
     """An eval_nvs frame that ends in one row of metrics on the device.
 
         ev = FusedNVSEval(wrapped, sampler, eval_resolution=(192, 640))
@@ -73,34 +74,22 @@ class FusedNVSEval:
     left out (utils/metrics.py:25-35); an infinite PSNR propagates.  Past ``capacity`` frames ``frame`` raises; it never wraps."""
 
     def __init__(self, wrapped, sampler, eval_resolution, capacity=4096):
-        if int(capacity) <= 0:
-            raise BtsNativeError(f"capacity: a positive number of frames expected, got {capacity}")
-        self.eval_resolution, self.capacity = _resolution(eval_resolution), int(capacity)
+        super().__init__(_lib.BTS_NVS_METRICS_ROW, torch.float64, capacity, "FusedNVSEval")
+        self.eval_resolution = _resolution(eval_resolution)
         self.eval_frame = FusedEvalFrame(wrapped, sampler)
         self.depth = FusedDepthEval(wrapped, sampler, None, capacity=self.capacity)
-        self.rows = None
-        self.n_frames = 0
 
     def reset(self):
-        if self.rows is not None:
-            self.rows.zero_()
-        self.n_frames = 0
+        super().reset()
         self.depth.reset()
-
-    def _full(self):
-        if self.n_frames >= self.capacity:
-            raise BtsNativeError(f"FusedNVSEval: {self.capacity} frames are stored; compute() / reset() first or construct with a larger capacity")
 
     def update(self, rgb_pred, rgb_gt):
         """The metrics of one frame from a render the caller already holds (the shapes of ``compute_nvs_metrics``): the next row."""
-        self._full()
+        self.full()
         pred, gt = _views(rgb_pred, rgb_gt)
         if not pred.is_cuda:
             raise BtsNativeError(f"rgb_pred: must live on the GPU (got {pred.device}); the HIP renderer has no CPU path")
-        if self.rows is None or self.rows.device != pred.device:
-            self.rows = torch.zeros((self.capacity, _lib.BTS_NVS_METRICS_ROW), device=pred.device, dtype=torch.float64)
-            self.n_frames = 0
-        row = self.rows[self.n_frames:self.n_frames + 1]
+        row = self.next_row(pred.device)
         native.nvs_metrics(pred, gt, self.eval_resolution, out=row)
         self.n_frames += 1
         return row[0]
@@ -113,9 +102,9 @@ class FusedNVSEval:
             size = tuple(images.shape[-2:]) if isinstance(images, torch.Tensor) and images.dim() >= 2 else None
             raise BtsNativeError(f"FusedNVSEval: eval_resolution {self.eval_resolution} is not the frame size {size}; render such a frame "
                                  "yourself (images_alt) and call compute_nvs_metrics / update on it")
-        self._full()                             # before the render, not after it
-        if depth_gt is not None and self.depth.n_frames >= self.capacity:
-            raise BtsNativeError(f"FusedNVSEval: {self.capacity} depth frames are stored; compute() / reset() first or construct with a larger capacity")
+        self.full()                              # before the render, not after it
+        if depth_gt is not None:
+            self.depth.full()
         data = self.eval_frame(images, projs, poses, to_z=False, **kwargs)
         row = self.update(data["fine"][0]["rgb"], data["rgb_gt"])
         data.update(_as_dict(row))
@@ -140,7 +129,5 @@ class FusedNVSEval:
             parts.append((DEPTH_METRIC_KEYS, host[self.n_frames * len(METRIC_KEYS):].reshape(n_depth, -1)))
         means = {}
         for keys, vals in parts:
-            keep = ~torch.isnan(vals)
-            sums, n = torch.where(keep, vals, torch.zeros_like(vals)).sum(dim=0), keep.sum(dim=0)
-            means.update({k: (sums[i].item() / int(n[i]) if int(n[i]) else float("nan")) for i, k in enumerate(keys)})
+            means.update(nan_skipping_means(vals, keys))
         return means

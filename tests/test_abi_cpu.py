@@ -152,6 +152,20 @@ def test_loss_workspace_sizes_are_the_recorded_ones(lib):
         assert lib.bts_pixel_loss_workspace(n_patches * ph * pw, 2, ph, pw) == pixel_n2
 
 
+def test_eval_workspace_sizes_are_the_recorded_ones(lib):
+    """The five evaluation workspaces count their bytes with the layout function that carves the pointers (lidar_bins_layout,
+    occ_eval_layout, bbox_eval_layout, depth_layout, nvs_layout over csrc/bts_host.h's Carver).  The literals were printed by the library
+    of the commit that introduced those functions -- every buffer rounded up to 256 bytes, plus the 256 the workspace pointer's own
+    rounding may cost -- so that the next change to a layout is a deliberate one.  Invalid arguments still size to 0."""
+    assert lib.bts_lidar_slices_workspace(3, 2) == 9216                  # T, y_res
+    assert lib.bts_occupancy_eval_workspace(1000, 3, 2) == 33536         # P, T, y_res
+    assert lib.bts_bbox_occupancy_eval_workspace(1000, 5, 12, 40) == 10496   # P, boxes, ph, pw
+    assert lib.bts_depth_metrics_workspace(2, 37, 121, 1) == 99840       # B, Hg, Wg, mode
+    assert lib.bts_nvs_metrics_workspace(2, 48, 160) == 1280             # B, He, We
+    assert (lib.bts_lidar_slices_workspace(0, 1), lib.bts_occupancy_eval_workspace(0, 1, 1), lib.bts_bbox_occupancy_eval_workspace(1, 0, 1, 1),
+            lib.bts_depth_metrics_workspace(0, 1, 1, 0), lib.bts_nvs_metrics_workspace(0, 1, 1)) == (0, 0, 0, 0, 0)
+
+
 def test_errors_are_codes_with_messages_never_exceptions(lib):
     assert lib.bts_render_fwd(None, None, None, None) == -1                       # BTS_E_INVALID
     assert b"NULL" in lib.bts_last_error()

@@ -199,6 +199,9 @@ SYMBOLS = {
     "bts_photometric_loss_tiled_automask_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "bts_photometric_loss_tiled_automask": (C.c_int, [C.POINTER(BtsLossArgs), _P, _P, C.c_size_t, _P]),
     "bts_pixel_loss_automask": (C.c_int, [C.POINTER(BtsPixelLossArgs), _P, _P, C.c_size_t, _P]),
+    # l1+ssim with median thresholding: the tiled passes joined to the radix selection (csrc/bts_loss_tiled.hip)
+    "bts_photometric_loss_median_workspace": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "bts_photometric_loss_median": (C.c_int, [C.POINTER(BtsLossArgs), _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "bts_sample_coarse": (C.c_int, [_P, _P, C.c_int64, _I, _I, _P, _P]),
     "bts_distance_to_z": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
     "bts_invert_small": (C.c_int, [_P, _P, _I, _I, _P]),

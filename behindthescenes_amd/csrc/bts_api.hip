@@ -333,6 +333,40 @@ int bts_photometric_loss_tiled_automask(const BtsLossArgs* a, const float* thres
   if (int rc = check_thresh(thresh, who)) return rc;
   return photometric_loss_tiled_entry(a, thresh, workspace, workspace_bytes, stream, who);
 }
+size_t bts_photometric_loss_median_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv, int32_t n) {
+  return loss_median_bytes(n_patches, patch_h, patch_w, nv, n);
+}
+int bts_photometric_loss_median(const BtsLossArgs* a, int32_t n, const float* thresh, float* out, float* thresholds, int64_t* kept, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  static const char who[] = "bts_photometric_loss_median";
+  if (!a || !a->rgb || !a->rgb_gt || !a->parts || !out || (a->edge_aware_smoothness && !a->depth)) {
+    set_error("%s: NULL required pointer (args, rgb, rgb_gt, parts, out; depth with edge_aware_smoothness)", who);
+    return BTS_E_INVALID;
+  }
+  if (n <= 0 || a->n_patches <= 0 || a->patch_h <= 0 || a->patch_w <= 0 || a->nv <= 0) {
+    set_error("%s: non-positive size (n, n_patches, patch_h, patch_w, nv)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->n_patches % n != 0) {
+    set_error("%s: %ld patches are not a multiple of n = %ld batch samples", who, (long)a->n_patches, (long)n);
+    return BTS_E_INVALID;
+  }
+  if (a->invalid_policy < 0 || a->invalid_policy > 2) {
+    set_error("%s: unknown invalid_policy %ld (0 none, 1 strict, 2 weight_guided)", who, (long)a->invalid_policy);
+    return BTS_E_INVALID;
+  }
+  if (int rc = check_policy_inputs(a->invalid_policy, a->invalid_any, a->invalid_wsum, a->invalid, a->weights, a->K, who)) return rc;
+  if ((long)a->n_patches * a->patch_h * a->patch_w > 2147483647L) {
+    set_error("%s: %ld patches of %ld x %ld pixels are more than 2^31 - 1 rays", who, (long)a->n_patches, (long)a->patch_h, (long)a->patch_w);
+    return BTS_E_INVALID;
+  }
+  const size_t need = loss_median_bytes(a->n_patches, a->patch_h, a->patch_w, a->nv, n);
+  if (!workspace || workspace_bytes < need) {
+    set_error("%s: workspace too small (%ld bytes needed, see bts_photometric_loss_median_workspace)", who, (long)need);
+    return BTS_E_INVALID;
+  }
+  return launched(photometric_loss_median_impl(a, n, thresh, out, thresholds, kept, workspace, (hipStream_t)stream), who);
+}
 size_t bts_pixel_loss_workspace(int64_t B, int32_t n, int32_t patch_h, int32_t patch_w) { return pixel_loss_bytes((long)B, n, patch_h, patch_w); }
 static int pixel_loss_entry(const BtsPixelLossArgs* a, const float* thresh, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
   if (!a || !a->rgb || !a->rgb_gt || !a->out || (a->edge_aware_smoothness && !a->depth)) {

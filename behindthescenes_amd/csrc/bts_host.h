@@ -91,6 +91,10 @@ int eval_handover_launch(const float* Ks, const float* poses, const float* image
 int photometric_loss_impl(const BtsLossArgs* a, hipStream_t s, const float* thresh = nullptr);
 size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv, bool with_thresh = false);
 int photometric_loss_tiled_impl(const BtsLossArgs* a, void* workspace, hipStream_t s, const float* thresh = nullptr);
+// ... with median thresholding over n batch samples (bts_loss_tiled.hip's median variant of the passes); thresh may be NULL
+size_t loss_median_bytes(int n_patches, int ph, int pw, int nv, int n);
+int photometric_loss_median_impl(const BtsLossArgs* a, int n, const float* thresh, float* out, float* thresholds, int64_t* kept, void* workspace,
+                                 hipStream_t s);
 // ---- bts_loss_pixel.hip: criteria l1 / l2, median thresholding, the diverse flags
 size_t pixel_loss_bytes(long B, int n, int ph, int pw);
 int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, const float* thresh = nullptr);

@@ -22,6 +22,22 @@
 // different d round to the same dn, where the reference sits on the kink of |.| anyway.
 // LDS: pass 1 8 planes of 324 floats + 16 partials = 10 432 bytes; pass 3 10 planes of 324 = 12 960 bytes.  Four waves share the
 // planes, so every hand-over is a real __syncthreads() (the wave kernel's wave-scope fence is not enough here).
+//
+// MEDIAN THRESHOLDING (loss.py:163-167) for l1+ssim, bts_photometric_loss_median: the same passes over a third parameter struct
+// (TiledParamsMed), joined to the exact radix selection of bts_loss_pixel.hip (bts_loss_device.h: select_bin).  Every pixel's error must
+// exist before any pixel's gradient can be written and the normaliser 1 / count is only known on the device, so:
+//   pass 1 (median)    as above with a UNIT upstream gradient (times the automasking factor when a bound is given: a run-time NULL);
+//                      e = min(e_min, t) * keep -> workspace (B); bits 31..21 of e's pattern -> the batch sample's histogram (in LDS,
+//                      flushed with integer atomics; a tile lies in one patch, a patch in one sample)
+//   hist<1>, <2>, kept ray-wise over that plane: bits 20..10, bits 9..0, then thr[sample] (rank (N - 1) / 2: torch's LOWER median) and per
+//                      work-group the sum and the number of e <= thr (ties all kept)
+//   pass 2             unchanged: parts[patch] = [sum of e BEFORE thresholding, edges / m, invalid rays, 0]
+//   final              one work-group, partials in index order: out[4] = [sum of kept e / count, sum of the smoothness term, invalid
+//                      rays, count], the count as int64, fin[0] = s_rgb / count
+//   pass 3 (median)    a neighbour q with e[q] > thr[sample] is staged with v* = -1 (it hands nothing on, whether or not the receiving
+//                      pixel is kept); the gathered sum, the centre's L1 term included, is multiplied by fin[0] -- the coefficients are
+//                      linear in the upstream gradient, so scaling after the gather is exact up to one rounding
+// LDS of the median pass 1: the 10 432 bytes above + 8 192 of histogram; pass 3 as above.
 #include <hip/hip_runtime.h>
 
 #include "bts_host.h"
@@ -68,6 +84,35 @@ struct TiledParamsThr : TiledParams {
   const float* thresh;     // (B)
   float* fthr;             // workspace (B): d min(e, thresh) / d e
 };
+
+// ... with median thresholding (loss.py:163-167; the header has the pipeline).  `thresh` may be NULL here (no automasking bound): a
+// run-time branch of this variant only.  A third type: the two above keep their arguments and their code
+struct TiledParamsMed : TiledParamsThr {
+  float* out;              // (4)
+  float* thresholds;       // (n) or NULL
+  long long* kept;         // (1) or NULL
+  int n, pps;              // batch samples, patches per sample
+  long Bs;                 // rays per sample
+  int blocks_per_sample;   // work-groups of 256 rays per sample (hist / kept kernels)
+  long n_blocks;
+  // workspace
+  float* e;                // (B): min(e_min, t) * keep
+  unsigned* hist;          // (n, 3, 2048)
+  unsigned* state;         // (n, 8): [0, 1] prefix and rank after the first histogram, [4, 5] after the second
+  float* thr;              // (n)
+  float* blk_sum;          // (n_blocks) sum of the kept e
+  unsigned* blk_cnt;       // (n_blocks) kept pixels
+  float* fin;              // [0] = s_rgb / count
+};
+// (the names of bts_loss_pixel.hip's kBins, kHistSample, kStateSample are taken where both files share a translation unit: tools/loss_workspace_check.hip)
+constexpr int kMedBins = 2048;
+constexpr int kMedHistSample = 3 * kMedBins;      // three radix passes per batch sample
+constexpr int kMedStateSample = 8;
+// the tile's histogram of the median pass 1: LDS of the kernels that call this, and of no other
+__device__ __forceinline__ unsigned* med_hist() {
+  __shared__ unsigned s_hist[kMedBins];
+  return s_hist;
+}
 
 // gauss9 (bts_loss_device.h) of the product of two planes, in its order of additions
 __device__ __forceinline__ float gauss9_prod(const float* pa, const float* pb, int ctr) {
@@ -118,6 +163,7 @@ __global__ __launch_bounds__(256) void loss_tiled_keep(const TiledParams p) {
 template <class P>
 __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_tiles) {
   constexpr bool kThr = std::is_same<P, TiledParamsThr>::value;
+  constexpr bool kMed = std::is_same<P, TiledParamsMed>::value;
   __shared__ float sY[3][kHalo], sX[3][kHalo], sD[kHalo], sK[kHalo];
   __shared__ float sRed[4][4];
   const int tid = threadIdx.x;
@@ -125,6 +171,8 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
   if (blk != blockIdx.x) __syncthreads();      // the previous tile's readers are done with the planes and sRed
   const TilePos tp = tile_pos(p, blk);
   const int ph = p.ph, pw = p.pw, nv = p.nv;
+  if constexpr (kMed)      // (the barriers below stand between this, the atomics and the flush)
+    for (int i = tid; i < kMedBins; i += 256) med_hist()[i] = 0u;
 
   // ---- halo: ground truth, keep flag, d = 1 / clamp(depth); zero outside the patch (the SSIM window's zero padding)
   for (int i = tid; i < kHalo; i += 256) {
@@ -192,7 +240,22 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
     }
   }
   float up = keep * p.s_rgb;             // d loss / d e_{v*}(this pixel)
-  if constexpr (kThr) {
+  if constexpr (kMed) {
+    // a UNIT upstream gradient: the normaliser s_rgb / count is pass 3's, once the count is known
+    float f = 1.0f;
+    if (p.thresh) {
+      const float t = act ? p.thresh[ray] : 0.0f;
+      f = min_grad_factor(e_min, t);
+      e_min = fminf(e_min, t);
+    }
+    up = keep * f;
+    if (act) {
+      if (p.g_rgb) p.fthr[ray] = f;
+      const float e = e_min * keep;        // >= 0: the order of the bit patterns is the order of the values
+      p.e[ray] = e;
+      atomicAdd(&med_hist()[__float_as_uint(e) >> 21], 1u);
+    }
+  } else if constexpr (kThr) {
     const float t = act ? p.thresh[ray] : 0.0f;
     const float f = min_grad_factor(e_min, t);
     up = up * f;
@@ -261,6 +324,13 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
     o.w = ((sRed[0][3] + sRed[1][3]) + sRed[2][3]) + sRed[3][3];
     p.tile_parts[blk] = o;
   }
+  if constexpr (kMed) {      // the tile's non-zero bins into its sample's first histogram (the barrier above is behind the atomics)
+    unsigned* dst = p.hist + (size_t)(tp.patch / p.pps) * kMedHistSample;
+    for (int i = tid; i < kMedBins; i += 256) {
+      const unsigned c = med_hist()[i];
+      if (c) atomicAdd(&dst[i], c);
+    }
+  }
   }
 }
 
@@ -290,6 +360,7 @@ __global__ __launch_bounds__(64) void loss_tiled_pass2(const TiledParams p) {
 template <class P>
 __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_tiles) {
   constexpr bool kThr = std::is_same<P, TiledParamsThr>::value;
+  constexpr bool kMed = std::is_same<P, TiledParamsMed>::value;
   __shared__ float sC[9][kHalo];
   __shared__ int sV[kHalo];
   const int tid = threadIdx.x;
@@ -297,6 +368,10 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_
   if (blk != blockIdx.x) __syncthreads();      // the previous tile's readers are done with the planes
   const TilePos tp = tile_pos(p, blk);
   const int ph = p.ph, pw = p.pw, nv = p.nv;
+  float thr_s = 0.0f, fin = 0.0f;              // median: the sample's threshold, s_rgb / count
+  if constexpr (kMed) {
+    if (p.g_rgb) thr_s = p.thr[tp.patch / p.pps], fin = p.fin[0];
+  }
   if (p.g_rgb) {
     for (int i = tid; i < kHalo; i += 256) {
       const int hy = i / kLd, hx = i - hy * kLd;
@@ -306,6 +381,9 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_
       if (qy >= 0 && qy < ph && qx >= 0 && qx < pw) {
         const long q = tp.base + (long)qy * pw + qx;
         vs = p.vstar[q];
+        if constexpr (kMed) {
+          if (p.e[q] > thr_s) vs = -1;        // a dropped pixel hands nothing on (its kept neighbours still hand to it)
+        }
 #pragma unroll
         for (int j = 0; j < 9; ++j) k[j] = p.coef[(long)j * p.B + q];
       }
@@ -329,7 +407,10 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_
       for (int c = 0; c < 3; ++c) vq[r * 3 + c] = sV[ctr + (r - 1) * kLd + (c - 1)];
     const float y[3] = {p.rgb_gt[ray * 3], p.rgb_gt[ray * 3 + 1], p.rgb_gt[ray * 3 + 2]};
     float up_c = p.s_rgb;                 // the centre's upstream gradient when it is kept
-    if constexpr (kThr) up_c = up_c * p.fthr[ray];
+    if constexpr (kMed)
+      up_c = p.fthr[ray];                 // (unit upstream gradient in pass 1: `fin` scales the sum below)
+    else if constexpr (kThr)
+      up_c = up_c * p.fthr[ray];
     for (int v = 0; v < nv; ++v) {
       unsigned m = 0;
 #pragma unroll
@@ -347,7 +428,11 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_
                     t_xy = gauss9_masked(sC[c * 3 + 2], ctr, m);
         // the L1 term's gradient: a centre with v* >= 0 is kept, so its upstream gradient is s_rgb
         const float g_l1 = (m & 16u) ? up_c * (0.15f / 3.0f) * sign0(x - y[c]) : 0.0f;
-        dst[c] = t_mu + 2.0f * x * t_xx + y[c] * t_xy + g_l1;
+        const float g = t_mu + 2.0f * x * t_xx + y[c] * t_xy + g_l1;
+        if constexpr (kMed)
+          dst[c] = g * fin;
+        else
+          dst[c] = g;
       }
     }
   }
@@ -361,6 +446,121 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_
     }
     p.g_depth[ray] = g;
   }
+  }
+}
+
+// ---- median thresholding: the ray-wise kernels over the one-channel plane e (B), modelled on bts_loss_pixel.hip's hist / kept / final
+// (three channels per ray there, one here; the selection itself is the shared select_bin).  Work-groups of 256 rays that never straddle
+// two samples: which sample and which ray a thread takes
+struct MedRay {
+  int sample;
+  long ray;
+  bool act;
+};
+__device__ __forceinline__ MedRay med_ray(const TiledParamsMed& p) {
+  MedRay r;
+  r.sample = (int)(blockIdx.x / p.blocks_per_sample);
+  const long in_sample = (long)(blockIdx.x - (unsigned)r.sample * p.blocks_per_sample) * 256 + threadIdx.x;
+  r.act = in_sample < p.Bs;
+  r.ray = (long)r.sample * p.Bs + (r.act ? in_sample : 0);
+  return r;
+}
+
+// radix passes 1 and 2 of a sample's median.  What a work-group notes down (the prefix and the rank inside it) is read by the NEXT launch only
+template <int PASS>
+__global__ __launch_bounds__(256) void loss_med_hist(const TiledParamsMed p) {
+  __shared__ unsigned s_scan[256];
+  __shared__ unsigned s_sel[2];
+  unsigned* s_hist = med_hist();
+  const MedRay r = med_ray(p);
+  unsigned* hist_s = p.hist + (size_t)r.sample * kMedHistSample;
+  unsigned* state_s = p.state + (size_t)r.sample * kMedStateSample;
+  for (int i = threadIdx.x; i < kMedBins; i += 256) s_hist[i] = 0u;
+  unsigned want;
+  if (PASS == 1) {
+    select_bin<false>(hist_s, 1, 0u, s_scan, s_sel);
+    want = s_sel[0];
+    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[0] = want, state_s[1] = s_sel[1];
+  } else {
+    select_bin<false>(hist_s + kMedBins, 0, state_s[1], s_scan, s_sel);
+    want = (state_s[0] << 11) | s_sel[0];
+    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[4] = want, state_s[5] = s_sel[1];
+  }
+  __syncthreads();
+  if (r.act) {
+    const unsigned key = __float_as_uint(p.e[r.ray]);
+    if (PASS == 1) {
+      if ((key >> 21) == want) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u);
+    } else {
+      if ((key >> 10) == want) atomicAdd(&s_hist[key & 1023u], 1u);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kMedBins; i += 256) {
+    const unsigned c = s_hist[i];
+    if (c) atomicAdd(&hist_s[PASS * kMedBins + i], c);
+  }
+}
+
+// thr[sample] = the value whose pattern is the 22-bit prefix and the last histogram's bin; the kept set e <= thr of this work-group's rays:
+// its sum (butterfly per wave, then the four waves in order) and its size
+__global__ __launch_bounds__(256) void loss_med_kept(const TiledParamsMed p) {
+  __shared__ unsigned s_scan[256];
+  __shared__ unsigned s_sel[2];
+  __shared__ float s_f[4];
+  __shared__ unsigned s_u[4];
+  const MedRay r = med_ray(p);
+  const unsigned* state_s = p.state + (size_t)r.sample * kMedStateSample;
+  select_bin<false>(p.hist + (size_t)r.sample * kMedHistSample + 2 * kMedBins, 0, state_s[5], s_scan, s_sel);
+  const float thr = __uint_as_float((state_s[4] << 10) | s_sel[0]);
+  if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) {
+    p.thr[r.sample] = thr;
+    if (p.thresholds) p.thresholds[r.sample] = thr;
+  }
+  float sum = 0.0f;
+  unsigned cnt = 0u;
+  if (r.act) {
+    const float e = p.e[r.ray];
+    if (e <= thr) sum = e, cnt = 1u;
+  }
+  sum = wave_sum(sum), cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) s_f[threadIdx.x >> 6] = sum, s_u[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    p.blk_sum[blockIdx.x] = ((s_f[0] + s_f[1]) + s_f[2]) + s_f[3];
+    p.blk_cnt[blockIdx.x] = ((s_u[0] + s_u[1]) + s_u[2]) + s_u[3];
+  }
+}
+
+// one work-group: thread t takes partials t, t + 256, ... in order, then the waves' butterflies, then the four waves in order.  The
+// smoothness term: pass 2's per-patch terms added in fp64 and rounded once (the fp32 number nearest to their sum); the invalid rays:
+// pass 2's per-patch counts (whole numbers below 2^24) added as integers
+__global__ __launch_bounds__(256) void loss_med_final(const TiledParamsMed p) {
+  __shared__ float s_f[4];
+  __shared__ double s_d[4];
+  __shared__ unsigned long long s_c[2][4];
+  float sum = 0.0f;
+  double eas = 0.0;
+  unsigned long long cnt = 0ull, inv = 0ull;
+  for (long i = threadIdx.x; i < p.n_blocks; i += 256) sum += p.blk_sum[i], cnt += p.blk_cnt[i];
+  for (long i = threadIdx.x; i < p.n_patches; i += 256) eas += p.parts[i * 4 + 1], inv += (unsigned long long)p.parts[i * 4 + 2];
+  sum = wave_sum(sum);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64), inv += __shfl_xor(inv, off, 64), eas += __shfl_xor(eas, off, 64);
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    s_f[w] = sum, s_c[0][w] = cnt, s_c[1][w] = inv, s_d[w] = eas;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long count = s_c[0][0] + s_c[0][1] + s_c[0][2] + s_c[0][3];
+    const unsigned long long bad = s_c[1][0] + s_c[1][1] + s_c[1][2] + s_c[1][3];
+    p.out[0] = (((s_f[0] + s_f[1]) + s_f[2]) + s_f[3]) / (float)count;
+    p.out[1] = (float)(((s_d[0] + s_d[1]) + s_d[2]) + s_d[3]);
+    p.out[2] = (float)bad;
+    p.out[3] = (float)count;
+    if (p.kept) p.kept[0] = (long long)count;
+    p.fin[0] = p.s_rgb / (float)count;
   }
 }
 
@@ -378,7 +578,72 @@ inline void tiled_layout(Carver& w, TiledParamsThr& p, size_t n_patches, size_t 
   p.fthr = with_thresh ? w.take<float>(B) : nullptr;
 }
 
+// THE layout of bts_photometric_loss_median's workspace: the tiled layout with the gradient factors, then e, the histograms, the
+// selection state, the thresholds, two partials per work-group of 256 rays, the final words
+inline void median_layout(Carver& w, TiledParamsMed& p, size_t n_patches, size_t n_tiles, size_t B, size_t n, size_t n_blocks) {
+  tiled_layout(w, p, n_patches, n_tiles, B, true);
+  p.e = w.take<float>(B);
+  p.hist = w.take<unsigned>(n * kMedHistSample);
+  p.state = w.take<unsigned>(n * kMedStateSample);
+  p.thr = w.take<float>(n);
+  p.blk_sum = w.take<float>(n_blocks);
+  p.blk_cnt = w.take<unsigned>(n_blocks);
+  p.fin = w.take<float>(4);
+}
+inline size_t median_blocks_per_sample(size_t n_patches, size_t n, int ph, int pw) { return (n_patches / n * (size_t)ph * (size_t)pw + 255) / 256; }
+
 }  // namespace
+
+size_t loss_median_bytes(int n_patches, int ph, int pw, int nv, int n) {
+  if (n_patches <= 0 || ph <= 0 || pw <= 0 || nv <= 0 || n <= 0 || n_patches % n != 0) return 0;
+  Carver count(nullptr);
+  TiledParamsMed p;
+  median_layout(count, p, (size_t)n_patches, (size_t)n_patches * (size_t)tiles_of(ph, pw), (size_t)n_patches * (size_t)ph * (size_t)pw, (size_t)n,
+                (size_t)n * median_blocks_per_sample((size_t)n_patches, (size_t)n, ph, pw));
+  return count.bytes();
+}
+
+int photometric_loss_median_impl(const BtsLossArgs* a, int n, const float* thresh, float* out, float* thresholds, int64_t* kept, void* workspace,
+                                 hipStream_t s) {
+  TiledParamsMed p;
+  p.rgb = a->rgb, p.depth = a->depth, p.weights = a->weights, p.invalid = a->invalid, p.rgb_gt = a->rgb_gt;
+  p.invalid_wsum = a->invalid_wsum, p.invalid_any = a->invalid_any;
+  p.parts = a->parts, p.g_rgb = a->g_rgb, p.g_depth = a->g_depth;
+  p.n_patches = a->n_patches, p.ph = a->patch_h, p.pw = a->patch_w, p.nv = a->nv, p.K = a->K, p.policy = a->invalid_policy;
+  p.s_rgb = a->scale_rgb, p.s_eas = a->scale_eas, p.has_eas = a->edge_aware_smoothness;
+  p.tiles_x = (p.pw + kTile - 1) / kTile;
+  p.tiles = (int)tiles_of(p.ph, p.pw);
+  p.B = (long)p.n_patches * p.ph * p.pw;
+  p.thresh = thresh;
+  p.out = out, p.thresholds = thresholds, p.kept = (long long*)kept;
+  p.n = n, p.pps = p.n_patches / n, p.Bs = p.B / n;
+  p.blocks_per_sample = (int)median_blocks_per_sample((size_t)p.n_patches, (size_t)n, p.ph, p.pw);
+  p.n_blocks = (long)n * p.blocks_per_sample;
+  const size_t nt = (size_t)p.n_patches * (size_t)p.tiles;
+  Carver carve(workspace);
+  median_layout(carve, p, (size_t)p.n_patches, nt, (size_t)p.B, (size_t)n, (size_t)p.n_blocks);
+  const TiledParams& base = p;
+  p.vec4 = p.nv == 1 && p.K > 0 && (p.K & 3) == 0 && ((uintptr_t)p.invalid & 15) == 0 && ((uintptr_t)p.weights & 15) == 0;
+  const unsigned grid = (unsigned)((long)nt < kMaxGrid ? (long)nt : kMaxGrid);
+  const unsigned grid2 = (unsigned)(p.n_patches < kMaxGrid ? (long)p.n_patches : kMaxGrid);
+  const unsigned gridr = (unsigned)p.n_blocks;
+  if (hipMemsetAsync(p.hist, 0, (size_t)n * kMedHistSample * sizeof(unsigned), s) != hipSuccess) {
+    set_error("%s: clearing the histograms failed", "bts_photometric_loss_median");
+    return BTS_E_LAUNCH;
+  }
+  if (p.policy != 0) {
+    const long kb = (p.B + 255) / 256;
+    loss_tiled_keep<<<(unsigned)(kb < kMaxGrid ? kb : kMaxGrid), 256, 0, s>>>(base);
+  }
+  loss_tiled_pass1<TiledParamsMed><<<grid, 256, 0, s>>>(p, (long)nt);
+  loss_med_hist<1><<<gridr, 256, 0, s>>>(p);
+  loss_med_hist<2><<<gridr, 256, 0, s>>>(p);
+  loss_med_kept<<<gridr, 256, 0, s>>>(p);
+  loss_tiled_pass2<<<grid2, 64, 0, s>>>(base);
+  loss_med_final<<<1, 256, 0, s>>>(p);
+  if (p.g_rgb || p.g_depth) loss_tiled_pass3<TiledParamsMed><<<grid, 256, 0, s>>>(p, (long)nt);
+  return launch_check("%s: median loss kernel launch failed (%ld)");
+}
 
 size_t loss_tiled_bytes(int n_patches, int ph, int pw, int nv, bool with_thresh) {
   if (n_patches < 0 || ph <= 0 || pw <= 0 || nv <= 0) return 0;

@@ -10,7 +10,9 @@ pixels (every shipped config: ``patch_size: 8``) one wave takes one patch; above
 three); ``native.photometric_loss`` chooses.  With the config key ``native_pixel_loss: true`` the reference's other options run on
 HIP kernels too: criterion "l1" / "l2" with or without ``median_thresholding`` under any invalid policy (``bts_pixel_loss``,
 csrc/bts_loss_pixel.hip: ``native.pixel_loss``), and "l1+ssim" under ``weight_guided_diverse`` (``bts_loss_diverse_flags``, then the
-kernels above under the strict policy); "l1+ssim" with median thresholding stays refused.  With ``native_automask: true``
+kernels above under the strict policy).  With ``native_ssim_median: true`` "l1+ssim" with ``median_thresholding`` runs on the median
+variant of the tiled passes (``bts_photometric_loss_median``, csrc/bts_loss_tiled.hip: ``native.photometric_loss_median``; every patch
+size, per scale and batch sample its own threshold, the rgb term normalised by the kept count on the device).  With ``native_automask: true``
 ``use_automasking=True`` runs on the same kernels' ``_automask`` entry points: ``rgb_gt`` then carries the error map of
 ``automask.automask_images`` as a fourth channel, which bounds every pixel's error (``min(e, thresh)`` after the minimum over the views,
 before the invalid-ray mask and the median ranking; torch's binary-min gradient, a tie taking half).  The reference renders that fourth
@@ -48,6 +50,30 @@ class _PhotometricSums(torch.autograd.Function):
         d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
         d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
         return d_rgb, d_depth, None, None, None, None, None, None, None, None, None, None
+
+
+class _MedianTerms(torch.autograd.Function):
+    """(rgb term, sum of the smoothness term, number of invalid rays) of l1+ssim with median thresholding
+    (``native.photometric_loss_median``); the rgb term arrives normalised by the kept count; differentiable w.r.t. rgb, depth."""
+
+    @staticmethod
+    def forward(ctx, rgb, depth, weights, invalid, rgb_gt, n, ph, pw, policy, eas, invalid_wsum=None, invalid_any=None, thresh=None):
+        ctx.set_materialize_grads(False)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out, _, _, g_rgb, g_depth = native.photometric_loss_median(rgb, depth if eas else None, weights, invalid, rgb_gt, n, ph, pw, policy, eas,
+                                                                   1.0, 1.0, need_grad=need, invalid_wsum=invalid_wsum,
+                                                                   invalid_any=invalid_any, thresh=thresh)
+        ctx.save_for_backward(g_rgb, g_depth)
+        return out[:3]
+
+    @staticmethod
+    def backward(ctx, g):
+        g_rgb, g_depth = ctx.saved_tensors
+        if g is None:
+            return (None,) * 13
+        d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
+        d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
+        return (d_rgb, d_depth) + (None,) * 11
 
 
 class _PixelTerms(torch.autograd.Function):
@@ -171,9 +197,12 @@ class ReconstructionLoss:
             raise NotImplementedError("use_automasking=True runs on the HIP loss kernels' threshold variants with the config key "
                                       "`native_automask: true` (rgb_gt then carries automask.automask_images' error map as a fourth "
                                       "channel; the rendered rgb keeps 3); got " + got)
-        if self.criterion_str == "l1+ssim" and self.median_thresholding:
-            raise NotImplementedError("criterion 'l1+ssim' with median_thresholding=True is not covered by the HIP loss (the SSIM gradient "
-                                      "couples neighbouring pixels: the mask would have to enter the tile kernel's coefficient gather); got " + got)
+        # opt-in: l1+ssim with median thresholding on bts_photometric_loss_median (the median variant of the tiled passes)
+        self.native_ssim_median = bool(config.get("native_ssim_median", False))
+        self.ssim_median = self.criterion_str == "l1+ssim" and bool(self.median_thresholding)
+        if self.ssim_median and not self.native_ssim_median:
+            raise NotImplementedError("criterion 'l1+ssim' with median_thresholding=True runs on the HIP loss' median variant of the tiled "
+                                      "passes with the config key `native_ssim_median: true`; got " + got)
         if (self.pixel_criterion or self.diverse) and not self.native_pixel_loss:
             raise NotImplementedError("the fused HIP loss covers criterion 'l1+ssim' with invalid_policy strict / weight_guided / none, "
                                       "without automasking / median thresholding (every shipped config); criterion 'l1' / 'l2' (with or "
@@ -203,23 +232,26 @@ class ReconstructionLoss:
         if c != 3:
             raise NotImplementedError("the fused HIP loss takes 3 colour channels")
         B = n * pc * h * w
+        # with median thresholding the same arguments go to _MedianTerms with the number of batch samples (and come back as terms, the
+        # rgb one normalised by the kept count: _photometric)
+        fn = (lambda *a: _MedianTerms.apply(*a[:5], n, *a[5:])) if self.ssim_median else _PhotometricSums.apply
         if self.diverse:
             # l1+ssim under weight_guided_diverse: the per-(ray, view) flags (bts_loss_diverse_flags) as `invalid_any` of the strict
             # policy, whose all_v(flag > .5) is the diverse rule -- the shipped loss kernels serve it unchanged
-            sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
-                                          rgb_gt, h, w, "strict", eas, None, self._diverse_flags(level0), *bound)
+            sums = fn(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
+                      rgb_gt, h, w, "strict", eas, None, self._diverse_flags(level0), *bound)
             return sums, B
         if "weights" not in level0:     # lean training outputs: the renderer's epilogue reduced weights / invalid per ray and view
-            sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
-                                          rgb_gt, h, w, self.invalid_policy, eas,
-                                          _flat(level0["invalid_wsum"], (nv,)).detach() if self.invalid_policy == "weight_guided" else None,
-                                          _flat(level0["invalid_any"], (nv,)).detach() if self.invalid_policy == "strict" else None, *bound)
+            sums = fn(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
+                      rgb_gt, h, w, self.invalid_policy, eas,
+                      _flat(level0["invalid_wsum"], (nv,)).detach() if self.invalid_policy == "weight_guided" else None,
+                      _flat(level0["invalid_any"], (nv,)).detach() if self.invalid_policy == "strict" else None, *bound)
             return sums, B
         K = level0["weights"].shape[-1]
-        sums = _PhotometricSums.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None,
-                                      _flat(level0["weights"], (K,)).detach() if self.invalid_policy == "weight_guided" else None,
-                                      _flat(level0["invalid"], (K, nv)).detach() if self.ignore_invalid else None,
-                                      rgb_gt, h, w, self.invalid_policy, eas, *((None, None) + bound if bound else ()))
+        sums = fn(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None,
+                  _flat(level0["weights"], (K,)).detach() if self.invalid_policy == "weight_guided" else None,
+                  _flat(level0["invalid"], (K, nv)).detach() if self.ignore_invalid else None,
+                  rgb_gt, h, w, self.invalid_policy, eas, *((None, None) + bound if bound else ()))
         return sums, B
 
     def _diverse_inputs(self, level0):
@@ -270,6 +302,8 @@ class ReconstructionLoss:
             terms, B = self._pixel(level, level0, gt, eas)
             return terms[0], terms[1] / B, terms[2] / B
         sums, B = self._sums(level, level0, gt, eas)
+        if self.ssim_median:      # (the rgb term arrives as sum of kept e / count)
+            return sums[0], sums[1] / B, sums[2] / B
         return sums[0] / B, sums[1] / B, sums[2] / B
 
     _KEYS = ["loss_rgb_coarse", "loss_rgb_fine", "loss_ray_entropy", "loss_depth_reg", "loss_alpha_reg", "loss_eas",
@@ -338,7 +372,7 @@ class ReconstructionLoss:
                 self._flags = None
 
     def _call(self, data):
-        if not self.pixel_criterion and not (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0 or self.lambda_depth_smoothness > 0
+        if not self.pixel_criterion and not self.ssim_median and not (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0 or self.lambda_depth_smoothness > 0
                 or self.lambda_entropy > 0):
             res = self._call_photometric_only(data)
             if res is not None:

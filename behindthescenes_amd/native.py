@@ -297,6 +297,62 @@ def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch
     return out, thresholds, kept, g_rgb, g_depth
 
 
+def photometric_loss_median(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch_w: int, invalid_policy, eas: bool,
+                            scale_rgb: float = 1.0, scale_eas: float = 1.0, need_grad: bool = True, invalid_wsum=None, invalid_any=None,
+                            thresh=None, parts=None):
+    """Criterion "l1+ssim" with median thresholding (bts_photometric_loss_median, csrc/bts_loss_tiled.hip): the flat layout of
+    ``photometric_loss`` -- rgb (B, nv*3), depth (B) | None, weights (B, K) | None, invalid (B, K, nv) | None, rgb_gt (B, 3), thresh (B) |
+    None (the automasking bound) -- in ``n`` batch samples of B / n rays each, every sample a whole number of patch_h x patch_w patches of
+    any size.  ``parts`` (B / (ph*pw), 4) | None: receives the per-patch sums [e before thresholding, smoothness term, invalid rays, 0]
+    (allocated here when not given).
+    -> out (4) = [sum of kept e / count, sum of the smoothness term, invalid rays, count], thresholds (n), kept (1) int64,
+    g_rgb (B, nv*3) | None = scale_rgb * d out[0] / d rgb, g_depth (B) | None = scale_eas * d out[1] / d depth."""
+    if invalid_policy not in INVALID_POLICIES:
+        raise BtsNativeError(f"photometric_loss_median: invalid_policy {invalid_policy!r} is not one of none / strict / weight_guided (the "
+                             "diverse rule goes in as invalid_any under strict: loss_diverse_flags)")
+    B = rgb_gt.shape[0]
+    area = patch_h * patch_w
+    if n <= 0 or area <= 0 or B % (n * area):
+        raise BtsNativeError(f"{B} rays are not {n} samples of whole {patch_h}x{patch_w} patches")
+    nv = rgb.shape[-1] // 3
+    policy = INVALID_POLICIES[invalid_policy]
+    _req(rgb, "rgb", (B, nv * 3)), _req(rgb_gt, "rgb_gt", (B, 3))
+    K = 0
+    sums = (policy == 2 and invalid_wsum is not None) or (policy == 1 and invalid_any is not None)
+    if sums:
+        _req(invalid_wsum if policy == 2 else invalid_any, "invalid_wsum / invalid_any", (B, nv))
+        weights = invalid = None
+    elif policy:
+        K = invalid.shape[1]
+        _req(invalid, "invalid", (B, K, nv))
+        if policy == 2:
+            _req(weights, "weights", (B, K))
+    if eas:
+        _req(depth, "depth", (B,))
+    if thresh is not None:
+        _req(thresh, "thresh", (B,))
+    dev = rgb.device
+    if parts is None:
+        parts = torch.empty((B // area, 4), device=dev, dtype=torch.float32)
+    _req(parts, "parts", (B // area, 4))
+    out = torch.empty((4,), device=dev, dtype=torch.float32)
+    thresholds = torch.empty((n,), device=dev, dtype=torch.float32)
+    kept = torch.empty((1,), device=dev, dtype=torch.int64)
+    g_rgb = torch.empty_like(rgb) if need_grad else None
+    g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and eas) else None
+    a = _lib.BtsLossArgs(rgb=rgb.data_ptr(), depth=_addr(depth if eas else None), weights=_addr(weights if policy == 2 else None),
+                         invalid=_addr(invalid if policy else None), rgb_gt=rgb_gt.data_ptr(), parts=parts.data_ptr(), g_rgb=_addr(g_rgb),
+                         g_depth=_addr(g_depth), n_patches=B // area, patch_h=patch_h, patch_w=patch_w,
+                         nv=nv, K=K, invalid_policy=policy, edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
+                         scale_eas=scale_eas, invalid_wsum=_addr(invalid_wsum if (sums and policy == 2) else None),
+                         invalid_any=_addr(invalid_any if (sums and policy == 1) else None))
+    lib = _lib.load()
+    ws = _scratch(dev, lib.bts_photometric_loss_median_workspace(B // area, patch_h, patch_w, nv, n))
+    _lib.check(lib.bts_photometric_loss_median(C.byref(a), n, _ptr(thresh), _ptr(out), _ptr(thresholds), _ptr(kept), ws.data_ptr(), ws.numel(),
+                                               _stream(rgb)), "bts_photometric_loss_median")
+    return out, thresholds, kept, g_rgb, g_depth
+
+
 def automask_errors(images: torch.Tensor, ids_loss, scale: float = 0.5, want_errors: bool = True, want_images4: bool = False):
     """The error map of use_automasking (trainer.py:203-206; bts_automask_errors, csrc/bts_automask.hip): images (n, v, 3, H, W), the
     processed frames in [0, 1]; ids_loss: 1 .. BTS_MAX_VIEWS frame indices in [0, v) -> errors (n, v, H, W) | None, images4

@@ -397,6 +397,40 @@ size_t bts_photometric_loss_tiled_automask_workspace(int32_t n_patches, int32_t 
 int bts_photometric_loss_tiled_automask(const BtsLossArgs* args, const float* thresh, void* workspace, size_t workspace_bytes, void* stream);
 int bts_pixel_loss_automask(const BtsPixelLossArgs* args, const float* thresh, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Criterion "l1+ssim" WITH median_thresholding (loss.py:151-167): bts_photometric_loss_tiled's passes over the same BtsLossArgs, joined to
+ * bts_pixel_loss' exact radix selection (csrc/bts_loss_tiled.hip has the pipeline: up to eight launches and one memset on one stream).
+ * Patches of ANY size go through the 16 x 16 tiles, the 8 x 8 training patch included (it then uses a quarter of a work-group's lanes;
+ * bts_photometric_loss' wave kernel sees one patch per wave and cannot rank another patch's errors).  n: batch samples, n_patches a
+ * multiple of it, every sample n_patches / n consecutive patches.  thresh (B) or NULL: the automasking bound of the _automask entry points.
+ * With e[p] = min(min_v e_v[p], thresh[p]) * keep[p], ONE value per pixel:
+ *   thr[sample] = the element of rank (N - 1) / 2 of the sample's N = B / n values ascending; kept = { p : e[p] <= thr[sample of p] };
+ *   out (4) = [sum of the kept e / count, sum over the rays of the smoothness term, number of invalid rays, count as a float], count = the
+ *   size of the kept set over ALL samples; thresholds (n) and kept (1, the count as an integer) are optional.
+ * args->parts (n_patches, 4) per patch: column 0 the sum of e BEFORE thresholding, columns 1 and 2 bts_photometric_loss_tiled's values bit
+ * for bit (the smoothness passes are that entry's: out[1] is the fp32 number nearest to the sum of column 1, g_depth is its g_depth).
+ * g_rgb (B, nv, 3) = scale_rgb * d out[0] / d rgb, g_depth (B) = scale_eas * d out[1] / d depth; both NULL: forward only.
+ * The reference's quirks, kept on purpose:
+ *   - the threshold is torch's LOWER median (rank (N - 1) / 2, not N / 2), exact: thr is an element of e, bit for bit;
+ *   - the kept set is e <= thr: ties at the threshold are ALL kept;
+ *   - ONE count over all samples divides the sum (not a mean of per-sample means);
+ *   - invalid rays rank as zeros (e * keep is ranked): a sample with more than half of its rays invalid has threshold 0 and keeps only zeros;
+ *   - the automasking bound is applied BEFORE the keep factor and before the ranking;
+ *   - a pixel whose two best views tie exactly goes to the FIRST of them, as in every l1+ssim entry here (the reference's amin would
+ *     split the gradient; the tests keep every pixel's two smallest e_v apart).
+ * No gradient flows through the threshold; a kept pixel's upstream gradient is 1 / count and it hands its SSIM coefficients to its 3 x 3
+ * neighbours whether or not those are kept themselves; a dropped pixel hands on nothing.  No float atomics (integer atomics build the
+ * histograms, every float sum is a fixed-order sum of partials): reruns are bit-identical.
+ * `workspace`: at least bts_photometric_loss_median_workspace(n_patches, patch_h, patch_w, nv, n) bytes of device memory (the tiled
+ * automask layout plus one float per ray and 24 KB per batch sample; any alignment; contents need not be initialised or kept; the
+ * size function returns 0 for arguments the entry would reject).  BTS_E_INVALID with a bts_last_error text, nothing launched, for: a NULL
+ * required pointer (args, rgb, rgb_gt, parts, out; depth with edge_aware_smoothness), a non-positive size, n <= 0, n_patches not a
+ * multiple of n, more than 2^31 - 1 rays, an invalid_policy outside 0 .. 2 or without the tensors it reads (the combinations
+ * bts_photometric_loss checks), a workspace that is NULL or too small. */
+size_t bts_photometric_loss_median_workspace(int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t nv, int32_t n);
+int bts_photometric_loss_median(const BtsLossArgs* args, int32_t n, const float* thresh /* (B) | NULL: no automasking bound */,
+                                float* out /* (4) */, float* thresholds /* (n) | NULL */, int64_t* kept /* (1) | NULL */,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* PatchRaySampler.sample (models/bts/model/ray_sampler.py:125-162) on device: for each of the n samples, P patches given by
  * (view, y0, x0) triples (int32, (n, P) each; the caller draws them -- the reference uses the CPU RNG) of ph x pw pixels.
  * poses_c2w (n, v, 4, 4), projs (n, v, 3, 3), images (n, v, c, H, W) or NULL -> rays (n, P*ph*pw, 8) and, with images,

@@ -1,4 +1,4 @@
-// Host check of the loss workspaces (csrc/bts_host.h: Carver; tiled_layout, pixel_layout): the counted size is where the carved pointers end.
+// Host check of the loss workspaces (csrc/bts_host.h: Carver; tiled_layout, median_layout, pixel_layout): the counted size is where the carved pointers end.
 //   hipcc -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined tools/loss_workspace_check.hip -o /tmp/loss_workspace_check
 //   /tmp/loss_workspace_check          (launches nothing: needs no GPU)
 // The two .hip files are compiled INTO this program, so it calls the layout functions the library calls (they live in the files'
@@ -41,6 +41,19 @@ int main() {
       bad += carve.bytes() != bytes;
       bad += thr ? check("tiled, automask", given, ws + bytes, bytes, p.tile_parts, p.fthr, B * sizeof(float), s)
                  : check("tiled", given, ws + bytes, bytes, p.tile_parts, p.keep, B, s);
+      free(ws);
+    }
+    for (int n = 1; n <= 2; ++n) {
+      if (s[0] % n) continue;
+      const size_t bytes = loss_median_bytes(s[0], s[1], s[2], s[3], n);
+      char* ws = static_cast<char*>(malloc(bytes));
+      char* given = ws + (n - 1);      // once as malloc aligned it, once off by one byte
+      Carver carve(given);
+      TiledParamsMed p;
+      median_layout(carve, p, (size_t)s[0], nt, B, (size_t)n, (size_t)n * median_blocks_per_sample((size_t)s[0], (size_t)n, s[1], s[2]));
+      bad += carve.bytes() != bytes;
+      const int shape[4] = {s[0], s[1], s[2], n};
+      bad += check("tiled, median (.., n)", given, ws + bytes, bytes, p.tile_parts, p.fin, 4 * sizeof(float), shape);
       free(ws);
     }
     for (int n = 1; n <= 2; ++n) {

@@ -61,6 +61,14 @@ class BtsPixelLossArgs(C.Structure):
                                          "edge_aware_smoothness", "reserved_")] + [("scale_rgb", C.c_float), ("scale_eas", C.c_float)]
 
 
+class BtsLossRegArgs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("alphas", "depth", "weights", "invalid", "invalid_wsum", "invalid_any", "rgb_samps", "terms", "reg",
+                                          "g_alphas", "g_depth")] + [("B", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("n_patches", "patch_h", "patch_w", "nv", "K", "K_invalid", "invalid_policy", "alpha_reg_slice")] + \
+               [(k, C.c_float) for k in ("alpha_reg_fraction", "coef_alpha_reg", "coef_surfaceness", "coef_entropy", "coef_depth")] + \
+               [("reserved_", C.c_int32)]
+
+
 class BtsTrainScale(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("feat_nchw", "jitter", "rgb", "depth", "invalid_wsum", "invalid_any", "proj_nhwc", "sampled_tiles",
                                           "z_samp", "sigma_raw", "trans", "rgb_samps", "loss_parts", "g_rgb", "g_depth", "gs_rgb", "gs_depth",
@@ -202,6 +210,9 @@ SYMBOLS = {
     # l1+ssim with median thresholding: the tiled passes joined to the radix selection (csrc/bts_loss_tiled.hip)
     "bts_photometric_loss_median_workspace": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "bts_photometric_loss_median": (C.c_int, [C.POINTER(BtsLossArgs), _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    # the alpha / surfaceness / entropy / depth regularisers (csrc/bts_loss_reg.hip)
+    "bts_loss_regularisers_workspace": (C.c_size_t, [C.c_int64, _I, _I, _I, _I]),
+    "bts_loss_regularisers": (C.c_int, [C.POINTER(BtsLossRegArgs), _P, C.c_size_t, _P]),
     "bts_sample_coarse": (C.c_int, [_P, _P, C.c_int64, _I, _I, _P, _P]),
     "bts_distance_to_z": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
     "bts_invert_small": (C.c_int, [_P, _P, _I, _I, _P]),

@@ -413,6 +413,59 @@ int bts_pixel_loss_automask(const BtsPixelLossArgs* a, const float* thresh, void
   if (int rc = check_thresh(thresh, who)) return rc;
   return pixel_loss_entry(a, thresh, workspace, workspace_bytes, stream, who);
 }
+size_t bts_loss_regularisers_workspace(int64_t B, int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t K) {
+  if (K < 2 || K > 256 || B > (1L << 29)) return 0;
+  return loss_reg_bytes((long)B, n_patches, patch_h, patch_w, K);
+}
+int bts_loss_regularisers(const BtsLossRegArgs* a, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char who[] = "bts_loss_regularisers";
+  const bool depth_on = a && a->coef_depth > 0.0f;
+  const bool alpha_on = a && (a->coef_alpha_reg > 0.0f || a->coef_surfaceness > 0.0f || a->coef_entropy > 0.0f);
+  if (!a || (alpha_on && !a->alphas) || !a->terms || !a->reg || (depth_on && !a->depth)) {
+    set_error("%s: NULL required pointer (args, terms, reg; alphas with an alpha term, depth with the depth term)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->B <= 0 || a->n_patches <= 0 || a->patch_h <= 0 || a->patch_w <= 0 || a->K <= 0 || (a->invalid_policy != 0 && a->nv <= 0)) {
+    set_error("%s: non-positive size (B, n_patches, patch_h, patch_w, K; nv with an invalid policy)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->K < 2 || a->K > 256) {
+    set_error("%s: K = %ld samples per ray are outside [2, 256]", who, (long)a->K);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (depth_on && (a->patch_h < 2 || a->patch_w < 2)) {
+    set_error("%s: the depth term needs patch_h >= 2 and patch_w >= 2, got %ld x %ld (the reference's mean of an empty tensor is NaN)", who,
+              (long)a->patch_h, (long)a->patch_w);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (a->B != (int64_t)a->n_patches * a->patch_h * a->patch_w) {
+    set_error("%s: B = %ld rays are not n_patches * patch_h * patch_w = %ld", who, (long)a->B, (long)a->n_patches * a->patch_h * a->patch_w);
+    return BTS_E_INVALID;
+  }
+  if (a->B > (1L << 29)) {
+    set_error("%s: %ld rays are more than 2^29", who, (long)a->B);
+    return BTS_E_INVALID;
+  }
+  if (a->invalid_policy < 0 || a->invalid_policy > 3) {
+    set_error("%s: unknown invalid_policy %ld", who, (long)a->invalid_policy);
+    return BTS_E_INVALID;
+  }
+  if (a->invalid_policy == 3 && !(a->rgb_samps && a->weights && a->invalid && a->K_invalid > 0)) {
+    set_error("%s: weight_guided_diverse needs rgb_samps, weights and invalid with K_invalid > 0", who);
+    return BTS_E_INVALID;
+  }
+  if (int rc = check_policy_inputs(a->invalid_policy, a->invalid_any, a->invalid_wsum, a->invalid, a->weights, a->K_invalid, who)) return rc;
+  if ((a->g_alphas && !alpha_on) || (a->g_depth && !depth_on)) {
+    set_error("%s: g_alphas needs an alpha term (alpha_reg, surfaceness, entropy) and g_depth the depth term with a coefficient > 0", who);
+    return BTS_E_INVALID;
+  }
+  const size_t need = loss_reg_bytes((long)a->B, a->n_patches, a->patch_h, a->patch_w, a->K);
+  if (!workspace || workspace_bytes < need) {
+    set_error("%s: workspace too small (%ld bytes needed, see bts_loss_regularisers_workspace)", who, (long)need);
+    return BTS_E_INVALID;
+  }
+  return launched(loss_reg_impl(a, workspace, (hipStream_t)stream), who);
+}
 int bts_automask_errors(const float* images, int32_t n, int32_t v, int32_t H, int32_t W, const int32_t* ids_loss, int32_t n_loss, float scale,
                         float* errors, float* images4, void* stream) {
   static const char who[] = "bts_automask_errors";

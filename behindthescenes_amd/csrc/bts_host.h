@@ -98,6 +98,9 @@ int photometric_loss_median_impl(const BtsLossArgs* a, int n, const float* thres
 // ---- bts_loss_pixel.hip: criteria l1 / l2, median thresholding, the diverse flags
 size_t pixel_loss_bytes(long B, int n, int ph, int pw);
 int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, const float* thresh = nullptr);
+// ---- bts_loss_reg.hip: the alpha / surfaceness / entropy / depth regularisers
+size_t loss_reg_bytes(long B, int n_patches, int ph, int pw, int K);
+int loss_reg_impl(const BtsLossRegArgs* a, void* workspace, hipStream_t s);
 // ---- bts_automask.hip: the error map of use_automasking
 long automask_tiles(int n, int H, int W);
 int automask_errors_launch(const float* images, int n, int v, int H, int W, const int* ids_loss, int L, float scale, float* errors,

@@ -19,7 +19,8 @@ before the invalid-ray mask and the median ranking; torch's binary-min gradient,
 channel as well and cuts it off first thing; its gradient is exactly 0, so the render kernels keep their three channels and the rendered
 ``rgb`` arrives with 3.  The optional regularisers (depth /
 alpha / surfaceness / depth-smoothness / ray-entropy, all off in the shipped configs) are a few elementwise torch expressions on
-top.  Same constructor keys, same call signature, same ``(loss, loss_dict)`` result as the reference."""
+top; with ``native_regularisers: true`` every one of them whose lambda is > 0 comes, forward and gradient, from one call per scale
+(``bts_loss_regularisers``, csrc/bts_loss_reg.hip: ``native.loss_regularisers``).  Same constructor keys, same call signature, same ``(loss, loss_dict)`` result as the reference."""
 import math
 from collections.abc import MutableMapping
 
@@ -99,6 +100,32 @@ class _PixelTerms(torch.autograd.Function):
         d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
         d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
         return (d_rgb, d_depth) + (None,) * 14
+
+
+class _RegTerms(torch.autograd.Function):
+    """One scale's regularisers (``native.loss_regularisers``) as one (6,) tensor: [alpha_reg, surfaceness, entropy, depth term, invalid
+    rays, reg = sum_t coef_t term_t]; differentiable w.r.t. alphas and depth THROUGH ENTRY 5 (the terms are read for the logging dict)."""
+
+    @staticmethod
+    def forward(ctx, alphas, depth, layout, policy, weights, invalid, invalid_wsum, invalid_any, rgb_samps, coef, reduction, fraction):
+        ctx.set_materialize_grads(False)
+        need = (alphas is not None and ctx.needs_input_grad[0]) or (depth is not None and ctx.needs_input_grad[1])
+        n, pc, ph, pw = layout
+        _, _, g_alphas, g_depth, out = native.loss_regularisers_packed(alphas, depth, n=n, pc=pc, ph=ph, pw=pw, policy=policy, weights=weights,
+                                                                       invalid=invalid, invalid_wsum=invalid_wsum, invalid_any=invalid_any,
+                                                                       rgb_samps=rgb_samps, coef=coef, alpha_reg_reduction=reduction,
+                                                                       alpha_reg_fraction=fraction, need_grad=need)
+        ctx.save_for_backward(g_alphas, g_depth)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g_alphas, g_depth = ctx.saved_tensors
+        if g is None:
+            return (None,) * 12
+        d_alphas = g_alphas * g[5] if (g_alphas is not None and ctx.needs_input_grad[0]) else None
+        d_depth = g_depth * g[5] if (g_depth is not None and ctx.needs_input_grad[1]) else None
+        return (d_alphas, d_depth) + (None,) * 10
 
 
 def _flat(t, tail):
@@ -203,6 +230,9 @@ class ReconstructionLoss:
         if self.ssim_median and not self.native_ssim_median:
             raise NotImplementedError("criterion 'l1+ssim' with median_thresholding=True runs on the HIP loss' median variant of the tiled "
                                       "passes with the config key `native_ssim_median: true`; got " + got)
+        # opt-in: the regularisers (alpha_reg, surfaceness, entropy, depth_reg / depth_smoothness) on bts_loss_regularisers
+        # (csrc/bts_loss_reg.hip) in place of the torch expressions of _call
+        self.native_regularisers = bool(config.get("native_regularisers", False))
         if (self.pixel_criterion or self.diverse) and not self.native_pixel_loss:
             raise NotImplementedError("the fused HIP loss covers criterion 'l1+ssim' with invalid_policy strict / weight_guided / none, "
                                       "without automasking / median thresholding (every shipped config); criterion 'l1' / 'l2' (with or "
@@ -364,6 +394,37 @@ class ReconstructionLoss:
             return ("rgb_samps", "weights", "invalid")
         return ("weights", "invalid") if "weights" in coarse_0 else ("invalid_wsum", "invalid_any")
 
+    def _regularisers(self, coarse, coarse_0, scale, n_scales):
+        """-> (6,) [alpha_reg, surfaceness, entropy, depth term, invalid rays, this scale's share of the loss] or None when no term is on
+        at this scale: every regulariser whose lambda is > 0, one library call (``native_regularisers: true``).  The coefficients are
+        read per call (a schedule may change the lambdas): lambda / n_scales, the entropy's undivided and at scale 0 only (the reference
+        adds it after the division)."""
+        on = lambda lam: float(lam) if lam > 0 else 0.0
+        lam_depth = on(self.lambda_depth_reg) + on(self.lambda_depth_smoothness)
+        coef = (on(self.lambda_alpha_reg) / n_scales, on(self.lambda_surfaceness_reg) / n_scales,
+                on(self.lambda_entropy) if scale == 0 else 0.0, lam_depth / n_scales)
+        if not any(c > 0 for c in coef):      # (the entropy alone: nothing to do at the scales behind the first)
+            return None
+        n, pc, h, w = coarse["depth"].shape
+        alphas = _flat(coarse["alphas"], (coarse["alphas"].shape[-1],)) if (coef[0] > 0 or coef[1] > 0 or coef[2] > 0) else None
+        depth = _flat(coarse["depth"], ()) if coef[3] > 0 else None
+        masked = self.ignore_invalid and alphas is not None      # (the depth term is never masked: alone it needs no keep flags)
+        policy, weights, invalid, wsum, any_ = self.invalid_policy if masked else "none", None, None, None, None
+        if masked and self.diverse:          # the per-(ray, view) diverse flags as `invalid_any` of the strict policy, as in _sums
+            policy, any_ = "strict", self._diverse_flags(coarse_0)
+        elif masked and "weights" not in coarse_0:     # lean training outputs
+            nv = coarse_0["invalid_any"].shape[-1]
+            if policy == "weight_guided":
+                wsum = _flat(coarse_0["invalid_wsum"], (nv,)).detach()
+            else:
+                any_ = _flat(coarse_0["invalid_any"], (nv,)).detach()
+        elif masked:
+            K, nv = coarse_0["invalid"].shape[-2:]
+            invalid = _flat(coarse_0["invalid"], (K, nv)).detach()
+            weights = _flat(coarse_0["weights"], (K,)).detach() if policy == "weight_guided" else None
+        return _RegTerms.apply(alphas, depth, (n, pc, h, w), policy, weights, invalid, wsum, any_, None, coef, self.alpha_reg_reduction,
+                               float(self.alpha_reg_fraction))
+
     def __call__(self, data):
         with profiler.record_function("loss_computation"):       # loss.py:84
             try:
@@ -389,6 +450,10 @@ class ReconstructionLoss:
         gt = self._split_gt(data["rgb_gt"])
         m = dict(coarse=zero, fine=zero, depth_reg=zero, alpha_reg=zero, surf=zero, eas=zero, dsmooth=zero, inv=zero)
         keep_cache = None
+        # `native_regularisers: true`: the blocks between the photometric term and the logging dict are one library call per scale
+        native_reg = self.native_regularisers and (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0
+                                                   or self.lambda_depth_smoothness > 0 or self.lambda_entropy > 0)
+        reg, ent = None, zero
 
         def keep():   # 1 - invalid ray mask (n, pc, h, w) for the optional regularisers
             nonlocal keep_cache
@@ -432,6 +497,24 @@ class ReconstructionLoss:
                 rgb_loss = rgb_loss * self.lambda_coarse + fine_loss * self.lambda_fine
             loss = loss + rgb_loss
 
+            if native_reg:
+                if eas_on:
+                    m["eas"] = m["eas"] + eas.detach()
+                    loss = loss + eas * self.lambda_edge_aware_smoothness / (2 ** scale)
+                out = self._regularisers(coarse, coarse_0, scale, n_scales)
+                if out is None:
+                    continue
+                terms = out.detach()
+                reg = out[5] if reg is None else reg + out[5]
+                if self.lambda_depth_reg > 0:
+                    m["depth_reg"] = m["depth_reg"] + terms[3]
+                if self.lambda_depth_smoothness > 0:
+                    m["dsmooth"] = m["dsmooth"] + terms[3]
+                if self.lambda_alpha_reg > 0:
+                    m["alpha_reg"] = m["alpha_reg"] + terms[0]
+                if scale == 0 and self.lambda_entropy > 0:
+                    ent = terms[2]
+                continue
             if self.lambda_depth_reg > 0:
                 d = coarse["depth"]
                 s = ((d[:, :, 1:, :] - d[:, :, :-1, :]) ** 2).mean() + ((d[:, :, :, 1:] - d[:, :, :, :-1]) ** 2).mean()
@@ -468,8 +551,9 @@ class ReconstructionLoss:
                 loss = loss + s * self.lambda_depth_smoothness
 
         loss = loss / n_scales
-        ent = zero
-        if self.lambda_entropy > 0:
+        if native_reg:
+            loss = loss + reg
+        elif self.lambda_entropy > 0:
             a = coarse_0["alphas"] + 1e-5
             dens = a / a.sum(dim=-1, keepdim=True)
             ent = (-(dens * torch.log(dens)).sum(-1) / math.log2(a.shape[-1]) * keep()).mean()

@@ -353,6 +353,76 @@ def photometric_loss_median(rgb, depth, weights, invalid, rgb_gt, n: int, patch_
     return out, thresholds, kept, g_rgb, g_depth
 
 
+def loss_regularisers(alphas, depth, **kw):
+    """-> (terms, reg, g_alphas | None, g_depth | None) of ``loss_regularisers_packed``"""
+    return loss_regularisers_packed(alphas, depth, **kw)[:4]
+
+
+def loss_regularisers_packed(alphas, depth, *, n: int, pc: int, ph: int, pw: int, policy, weights=None, invalid=None, invalid_wsum=None,
+                             invalid_any=None, rgb_samps=None, coef, alpha_reg_reduction: str = "ray", alpha_reg_fraction: float = 1 / 8,
+                             need_grad: bool = True):
+    """The optional regularisers of the reference's loss for one scale (bts_loss_regularisers, csrc/bts_loss_reg.hip): alphas (B, K),
+    depth (B) | None in the flat patch layout of ``photometric_loss`` (B = n * pc * ph * pw); the invalid-ray inputs of scale 0 in one of
+    the forms ``pixel_loss`` takes -- weights (B, Ki) / invalid (B, Ki, nv), invalid_wsum / invalid_any (B, nv), or with
+    weight_guided_diverse rgb_samps (B, Ki, nv, 3) too.  coef = (alpha_reg, surfaceness, entropy, depth): a term runs when its coefficient
+    is > 0 (the caller passes lambda / n_scales, the entropy's undivided and at scale 0 only).
+    alphas may be None when no alpha term is on (a lean render dict with the depth term alone).
+    -> terms (5) = [alpha_reg, surfaceness, entropy, depth term, invalid rays], reg (1) = sum_t coef_t terms_t,
+    g_alphas (B, K) | None = d reg / d alphas (with an alpha term), g_depth (B) | None = d reg / d depth (with the depth term), and the
+    (6,) tensor terms and reg are views of.  Asynchronous on the current stream."""
+    if policy not in PIXEL_POLICIES:
+        raise BtsNativeError(f"loss_regularisers: unknown invalid_policy {policy!r}")
+    if alpha_reg_reduction not in ("ray", "slice"):
+        raise BtsNativeError(f"loss_regularisers: alpha_reg_reduction {alpha_reg_reduction!r} is not 'ray' or 'slice'")
+    c_alpha, c_surf, c_ent, c_depth = (float(c) for c in coef)
+    alpha_on, depth_on = c_alpha > 0 or c_surf > 0 or c_ent > 0, c_depth > 0
+    if depth_on and (ph < 2 or pw < 2):
+        raise ValueError(f"loss_regularisers: the depth term (lambda_depth_reg / lambda_depth_smoothness) needs patches of at least 2 x 2 "
+                         f"pixels, got {ph} x {pw}: the reference's mean over an empty set of differences is NaN (BTS_E_UNSUPPORTED)")
+    if alpha_on or alphas is not None:
+        _req(alphas, "alphas")
+        if alphas.dim() != 2:
+            raise BtsNativeError(f"alphas: expected (B, K), got {tuple(alphas.shape)}")
+        B, K = alphas.shape
+    else:
+        _req(depth, "depth")
+        B, K = depth.shape[0], 2
+    if n <= 0 or pc <= 0 or ph <= 0 or pw <= 0 or B != n * pc * ph * pw:
+        raise BtsNativeError(f"{B} rays are not {n} x {pc} patches of {ph}x{pw}")
+    pol = PIXEL_POLICIES[policy]
+    nv = Ki = 0
+    sums = (pol == 2 and invalid_wsum is not None) or (pol == 1 and invalid_any is not None)
+    if sums:
+        nv = (invalid_wsum if pol == 2 else invalid_any).shape[-1]
+        _req(invalid_wsum if pol == 2 else invalid_any, "invalid_wsum / invalid_any", (B, nv))
+        weights = invalid = None
+    elif pol:
+        _req(invalid, "invalid")
+        Ki, nv = invalid.shape[1:]
+        _req(invalid, "invalid", (B, Ki, nv))
+        if pol >= 2:
+            _req(weights, "weights", (B, Ki))
+        if pol == 3:
+            _req(rgb_samps, "rgb_samps", (B, Ki, nv, 3))
+    if depth_on:
+        _req(depth, "depth", (B,))
+    dev = (alphas if alphas is not None else depth).device
+    out = torch.empty((6,), device=dev, dtype=torch.float32)
+    g_alphas = torch.empty_like(alphas) if (need_grad and alpha_on) else None
+    g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and depth_on) else None
+    a = _lib.BtsLossRegArgs(alphas=_addr(alphas), depth=_addr(depth if depth_on else None), weights=_addr(weights if pol >= 2 else None),
+                            invalid=_addr(invalid if pol else None), invalid_wsum=_addr(invalid_wsum if (sums and pol == 2) else None),
+                            invalid_any=_addr(invalid_any if (sums and pol == 1) else None), rgb_samps=_addr(rgb_samps if pol == 3 else None),
+                            terms=out.data_ptr(), reg=out.data_ptr() + 20, g_alphas=_addr(g_alphas), g_depth=_addr(g_depth), B=B,
+                            n_patches=n * pc, patch_h=ph, patch_w=pw, nv=nv, K=K, K_invalid=Ki, invalid_policy=pol,
+                            alpha_reg_slice=int(alpha_reg_reduction == "slice"), alpha_reg_fraction=alpha_reg_fraction,
+                            coef_alpha_reg=c_alpha, coef_surfaceness=c_surf, coef_entropy=c_ent, coef_depth=c_depth)
+    lib = _lib.load()
+    ws = _scratch(dev, lib.bts_loss_regularisers_workspace(B, n * pc, ph, pw, K))
+    _lib.check(lib.bts_loss_regularisers(C.byref(a), ws.data_ptr(), ws.numel(), _stream(out)), "bts_loss_regularisers")
+    return out[:5], out[5:], g_alphas, g_depth, out
+
+
 def automask_errors(images: torch.Tensor, ids_loss, scale: float = 0.5, want_errors: bool = True, want_images4: bool = False):
     """The error map of use_automasking (trainer.py:203-206; bts_automask_errors, csrc/bts_automask.hip): images (n, v, 3, H, W), the
     processed frames in [0, 1]; ids_loss: 1 .. BTS_MAX_VIEWS frame indices in [0, v) -> errors (n, v, H, W) | None, images4

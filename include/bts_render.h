@@ -431,6 +431,67 @@ int bts_photometric_loss_median(const BtsLossArgs* args, int32_t n, const float*
                                 float* out /* (4) */, float* thresholds /* (n) | NULL */, int64_t* kept /* (1) | NULL */,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* The optional REGULARISERS of ReconstructionLoss (loss.py:192-245, 261-281) for one scale: alpha_reg, surfaceness, ray entropy and the
+ * depth term, forward and gradient (csrc/bts_loss_reg.hip: up to five launches on one stream).  Rays in the flat patch layout of the
+ * other loss entries: ray = ((s * pc + p) * patch_h + y) * patch_w + x, B = n_patches * patch_h * patch_w.  alphas (B, K) and depth (B)
+ * are THIS scale's; the invalid-ray inputs are scale 0's, in one of the forms the other loss entries take (per-sample weights + invalid,
+ * the renderer's invalid_wsum / invalid_any, the diverse rgb_samps + weights + invalid, or bts_loss_diverse_flags' result as invalid_any
+ * under the strict policy); keep[ray] = 1 - invalid ray.  A term runs when its coefficient is > 0; a term that is off costs nothing and
+ * its entry of `terms` is 0.  With K samples per ray, in plain fp32:
+ *   terms[0] alpha_reg    A = sum_{k < K-1} a_k, cap = K * alpha_reg_fraction;
+ *                         ray:   mean_B clamp_min(A keep - cap keep, 0)
+ *                         slice: per patch row clamp_min(sum_x A keep - sum_x cap keep, 0) / patch_w, mean over the n_patches * patch_h rows
+ *   terms[1] surfaceness  mean_B keep * mean_k -log(exp(-|a_k|) + exp(-|1 - a_k|))
+ *   terms[2] entropy      a' = a + 1e-5, d = a' / sum_k a': mean_B keep * (-sum_k d ln d) / log2(K)
+ *   terms[3] depth        mean((d[y+1] - d[y])^2) + mean((d[x+1] - d[x])^2) over the pairs inside a patch
+ *   terms[4]              the number of invalid rays
+ *   reg[0] = coef_alpha_reg terms[0] + coef_surfaceness terms[1] + coef_entropy terms[2] + coef_depth terms[3]
+ * g_alphas (B, K) = d reg / d alphas, g_depth (B) = d reg / d depth (upstream 1); every element is written exactly once.
+ * The reference's quirks, kept on purpose:
+ *   - alpha_reg leaves the LAST sample out of A but counts it in cap = K * fraction (not (K - 1) * fraction); its gradient is 0 there;
+ *   - under an invalid policy other than none both A and cap are multiplied by keep (an invalid ray adds 0 to a slice row's sum AND to its cap);
+ *   - clamp_min's gradient is torch's: it passes at an exact tie (>=), so an invalid ray's gate is open and its gradient is keep = 0;
+ *   - surfaceness is masked by keep only under an invalid policy other than none; its gradient has sign(0) = 0 for |a| and |1 - a|
+ *     (hard_alpha_cap's last sample is exactly 1); the reference adds the term to the loss and never logs it;
+ *   - the entropy's logarithm is natural while its normaliser is log2(K); it is masked by keep under EVERY policy (policy none has no
+ *     invalid rays, so keep = 1); the reference evaluates it at scale 0 only and adds it AFTER the division by the number of scales --
+ *     the caller passes coef_entropy = lambda_entropy at scale 0 and 0 elsewhere, the other coefficients as lambda / n_scales;
+ *   - lambda_depth_reg and lambda_depth_smoothness name the SAME number (the differences inside a patch, never across a patch border,
+ *     never masked by keep): the term is computed once, coef_depth is the sum of both.
+ * DIVERGENCE, on purpose: with patch_h == 1 or patch_w == 1 the reference's depth term is NaN (the mean of an empty tensor); here
+ * that is BTS_E_UNSUPPORTED.
+ * No float atomics: every sum is a wave reduction, then per-work-group partials a last small launch adds in index order (in fp64,
+ * rounded once); reruns are bit-identical.  `workspace`: at least bts_loss_regularisers_workspace(B, n_patches, patch_h, patch_w, K)
+ * bytes of device memory (about 17 bytes per ray; any alignment; contents need not be initialised or kept; 0 for arguments the entry
+ * would reject).  BTS_E_INVALID with a bts_last_error text, nothing launched, for: a NULL required pointer (args, terms, reg; alphas
+ * with an alpha term, depth with the depth term), a non-positive size, B != n_patches * patch_h * patch_w, more than 2^29 rays, an unknown invalid_policy or one
+ * without the tensors it reads, g_alphas without an alpha term, g_depth without the depth term, a workspace that is NULL or too small.
+ * BTS_E_UNSUPPORTED for K < 2, K > 256, or the depth term with patch_h < 2 or patch_w < 2. */
+typedef struct {
+  const float* alphas;        /* (B, K); may be NULL when alpha_reg, surfaceness and entropy are all off */
+  const float* depth;         /* (B) or NULL without the depth term */
+  const float* weights;       /* (B, K_invalid)         policies 2, 3 */
+  const float* invalid;       /* (B, K_invalid, nv)     policies 1, 2, 3 */
+  const float* invalid_wsum;  /* (B, nv) or NULL: replaces weights / invalid for policy 2 */
+  const float* invalid_any;   /* (B, nv) or NULL: replaces invalid for policy 1 */
+  const float* rgb_samps;     /* (B, K_invalid, nv, 3)  policy 3 */
+  float* terms;               /* (5) */
+  float* reg;                 /* (1) */
+  float* g_alphas;            /* (B, K) or NULL */
+  float* g_depth;             /* (B) or NULL */
+  int64_t B;
+  int32_t n_patches, patch_h, patch_w, nv;
+  int32_t K;                  /* samples per ray of alphas */
+  int32_t K_invalid;          /* samples per ray of weights / invalid / rgb_samps (0 with invalid_wsum / invalid_any) */
+  int32_t invalid_policy;     /* 0 none, 1 strict, 2 weight_guided, 3 weight_guided_diverse */
+  int32_t alpha_reg_slice;    /* 0 ray, 1 slice */
+  float alpha_reg_fraction;
+  float coef_alpha_reg, coef_surfaceness, coef_entropy, coef_depth;
+  int32_t reserved_;
+} BtsLossRegArgs;
+size_t bts_loss_regularisers_workspace(int64_t B, int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t K);
+int bts_loss_regularisers(const BtsLossRegArgs* args, void* workspace, size_t workspace_bytes, void* stream);
+
 /* PatchRaySampler.sample (models/bts/model/ray_sampler.py:125-162) on device: for each of the n samples, P patches given by
  * (view, y0, x0) triples (int32, (n, P) each; the caller draws them -- the reference uses the CPU RNG) of ph x pw pixels.
  * poses_c2w (n, v, 4, 4), projs (n, v, 3, 3), images (n, v, c, H, W) or NULL -> rays (n, P*ph*pw, 8) and, with images,

@@ -105,6 +105,8 @@ class BtsEvalFrame(C.Structure):
     # likewise: bts_eval_frame_prep's arguments as a dict -- params: the MLP's parameter tensors in the packed vector's order, packed / image:
     # the float32 scratch tensors (image may be None) -- or None: the entry points that read mlp_params
     prep = None
+    # likewise: False = bts_eval_frame_prep_unpinned (the render launch never takes the kernel with the frame's switches compiled in)
+    pinned = True
 
 
 BTS_MLP_MAX_TENSORS = 12
@@ -224,6 +226,8 @@ SYMBOLS = {
     "bts_mlp_image_floats": (C.c_int64, [C.POINTER(BtsFieldCfg)]),
     "bts_eval_frame_prep": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P, C.POINTER(BtsMlpTensors), _P, _P, _P]),
     "bts_render_dyn_first": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
+    "bts_render_pinned": (C.c_int32, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsRenderArgs)]),
+    "bts_eval_frame_prep_unpinned": (C.c_int, [C.POINTER(BtsEvalFrame), _P, _P, C.POINTER(BtsMlpTensors), _P, _P, _P]),
     "bts_conv3x3_fwd": (C.c_int, [C.POINTER(BtsConv3x3), _P]),
     "bts_conv3x3_bwd_workspace": (C.c_size_t, [C.POINTER(BtsConv3x3)]),
     "bts_conv3x3_bwd": (C.c_int, [C.POINTER(BtsConv3x3), _P, _P, C.c_size_t, _P, _P, _P, _P]),

@@ -88,6 +88,23 @@ struct FwdParams {
   long groups;   // number of ray groups (= n * Bp * lpr / 64)
 };
 
+// The pinned set: what the evaluation frame (bts_eval_frame*) and the shipped KITTI model configs fix before every render launch of
+// theirs -- 64 samples per ray drawn inside the kernel, disparity-linear; one render view, the encoder's own; the z depth code, inverted;
+// the learned empty feature; the hard alpha cap; rgb, depth, weights, alphas and invalid written, nothing else.  render_kernel_p's PINNED
+// instantiation (bts_render_kernel.h) takes these as compile-time constants and never reads them from its parameters; `matches` is the
+// ONE test that lets a launch take it (launch_render_p_one; exported for tests as bts_render_pinned).  Sizes, float constants and every
+// pointer stay run-time values.
+struct PinnedSet {
+  static constexpr int K = 64, nv = 1, fs = 0, enc_view = 0, lindisp = 1, empty_empty = 0, white_bkgd = 0;
+  static constexpr int code_mode = 0, inv_z = 1, learn_empty = 1, hard_cap = 1;
+  static bool matches(const FwdParams& p) {
+    return p.lpr == 64 && p.K == K && p.nv == nv && p.fs == fs && p.enc_view == enc_view && !p.z_samp && p.jitter && !p.z_out && p.lindisp != 0 &&
+           !p.sigma_noise && p.empty_empty == 0 && p.white_bkgd == 0 && p.code_mode == code_mode && p.inv_z != 0 && p.learn_empty != 0 &&
+           p.hard_cap != 0 && p.rgb && p.depth && p.weights && p.alphas && p.invalid && !p.rgb_samps && !p.sigma_raw && !p.trans &&
+           !p.invalid_wsum && !p.invalid_any;
+  }
+};
+
 #ifdef BTS_PROBE
 #define BTS_ABL(bit) ((p.ablate & (bit)) != 0)
 #else

@@ -106,8 +106,8 @@ long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div) {
 
 int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s) { return render_fwd_sched_impl(cfg, t, a, nullptr, s); }
 
-int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s,
-                          const float* mlp_image) {
+// the parameters of a render launch in front of the grid's geometry
+static FwdParams render_params(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const float* mlp_image) {
   FwdParams p = make_params(cfg, t);
   p.mlp_image = t->proj_nhwc ? mlp_image : nullptr;   // (the pipelined kernels' slot: render launches have no q_sigma)
   p.rays = a->rays, p.z_samp = a->z_samp;
@@ -118,11 +118,21 @@ int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, cons
   p.invalid_wsum = a->invalid_wsum, p.invalid_any = a->invalid_any;
   p.sigma_noise = a->sigma_noise;
   p.tiles_per_sample = (a->rays_per_sample + 255) / 256;
+  render_geometry(p, cfg->n);
+  return p;
+}
+
+bool render_args_pinned(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a) {
+  return PinnedSet::matches(render_params(cfg, t, a, nullptr));
+}
+
+int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s,
+                          const float* mlp_image, bool pin) {
+  FwdParams p = render_params(cfg, t, a, mlp_image);
 #ifdef BTS_PROBE   // the instruments of the probe build (python -m behindthescenes_amd.build --probe): section ablation bits, cycle counters
   if (const char* e = getenv("BTS_ABLATE")) p.ablate |= atoi(e);
   if (const char* e = getenv("BTS_DBG_PTR")) p.dbg = (unsigned long long*)strtoull(e, nullptr, 0);
 #endif
-  render_geometry(p, cfg->n);
   if (!p.proj && p.lpr == 48) p.lpr = 64, p.groups = (long)cfg->n * p.Bp;   // (the raw-feature route's compact kernel knows power-of-two groups only)
   if (p.groups > 0x7FF00000L) {   // the kernels index ray groups with 32 bits
     set_error("%s: too many rays in one call (%ld groups)", "bts_render_fwd", p.groups);
@@ -139,7 +149,7 @@ int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, cons
     p.dyn_first = (int)render_dyn_first(grid, p.chunk_log2, p.groups, div);
     if (p.dyn_first < p.groups) p.sched = sched;
   }
-  if (p.proj) return launch_render_pipelined(p, cfg->C, cfg->d_hidden, cfg->n_blocks, grid, s);
+  if (p.proj) return launch_render_pipelined(p, cfg->C, cfg->d_hidden, cfg->n_blocks, grid, s, pin);
   if (p.invalid_wsum || p.invalid_any) {
     set_error("%s: invalid_wsum / invalid_any need the projected feature map (proj_nhwc)", "bts_render_fwd");
     return BTS_E_UNSUPPORTED;

@@ -4,8 +4,8 @@
 #include "bts_host.h"
 
 namespace bts {
-int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s) {
+int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s, bool pin) {
   if (p.invalid_wsum || p.invalid_any) return launch_render_pipelined_epi(p, C, HD, NB, grid, s);
-  return launch_render_p<false>(p, C, HD, NB, grid, s);
+  return launch_render_p<false>(p, C, HD, NB, grid, s, pin);
 }
 }  // namespace bts

@@ -24,15 +24,18 @@ int render_grid(const FwdParams& p);
 int render_chunk_log2(int grid, long groups);
 long render_dyn_first(int grid, int chunk_log2, long groups, int tail_div);
 int render_fwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, hipStream_t s);
-// mlp_image: the staged MLP of bts_eval_frame_prep (bts_render_kernel.h: MlpImage) or NULL
+// mlp_image: the staged MLP of bts_eval_frame_prep (bts_render_kernel.h: MlpImage) or NULL; pin: the launch may take the kernel with the
+// evaluation frame's switches compiled in where its parameters match them (bts_field_kernel.h: PinnedSet)
 int render_fwd_sched_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, unsigned* sched, hipStream_t s,
-                          const float* mlp_image = nullptr);
+                          const float* mlp_image = nullptr, bool pin = false);
+// PinnedSet::matches on the parameters render_fwd_sched_impl fills from these arguments (no launch, nothing dereferenced)
+bool render_args_pinned(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a);
 int field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb,
                      float* invalid, float* sigma, hipStream_t s);
 int occupancy_profile_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int Y, int cols, float threshold,
                            int only_density, float* profile, float* sigma, hipStream_t s);
 // bts_fwd_proj.hip, bts_fwd_epi.hip: the pipelined render kernel without / with the loss epilogue
-int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s);
+int launch_render_pipelined(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s, bool pin = false);
 int launch_render_pipelined_epi(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s);
 // bts_query.hip.  Plain query: cols = 0; profile: cols = columns per sample, col_len = Y, P = Y * cols
 int query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const float* xyz, int P, int only_density, float* rgb, float* invalid,

@@ -12,7 +12,7 @@
     auto q = kernarg_view<FwdParams>();
     asm volatile("" : "+s"(q));
     IterHead ih(q);   // the geometry's share of the parameters (see IterHead: batching their loads was measured and not kept)
-    const int K = ih.K, H = ih.H, W = ih.W, nv = ih.nv, fs = ih.fs;
+    const int K = BTS_PIN(PinnedSet::K, ih.K), H = ih.H, W = ih.W, nv = BTS_PIN(PinnedSet::nv, ih.nv), fs = BTS_PIN(PinnedSet::fs, ih.fs);
     long ray = lane_ray(g, 0);   // (48-lane mode: lanes 0-47 move on to the group's next ray with every chunk of the loop below)
     // all rays of a group belong to one batch element; g only grows along a wave's chunk list, so the element is tracked by a
     // running boundary (the 64-bit division this replaces was ~140 dependent scalar instructions at the top of every iteration)
@@ -20,7 +20,7 @@
     const Cam enc = load_cam(ih.w2c_enc + sample * 16, ih.K_enc + sample * 9);
     const float4* __restrict__ G = reinterpret_cast<const float4*>(ih.proj) + (long)sample * (H >> fs) * (W >> fs) * (HD / 4);
     float ox, oy, oz, dx, dy, dz, near = 0.0f, far = 0.0f;
-    const bool from_jitter = ih.z_samp == nullptr;   // wave-uniform
+    const bool from_jitter = BTS_PIN(true, ih.z_samp == nullptr);   // wave-uniform
     if constexpr (ONE_RAY) {  // wave-uniform ray, fetched during the previous iteration (nr0 / nr1 above)
       ox = lane_value(nrec, 0), oy = lane_value(nrec, 1), oz = lane_value(nrec, 2), dx = lane_value(nrec, 3), dy = lane_value(nrec, 4);
       dz = lane_value(nrec, 5), near = lane_value(nrec, 6), far = lane_value(nrec, 7);
@@ -51,7 +51,7 @@
 #pragma unroll
     for (int i = 0; i < NVMAX * 3; ++i) rgb_part[i] = 0.0f;
 
-    float *o_rgb = nullptr, *o_depth = nullptr;   // (read in the chunk loop with the other output pointers, used behind it as well)
+    OutP o_rgb = nullptr, o_depth = nullptr;   // (read in the chunk loop with the other output pointers, used behind it as well)
     int white_bkgd = 0;
     for (int kc = 0; kc < (pk48 ? 192 : K); kc += 64) {
       const int it = kc >> 6;
@@ -83,11 +83,11 @@
         // 8 B per sample of HBM traffic less per render.  The next sample's depth is the neighbour lane's (rays of more than 64
         // samples: computed from its own jitter, the neighbour of lane 63 belongs to the next chunk).
         const int kk = valid ? k : K - 1;
-        const bool lindisp = q->lindisp != 0;
+        const bool lindisp = BTS_PIN(PinnedSet::lindisp, q->lindisp) != 0;
         z_cur = coarse_depth(z_cur, (kc == 0 && !pk48) ? base0 : coarse_base(K, kk), step0, near, far, lindisp);
         zn_cur = dpp_f<kDppWaveShl1>(z_cur, z_cur);
         if (K > 64 || pk48) zn_cur = coarse_depth(zrow[min(kk + 1, K - 1)], coarse_base(K, min(kk + 1, K - 1)), step0, near, far, lindisp);
-        if (q->z_out && valid) q->z_out[ray * K + k] = z_cur;
+        if (BTS_PIN(false, q->z_out != nullptr) && valid) q->z_out[ray * K + k] = z_cur;
       }
       const float z = z_cur, z_nx = zn_cur;
       // nerf.py:231  points = o + z * d   (mul, then add)
@@ -102,7 +102,8 @@
       }
 
       // ---------------- encoder view: projection, taps, depth code
-      const Proj pe = ih.code_mode == 1 ? project<true>(enc, px, py, pz) : project<false>(enc, px, py, pz);
+      const int code_mode = BTS_PIN(PinnedSet::code_mode, ih.code_mode);
+      const Proj pe = code_mode == 1 ? project<true>(enc, px, py, pz) : project<false>(enc, px, py, pz);
       Taps tp = make_taps(pe.x, pe.y, H, W, fs);
       int s00 = 0, s01 = 0, s10 = 0;   // the taps of lane 0's sample, wave-uniform
       if constexpr (kTwoLoops) {
@@ -118,8 +119,8 @@
       }
       float v3[3];
       v3[0] = pe.x, v3[1] = pe.y;
-      v3[2] = depth_code(pe, ih.code_mode == 1, ih.inv_z != 0, ih.inv_dmax, ih.inv_range, ih.d_min, ih.range);
-      const bool use_empty = (ih.learn_empty != 0) & pe.invalid;
+      v3[2] = depth_code(pe, code_mode == 1, BTS_PIN(PinnedSet::inv_z, ih.inv_z) != 0, ih.inv_dmax, ih.inv_range, ih.d_min, ih.range);
+      const bool use_empty = (BTS_PIN(PinnedSet::learn_empty, ih.learn_empty) != 0) & pe.invalid;
       const Taps tp_enc = tp;   // as grid_sample has them: a render view that IS the encoder view (FwdParams::enc_view) takes its colour taps from here
       if (use_empty) tp.w00 = tp.w01 = tp.w10 = tp.w11 = 0.0f;  // the empty feature is added after the blend
       tp.w00 *= scale, tp.w01 *= scale, tp.w10 *= scale, tp.w11 *= scale;  // exact: power of two
@@ -195,7 +196,7 @@
           g_step<HD, 14, SHARED>(acc, gl, rows, G, wq, off_next, h), g_step<HD, 15, SHARED>(acc, gl, rows, G, wq, off_next, h);
         }
       }
-      if (q->learn_empty && __any(use_empty)) {
+      if (BTS_PIN(PinnedSet::learn_empty, q->learn_empty) && __any(use_empty)) {
 #pragma unroll
         for (int ht = 0; ht < HT; ++ht)
 #pragma unroll
@@ -258,17 +259,22 @@
       s_raw = __builtin_fmaf(p0 + p1, inv_scale, b_out);
       }
       float sigma = softplus(s_raw);
-      if (q->empty_empty) sigma = pe.invalid ? 0.0f : sigma;
-      if (q->sigma_noise) sigma += q->sigma_noise[ray * K + min(k, K - 1)];   // nerf.py:279-280, the caller drew it
+      if (BTS_PIN(PinnedSet::empty_empty, q->empty_empty)) sigma = pe.invalid ? 0.0f : sigma;
+      if (BTS_PIN(false, q->sigma_noise != nullptr)) sigma += q->sigma_noise[ray * K + min(k, K - 1)];   // nerf.py:279-280, the caller drew it
       BTS_TICK(2)
 
       // ---------------- the iteration's ten output pointers in ONE batch of scalar loads (they are neighbours in the kernarg segment),
       // issued here so that the round trip runs under the colour taps.  Read where they are used -- each inside its own `if (pointer)` --
       // they were ten dependent load / wait / branch steps behind each other in the store section (profiles/r04t: 3.8 k of the training
       // forward's 28 k cycles per iteration).
-      o_rgb = q->rgb, o_depth = q->depth, white_bkgd = q->white_bkgd;
-      float *o_weights = q->weights, *o_alphas = q->alphas, *o_invalid = q->invalid, *o_rgb_samps = q->rgb_samps;
-      float *o_sigma_raw = q->sigma_raw, *o_trans = q->trans, *o_iw = q->invalid_wsum, *o_ia = q->invalid_any;
+      // (PINNED: the five arrays of the pinned set, as global pointers -- the stores are global_store with a scalar base, not flat stores
+      // with a 64-bit address per lane that also count on lgkmcnt; the other five are null by the set and are not read)
+      o_rgb = (OutP)q->rgb, o_depth = (OutP)q->depth, white_bkgd = BTS_PIN(PinnedSet::white_bkgd, q->white_bkgd);
+      OutP o_weights = (OutP)q->weights, o_alphas = (OutP)q->alphas, o_invalid = (OutP)q->invalid;
+      float *o_rgb_samps = BTS_PIN((float*)nullptr, q->rgb_samps), *o_sigma_raw = BTS_PIN((float*)nullptr, q->sigma_raw);
+      float *o_trans = BTS_PIN((float*)nullptr, q->trans), *o_iw = BTS_PIN((float*)nullptr, q->invalid_wsum), *o_ia = BTS_PIN((float*)nullptr, q->invalid_any);
+      if constexpr (PINNED) asm volatile("" : "+s"(o_rgb), "+s"(o_depth), "+s"(o_weights), "+s"(o_alphas), "+s"(o_invalid));
+      else
       asm volatile("" : "+s"(o_rgb), "+s"(o_depth), "+s"(o_weights), "+s"(o_alphas), "+s"(o_invalid), "+s"(o_rgb_samps), "+s"(o_sigma_raw), "+s"(o_trans),
                    "+s"(o_iw), "+s"(o_ia));
 
@@ -293,7 +299,7 @@
           for (int b = 0; b < NB4; ++b) {
             const int jj = min(j0 + b, nv - 1);   // uniform
             tcs[b] = tp_enc, invs[b] = pe.invalid;
-            if (jj != q->enc_view) {   // wave-uniform
+            if (jj != BTS_PIN(PinnedSet::enc_view, q->enc_view)) {   // wave-uniform
               const Cam cj = load_cam(q->w2c_r + ((long)sample * nv + jj) * 16, q->K_r + ((long)sample * nv + jj) * 9);
               const Proj pc = project<false>(cj, px, py, pz);
               tcs[b] = make_taps(pc.x, pc.y, H, W);
@@ -323,7 +329,7 @@
       // ---------------- alpha compositing (nerf.py:225-299): segmented DPP scan over the lanes of each ray
       const float delta = (k + 1 < K) ? (z_nx - z) : 1e10f;
       float alpha = 1.0f - transmittance(delta, sigma);
-      if (q->hard_cap && k == K - 1) alpha = 1.0f;
+      if (BTS_PIN(PinnedSet::hard_cap, q->hard_cap) && k == K - 1) alpha = 1.0f;
       const float t = valid ? (1.0f - alpha) + 1e-10f : 1.0f;
       const float incl = seg_scan_mul(t, lpr, kl);
       float excl = dpp_f<kDppWaveShr1>(1.0f, incl);
@@ -371,11 +377,18 @@
       for (int i = 0; i < NVMAX * 3; ++i) rgb_part[i] = rgb_part[i] + wgt * col[i];
       if (valid && !BTS_ABL(16)) {
         const long pk = ray * K + k;
-        if (o_weights) o_weights[pk] = wgt;
-        if (o_alphas) o_alphas[pk] = alpha;
+        if constexpr (PINNED) {
+          // weights, alphas and invalid of the pinned set: the ray's row is the scalar base and the lane's sample a 32-bit offset, the same
+          // register for the three arrays (base[pk] is a 64-bit address per lane and array).  Nontemporal: 189 MB per eval frame that the
+          // kernel never reads again, through the L2 slices that hold G (measured on its own: profiles/r20a)
+          __builtin_nontemporal_store(wgt, &(o_weights + ray * K)[(unsigned)k]), __builtin_nontemporal_store(alpha, &(o_alphas + ray * K)[(unsigned)k]);
+          __builtin_nontemporal_store(inv[0] ? 1.0f : 0.0f, &(o_invalid + ray * K)[(unsigned)k]);
+        }
+        if (BTS_PIN(false, o_weights != nullptr)) o_weights[pk] = wgt;
+        if (BTS_PIN(false, o_alphas != nullptr)) o_alphas[pk] = alpha;
         if (o_sigma_raw) o_sigma_raw[pk] = s_raw;
         if (o_trans) o_trans[pk] = T;
-        if (o_invalid) {
+        if (BTS_PIN(false, o_invalid != nullptr)) {
 #pragma unroll
           for (int j = 0; j < NVMAX; ++j)
             if (j < nv) o_invalid[pk * nv + j] = inv[j] ? 1.0f : 0.0f;
@@ -432,7 +445,7 @@
         if (nv == NVMAX && (NVMAX * 3) % 4 == 0) {   // one lane, whole row: 16-byte stores
 #pragma unroll
           for (int i = 0; i < NVMAX * 3 / 4; ++i)
-            reinterpret_cast<float4*>(o_rgb + ray * (NVMAX * 3))[i] = make_float4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
+            store4(o_rgb + ray * (NVMAX * 3) + 4 * i, make_float4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]));
         } else {
 #pragma unroll
           for (int i = 0; i < NVMAX * 3; ++i)

@@ -646,6 +646,12 @@ struct IterHeadT {
 };
 using IterHead = IterHeadT<false>;
 
+// one 16-byte store through either kind of output pointer of render_kernel_p (generic, or global: PINNED)
+__device__ __forceinline__ void store4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void store4(float __attribute__((address_space(1)))* p, const float4& v) {
+  *(f32x4 __attribute__((address_space(1)))*)p = (f32x4){v.x, v.y, v.z, v.w};
+}
+
 // EPI: also reduce weights * invalid and max invalid over each ray's samples (BtsRenderArgs.invalid_wsum / invalid_any).  A template
 // parameter, not a run-time test: the evaluation instantiations carry no trace of it (16 more spilled SGPRs otherwise).
 // DYN: the groups behind FwdParams::dyn_first are not on the waves' lists, they are claimed from the counter FwdParams::sched (below:
@@ -654,9 +660,17 @@ using IterHead = IterHeadT<false>;
 // DYN, and for the same reason: the instantiations without it are, instruction for instruction, the kernels they were -- a run-time
 // test in the preheader re-colours the registers of the whole per-ray loop.  Built for the evaluation frame's kernels (no loss epilogue,
 // at most two render views); a launch with an image and no such instantiation stages in place.
-template <int C, int HD, int NB, int NVMAX, bool ONE_RAY, bool F16, bool EPI = false, bool DYN = false, bool IMG = false>
+// PINNED: the switches of PinnedSet (bts_field_kernel.h) are compile-time constants -- BTS_PIN(constant, field) below is the constant here
+// and the field everywhere else -- so their scalar loads from the kernarg segment, their branches and the registers both hold are not
+// in the kernel, and the five arrays it writes are global pointers.  The same arithmetic in the same order: only tests whose outcome the
+// set fixes go away.  One more form of the evaluation frame's DYN + IMG kernel with one render view; like DYN and IMG it leaves no trace
+// in any other instantiation.
+#define BTS_PIN(constant, field) (PINNED ? (constant) : (field))
+template <int C, int HD, int NB, int NVMAX, bool ONE_RAY, bool F16, bool EPI = false, bool DYN = false, bool IMG = false, bool PINNED = false>
 __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParams p) {
   static_assert(F16, "lin_in runs on the f16 matrix pipe in split precision: the fp32-input-MFMA form of rounds 1 - 2 is gone (git history)");
+  static_assert(!PINNED || (ONE_RAY && !EPI && DYN && IMG && NB == 0 && NVMAX == PinnedSet::nv), "the pinned set is the evaluation frame's");
+  using OutP = std::conditional_t<PINNED, float __attribute__((address_space(1)))*, float*>;   // the arrays the iteration writes
   using L = Lds<C, HD, NB, true>;
   using LH = LdsH<C, HD, NB>;
   constexpr int HT = HD / 32;
@@ -796,10 +810,10 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   // z of the first ray group -- or, without z_samp, its jitter u: sample_coarse then runs at the top of the iteration (coarse_depth)
   float z_pre = 0.0f, zn_pre = 0.0f;
   if (g >= 0) {
-    const int K = p.K;
+    const int K = BTS_PIN(PinnedSet::K, p.K);
     const long row = lane_ray(g, 0) * K;
     const int kk = min(lane_k(0), K - 1);
-    if (p.z_samp) z_pre = p.z_samp[row + kk], zn_pre = p.z_samp[row + min(kk + 1, K - 1)];
+    if (BTS_PIN(false, p.z_samp != nullptr)) z_pre = p.z_samp[row + kk], zn_pre = p.z_samp[row + min(kk + 1, K - 1)];
     else z_pre = p.jitter[row + kk];
   }
   // one ray per iteration: the ray (origin, direction, near, far: 32 bytes, wave-uniform) of the NEXT iteration is fetched while this one
@@ -810,8 +824,9 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   if constexpr (ONE_RAY) {
     if (g >= 0) nrec = p.rays[(long)g * 8 + (lane & 7)];
   }
-  const float step0 = 1.0f / (float)p.K;                       // nerf.py:107
-  const float base0 = coarse_base(p.K, min(kl, p.K - 1));      // linspace(0, 1 - step, K)[k] of this lane's sample (first chunk)
+  const int K0 = BTS_PIN(PinnedSet::K, p.K);
+  const float step0 = 1.0f / (float)K0;                        // nerf.py:107
+  const float base0 = coarse_base(K0, min(kl, K0 - 1));        // linspace(0, 1 - step, K)[k] of this lane's sample (first chunk)
 
   // Two loops (kTwoLoops: one ray per wave): the general one, and one for rays whose 64 samples hit the same four texels
   // of G (every ray that starts at the encoder camera's centre: half of the eval frame) -- see gs_issue.  The test sits behind
@@ -827,7 +842,7 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
   constexpr bool kTwoLoops = false;
 #endif
   if constexpr (kTwoLoops) {
-    bool shared_loop = p.K <= 64;
+    bool shared_loop = K0 <= 64;
     while (g >= 0) {
       if (shared_loop) {
         for (; g >= 0; idx += waves_per_xcd, g = DYN ? next_group() : group_of(idx))
@@ -857,11 +872,11 @@ __global__ __launch_bounds__(256, kFwdWaves) void render_kernel_p(const FwdParam
 }
 
 #ifndef BTS_NO_LAUNCH_GLUE
-// One of up to six instantiations per (shape, NVMAX, EPI): ONE_RAY x {plain, IMG}, plus DYN (with and without IMG) for the evaluation
-// frame's one-ray kernels with two loops.  A launch that asks for a form its shape was not built in takes the next plainer one: a
+// One of up to seven instantiations per (shape, NVMAX, EPI): ONE_RAY x {plain, IMG}, plus DYN (with and without IMG) for the evaluation
+// frame's one-ray kernels with two loops, plus PINNED on top of DYN + IMG at one render view (`pin`: the caller allows it).  A launch that asks for a form its shape was not built in takes the next plainer one: a
 // staged image without an IMG kernel is staged in place, a claimed tail without a DYN kernel is walked as static lists.
 template <int C, int HD, int NB, int NVMAX, bool EPI>
-static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
+static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s, bool pin) {
   auto go = [&](auto kern) {
     launch_dyn_lds(kern, grid, 4 * kGatherLdsPerWave, s, p);
     return launch_check();
@@ -871,6 +886,9 @@ static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
   const bool one_ray = p.lpr == 64;
   const bool dyn = kDyn && one_ray && p.sched && p.dyn_first < p.groups;
   const bool img = kImg && p.mlp_image;
+  if constexpr (kDyn && NVMAX == PinnedSet::nv) {   // the evaluation frame's kernel with the frame's switches compiled in (PinnedSet)
+    if (dyn && img && pin && PinnedSet::matches(p)) return go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true, true, true>);
+  }
   if constexpr (kDyn) {
     if (dyn) return img ? go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true, true>) : go(render_kernel_p<C, HD, NB, NVMAX, true, true, EPI, true>);
   }
@@ -881,10 +899,10 @@ static int launch_render_p_one(const FwdParams& p, int grid, hipStream_t s) {
 }
 
 template <bool EPI>
-inline int launch_render_p(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s) {
+inline int launch_render_p(const FwdParams& p, int C, int HD, int NB, int grid, hipStream_t s, bool pin = false) {
   return with_shape(C, HD, NB, [&](auto sh) {
     using S = decltype(sh);
-    return with_nvmax(p.nv, [&](auto nvmax) { return launch_render_p_one<S::C, S::HD, S::NB, nvmax(), EPI>(p, grid, s); });
+    return with_nvmax(p.nv, [&](auto nvmax) { return launch_render_p_one<S::C, S::HD, S::NB, nvmax(), EPI>(p, grid, s, pin); });
   });
 }
 #endif  // BTS_NO_LAUNCH_GLUE

@@ -375,7 +375,8 @@ struct EvalPrep {
   const BtsMlpTensors* params;
   float *packed, *image;
 };
-int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipStream_t stream, const EvalPrep* prep = nullptr) {
+// pin: the render launch may take the kernel with the frame's switches compiled in (PinnedSet); false: the kernel it took without one
+int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipStream_t stream, const EvalPrep* prep = nullptr, bool pin = true) {
   const BtsFieldCfg& c = f->cfg;
   const int n = c.n, nv = c.nv;
   // cameras, inverse intrinsics (for distance_to_z behind the render), rgb0 packing, rays and rgb_gt: one launch (it also zeroes `sched`,
@@ -404,7 +405,7 @@ int eval_frame_impl(const BtsEvalFrame* f, float* rgb_gt, unsigned* sched, hipSt
   memset(&a, 0, sizeof(a));
   a.rays_per_sample = f->v * c.H * c.W, a.K = f->K, a.hard_alpha_cap = f->hard_alpha_cap, a.rays = f->rays, a.jitter = f->jitter, a.lindisp = f->lindisp;
   a.rgb = f->rgb, a.depth = f->depth, a.weights = f->weights, a.alphas = f->alphas, a.invalid = f->invalid;
-  rc = render_fwd_sched_impl(&cfg, &t, &a, sched, stream, prep ? prep->image : nullptr);
+  rc = render_fwd_sched_impl(&cfg, &t, &a, sched, stream, prep ? prep->image : nullptr, pin);
   if (rc) return rc;
   if (f->depth_z) {
     rc = distance_to_z_launch(f->depth, f->inv_K, n * f->v, c.H, c.W, f->depth_z, stream);
@@ -462,8 +463,8 @@ int bts_eval_frame_sched(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, 
 
 int64_t bts_mlp_image_floats(const BtsFieldCfg* cfg) { return cfg ? mlp_image_floats(cfg->C, cfg->d_hidden, cfg->n_blocks) : 0; }
 
-int bts_eval_frame_prep(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, const BtsMlpTensors* params, float* mlp_packed, float* mlp_image,
-                        void* stream) {
+static int eval_frame_prep(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, const BtsMlpTensors* params, float* mlp_packed, float* mlp_image,
+                           void* stream, bool pin) {
   const char* who = "bts_eval_frame_prep";
   if (int rc = check_eval_frame(f, who, false)) return rc;
   if (!params || !mlp_packed) {
@@ -485,7 +486,15 @@ int bts_eval_frame_prep(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, c
     return BTS_E_INVALID;
   }
   const EvalPrep prep{params, mlp_packed, mlp_image};
-  return eval_frame_impl(f, rgb_gt, sched, (hipStream_t)stream, &prep);
+  return eval_frame_impl(f, rgb_gt, sched, (hipStream_t)stream, &prep, pin);
+}
+int bts_eval_frame_prep(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, const BtsMlpTensors* params, float* mlp_packed, float* mlp_image,
+                        void* stream) {
+  return eval_frame_prep(f, rgb_gt, sched, params, mlp_packed, mlp_image, stream, true);
+}
+int bts_eval_frame_prep_unpinned(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, const BtsMlpTensors* params, float* mlp_packed,
+                                 float* mlp_image, void* stream) {
+  return eval_frame_prep(f, rgb_gt, sched, params, mlp_packed, mlp_image, stream, false);
 }
 
 int bts_eval_frame_gt(const BtsEvalFrame* f, float* rgb_gt, void* stream) { return bts_eval_frame_sched(f, rgb_gt, nullptr, stream); }
@@ -497,6 +506,14 @@ int64_t bts_render_dyn_first(int32_t grid, int64_t groups, int32_t* chunk_log2) 
   const int l = render_chunk_log2(grid, groups);
   if (chunk_log2) *chunk_log2 = l;
   return render_dyn_first(grid, l, groups, 0);
+}
+
+// whether a render launch of these arguments matches the pinned set (bts_field_kernel.h: PinnedSet, on the parameters bts_render_fwd fills), for
+// tests: 1 / 0, -1 for a NULL argument.  Host only; no pointer is dereferenced.  The launch takes the pinned kernel where, besides, it has
+// a claimed tail and a staged MLP (bts_eval_frame_prep)
+int32_t bts_render_pinned(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a) {
+  if (!cfg || !t || !a) return -1;
+  return render_args_pinned(cfg, t, a) ? 1 : 0;
 }
 
 int bts_train_step_fwd(const BtsTrainStep* st, void* stream) {

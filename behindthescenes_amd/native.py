@@ -1076,7 +1076,8 @@ def eval_frame(fr, stream, rgb_gt=None):
     ``images * img_scale + img_shift`` into it.  With ``fr.sched`` -- 256 int32 words on the device, the frame's own while it runs --
     bts_eval_frame_sched: the render's waves claim the last part of the rays from its counters instead of walking fixed lists to the end.
     With ``fr.prep`` -- ``dict(params=[the MLP's tensors], packed=scratch, image=scratch or None)`` -- bts_eval_frame_prep: the projection's
-    launch also reads the parameter tensors themselves, packs and stages them (``fr.mlp_params`` is not read), with or without ``sched`` and ``rgb_gt``."""
+    launch also reads the parameter tensors themselves, packs and stages them (``fr.mlp_params`` is not read), with or without ``sched`` and ``rgb_gt``;
+    ``fr.pinned = False``: bts_eval_frame_prep_unpinned, the same frame without the render kernel that has the frame's switches compiled in."""
     if rgb_gt is None:
         rgb_gt = fr.rgb_gt
     sched = getattr(fr, "sched", None)
@@ -1103,7 +1104,8 @@ def eval_frame(fr, stream, rgb_gt=None):
         for name, t, want in (("packed", packed, sum(sizes)), ("image", image, int(lib.bts_mlp_image_floats(C.byref(fr.cfg))))):
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < want or want <= 0):
                 raise BtsNativeError(f"prep: {name} must be {want} contiguous float32 values on the device")
-        _lib.check(lib.bts_eval_frame_prep(C.byref(fr), _ptr(rgb_gt), _ptr(sched), C.byref(mt), _ptr(packed), _ptr(image), stream), "bts_eval_frame_prep")
+        entry = lib.bts_eval_frame_prep if getattr(fr, "pinned", True) else lib.bts_eval_frame_prep_unpinned
+        _lib.check(entry(C.byref(fr), _ptr(rgb_gt), _ptr(sched), C.byref(mt), _ptr(packed), _ptr(image), stream), "bts_eval_frame_prep")
         return
     if sched is not None:
         _lib.check(_lib.load().bts_eval_frame_sched(C.byref(fr), _ptr(rgb_gt), _ptr(sched), stream), "bts_eval_frame_sched")

@@ -445,6 +445,10 @@ class FusedEvalFrame(torch.nn.Module):
         # ... and whether that launch also stages the MLP for the render's work-groups (False: it packs the parameters only, every render
         # work-group stages for itself as without the prep launch).  Same outputs.
         self.staged_mlp = True
+        # the render launch may take the kernel with the frame's fixed switches compiled in (bts_render_pinned: the shipped KITTI eval
+        # configuration with a claimed tail and a staged MLP; any other frame takes the general kernel anyway).  False: the general kernel
+        # always (bts_eval_frame_prep_unpinned).  Same outputs.
+        self.pinned_kernel = True
 
     def why_not(self, images=None, ids_encoder=(0,), ids_render=(0,)):
         from .ray_sampler import ImageRaySampler
@@ -561,6 +565,7 @@ class FusedEvalFrame(torch.nn.Module):
         fr.rgb_gt = out["rgb_gt"]          # (host-side attribute, no struct field: selects bts_eval_frame_gt in native.eval_frame)
         fr.sched = sc["sched"] if self.dynamic_tail else None      # (likewise: bts_eval_frame_sched)
         fr.prep = prep                                              # (likewise: bts_eval_frame_prep)
+        fr.pinned = self.pinned_kernel                              # (likewise: bts_eval_frame_prep_unpinned)
         native.eval_frame(fr, native._stream(images))
         part = dict(rgb=out["rgb"], depth=out["depth_z"] if to_z else out["depth"], invalid=out["invalid"])
         if want_weights:

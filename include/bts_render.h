@@ -755,6 +755,16 @@ int bts_eval_frame_prep(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, c
 /* The split that launch uses, on the host (no GPU): `grid` work-groups of four waves, `groups` rays -> the first claimed ray (= groups: no
  * tail), a multiple of 8 << *chunk_log2 (the XCD interleave's chunk, written when chunk_log2 is not NULL). */
 int64_t bts_render_dyn_first(int32_t grid, int64_t groups, int32_t* chunk_log2);
+/* The pinned set (additive to ABI 9, no struct changes).  A render launch with a claimed tail and a staged MLP -- bts_eval_frame_prep's with
+ * `sched` and `mlp_image` -- whose arguments are the evaluation frame's under the shipped KITTI configs takes a kernel with those
+ * switches compiled in: K = 64 drawn inside the kernel (jitter, no z_samp, no z_samp_out), lindisp; nv = 1 and enc_render_view = 0, feat_shift
+ * = 0; code_mode 0 with inv_z, learn_empty, no empty_empty; hard_alpha_cap, no white_bkgd, no sigma_noise; rgb, depth, weights, alphas
+ * and invalid given, every other output NULL.  The same arithmetic: every output is the same bits.  Any other launch takes the kernel it
+ * took before.  bts_render_pinned: that test on the host (no GPU, nothing is dereferenced), 1 / 0, -1 for a NULL argument.
+ * bts_eval_frame_prep_unpinned: bts_eval_frame_prep whose render launch never takes the pinned kernel (A/B and tests). */
+int32_t bts_render_pinned(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a);
+int bts_eval_frame_prep_unpinned(const BtsEvalFrame* f, float* rgb_gt, uint32_t* sched, const BtsMlpTensors* params, float* mlp_packed,
+                                 float* mlp_image, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,8 @@
 //   - the 3 x 3 Gaussian window of SSIM (layers.py:92-101), the per-channel SSIM term and its three backward coefficients
 //   - edge-aware smoothness (loss.py:21-40): the inverse clamped depth, a pixel's own edges and their part of u_p, the depth gradient
 //   - the rank selection in a histogram of 2 048 bins
+//   - the median of a plane per batch sample on top of it: the workspace constants, the (sample, 256 rays) position, the radix passes,
+//     the threshold (bts_loss_pixel.hip and bts_loss_tiled.hip's median variant; bts_depth_metrics.hip selects two keys at once)
 // What is NOT here although two files write it: a rule stays in its kernel where calling it from this header changes that kernel's
 // instructions (every kernel of the five files is the instruction stream it was before the header existed, tools/asm_compare.py).  The
 // compiler simplifies a function on its own before it inlines it, so a function with a loop, or one whose arguments are loaded in another
@@ -227,6 +229,86 @@ __device__ void select_bin(const unsigned* __restrict__ hist, int median, unsign
     out[0] = (unsigned)(t * 8 + bin), out[1] = rem;
   }
   __syncthreads();
+}
+
+// ---- the median of a plane e of CHANNELS values per ray, per batch sample (loss.py:163-167): three radix passes over select_bin, run by
+// work-groups of 256 rays that never straddle two samples.  bts_loss_pixel.hip (three channels per ray) and the median variant of
+// bts_loss_tiled.hip (one) launch them; P, the kernel's parameter struct, has e, hist (n, 3, 2 048), state (n, 8), thr (n), thresholds,
+// Bs (rays per sample) and blocks_per_sample.  THE protocol between the launches: a sample's first work-group notes the selected prefix
+// and the rank inside it in state[0, 1] after pass 0's histogram and in state[4, 5] after pass 1's; the NEXT launch reads them.
+// Two pieces of the passes stay in the kernels, because inside a function here they move a kernel's instructions (each kernel is the
+// stream it was, tools/asm_compare.py): the flush behind select_hist_pass -- bts_loss_pixel.hip's is flush_hist on a pointer,
+// bts_loss_tiled.hip's two are loops written out, one of them indexing from the sample's base -- and the note-down of thr behind
+// select_threshold.  Both sites say what was tried.
+constexpr int kSelBins = 2048;
+constexpr int kSelHistSample = 3 * kSelBins;      // three radix passes per batch sample
+constexpr int kSelStateSample = 8;
+
+// which sample and which ray a thread of the (sample, 256 rays) work-groups takes
+struct RayPos {
+  int sample;
+  long ray;
+  bool act;
+};
+template <class P>
+__device__ __forceinline__ RayPos ray_pos(const P& p) {
+  RayPos r;
+  r.sample = (int)(blockIdx.x / p.blocks_per_sample);
+  const long in_sample = (long)(blockIdx.x - (unsigned)r.sample * p.blocks_per_sample) * 256 + threadIdx.x;
+  r.act = in_sample < p.Bs;
+  r.ray = (long)r.sample * p.Bs + (r.act ? in_sample : 0);
+  return r;
+}
+
+// the work-group's non-zero bins into the sample's histogram (bts_loss_pixel.hip's three flushes)
+__device__ __forceinline__ void flush_hist(const unsigned* s_hist, unsigned* dst) {
+  for (int i = threadIdx.x; i < kSelBins; i += 256) {
+    const unsigned c = s_hist[i];
+    if (c) atomicAdd(&dst[i], c);
+  }
+}
+
+// radix passes 1 and 2 up to the flush: bits 20..10 of the e that share the wanted 11 bits, then bits 9..0 of those that share 22, counted
+// in s_hist.  -> the sample's three histograms; the caller adds s_hist's non-zero bins to the one at PASS * kSelBins.  r: ray_pos(p), taken
+// in the kernel (taken in here, loss_med_hist's loads are scheduled in another order).  s_hist: kSelBins words, s_scan: 256, s_sel: 2 --
+// the calling kernel's LDS
+template <int PASS, int CHANNELS, class P>
+__device__ __forceinline__ unsigned* select_hist_pass(const P& p, const RayPos& r, unsigned* s_hist, unsigned* s_scan, unsigned* s_sel) {
+  unsigned* hist_s = p.hist + (size_t)r.sample * kSelHistSample;
+  unsigned* state_s = p.state + (size_t)r.sample * kSelStateSample;
+  for (int i = threadIdx.x; i < kSelBins; i += 256) s_hist[i] = 0u;
+  unsigned want;
+  if (PASS == 1) {
+    select_bin<false>(hist_s, 1, 0u, s_scan, s_sel);
+    want = s_sel[0];
+    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[0] = want, state_s[1] = s_sel[1];
+  } else {
+    select_bin<false>(hist_s + kSelBins, 0, state_s[1], s_scan, s_sel);
+    want = (state_s[0] << 11) | s_sel[0];
+    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[4] = want, state_s[5] = s_sel[1];
+  }
+  __syncthreads();
+  if (r.act) {
+#pragma unroll
+    for (int c = 0; c < CHANNELS; ++c) {
+      const unsigned key = __float_as_uint(p.e[r.ray * CHANNELS + c]);
+      if (PASS == 1) {
+        if ((key >> 21) == want) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u);
+      } else {
+        if ((key >> 10) == want) atomicAdd(&s_hist[key & 1023u], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  return hist_s;
+}
+
+// thr[sample] = the value whose pattern is the 22-bit prefix and the last histogram's bin; the sample's first work-group notes it down
+template <class P>
+__device__ __forceinline__ float select_threshold(const P& p, const RayPos& r, unsigned* s_scan, unsigned* s_sel) {
+  const unsigned* state_s = p.state + (size_t)r.sample * kSelStateSample;
+  select_bin<false>(p.hist + (size_t)r.sample * kSelHistSample + 2 * kSelBins, 0, state_s[5], s_scan, s_sel);
+  return __uint_as_float((state_s[4] << 10) | s_sel[0]);
 }
 
 }  // namespace bts

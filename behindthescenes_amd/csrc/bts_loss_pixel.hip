@@ -30,10 +30,7 @@ namespace bts {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kBins = 2048;
-constexpr int kHistSample = 3 * kBins;      // three radix passes per batch sample
-constexpr int kStateSample = 8;             // [0, 1] prefix and rank after pass 0's histogram, [4, 5] after pass 1's
+constexpr int kThreads = 256;      // (the median selection's work-groups of bts_loss_device.h are this size)
 
 struct PixelParams {
   const float* rgb;
@@ -120,21 +117,6 @@ __device__ __forceinline__ void write_grad(const P& p, long ray, float keep, flo
     }
 }
 
-// which sample and which ray a thread of the (sample, 256 rays) work-groups takes
-struct RayPos {
-  int sample;
-  long ray;
-  bool act;
-};
-__device__ __forceinline__ RayPos ray_pos(const PixelParams& p) {
-  RayPos r;
-  r.sample = (int)(blockIdx.x / p.blocks_per_sample);
-  const long in_sample = (long)(blockIdx.x - (unsigned)r.sample * p.blocks_per_sample) * kThreads + threadIdx.x;
-  r.act = in_sample < p.Bs;
-  r.ray = (long)r.sample * p.Bs + (r.act ? in_sample : 0);
-  return r;
-}
-
 // the work-group's sum: butterfly per wave, then the four waves in order; every thread gets it.  s_red: 4 words
 __device__ __forceinline__ float block_sum(float v, float* s_red) {
   v = wave_sum(v);
@@ -151,22 +133,14 @@ __device__ __forceinline__ unsigned block_sum(unsigned v, unsigned* s_red) {
   return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
 }
 
-// the work-group's non-zero bins into the sample's histogram
-__device__ __forceinline__ void flush_hist(const unsigned* s_hist, unsigned* dst) {
-  for (int i = threadIdx.x; i < kBins; i += kThreads) {
-    const unsigned c = s_hist[i];
-    if (c) atomicAdd(&dst[i], c);
-  }
-}
-
 template <class P>
 __global__ __launch_bounds__(kThreads) void pixel_err_kernel(const P p) {
   constexpr bool kThr = std::is_same<P, PixelParamsThr>::value;
-  __shared__ unsigned s_hist[kBins];
+  __shared__ unsigned s_hist[kSelBins];
   __shared__ float s_f[4];
   __shared__ unsigned s_u[4];
   if (p.median) {
-    for (int i = threadIdx.x; i < kBins; i += kThreads) s_hist[i] = 0u;
+    for (int i = threadIdx.x; i < kSelBins; i += kThreads) s_hist[i] = 0u;
     __syncthreads();
   }
   const RayPos r = ray_pos(p);
@@ -202,55 +176,29 @@ __global__ __launch_bounds__(kThreads) void pixel_err_kernel(const P p) {
   const float bs = block_sum(esum, s_f);
   const unsigned bi = block_sum(inv, s_u);
   if (threadIdx.x == 0) p.blk_sum[blockIdx.x] = bs, p.blk_cnt[blockIdx.x] = 0u, p.blk_inv[blockIdx.x] = bi;
-  if (p.median) flush_hist(s_hist, p.hist + (size_t)r.sample * kHistSample);     // (block_sum's barriers are behind the atomics)
+  if (p.median) flush_hist(s_hist, p.hist + (size_t)r.sample * kSelHistSample);     // (block_sum's barriers are behind the atomics)
 }
 
-// radix passes 1 and 2 of a sample's median.  What a work-group notes down (the prefix and the rank inside it) is read by the NEXT launch only
+// radix passes 1 and 2 of a sample's median (bts_loss_device.h: select_hist_pass, three channels per ray)
 template <int PASS>
 __global__ __launch_bounds__(kThreads) void pixel_hist_kernel(const PixelParams p) {
-  __shared__ unsigned s_hist[kBins];
+  __shared__ unsigned s_hist[kSelBins];
   __shared__ unsigned s_scan[kThreads];
   __shared__ unsigned s_sel[2];
   const RayPos r = ray_pos(p);
-  unsigned* hist_s = p.hist + (size_t)r.sample * kHistSample;
-  unsigned* state_s = p.state + (size_t)r.sample * kStateSample;
-  for (int i = threadIdx.x; i < kBins; i += kThreads) s_hist[i] = 0u;
-  unsigned want;
-  if (PASS == 1) {
-    select_bin<false>(hist_s, 1, 0u, s_scan, s_sel);
-    want = s_sel[0];
-    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[0] = want, state_s[1] = s_sel[1];
-  } else {
-    select_bin<false>(hist_s + kBins, 0, state_s[1], s_scan, s_sel);
-    want = (state_s[0] << 11) | s_sel[0];
-    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[4] = want, state_s[5] = s_sel[1];
-  }
-  __syncthreads();
-  if (r.act) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const unsigned key = __float_as_uint(p.e[r.ray * 3 + c]);
-      if (PASS == 1) {
-        if ((key >> 21) == want) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u);
-      } else {
-        if ((key >> 10) == want) atomicAdd(&s_hist[key & 1023u], 1u);
-      }
-    }
-  }
-  __syncthreads();
-  flush_hist(s_hist, hist_s + PASS * kBins);
+  flush_hist(s_hist, select_hist_pass<PASS, 3>(p, r, s_hist, s_scan, s_sel) + PASS * kSelBins);
 }
 
-// thr[sample] = the value whose pattern is the 22-bit prefix and the last histogram's bin; the kept set e <= thr of this work-group's rays
+// thr[sample] (bts_loss_device.h: select_threshold); the kept set e <= thr of this work-group's rays.  The note-down stays written out here
+// and in loss_med_kept: as a function (p and r by reference or by value, the sample alone handed over) 47 lines of both kernels move.
+// So do the sums: this one's block_sum hands every thread the sum, that one adds the four waves in thread 0 -- other instructions
 __global__ __launch_bounds__(kThreads) void pixel_kept_kernel(const PixelParams p) {
   __shared__ unsigned s_scan[kThreads];
   __shared__ unsigned s_sel[2];
   __shared__ float s_f[4];
   __shared__ unsigned s_u[4];
   const RayPos r = ray_pos(p);
-  const unsigned* state_s = p.state + (size_t)r.sample * kStateSample;
-  select_bin<false>(p.hist + (size_t)r.sample * kHistSample + 2 * kBins, 0, state_s[5], s_scan, s_sel);
-  const float thr = __uint_as_float((state_s[4] << 10) | s_sel[0]);
+  const float thr = select_threshold(p, r, s_scan, s_sel);
   if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) {
     p.thr[r.sample] = thr;
     if (p.thresholds) p.thresholds[r.sample] = thr;
@@ -352,7 +300,8 @@ __global__ __launch_bounds__(64) void pixel_patch_kernel(const PixelParams p) {
   }
 }
 
-// one work-group: thread t takes partials t, t + 256, ... in order, then the waves' butterflies, then the four waves in order
+// one work-group: thread t takes partials t, t + 256, ... in order, then the waves' butterflies, then the four waves in order.  Written
+// out here and in loss_med_final: this one reads the smoothness term and the invalid count from patch_stats / blk_inv, that one from parts
 __global__ __launch_bounds__(kThreads) void pixel_final_kernel(const PixelParams p) {
   __shared__ float s_f[4];
   __shared__ double s_d[4];
@@ -430,8 +379,8 @@ inline Geom geom_of(long B, int n, int ph, int pw) {
 inline void pixel_layout(Carver& w, PixelParams& p, size_t B, size_t n, const Geom& g) {
   p.e = w.take<float>(B * 3);
   p.keep = w.take<unsigned char>(B);
-  p.hist = w.take<unsigned>(n * kHistSample);
-  p.state = w.take<unsigned>(n * kStateSample);
+  p.hist = w.take<unsigned>(n * kSelHistSample);
+  p.state = w.take<unsigned>(n * kSelStateSample);
   p.thr = w.take<float>(n);
   p.blk_sum = w.take<float>((size_t)g.n_blocks);
   p.blk_cnt = w.take<unsigned>((size_t)g.n_blocks);
@@ -469,7 +418,7 @@ int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, c
   Carver carve(workspace);
   pixel_layout(carve, p, (size_t)p.B, (size_t)p.n, g);
   const unsigned grid = (unsigned)g.n_blocks;
-  if (p.median && hipMemsetAsync(p.hist, 0, (size_t)p.n * kHistSample * sizeof(unsigned), s) != hipSuccess) {
+  if (p.median && hipMemsetAsync(p.hist, 0, (size_t)p.n * kSelHistSample * sizeof(unsigned), s) != hipSuccess) {
     set_error("%s: clearing the histograms failed", "bts_pixel_loss");
     return BTS_E_LAUNCH;
   }

@@ -104,13 +104,9 @@ struct TiledParamsMed : TiledParamsThr {
   unsigned* blk_cnt;       // (n_blocks) kept pixels
   float* fin;              // [0] = s_rgb / count
 };
-// (the names of bts_loss_pixel.hip's kBins, kHistSample, kStateSample are taken where both files share a translation unit: tools/loss_workspace_check.hip)
-constexpr int kMedBins = 2048;
-constexpr int kMedHistSample = 3 * kMedBins;      // three radix passes per batch sample
-constexpr int kMedStateSample = 8;
 // the tile's histogram of the median pass 1: LDS of the kernels that call this, and of no other
 __device__ __forceinline__ unsigned* med_hist() {
-  __shared__ unsigned s_hist[kMedBins];
+  __shared__ unsigned s_hist[kSelBins];
   return s_hist;
 }
 
@@ -172,7 +168,7 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
   const TilePos tp = tile_pos(p, blk);
   const int ph = p.ph, pw = p.pw, nv = p.nv;
   if constexpr (kMed)      // (the barriers below stand between this, the atomics and the flush)
-    for (int i = tid; i < kMedBins; i += 256) med_hist()[i] = 0u;
+    for (int i = tid; i < kSelBins; i += 256) med_hist()[i] = 0u;
 
   // ---- halo: ground truth, keep flag, d = 1 / clamp(depth); zero outside the patch (the SSIM window's zero padding)
   for (int i = tid; i < kHalo; i += 256) {
@@ -324,9 +320,10 @@ __global__ __launch_bounds__(256) void loss_tiled_pass1(const P p, const long n_
     o.w = ((sRed[0][3] + sRed[1][3]) + sRed[2][3]) + sRed[3][3];
     p.tile_parts[blk] = o;
   }
-  if constexpr (kMed) {      // the tile's non-zero bins into its sample's first histogram (the barrier above is behind the atomics)
-    unsigned* dst = p.hist + (size_t)(tp.patch / p.pps) * kMedHistSample;
-    for (int i = tid; i < kMedBins; i += 256) {
+  if constexpr (kMed) {      // the tile's non-zero bins into its sample's first histogram (the barrier above is behind the atomics);
+                             // written out: as bts_loss_device.h's flush_hist, forced inline or not, 25 lines of this kernel's tail move
+    unsigned* dst = p.hist + (size_t)(tp.patch / p.pps) * kSelHistSample;
+    for (int i = tid; i < kSelBins; i += 256) {
       const unsigned c = med_hist()[i];
       if (c) atomicAdd(&dst[i], c);
     }
@@ -449,70 +446,33 @@ __global__ __launch_bounds__(256) void loss_tiled_pass3(const P p, const long n_
   }
 }
 
-// ---- median thresholding: the ray-wise kernels over the one-channel plane e (B), modelled on bts_loss_pixel.hip's hist / kept / final
-// (three channels per ray there, one here; the selection itself is the shared select_bin).  Work-groups of 256 rays that never straddle
-// two samples: which sample and which ray a thread takes
-struct MedRay {
-  int sample;
-  long ray;
-  bool act;
-};
-__device__ __forceinline__ MedRay med_ray(const TiledParamsMed& p) {
-  MedRay r;
-  r.sample = (int)(blockIdx.x / p.blocks_per_sample);
-  const long in_sample = (long)(blockIdx.x - (unsigned)r.sample * p.blocks_per_sample) * 256 + threadIdx.x;
-  r.act = in_sample < p.Bs;
-  r.ray = (long)r.sample * p.Bs + (r.act ? in_sample : 0);
-  return r;
-}
-
-// radix passes 1 and 2 of a sample's median.  What a work-group notes down (the prefix and the rank inside it) is read by the NEXT launch only
+// ---- median thresholding: the ray-wise kernels over the one-channel plane e (B).  The selection is bts_loss_pixel.hip's, three channels
+// per ray there and one here: both call bts_loss_device.h (ray_pos, select_hist_pass, select_threshold).  The flush stays written out:
+// this kernel addresses the bins from the sample's base (a 64-bit vector address), flush_hist on `hist_s + PASS * kSelBins` from a scalar
+// one (35 lines fewer), and flush_hist with the index handed over moves the loop's tail (26 lines)
 template <int PASS>
 __global__ __launch_bounds__(256) void loss_med_hist(const TiledParamsMed p) {
   __shared__ unsigned s_scan[256];
   __shared__ unsigned s_sel[2];
   unsigned* s_hist = med_hist();
-  const MedRay r = med_ray(p);
-  unsigned* hist_s = p.hist + (size_t)r.sample * kMedHistSample;
-  unsigned* state_s = p.state + (size_t)r.sample * kMedStateSample;
-  for (int i = threadIdx.x; i < kMedBins; i += 256) s_hist[i] = 0u;
-  unsigned want;
-  if (PASS == 1) {
-    select_bin<false>(hist_s, 1, 0u, s_scan, s_sel);
-    want = s_sel[0];
-    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[0] = want, state_s[1] = s_sel[1];
-  } else {
-    select_bin<false>(hist_s + kMedBins, 0, state_s[1], s_scan, s_sel);
-    want = (state_s[0] << 11) | s_sel[0];
-    if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) state_s[4] = want, state_s[5] = s_sel[1];
-  }
-  __syncthreads();
-  if (r.act) {
-    const unsigned key = __float_as_uint(p.e[r.ray]);
-    if (PASS == 1) {
-      if ((key >> 21) == want) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u);
-    } else {
-      if ((key >> 10) == want) atomicAdd(&s_hist[key & 1023u], 1u);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kMedBins; i += 256) {
+  const RayPos r = ray_pos(p);
+  unsigned* hist_s = select_hist_pass<PASS, 1>(p, r, s_hist, s_scan, s_sel);
+  for (int i = threadIdx.x; i < kSelBins; i += 256) {
     const unsigned c = s_hist[i];
-    if (c) atomicAdd(&hist_s[PASS * kMedBins + i], c);
+    if (c) atomicAdd(&hist_s[PASS * kSelBins + i], c);
   }
 }
 
-// thr[sample] = the value whose pattern is the 22-bit prefix and the last histogram's bin; the kept set e <= thr of this work-group's rays:
-// its sum (butterfly per wave, then the four waves in order) and its size
+// thr[sample]; the kept set e <= thr of this work-group's rays: its sum (butterfly per wave, then the four waves in order) and its size.
+// The note-down and the sums stay written out here and in pixel_kept_kernel (see there): thread 0 adds the four waves here, block_sum
+// hands every thread the sum there
 __global__ __launch_bounds__(256) void loss_med_kept(const TiledParamsMed p) {
   __shared__ unsigned s_scan[256];
   __shared__ unsigned s_sel[2];
   __shared__ float s_f[4];
   __shared__ unsigned s_u[4];
-  const MedRay r = med_ray(p);
-  const unsigned* state_s = p.state + (size_t)r.sample * kMedStateSample;
-  select_bin<false>(p.hist + (size_t)r.sample * kMedHistSample + 2 * kMedBins, 0, state_s[5], s_scan, s_sel);
-  const float thr = __uint_as_float((state_s[4] << 10) | s_sel[0]);
+  const RayPos r = ray_pos(p);
+  const float thr = select_threshold(p, r, s_scan, s_sel);
   if (blockIdx.x == (unsigned)r.sample * p.blocks_per_sample && threadIdx.x == 0) {
     p.thr[r.sample] = thr;
     if (p.thresholds) p.thresholds[r.sample] = thr;
@@ -534,7 +494,8 @@ __global__ __launch_bounds__(256) void loss_med_kept(const TiledParamsMed p) {
 
 // one work-group: thread t takes partials t, t + 256, ... in order, then the waves' butterflies, then the four waves in order.  The
 // smoothness term: pass 2's per-patch terms added in fp64 and rounded once (the fp32 number nearest to their sum); the invalid rays:
-// pass 2's per-patch counts (whole numbers below 2^24) added as integers
+// pass 2's per-patch counts (whole numbers below 2^24) added as integers.  Written out here and in pixel_final_kernel: this one reads the
+// smoothness term and the invalid count from parts, that one from patch_stats / blk_inv
 __global__ __launch_bounds__(256) void loss_med_final(const TiledParamsMed p) {
   __shared__ float s_f[4];
   __shared__ double s_d[4];
@@ -583,8 +544,8 @@ inline void tiled_layout(Carver& w, TiledParamsThr& p, size_t n_patches, size_t 
 inline void median_layout(Carver& w, TiledParamsMed& p, size_t n_patches, size_t n_tiles, size_t B, size_t n, size_t n_blocks) {
   tiled_layout(w, p, n_patches, n_tiles, B, true);
   p.e = w.take<float>(B);
-  p.hist = w.take<unsigned>(n * kMedHistSample);
-  p.state = w.take<unsigned>(n * kMedStateSample);
+  p.hist = w.take<unsigned>(n * kSelHistSample);
+  p.state = w.take<unsigned>(n * kSelStateSample);
   p.thr = w.take<float>(n);
   p.blk_sum = w.take<float>(n_blocks);
   p.blk_cnt = w.take<unsigned>(n_blocks);
@@ -627,7 +588,7 @@ int photometric_loss_median_impl(const BtsLossArgs* a, int n, const float* thres
   const unsigned grid = (unsigned)((long)nt < kMaxGrid ? (long)nt : kMaxGrid);
   const unsigned grid2 = (unsigned)(p.n_patches < kMaxGrid ? (long)p.n_patches : kMaxGrid);
   const unsigned gridr = (unsigned)p.n_blocks;
-  if (hipMemsetAsync(p.hist, 0, (size_t)n * kMedHistSample * sizeof(unsigned), s) != hipSuccess) {
+  if (hipMemsetAsync(p.hist, 0, (size_t)n * kSelHistSample * sizeof(unsigned), s) != hipSuccess) {
     set_error("%s: clearing the histograms failed", "bts_photometric_loss_median");
     return BTS_E_LAUNCH;
   }

@@ -30,107 +30,63 @@ from torch.autograd import profiler
 from . import native
 
 
-class _PhotometricSums(torch.autograd.Function):
-    """(sum of the rgb term, sum of the smoothness term, number of invalid rays) over all patches; differentiable w.r.t. rgb, depth."""
+class _NativeTerms(torch.autograd.Function):
+    """One native loss call as an autograd node: ``fn(x, y, need_grad, kw) -> (terms, g_x | None, g_y | None)`` with g_x = d terms[ix] /
+    d x and g_y = d terms[iy] / d y written for an upstream gradient of 1; differentiable w.r.t. x and y, each scaled in backward by its
+    entry of the upstream gradient.  (x, y) = (rgb, depth) with entries (0, 1) for the photometric terms, (alphas, depth) THROUGH ENTRY 5
+    for the regularisers (their terms are read for the logging dict)."""
 
     @staticmethod
-    def forward(ctx, rgb, depth, weights, invalid, rgb_gt, ph, pw, policy, eas, invalid_wsum=None, invalid_any=None, thresh=None):
+    def forward(ctx, fn, entries, x, y, kw):
         ctx.set_materialize_grads(False)
-        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        parts, g_rgb, g_depth = native.photometric_loss(rgb, depth if eas else None, weights, invalid, rgb_gt, ph, pw, policy, eas, 1.0, 1.0,
-                                                        need_grad=need, invalid_wsum=invalid_wsum, invalid_any=invalid_any, thresh=thresh)
-        ctx.save_for_backward(g_rgb, g_depth)
-        ctx.had_depth = depth is not None
-        return parts.sum(0)[:3]
+        terms, g_x, g_y = fn(x, y, ctx.needs_input_grad[2] or ctx.needs_input_grad[3], kw)
+        ctx.save_for_backward(g_x, g_y)
+        ctx.entries = entries
+        return terms
 
     @staticmethod
     def backward(ctx, g):
-        g_rgb, g_depth = ctx.saved_tensors
+        g_x, g_y = ctx.saved_tensors
         if g is None:
-            return (None,) * 12
-        d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
-        d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
-        return d_rgb, d_depth, None, None, None, None, None, None, None, None, None, None
+            return (None,) * 5
+        ix, iy = ctx.entries
+        d_x = g_x * g[ix] if (g_x is not None and ctx.needs_input_grad[2]) else None
+        d_y = g_y * g[iy] if (g_y is not None and ctx.needs_input_grad[3]) else None
+        return None, None, d_x, d_y, None
 
 
-class _MedianTerms(torch.autograd.Function):
-    """(rgb term, sum of the smoothness term, number of invalid rays) of l1+ssim with median thresholding
-    (``native.photometric_loss_median``); the rgb term arrives normalised by the kept count; differentiable w.r.t. rgb, depth."""
-
-    @staticmethod
-    def forward(ctx, rgb, depth, weights, invalid, rgb_gt, n, ph, pw, policy, eas, invalid_wsum=None, invalid_any=None, thresh=None):
-        ctx.set_materialize_grads(False)
-        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        out, _, _, g_rgb, g_depth = native.photometric_loss_median(rgb, depth if eas else None, weights, invalid, rgb_gt, n, ph, pw, policy, eas,
-                                                                   1.0, 1.0, need_grad=need, invalid_wsum=invalid_wsum,
-                                                                   invalid_any=invalid_any, thresh=thresh)
-        ctx.save_for_backward(g_rgb, g_depth)
-        return out[:3]
-
-    @staticmethod
-    def backward(ctx, g):
-        g_rgb, g_depth = ctx.saved_tensors
-        if g is None:
-            return (None,) * 13
-        d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
-        d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
-        return (d_rgb, d_depth) + (None,) * 11
+# the native entries as _NativeTerms' fn (kw: the entry's keywords).  The photometric ones -> (rgb term, sum of the smoothness term, number of invalid rays):
+def _photometric_sums(rgb, depth, need_grad, kw):
+    """l1+ssim: the three as SUMS over all patches"""
+    parts, g_rgb, g_depth = native.photometric_loss(rgb, depth, scale_rgb=1.0, scale_eas=1.0, need_grad=need_grad, **kw)
+    return parts.sum(0)[:3], g_rgb, g_depth
 
 
-class _PixelTerms(torch.autograd.Function):
-    """(rgb term, sum of the smoothness term, number of invalid rays) of the per-pixel criteria l1 / l2 (``native.pixel_loss``); the rgb
-    term arrives normalised -- by 3 B, or with median thresholding by the kept count; differentiable w.r.t. rgb, depth."""
-
-    @staticmethod
-    def forward(ctx, rgb, depth, weights, invalid, rgb_samps, rgb_gt, n, ph, pw, criterion, policy, median, eas, invalid_wsum=None,
-                invalid_any=None, thresh=None):
-        ctx.set_materialize_grads(False)
-        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        out, _, _, g_rgb, g_depth = native.pixel_loss(rgb, depth if eas else None, weights, invalid, rgb_gt, n, ph, pw, criterion, policy, median,
-                                                      eas, 1.0, 1.0, need_grad=need, invalid_wsum=invalid_wsum, invalid_any=invalid_any,
-                                                      rgb_samps=rgb_samps, thresh=thresh)
-        ctx.save_for_backward(g_rgb, g_depth)
-        return out[:3]
-
-    @staticmethod
-    def backward(ctx, g):
-        g_rgb, g_depth = ctx.saved_tensors
-        if g is None:
-            return (None,) * 16
-        d_rgb = g_rgb * g[0] if (g_rgb is not None and ctx.needs_input_grad[0]) else None
-        d_depth = g_depth * g[1] if (g_depth is not None and ctx.needs_input_grad[1]) else None
-        return (d_rgb, d_depth) + (None,) * 14
+def _median_terms(rgb, depth, need_grad, kw):
+    """l1+ssim with median thresholding: the rgb term arrives normalised by the kept count"""
+    out, _, _, g_rgb, g_depth = native.photometric_loss_median(rgb, depth, need_grad=need_grad, **kw)
+    return out[:3], g_rgb, g_depth
 
 
-class _RegTerms(torch.autograd.Function):
-    """One scale's regularisers (``native.loss_regularisers``) as one (6,) tensor: [alpha_reg, surfaceness, entropy, depth term, invalid
-    rays, reg = sum_t coef_t term_t]; differentiable w.r.t. alphas and depth THROUGH ENTRY 5 (the terms are read for the logging dict)."""
+def _pixel_terms(rgb, depth, need_grad, kw):
+    """l1 / l2: the rgb term arrives normalised -- by 3 B, or with median thresholding by the kept count"""
+    out, _, _, g_rgb, g_depth = native.pixel_loss(rgb, depth, need_grad=need_grad, **kw)
+    return out[:3], g_rgb, g_depth
 
-    @staticmethod
-    def forward(ctx, alphas, depth, layout, policy, weights, invalid, invalid_wsum, invalid_any, rgb_samps, coef, reduction, fraction):
-        ctx.set_materialize_grads(False)
-        need = (alphas is not None and ctx.needs_input_grad[0]) or (depth is not None and ctx.needs_input_grad[1])
-        n, pc, ph, pw = layout
-        _, _, g_alphas, g_depth, out = native.loss_regularisers_packed(alphas, depth, n=n, pc=pc, ph=ph, pw=pw, policy=policy, weights=weights,
-                                                                       invalid=invalid, invalid_wsum=invalid_wsum, invalid_any=invalid_any,
-                                                                       rgb_samps=rgb_samps, coef=coef, alpha_reg_reduction=reduction,
-                                                                       alpha_reg_fraction=fraction, need_grad=need)
-        ctx.save_for_backward(g_alphas, g_depth)
-        return out
 
-    @staticmethod
-    def backward(ctx, g):
-        g_alphas, g_depth = ctx.saved_tensors
-        if g is None:
-            return (None,) * 12
-        d_alphas = g_alphas * g[5] if (g_alphas is not None and ctx.needs_input_grad[0]) else None
-        d_depth = g_depth * g[5] if (g_depth is not None and ctx.needs_input_grad[1]) else None
-        return (d_alphas, d_depth) + (None,) * 10
+def _reg_terms(alphas, depth, need_grad, kw):
+    """one scale's regularisers as one (6,) tensor: [alpha_reg, surfaceness, entropy, depth term, invalid rays, reg = sum_t coef_t term_t]"""
+    _, _, g_alphas, g_depth, out = native.loss_regularisers_packed(alphas, depth, need_grad=need_grad, **kw)
+    return out, g_alphas, g_depth
+
+
+_MASKS = ("weights", "invalid", "invalid_wsum", "invalid_any", "rgb_samps")      # the invalid-ray inputs, by the native entries' keywords
 
 
 def _flat(t, tail):
     """(n, pc, h, w, *tail) -> contiguous float32 (B, prod(tail))"""
-    return t.reshape((-1,) + tuple(tail)).float().contiguous()
+    t = t.reshape((-1,) + tuple(tail))
+    return t if (t.dtype is torch.float32 and t.is_contiguous()) else t.float().contiguous()      # (the renderer's outputs are: no call)
 
 
 def _same_view(a, b):
@@ -209,7 +165,7 @@ class ReconstructionLoss:
         self.alpha_reg_fraction = config.get("alpha_reg_fraction", 1 / 8)
         if self.alpha_reg_reduction not in ("ray", "slice"):
             raise ValueError(f"Unknown reduction for alpha regularization: {self.alpha_reg_reduction}")
-        self._flags = None    # (scale 0's `invalid`, its diverse flags) of the call in flight
+        self._resolved = {}   # _mask_inputs' results of the call in flight (every scale reads scale 0's masks; one diverse-flags launch)
         self._lin = {}    # (scales, rays per scale, fine present, lambdas[, device]) -> the (9 x 3 S) matrix of loss_matrix()
         # opt-in (like native_mlp_color): criterion l1 / l2, median thresholding and weight_guided_diverse on bts_pixel_loss /
         # bts_loss_diverse_flags (csrc/bts_loss_pixel.hip)
@@ -252,79 +208,75 @@ class ReconstructionLoss:
                              f"with channels=4); got rgb_gt with {rgb_gt.shape[-1]} channels")
         return _flat(rgb_gt[..., :3], (3,)).detach(), _flat(rgb_gt[..., 3], ()).detach()
 
-    def _sums(self, level, level0, gt, eas):
-        """-> ((sum of the rgb term, sum of the smoothness term, number of invalid rays) as one (3,) tensor, number of rays) of one set
-        of renderer outputs in patch layout.  gt: _split_gt's pair."""
-        rgb_gt, thresh = gt
-        bound = () if thresh is None else (thresh,)          # (the autograd function's last argument, only with automasking)
-        rgb = level["rgb"]                                   # (n, pc, h, w, nv, 3)
-        n, pc, h, w, nv, c = rgb.shape
-        if c != 3:
-            raise NotImplementedError("the fused HIP loss takes 3 colour channels")
-        B = n * pc * h * w
-        # with median thresholding the same arguments go to _MedianTerms with the number of batch samples (and come back as terms, the
-        # rgb one normalised by the kept count: _photometric)
-        fn = (lambda *a: _MedianTerms.apply(*a[:5], n, *a[5:])) if self.ssim_median else _PhotometricSums.apply
+    @property
+    def regularisers_on(self):
+        """any optional regulariser's lambda > 0 (read per call: a schedule may change them)"""
+        return (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0 or self.lambda_depth_smoothness > 0
+                or self.lambda_entropy > 0)
+
+    def _mask_keys(self, level0):
+        """the entries of scale 0's render dict the invalid-ray policy reads (a fine dict that aliases them shares the coarse launch): the
+        per-sample tensors of a full dict, the renderer's per-ray reductions of a lean one, all three per-sample tensors under diverse"""
+        if not self.ignore_invalid:
+            return ()
         if self.diverse:
-            # l1+ssim under weight_guided_diverse: the per-(ray, view) flags (bts_loss_diverse_flags) as `invalid_any` of the strict
-            # policy, whose all_v(flag > .5) is the diverse rule -- the shipped loss kernels serve it unchanged
-            sums = fn(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
-                      rgb_gt, h, w, "strict", eas, None, self._diverse_flags(level0), *bound)
-            return sums, B
+            missing = [k for k in ("rgb_samps", "weights", "invalid") if k not in level0]
+            if missing:
+                raise KeyError("invalid_policy weight_guided_diverse reads the per-sample `rgb_samps`, `weights` and `invalid`, which this render "
+                               f"dict does not carry (missing: {', '.join(missing)}): call the renderer with want_rgb_samps=True and "
+                               "want_weights=True and without lean_training_outputs (NeRFRenderer drops the per-sample tensors in that mode)")
+            return ("rgb_samps", "weights", "invalid")
         if "weights" not in level0:     # lean training outputs: the renderer's epilogue reduced weights / invalid per ray and view
-            sums = fn(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, None, None,
-                      rgb_gt, h, w, self.invalid_policy, eas,
-                      _flat(level0["invalid_wsum"], (nv,)).detach() if self.invalid_policy == "weight_guided" else None,
-                      _flat(level0["invalid_any"], (nv,)).detach() if self.invalid_policy == "strict" else None, *bound)
-            return sums, B
-        K = level0["weights"].shape[-1]
-        sums = fn(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None,
-                  _flat(level0["weights"], (K,)).detach() if self.invalid_policy == "weight_guided" else None,
-                  _flat(level0["invalid"], (K, nv)).detach() if self.ignore_invalid else None,
-                  rgb_gt, h, w, self.invalid_policy, eas, *((None, None) + bound if bound else ()))
-        return sums, B
+            return ("invalid_wsum",) if self.invalid_policy == "weight_guided" else ("invalid_any",)
+        return ("weights", "invalid") if self.invalid_policy == "weight_guided" else ("invalid",)
 
-    def _diverse_inputs(self, level0):
-        """(rgb_samps (B, K, nv, 3), weights (B, K), invalid (B, K, nv)) of weight_guided_diverse, flat"""
-        missing = [k for k in ("rgb_samps", "weights", "invalid") if k not in level0]
-        if missing:
-            raise KeyError("invalid_policy weight_guided_diverse reads the per-sample `rgb_samps`, `weights` and `invalid`, which this render "
-                           f"dict does not carry (missing: {', '.join(missing)}): call the renderer with want_rgb_samps=True and "
-                           "want_weights=True and without lean_training_outputs (NeRFRenderer drops the per-sample tensors in that mode)")
-        K, nv = level0["invalid"].shape[-2:]
-        return (_flat(level0["rgb_samps"], (K, nv, 3)).detach(), _flat(level0["weights"], (K,)).detach(),
-                _flat(level0["invalid"], (K, nv)).detach())
+    def _mask_inputs(self, level0, per_sample=False):
+        """Scale 0's render dict -> (the policy for the kernels, {weights, invalid, invalid_wsum, invalid_any[, rgb_samps]: flat tensor |
+        None}) as the native entries take them by keyword: what _mask_keys names, flat (B, ...) and detached; a tensor the policy does not
+        read is None (and never flattened).  Under diverse the kernels of l1+ssim and the regularisers get the per-(ray, view) flags
+        (bts_loss_diverse_flags) as `invalid_any` of the strict policy, whose all_v(flag > .5) is the diverse rule -- they serve it
+        unchanged; ``per_sample``: the three per-sample tensors themselves (native.pixel_loss, and the flags' own inputs).  Resolved once
+        per render dict and call (every scale reads scale 0's: one flattening, one flags launch); the callers do not write to the result."""
+        hit = self._resolved.get((id(level0), per_sample))
+        if hit is not None and hit[0] is level0:
+            return hit[1:]
+        keys = self._mask_keys(level0)
+        policy, masks = self.invalid_policy, dict.fromkeys(_MASKS if per_sample else _MASKS[:4])
+        if self.diverse and not per_sample:
+            m = self._mask_inputs(level0, per_sample=True)[1]
+            policy, masks["invalid_any"] = "strict", native.loss_diverse_flags(m["rgb_samps"], m["weights"], m["invalid"])
+        else:
+            for k in keys:      # (n, pc, h, w, *tail) each; rgb_samps as (K, nv, 3) however the renderer folded its last two
+                tail = level0[k].shape[4:] if k != "rgb_samps" else tuple(level0["invalid"].shape[4:]) + (3,)
+                masks[k] = _flat(level0[k], tail).detach()
+        self._resolved[(id(level0), per_sample)] = (level0, policy, masks)
+        return policy, masks
 
-    def _diverse_flags(self, level0):
-        """(B, nv) 0 / 1 floats; one launch per render dict and call (every scale reads scale 0's)"""
-        if self._flags is None or self._flags[0] is not level0.get("invalid"):
-            self._flags = (level0.get("invalid"), native.loss_diverse_flags(*self._diverse_inputs(level0)))
-        return self._flags[1]
-
-    def _pixel(self, level, level0, gt, eas):
-        """-> (rgb term, sum of the smoothness term, number of invalid rays) as one (3,) tensor, number of rays: criterion l1 / l2"""
+    def _terms(self, fn, level, level0, gt, eas, per_sample=False, **kw):
+        """-> (fn's three terms of one set of renderer outputs in patch layout as one (3,) tensor, number of rays).  gt: _split_gt's pair;
+        kw: the entry's own keywords."""
         rgb_gt, thresh = gt
         rgb = level["rgb"]                                   # (n, pc, h, w, nv, 3)
         n, pc, h, w, nv, c = rgb.shape
         if c != 3:
             raise NotImplementedError("the HIP loss takes 3 colour channels")
-        B = n * pc * h * w
-        weights = invalid = samps = wsum = any_ = None
-        if self.diverse:
-            samps, weights, invalid = self._diverse_inputs(level0)
-        elif self.ignore_invalid and "weights" not in level0:     # lean training outputs
-            if self.invalid_policy == "weight_guided":
-                wsum = _flat(level0["invalid_wsum"], (nv,)).detach()
-            else:
-                any_ = _flat(level0["invalid_any"], (nv,)).detach()
-        elif self.ignore_invalid:
-            K = level0["weights"].shape[-1]
-            invalid = _flat(level0["invalid"], (K, nv)).detach()
-            weights = _flat(level0["weights"], (K,)).detach() if self.invalid_policy == "weight_guided" else None
-        terms = _PixelTerms.apply(_flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, weights, invalid, samps,
-                                  rgb_gt, n, h, w, self.criterion_str, self.invalid_policy, bool(self.median_thresholding),
-                                  eas, wsum, any_, *(() if thresh is None else (thresh,)))
-        return terms, B
+        policy, masks = self._mask_inputs(level0, per_sample)
+        kw.update(masks, rgb_gt=rgb_gt, patch_h=h, patch_w=w, invalid_policy=policy, eas=eas, thresh=thresh)
+        terms = _NativeTerms.apply(fn, (0, 1), _flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, kw)
+        return terms, n * pc * h * w
+
+    def _sums(self, level, level0, gt, eas):
+        """-> ((sum of the rgb term, sum of the smoothness term, number of invalid rays) as one (3,) tensor, number of rays): l1+ssim.  With
+        median thresholding the same arguments go to the median entry with the number of batch samples (and come back as terms, the rgb
+        one normalised by the kept count: _photometric)"""
+        if self.ssim_median:
+            return self._terms(_median_terms, level, level0, gt, eas, n=level["rgb"].shape[0])
+        return self._terms(_photometric_sums, level, level0, gt, eas)
+
+    def _pixel(self, level, level0, gt, eas):
+        """-> (rgb term, sum of the smoothness term, number of invalid rays) as one (3,) tensor, number of rays: criterion l1 / l2"""
+        return self._terms(_pixel_terms, level, level0, gt, eas, per_sample=True, n=level["rgb"].shape[0], criterion=self.criterion_str,
+                           median=bool(self.median_thresholding))
 
     def _photometric(self, level, level0, gt, eas):
         """-> (mean rgb term, mean smoothness term, invalid-ray ratio)"""
@@ -387,13 +339,6 @@ class ReconstructionLoss:
             return Md
         return M
 
-    def _mask_keys(self, coarse_0):
-        """the entries of scale 0's dict the invalid-ray policy reads (a fine dict that aliases them shares the coarse launch)"""
-        if self.diverse:
-            self._diverse_inputs(coarse_0)      # (a lean dict: the KeyError that says what to ask the renderer for)
-            return ("rgb_samps", "weights", "invalid")
-        return ("weights", "invalid") if "weights" in coarse_0 else ("invalid_wsum", "invalid_any")
-
     def _regularisers(self, coarse, coarse_0, scale, n_scales):
         """-> (6,) [alpha_reg, surfaceness, entropy, depth term, invalid rays, this scale's share of the loss] or None when no term is on
         at this scale: every regulariser whose lambda is > 0, one library call (``native_regularisers: true``).  The coefficients are
@@ -408,33 +353,23 @@ class ReconstructionLoss:
         n, pc, h, w = coarse["depth"].shape
         alphas = _flat(coarse["alphas"], (coarse["alphas"].shape[-1],)) if (coef[0] > 0 or coef[1] > 0 or coef[2] > 0) else None
         depth = _flat(coarse["depth"], ()) if coef[3] > 0 else None
-        masked = self.ignore_invalid and alphas is not None      # (the depth term is never masked: alone it needs no keep flags)
-        policy, weights, invalid, wsum, any_ = self.invalid_policy if masked else "none", None, None, None, None
-        if masked and self.diverse:          # the per-(ray, view) diverse flags as `invalid_any` of the strict policy, as in _sums
-            policy, any_ = "strict", self._diverse_flags(coarse_0)
-        elif masked and "weights" not in coarse_0:     # lean training outputs
-            nv = coarse_0["invalid_any"].shape[-1]
-            if policy == "weight_guided":
-                wsum = _flat(coarse_0["invalid_wsum"], (nv,)).detach()
-            else:
-                any_ = _flat(coarse_0["invalid_any"], (nv,)).detach()
-        elif masked:
-            K, nv = coarse_0["invalid"].shape[-2:]
-            invalid = _flat(coarse_0["invalid"], (K, nv)).detach()
-            weights = _flat(coarse_0["weights"], (K,)).detach() if policy == "weight_guided" else None
-        return _RegTerms.apply(alphas, depth, (n, pc, h, w), policy, weights, invalid, wsum, any_, None, coef, self.alpha_reg_reduction,
-                               float(self.alpha_reg_fraction))
+        if self.ignore_invalid and alphas is not None:
+            policy, masks = self._mask_inputs(coarse_0)
+        else:                                                    # (the depth term is never masked: alone it needs no keep flags)
+            policy, masks = "none", dict.fromkeys(_MASKS[:4])
+        return _NativeTerms.apply(_reg_terms, (5, 5), alphas, depth,
+                                  dict(masks, rgb_samps=None, n=n, pc=pc, ph=h, pw=w, policy=policy, coef=coef,
+                                       alpha_reg_reduction=self.alpha_reg_reduction, alpha_reg_fraction=float(self.alpha_reg_fraction)))
 
     def __call__(self, data):
         with profiler.record_function("loss_computation"):       # loss.py:84
             try:
                 return self._call(data)
             finally:
-                self._flags = None
+                self._resolved.clear()
 
     def _call(self, data):
-        if not self.pixel_criterion and not self.ssim_median and not (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0 or self.lambda_depth_smoothness > 0
-                or self.lambda_entropy > 0):
+        if not self.pixel_criterion and not self.ssim_median and not self.regularisers_on:
             res = self._call_photometric_only(data)
             if res is not None:
                 return res
@@ -451,31 +386,24 @@ class ReconstructionLoss:
         m = dict(coarse=zero, fine=zero, depth_reg=zero, alpha_reg=zero, surf=zero, eas=zero, dsmooth=zero, inv=zero)
         keep_cache = None
         # `native_regularisers: true`: the blocks between the photometric term and the logging dict are one library call per scale
-        native_reg = self.native_regularisers and (self.lambda_depth_reg > 0 or self.lambda_alpha_reg > 0 or self.lambda_surfaceness_reg > 0
-                                                   or self.lambda_depth_smoothness > 0 or self.lambda_entropy > 0)
+        native_reg = self.native_regularisers and self.regularisers_on
         reg, ent = None, zero
 
-        def keep():   # 1 - invalid ray mask (n, pc, h, w) for the optional regularisers
+        def keep():   # 1 - invalid ray mask (n, pc, h, w) for the optional regularisers: the rule of the kernels' ray_invalid on _mask_inputs' tensors
             nonlocal keep_cache
-            if keep_cache is None and self.diverse:
-                keep_cache = 1 - torch.all(self._diverse_flags(coarse_0) > .5, dim=-1).reshape(coarse_0["depth"].shape).to(torch.float32)
-            if keep_cache is None and "weights" not in coarse_0:    # lean training outputs
-                if self.invalid_policy == "strict":
-                    bad = torch.all(coarse_0["invalid_any"] > .5, dim=-1)
-                elif self.invalid_policy == "weight_guided":
-                    bad = torch.all(coarse_0["invalid_wsum"] > .9, dim=-1)
-                else:
-                    bad = torch.zeros(coarse_0["depth"].shape, dtype=torch.bool, device=dev)
-                keep_cache = 1 - bad.to(torch.float32)
             if keep_cache is None:
-                inv, wts = coarse_0["invalid"], coarse_0["weights"]
-                if self.invalid_policy == "strict":
-                    bad = torch.all(torch.any(inv > .5, dim=-2), dim=-1)
-                elif self.invalid_policy == "weight_guided":
-                    bad = torch.all((inv.to(torch.float32) * wts.unsqueeze(-1)).sum(-2) > .9, dim=-1)
+                policy, m = self._mask_inputs(coarse_0)
+                if m["invalid_any"] is not None:             # strict on the renderer's reductions; the diverse flags
+                    bad = torch.all(m["invalid_any"] > .5, dim=-1)
+                elif m["invalid_wsum"] is not None:
+                    bad = torch.all(m["invalid_wsum"] > .9, dim=-1)
+                elif policy == "strict":
+                    bad = torch.all(torch.any(m["invalid"] > .5, dim=-2), dim=-1)
+                elif policy == "weight_guided":
+                    bad = torch.all((m["invalid"] * m["weights"].unsqueeze(-1)).sum(-2) > .9, dim=-1)
                 else:
-                    bad = torch.zeros(inv.shape[:-2], dtype=torch.bool, device=dev)
-                keep_cache = 1 - bad.to(torch.float32)
+                    bad = torch.zeros(coarse_0["depth"].numel(), dtype=torch.bool, device=dev)
+                keep_cache = 1 - bad.reshape(coarse_0["depth"].shape).to(torch.float32)
             return keep_cache
 
         for scale in range(n_scales):

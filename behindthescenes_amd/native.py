@@ -163,10 +163,69 @@ def patch_rays(poses_c2w, projs, images, patch_v, patch_y, patch_x, ph: int, pw:
     return rays, gt
 
 
-INVALID_POLICIES = {None: 0, "none": 0, "strict": 1, "weight_guided": 2}
-
+PIXEL_CRITERIA = {"l1": 1, "l2": 2}
+# THE invalid-ray policies (loss.py:100-118) as the kernels number them.  The l1+ssim entry points take the prefix without the diverse rule
+# (its per-(ray, view) flags go in as invalid_any under strict: loss_diverse_flags)
+PIXEL_POLICIES = {None: 0, "none": 0, "strict": 1, "weight_guided": 2, "weight_guided_diverse": 3}
+INVALID_POLICIES = {name: p for name, p in PIXEL_POLICIES.items() if p <= 2}
 
 WAVE_PATCH_PIXELS = 64      # bts_photometric_loss: one wave per patch, lane = pixel
+
+
+def _invalid_inputs(invalid_policy, table, B, weights, invalid, invalid_wsum, invalid_any, rgb_samps=None, nv=None):
+    """THE rule for which invalid-ray inputs a policy reads, for the four loss entry points: ``table`` is the policy table the entry point
+    accepts, ``nv`` the number of views where the caller knows it (else it is the tensors').  The renderer's per-ray reductions
+    (render_fwd(want_invalid_sums=True)) stand in for the per-sample tensors when given: invalid_wsum (B, nv) under weight_guided,
+    invalid_any (B, nv) under strict.  Else strict reads invalid (B, K, nv), weight_guided weights (B, K) too, weight_guided_diverse
+    rgb_samps (B, K, nv, 3) too (and never the sums).
+    -> (policy number, K of the per-sample tensors | 0, nv | 0, {name: tensor | None} of the five, None where the policy does not read it)"""
+    policy = table[invalid_policy]
+    masks = dict(weights=None, invalid=None, invalid_wsum=None, invalid_any=None, rgb_samps=None)
+    K = 0
+    sums = invalid_wsum if policy == 2 else invalid_any if policy == 1 else None
+    if sums is not None:
+        nv = sums.shape[-1] if nv is None else nv
+        masks["invalid_wsum" if policy == 2 else "invalid_any"] = _req(sums, "invalid_wsum / invalid_any", (B, nv))
+    elif policy:
+        if nv is None:
+            _req(invalid, "invalid")
+            nv = invalid.shape[2]
+        K = invalid.shape[1]
+        masks["invalid"] = _req(invalid, "invalid", (B, K, nv))
+        if policy >= 2:
+            masks["weights"] = _req(weights, "weights", (B, K))
+        if policy == 3:
+            masks["rgb_samps"] = _req(rgb_samps, "rgb_samps", (B, K, nv, 3))
+    return policy, K, nv or 0, masks
+
+
+def _rgb_loss_inputs(rgb, depth, rgb_gt, thresh, eas, invalid_policy, table, weights, invalid, invalid_wsum, invalid_any, rgb_samps=None):
+    """the tensor checks photometric_loss, photometric_loss_median and pixel_loss share: rgb (B, nv*3), rgb_gt (B, 3), the invalid-ray
+    inputs, depth (B) with the smoothness term, thresh (B) when given -> _invalid_inputs' (policy, K, nv, masks)"""
+    B = rgb_gt.shape[0]
+    nv = rgb.shape[-1] // 3
+    _req(rgb, "rgb", (B, nv * 3)), _req(rgb_gt, "rgb_gt", (B, 3))
+    resolved = _invalid_inputs(invalid_policy, table, B, weights, invalid, invalid_wsum, invalid_any, rgb_samps, nv)
+    if eas:
+        _req(depth, "depth", (B,))
+    if thresh is not None:
+        _req(thresh, "thresh", (B,))
+    return resolved
+
+
+def _loss_args(rgb, depth, rgb_gt, parts, patch_h, patch_w, eas, scale_rgb, scale_eas, need_grad, with_depth, policy, K, nv, masks):
+    """The BtsLossArgs of the l1+ssim entry points and the gradients it points to -> (args, g_rgb | None, g_depth | None); the last four
+    arguments are _rgb_loss_inputs' result.  ``with_depth``: depth is handed over and gets its gradient -- photometric_loss says so whenever
+    depth is given, photometric_loss_median only with the smoothness term."""
+    depth = depth if with_depth else None
+    g_rgb = torch.empty_like(rgb) if need_grad else None
+    g_depth = torch.empty((rgb.shape[0],), device=rgb.device, dtype=torch.float32) if (need_grad and depth is not None) else None
+    a = _lib.BtsLossArgs(rgb=rgb.data_ptr(), depth=_addr(depth), weights=_addr(masks["weights"]), invalid=_addr(masks["invalid"]),
+                         rgb_gt=rgb_gt.data_ptr(), parts=parts.data_ptr(), g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), n_patches=parts.shape[0],
+                         patch_h=patch_h, patch_w=patch_w, nv=nv, K=K, invalid_policy=policy, edge_aware_smoothness=int(bool(eas)),
+                         scale_rgb=scale_rgb, scale_eas=scale_eas, invalid_wsum=_addr(masks["invalid_wsum"]),
+                         invalid_any=_addr(masks["invalid_any"]))
+    return a, g_rgb, g_depth
 
 
 def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w: int, invalid_policy, eas: bool,
@@ -180,34 +239,9 @@ def photometric_loss(rgb, depth, weights, invalid, rgb_gt, patch_h: int, patch_w
     area = patch_h * patch_w
     if B % area:
         raise BtsNativeError(f"{B} rays are not a whole number of {patch_h}x{patch_w} patches")
-    nv = rgb.shape[-1] // 3
-    policy = INVALID_POLICIES[invalid_policy]
-    _req(rgb, "rgb", (B, nv * 3)), _req(rgb_gt, "rgb_gt", (B, 3))
-    K = 0
-    # the renderer's per-ray reductions (render_fwd(want_invalid_sums=True)) stand in for the per-sample tensors
-    sums = (policy == 2 and invalid_wsum is not None) or (policy == 1 and invalid_any is not None)
-    if sums:
-        _req(invalid_wsum if policy == 2 else invalid_any, "invalid_wsum / invalid_any", (B, nv))
-        weights = invalid = None
-    elif policy:
-        K = invalid.shape[1]
-        _req(invalid, "invalid", (B, K, nv))
-        if policy == 2:
-            _req(weights, "weights", (B, K))
-    if eas:
-        _req(depth, "depth", (B,))
-    if thresh is not None:
-        _req(thresh, "thresh", (B,))
-    dev = rgb.device
-    parts = torch.empty((B // area, 4), device=dev, dtype=torch.float32)
-    g_rgb = torch.empty_like(rgb) if need_grad else None
-    g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and depth is not None) else None
-    a = _lib.BtsLossArgs(rgb=rgb.data_ptr(), depth=_addr(depth), weights=_addr(weights if policy == 2 else None),
-                         invalid=_addr(invalid if policy else None), rgb_gt=rgb_gt.data_ptr(), parts=parts.data_ptr(), g_rgb=_addr(g_rgb),
-                         g_depth=_addr(g_depth), n_patches=B // area, patch_h=patch_h, patch_w=patch_w,
-                         nv=nv, K=K, invalid_policy=policy, edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
-                         scale_eas=scale_eas, invalid_wsum=_addr(invalid_wsum if (sums and policy == 2) else None),
-                         invalid_any=_addr(invalid_any if (sums and policy == 1) else None))
+    resolved = _rgb_loss_inputs(rgb, depth, rgb_gt, thresh, eas, invalid_policy, INVALID_POLICIES, weights, invalid, invalid_wsum, invalid_any)
+    parts = torch.empty((B // area, 4), device=rgb.device, dtype=torch.float32)
+    a, g_rgb, g_depth = _loss_args(rgb, depth, rgb_gt, parts, patch_h, patch_w, eas, scale_rgb, scale_eas, need_grad, True, *resolved)
     if area > WAVE_PATCH_PIXELS:
         # larger patches and whole frames: 16 x 16 tiles of each patch (bts_photometric_loss_tiled)
         return photometric_loss_tiled(a, parts, g_rgb, g_depth, _stream(rgb), thresh)
@@ -233,10 +267,6 @@ def photometric_loss_tiled(a, parts, g_rgb, g_depth, stream, thresh=None):
     return parts, g_rgb, g_depth
 
 
-PIXEL_CRITERIA = {"l1": 1, "l2": 2}
-PIXEL_POLICIES = {None: 0, "none": 0, "strict": 1, "weight_guided": 2, "weight_guided_diverse": 3}
-
-
 def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch_w: int, criterion: str, invalid_policy, median: bool,
                eas: bool, scale_rgb: float = 1.0, scale_eas: float = 1.0, need_grad: bool = True, invalid_wsum=None, invalid_any=None,
                rgb_samps=None, thresh=None):
@@ -254,25 +284,8 @@ def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch
     B = rgb_gt.shape[0]
     if n <= 0 or patch_h <= 0 or patch_w <= 0 or B % (n * patch_h * patch_w):
         raise BtsNativeError(f"{B} rays are not {n} samples of whole {patch_h}x{patch_w} patches")
-    nv = rgb.shape[-1] // 3
-    policy = PIXEL_POLICIES[invalid_policy]
-    _req(rgb, "rgb", (B, nv * 3)), _req(rgb_gt, "rgb_gt", (B, 3))
-    K = 0
-    sums = (policy == 2 and invalid_wsum is not None) or (policy == 1 and invalid_any is not None)
-    if sums:
-        _req(invalid_wsum if policy == 2 else invalid_any, "invalid_wsum / invalid_any", (B, nv))
-        weights = invalid = None
-    elif policy:
-        K = invalid.shape[1]
-        _req(invalid, "invalid", (B, K, nv))
-        if policy >= 2:
-            _req(weights, "weights", (B, K))
-        if policy == 3:
-            _req(rgb_samps, "rgb_samps", (B, K, nv, 3))
-    if eas:
-        _req(depth, "depth", (B,))
-    if thresh is not None:
-        _req(thresh, "thresh", (B,))
+    policy, K, nv, masks = _rgb_loss_inputs(rgb, depth, rgb_gt, thresh, eas, invalid_policy, PIXEL_POLICIES, weights, invalid, invalid_wsum,
+                                            invalid_any, rgb_samps)
     dev = rgb.device
     out = torch.empty((4,), device=dev, dtype=torch.float32)
     thresholds = torch.empty((n,), device=dev, dtype=torch.float32) if median else None
@@ -280,10 +293,7 @@ def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch
     g_rgb = torch.empty_like(rgb) if need_grad else None
     g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and eas) else None
     a = _lib.BtsPixelLossArgs(rgb=rgb.data_ptr(), rgb_gt=rgb_gt.data_ptr(), depth=_addr(depth if eas else None),
-                              weights=_addr(weights if policy >= 2 else None), invalid=_addr(invalid if policy else None),
-                              invalid_wsum=_addr(invalid_wsum if (sums and policy == 2) else None),
-                              invalid_any=_addr(invalid_any if (sums and policy == 1) else None),
-                              rgb_samps=_addr(rgb_samps if policy == 3 else None), out=out.data_ptr(),
+                              **{name: _addr(t) for name, t in masks.items()}, out=out.data_ptr(),
                               thresholds=_addr(thresholds), kept=_addr(kept), g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), B=B, n=n,
                               patch_h=patch_h, patch_w=patch_w, nv=nv, K=K, criterion=PIXEL_CRITERIA[criterion], invalid_policy=policy,
                               median_thresholding=int(bool(median)), edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
@@ -314,23 +324,7 @@ def photometric_loss_median(rgb, depth, weights, invalid, rgb_gt, n: int, patch_
     area = patch_h * patch_w
     if n <= 0 or area <= 0 or B % (n * area):
         raise BtsNativeError(f"{B} rays are not {n} samples of whole {patch_h}x{patch_w} patches")
-    nv = rgb.shape[-1] // 3
-    policy = INVALID_POLICIES[invalid_policy]
-    _req(rgb, "rgb", (B, nv * 3)), _req(rgb_gt, "rgb_gt", (B, 3))
-    K = 0
-    sums = (policy == 2 and invalid_wsum is not None) or (policy == 1 and invalid_any is not None)
-    if sums:
-        _req(invalid_wsum if policy == 2 else invalid_any, "invalid_wsum / invalid_any", (B, nv))
-        weights = invalid = None
-    elif policy:
-        K = invalid.shape[1]
-        _req(invalid, "invalid", (B, K, nv))
-        if policy == 2:
-            _req(weights, "weights", (B, K))
-    if eas:
-        _req(depth, "depth", (B,))
-    if thresh is not None:
-        _req(thresh, "thresh", (B,))
+    resolved = _rgb_loss_inputs(rgb, depth, rgb_gt, thresh, eas, invalid_policy, INVALID_POLICIES, weights, invalid, invalid_wsum, invalid_any)
     dev = rgb.device
     if parts is None:
         parts = torch.empty((B // area, 4), device=dev, dtype=torch.float32)
@@ -338,16 +332,9 @@ def photometric_loss_median(rgb, depth, weights, invalid, rgb_gt, n: int, patch_
     out = torch.empty((4,), device=dev, dtype=torch.float32)
     thresholds = torch.empty((n,), device=dev, dtype=torch.float32)
     kept = torch.empty((1,), device=dev, dtype=torch.int64)
-    g_rgb = torch.empty_like(rgb) if need_grad else None
-    g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and eas) else None
-    a = _lib.BtsLossArgs(rgb=rgb.data_ptr(), depth=_addr(depth if eas else None), weights=_addr(weights if policy == 2 else None),
-                         invalid=_addr(invalid if policy else None), rgb_gt=rgb_gt.data_ptr(), parts=parts.data_ptr(), g_rgb=_addr(g_rgb),
-                         g_depth=_addr(g_depth), n_patches=B // area, patch_h=patch_h, patch_w=patch_w,
-                         nv=nv, K=K, invalid_policy=policy, edge_aware_smoothness=int(bool(eas)), scale_rgb=scale_rgb,
-                         scale_eas=scale_eas, invalid_wsum=_addr(invalid_wsum if (sums and policy == 2) else None),
-                         invalid_any=_addr(invalid_any if (sums and policy == 1) else None))
+    a, g_rgb, g_depth = _loss_args(rgb, depth, rgb_gt, parts, patch_h, patch_w, eas, scale_rgb, scale_eas, need_grad, bool(eas), *resolved)
     lib = _lib.load()
-    ws = _scratch(dev, lib.bts_photometric_loss_median_workspace(B // area, patch_h, patch_w, nv, n))
+    ws = _scratch(dev, lib.bts_photometric_loss_median_workspace(B // area, patch_h, patch_w, a.nv, n))
     _lib.check(lib.bts_photometric_loss_median(C.byref(a), n, _ptr(thresh), _ptr(out), _ptr(thresholds), _ptr(kept), ws.data_ptr(), ws.numel(),
                                                _stream(rgb)), "bts_photometric_loss_median")
     return out, thresholds, kept, g_rgb, g_depth
@@ -389,30 +376,14 @@ def loss_regularisers_packed(alphas, depth, *, n: int, pc: int, ph: int, pw: int
         B, K = depth.shape[0], 2
     if n <= 0 or pc <= 0 or ph <= 0 or pw <= 0 or B != n * pc * ph * pw:
         raise BtsNativeError(f"{B} rays are not {n} x {pc} patches of {ph}x{pw}")
-    pol = PIXEL_POLICIES[policy]
-    nv = Ki = 0
-    sums = (pol == 2 and invalid_wsum is not None) or (pol == 1 and invalid_any is not None)
-    if sums:
-        nv = (invalid_wsum if pol == 2 else invalid_any).shape[-1]
-        _req(invalid_wsum if pol == 2 else invalid_any, "invalid_wsum / invalid_any", (B, nv))
-        weights = invalid = None
-    elif pol:
-        _req(invalid, "invalid")
-        Ki, nv = invalid.shape[1:]
-        _req(invalid, "invalid", (B, Ki, nv))
-        if pol >= 2:
-            _req(weights, "weights", (B, Ki))
-        if pol == 3:
-            _req(rgb_samps, "rgb_samps", (B, Ki, nv, 3))
+    pol, Ki, nv, masks = _invalid_inputs(policy, PIXEL_POLICIES, B, weights, invalid, invalid_wsum, invalid_any, rgb_samps)
     if depth_on:
         _req(depth, "depth", (B,))
     dev = (alphas if alphas is not None else depth).device
     out = torch.empty((6,), device=dev, dtype=torch.float32)
     g_alphas = torch.empty_like(alphas) if (need_grad and alpha_on) else None
     g_depth = torch.empty((B,), device=dev, dtype=torch.float32) if (need_grad and depth_on) else None
-    a = _lib.BtsLossRegArgs(alphas=_addr(alphas), depth=_addr(depth if depth_on else None), weights=_addr(weights if pol >= 2 else None),
-                            invalid=_addr(invalid if pol else None), invalid_wsum=_addr(invalid_wsum if (sums and pol == 2) else None),
-                            invalid_any=_addr(invalid_any if (sums and pol == 1) else None), rgb_samps=_addr(rgb_samps if pol == 3 else None),
+    a = _lib.BtsLossRegArgs(alphas=_addr(alphas), depth=_addr(depth if depth_on else None), **{name: _addr(t) for name, t in masks.items()},
                             terms=out.data_ptr(), reg=out.data_ptr() + 20, g_alphas=_addr(g_alphas), g_depth=_addr(g_depth), B=B,
                             n_patches=n * pc, patch_h=ph, patch_w=pw, nv=nv, K=K, K_invalid=Ki, invalid_policy=pol,
                             alpha_reg_slice=int(alpha_reg_reduction == "slice"), alpha_reg_fraction=alpha_reg_fraction,

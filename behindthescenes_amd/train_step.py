@@ -217,8 +217,7 @@ class FusedTrainStep(torch.nn.Module):
             return "fine pass / sampling schedule / density noise / white background"
         if getattr(r.sample_coarse, "__func__", None) is not NeRFRenderer.sample_coarse:
             return "sample_coarse is overridden"
-        if (crit.lambda_depth_reg > 0 or crit.lambda_alpha_reg > 0 or crit.lambda_surfaceness_reg > 0 or crit.lambda_depth_smoothness > 0
-                or crit.lambda_entropy > 0):
+        if crit.regularisers_on:
             return "an optional regulariser of the loss is on"
         # the one-call step's loss pass is bts_photometric_loss: l1+ssim, no median thresholding, no diverse flags (native_pixel_loss)
         if crit.criterion_str != "l1+ssim":

@@ -158,6 +158,7 @@
       f32x16 acc[HT][2];
       unsigned off_next[4];
       GRows rows;
+      GTapRegs taps;   // PINNED: the general loop's tap table rows in registers (gl_read_taps); nothing touches it anywhere else
       if constexpr (SHARED) {
         gs_issue<HD>(gl, G, (unsigned)s00 * (HD * 4u), (unsigned)s01 * (HD * 4u), (unsigned)s10 * (HD * 4u), lane);
       } else {
@@ -168,7 +169,7 @@
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        gl_prologue<HD>(gl, rows, G, off_next);
+        gl_prologue<HD, PINNED>(gl, rows, G, off_next, &taps);
       }
       {
         // bias row (times 2^S, fp32): the C operand of the first MFMA of every accumulator tile.  The raw inputs x, y, code ride in
@@ -190,10 +191,10 @@
         __builtin_amdgcn_sched_barrier(0);
         int lane4 = lane * 4;
         asm volatile("" : "+v"(lane4));  // keep the A-operand reads inside the loop (see lane_off above)
-        region_seq_l<HD, 0, SHARED>(acc, gl, rows, G, wq, off_next, lh + LH::W_F16 + lane4, LH::TERM_STRIDE, raw, v3, ih.freq_factor, bias, h);
+        region_seq_l<HD, 0, SHARED, PINNED>(acc, gl, rows, G, wq, off_next, lh + LH::W_F16 + lane4, LH::TERM_STRIDE, raw, v3, ih.freq_factor, bias, h, &taps);
         if constexpr (NS > kNumFreqs) {   // HD = 64: the last four blocks
-          g_step<HD, 12, SHARED>(acc, gl, rows, G, wq, off_next, h), g_step<HD, 13, SHARED>(acc, gl, rows, G, wq, off_next, h);
-          g_step<HD, 14, SHARED>(acc, gl, rows, G, wq, off_next, h), g_step<HD, 15, SHARED>(acc, gl, rows, G, wq, off_next, h);
+          g_step<HD, 12, SHARED, PINNED>(acc, gl, rows, G, wq, off_next, h, &taps), g_step<HD, 13, SHARED, PINNED>(acc, gl, rows, G, wq, off_next, h, &taps);
+          g_step<HD, 14, SHARED, PINNED>(acc, gl, rows, G, wq, off_next, h, &taps), g_step<HD, 15, SHARED, PINNED>(acc, gl, rows, G, wq, off_next, h, &taps);
         }
       }
       if (BTS_PIN(PinnedSet::learn_empty, q->learn_empty) && __any(use_empty)) {

@@ -403,6 +403,36 @@ __device__ __forceinline__ void gl_offsets(const GatherLds& c, unsigned (&off)[4
     off[j] = (B::tap < 3 ? row[B::tap] : row[2] + row[1] - row[0]) + ((j & 1 ? c.piece16x : c.piece16) + kGlBias - 1024u * j);
   }
 }
+// The PINNED kernels' form of the table lookup (render_kernel_p: the only kernels with the registers for it, the unpinned two-loop
+// sibling sits at 256 VGPRs).  gl_offsets<HD, T> reads the lane's rows 8 j + m of point tile pt again for every block T, and each read is
+// a full LDS round trip in the step's serial chain (table read -> wait -> add -> next read); but the rows depend on (pt, j) alone -- the
+// tap is a choice among their three dwords, the hidden tile an instruction offset.  Here the lane reads its 4 x 3 dwords of a point
+// tile ONCE, back to back, and forms every block's offsets from registers with the same integer expression: the same numbers, 2 x 12
+// dword lookups per ray instead of 64 and no table wait in the step (profiles/r22a).
+struct GTapRegs {
+  unsigned t[2][4][3];   // [point tile][j][o00, o01, o10] of table row 32 pt + 8 j + m
+};
+template <int PT>
+__device__ __forceinline__ void gl_read_taps(const GatherLds& c, GTapRegs& t) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t.t[PT][j][i] = c.tab[(32 * PT + 8 * j + c.m) * 3 + i];
+}
+template <int HD, int T>
+__device__ __forceinline__ void gl_offsets_r(const GatherLds& c, const GTapRegs& t, unsigned (&off)[4]) {
+  using B = GBlock<HD, T>;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned (&row)[3] = t.t[B::pt][j];
+    off[j] = (B::tap < 3 ? row[B::tap] : row[2] + row[1] - row[0]) + ((j & 1 ? c.piece16x : c.piece16) + kGlBias - 1024u * j);
+  }
+}
+// the step whose offsets (block T + 4) are the last of point tile 0: tile 1's rows are read behind them, in front of the step's row
+// request -- LDS returns in order per wave, so they have landed when the next step's blend has its rows, a whole step before their
+// first use, and tile 0's registers are free by then.  (HD = 32: block 4 is tile 1 already, both tiles are read in the prologue.)
+template <int HD>
+constexpr int kTapsStep = GBlock<HD, 0>::NBLK / 2 - 5;
 // what the overwrite of a slot must wait for: one value computed from EACH of the four row pieces (ds_read_b128) of the block that
 // lived there.  See gl_issue.
 struct GDep {
@@ -445,9 +475,10 @@ __device__ __forceinline__ void gl_fetch(const GatherLds& c, GRows& r) {
 // out into T's slot, the offsets of block T + 4 are fetched from the table, and the rows of block T + 1 are requested from LDS -- last,
 // when block T + 1 has had the whole step to land (two blocks may still be in flight behind it).  -DBTS_GL_FETCH_EARLY requests them
 // first instead (rounds 1 - 2 shipped that order; 3 % slower on the eval frame, profiles/r03_experiments/r03k).
-template <int HD, int T>
+// PIN (the PINNED kernels): the offsets come from `taps` (GTapRegs above).
+template <int HD, int T, bool PIN = false>
 __device__ __forceinline__ void gl_consume(f32x16 (&acc)[HD / 32][2], const GatherLds& c, GRows& r, const float4* G, const float (&w)[2][4],
-                                           unsigned (&off_next)[4]) {
+                                           unsigned (&off_next)[4], GTapRegs* taps = nullptr) {
   using B = GBlock<HD, T>;
 #ifdef BTS_GL_FETCH_EARLY
   if constexpr (T + 1 < B::NBLK) gl_fetch<HD, T + 1, (T + 2 < B::NBLK ? 1 : 0)>(c, r);   // issued so far: blocks 0 .. T + 2
@@ -466,7 +497,13 @@ __device__ __forceinline__ void gl_consume(f32x16 (&acc)[HD / 32][2], const Gath
   }
   if constexpr (T + 3 < B::NBLK) {
     gl_issue<HD, T + 3>(c, G, off_next, GDep{{a[3], a[7], a[11], a[15]}});
-    if constexpr (T + 4 < B::NBLK) gl_offsets<HD, T + 4>(c, off_next);
+    if constexpr (PIN) {
+      if constexpr (T + 4 < B::NBLK) gl_offsets_r<HD, T + 4>(c, *taps, off_next);
+      // (the table is not written before the next ray's fences, and these reads are waited for long before: no new hazard)
+      if constexpr (T == kTapsStep<HD>) gl_read_taps<1>(c, *taps);
+    } else {
+      if constexpr (T + 4 < B::NBLK) gl_offsets<HD, T + 4>(c, off_next);
+    }
   }
 #ifndef BTS_GL_FETCH_EARLY
   if constexpr (T + 1 < B::NBLK) gl_fetch<HD, T + 1, (T + 3 < B::NBLK ? 2 : (T + 2 < B::NBLK ? 1 : 0))>(c, r);   // issued: blocks 0 .. T + 3
@@ -474,16 +511,25 @@ __device__ __forceinline__ void gl_consume(f32x16 (&acc)[HD / 32][2], const Gath
 }
 // start of a ray: table written and fenced by the caller; blocks 0, 1, 2 go out, block 0 is requested from LDS, the offsets of block 3
 // wait in off_next
-template <int HD>
-__device__ __forceinline__ void gl_prologue(const GatherLds& c, GRows& r, const float4* G, unsigned (&off_next)[4]) {
+template <int HD, bool PIN = false>
+__device__ __forceinline__ void gl_prologue(const GatherLds& c, GRows& r, const float4* G, unsigned (&off_next)[4], GTapRegs* taps = nullptr) {
   unsigned o0[4], o1[4], o2[4];
-  gl_offsets<HD, 0>(c, o0), gl_offsets<HD, 1>(c, o1), gl_offsets<HD, 2>(c, o2);
+  if constexpr (PIN) {
+    // the lane's twelve dwords of point tile 0, back to back, in front of the one wait below.  They are read after the caller's fences
+    // behind this ray's table write and waited for before anything else of the ray: the next ray's table write cannot overtake them.
+    gl_read_taps<0>(c, *taps);
+    if constexpr (kTapsStep<HD> < 0) gl_read_taps<1>(c, *taps);
+    gl_offsets_r<HD, 0>(c, *taps, o0), gl_offsets_r<HD, 1>(c, *taps, o1), gl_offsets_r<HD, 2>(c, *taps, o2);
+  } else {
+    gl_offsets<HD, 0>(c, o0), gl_offsets<HD, 1>(c, o1), gl_offsets<HD, 2>(c, o2);
+  }
   // nothing of the previous ray may still be queued in LDS when its slots are overwritten (gl_issue): the table reads above need the
   // wait anyway, LDS returns in order
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   const GDep none = {{0.0f, 0.0f, 0.0f, 0.0f}};
   gl_issue<HD, 0>(c, G, o0, none), gl_issue<HD, 1>(c, G, o1, none), gl_issue<HD, 2>(c, G, o2, none);
-  gl_offsets<HD, 3>(c, off_next);
+  if constexpr (PIN) gl_offsets_r<HD, 3>(c, *taps, off_next);
+  else gl_offsets<HD, 3>(c, off_next);
 }
 // ---------------------------------------------------------------------------------------------------------------
 // Rays whose samples share their texels (render_kernel_p's second loop).  A ray that starts at the encoder camera's centre projects
@@ -524,7 +570,10 @@ __device__ __forceinline__ void gs_first(const GatherLds& c, GRows& r, int h) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   gs_fetch<HD, 0>(c, r, h);
 }
-// gl_consume's step for a shared ray: blend block T (the same arithmetic in the same order), request the rows of block T + 1
+// gl_consume's step for a shared ray: blend block T (the same arithmetic in the same order), request the rows of block T + 1.
+// (Requested here, the four reads end up directly in front of their first FMA and the two halves of GRows::v fold into one.  Requesting
+// them in front of the blend, held there by an empty asm over block T's rows, hides that round trip under the eight packed FMAs -- and
+// gains nothing measurable on its own, the partner wave covers it already: profiles/r22a, not kept.)
 template <int HD, int T>
 __device__ __forceinline__ void gs_consume(f32x16 (&acc)[HD / 32][2], const GatherLds& c, GRows& r, const float (&w)[2][4], int h) {
   using B = GBlock<HD, T>;
@@ -542,21 +591,21 @@ __device__ __forceinline__ void gs_consume(f32x16 (&acc)[HD / 32][2], const Gath
   }
   if constexpr (T + 1 < B::NBLK) gs_fetch<HD, T + 1>(c, r, h);
 }
-// one step of either kind (SH: the ray shares its texels)
-template <int HD, int T, bool SH>
+// one step of either kind (SH: the ray shares its texels; PIN: the PINNED kernels' general step, offsets from `taps`)
+template <int HD, int T, bool SH, bool PIN = false>
 __device__ __forceinline__ void g_step(f32x16 (&acc)[HD / 32][2], const GatherLds& c, GRows& r, const float4* G, const float (&w)[2][4],
-                                       unsigned (&off_next)[4], int h) {
+                                       unsigned (&off_next)[4], int h, GTapRegs* taps = nullptr) {
   if constexpr (SH) gs_consume<HD, T>(acc, c, r, w, h);
-  else gl_consume<HD, T>(acc, c, r, G, w, off_next);
+  else gl_consume<HD, T, PIN>(acc, c, r, G, w, off_next, taps);
 }
 
 // Region R = octaves 2R (sines computed directly, one region ahead) and 2R + 1 (by angle doubling); the gather blocks 4R .. 4R + 3 are
 // blended behind the region's MFMAs.  The regions are not fenced from each other: the scheduler may pull the next region's
 // trigonometry under this region's MFMAs.
-template <int HD, int R, bool SH = false>
+template <int HD, int R, bool SH = false, bool PIN = false>
 __device__ __forceinline__ void region_seq_li(f32x16 (&acc)[HD / 32][2], const GatherLds& gl, GRows& rows, const float4* __restrict__ G,
                                               const float (&wq)[2][4], unsigned (&off_next)[4], const float* wf, int term_stride, SinCos3& raw,
-                                              SinCos3& pre, const float (&v3)[3], float ff, const f32x16* bias, int h = 0) {
+                                              SinCos3& pre, const float (&v3)[3], float ff, const f32x16* bias, int h = 0, GTapRegs* taps = nullptr) {
   constexpr int HT = HD / 32;
   constexpr int NS = 4 * HT;
   if constexpr (R < 3) {
@@ -580,21 +629,21 @@ __device__ __forceinline__ void region_seq_li(f32x16 (&acc)[HD / 32][2], const G
         if constexpr (SH) gs_first<HD>(gl, rows, h);
         else gl_fetch<HD, 0, 2>(gl, rows);   // blocks 1, 2 were issued after block 0
       }
-      g_step<HD, 4 * R + 0, SH>(acc, gl, rows, G, wq, off_next, h);
-      g_step<HD, 4 * R + 1, SH>(acc, gl, rows, G, wq, off_next, h);
-      g_step<HD, 4 * R + 2, SH>(acc, gl, rows, G, wq, off_next, h);
-      g_step<HD, 4 * R + 3, SH>(acc, gl, rows, G, wq, off_next, h);
+      g_step<HD, 4 * R + 0, SH, PIN>(acc, gl, rows, G, wq, off_next, h, taps);
+      g_step<HD, 4 * R + 1, SH, PIN>(acc, gl, rows, G, wq, off_next, h, taps);
+      g_step<HD, 4 * R + 2, SH, PIN>(acc, gl, rows, G, wq, off_next, h, taps);
+      g_step<HD, 4 * R + 3, SH, PIN>(acc, gl, rows, G, wq, off_next, h, taps);
     }
-    region_seq_li<HD, R + 1, SH>(acc, gl, rows, G, wq, off_next, wf, term_stride, raw, pre, v3, ff * 4.0f, bias, h);
+    region_seq_li<HD, R + 1, SH, PIN>(acc, gl, rows, G, wq, off_next, wf, term_stride, raw, pre, v3, ff * 4.0f, bias, h, taps);
   }
 }
-template <int HD, int R, bool SH = false>
+template <int HD, int R, bool SH = false, bool PIN = false>
 __device__ __forceinline__ void region_seq_l(f32x16 (&acc)[HD / 32][2], const GatherLds& gl, GRows& rows, const float4* __restrict__ G,
                                              const float (&wq)[2][4], unsigned (&off_next)[4], const float* wf, int term_stride, SinCos3& raw,
-                                             const float (&v3)[3], float ff, const f32x16* bias, int h = 0) {
+                                             const float (&v3)[3], float ff, const f32x16* bias, int h = 0, GTapRegs* taps = nullptr) {
   static_assert(R == 0, "entered at region 0");
   SinCos3 pre;
-  region_seq_li<HD, 0, SH>(acc, gl, rows, G, wq, off_next, wf, term_stride, raw, pre, v3, ff, bias, h);
+  region_seq_li<HD, 0, SH, PIN>(acc, gl, rows, G, wq, off_next, wf, term_stride, raw, pre, v3, ff, bias, h, taps);
 }
 
 // Cold path: a wave in which some sample's encoding argument leaves the fast sincos range (|arg| > 1e5: points within millimetres

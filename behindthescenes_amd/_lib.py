@@ -69,6 +69,15 @@ class BtsLossRegArgs(C.Structure):
                [("reserved_", C.c_int32)]
 
 
+class BtsSampleFineArgs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("rays", "weights", "z_coarse", "depth", "u", "t", "noise", "z_out", "z_depth_out", "nan_count")] + \
+               [("B", C.c_int64)] + [(k, C.c_int32) for k in ("mode", "Kc", "n_coarse", "Kf", "Kfd", "lindisp", "sorted")] + \
+               [("depth_std", C.c_float)]
+
+
+BTS_SAMPLE_FINE, BTS_SAMPLE_FROM_DIST = 0, 1
+
+
 class BtsTrainScale(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("feat_nchw", "jitter", "rgb", "depth", "invalid_wsum", "invalid_any", "proj_nhwc", "sampled_tiles",
                                           "z_samp", "sigma_raw", "trans", "rgb_samps", "loss_parts", "g_rgb", "g_depth", "gs_rgb", "gs_depth",
@@ -216,6 +225,8 @@ SYMBOLS = {
     "bts_loss_regularisers_workspace": (C.c_size_t, [C.c_int64, _I, _I, _I, _I]),
     "bts_loss_regularisers": (C.c_int, [C.POINTER(BtsLossRegArgs), _P, C.c_size_t, _P]),
     "bts_sample_coarse": (C.c_int, [_P, _P, C.c_int64, _I, _I, _P, _P]),
+    # importance / depth draws merged with the coarse depths, from-dist sampling (csrc/bts_sample_fine.hip)
+    "bts_sample_fine": (C.c_int, [C.POINTER(BtsSampleFineArgs), _P]),
     "bts_distance_to_z": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
     "bts_invert_small": (C.c_int, [_P, _P, _I, _I, _P]),
     "bts_train_step_fwd": (C.c_int, [C.POINTER(BtsTrainStep), _P]),

@@ -505,6 +505,47 @@ int bts_sample_coarse(const float* rays, const float* u, int64_t B, int32_t K, i
   BTS_CHECK_LAYOUT(rays && u && z_samp && B > 0 && K > 0, "bts_sample_coarse");
   return launched(sample_coarse_launch(rays, u, (long)B, K, lindisp, z_samp, (hipStream_t)stream), "bts_sample_coarse");
 }
+int bts_sample_fine(const BtsSampleFineArgs* a, void* stream) {
+  static const char who[] = "bts_sample_fine";
+  if (!a) {
+    set_error("%s: NULL args", who);
+    return BTS_E_INVALID;
+  }
+  if (a->mode != BTS_SAMPLE_FINE && a->mode != BTS_SAMPLE_FROM_DIST) {
+    set_error("%s: unknown mode %ld (BTS_SAMPLE_FINE = 0, BTS_SAMPLE_FROM_DIST = 1)", who, (long)a->mode);
+    return BTS_E_INVALID;
+  }
+  const bool from_dist = a->mode == BTS_SAMPLE_FROM_DIST;
+  if (a->B <= 0 || a->Kc <= 0 || (from_dist ? a->n_coarse <= 0 : (a->Kf <= 0 || a->Kfd < 0))) {
+    set_error(from_dist ? "%s: non-positive size (B, ns, n_coarse)" : "%s: non-positive size (B, Kc, Kf; Kfd < 0)", who);
+    return BTS_E_INVALID;
+  }
+  if (!from_dist && a->Kfd > a->Kf) {
+    set_error("%s: Kfd = %ld depth draws are more than the Kf = %ld fine samples", who, (long)a->Kfd, (long)a->Kf);
+    return BTS_E_INVALID;
+  }
+  if (from_dist && a->n_coarse > a->Kc) {
+    set_error("%s: n_coarse = %ld samples from ns = %ld bins would index past the borders (the reference raises)", who, (long)a->n_coarse,
+              (long)a->Kc);
+    return BTS_E_INVALID;
+  }
+  const bool imp = from_dist || a->Kf > a->Kfd, dep = !from_dist && a->Kfd > 0, pieces = !from_dist && !a->z_coarse;
+  if ((from_dist && !a->z_coarse) || (!from_dist && !a->rays) || (imp && (!a->weights || !a->u || !a->t)) || (dep && (!a->depth || !a->noise)) ||
+      ((!pieces || imp) && !a->z_out) || (pieces && dep && !a->z_depth_out)) {
+    set_error("%s: NULL required pointer (rays; weights, u, t with importance draws; depth, noise with depth draws; z_samp in from-dist mode; "
+              "the outputs)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->Kc < 2 || (from_dist ? a->Kc : a->Kc + a->Kf) > 256) {
+    set_error("%s: Kc = %ld, Kf = %ld are outside 2 <= Kc, Kc + Kf <= 256", who, (long)a->Kc, from_dist ? 0L : (long)a->Kf);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (a->B > (1L << 29)) {
+    set_error("%s: %ld rays are more than 2^29", who, (long)a->B);
+    return BTS_E_UNSUPPORTED;
+  }
+  return launched(sample_fine_launch(a, (hipStream_t)stream), who);
+}
 int bts_distance_to_z(const float* depths, const float* inv_K, int32_t N, int32_t H, int32_t W, float* out, void* stream) {
   BTS_CHECK_LAYOUT(depths && inv_K && out && N > 0 && H > 0 && W > 0, "bts_distance_to_z");
   return launched(distance_to_z_launch(depths, inv_K, N, H, W, out, (hipStream_t)stream), "bts_distance_to_z");

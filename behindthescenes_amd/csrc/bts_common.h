@@ -322,6 +322,14 @@ __device__ __forceinline__ float coarse_depth(float u, float base, float step, f
   const float den = inv_near * (1.0f - sv) + inv_far * sv;
   return div_by(1.0f, den, __builtin_amdgcn_rcpf(den));
 }
+// coarse_depth's near / far map for a z_step `sv` the caller formed itself (NeRFRenderer.sample_fine, nerf.py:176-185: the same
+// arithmetic on (ind + t) / n_coarse); bts_sample_fine.hip's
+__device__ __forceinline__ float depth_at(float sv, float near, float far, bool lindisp) {
+  if (!lindisp) return near * (1.0f - sv) + far * sv;
+  const float inv_near = div_by(1.0f, near, __builtin_amdgcn_rcpf(near)), inv_far = div_by(1.0f, far, __builtin_amdgcn_rcpf(far));
+  const float den = inv_near * (1.0f - sv) + inv_far * sv;
+  return div_by(1.0f, den, __builtin_amdgcn_rcpf(den));
+}
 
 // PE entry i of [x, y, zn | per octave k: sin(f_k x), sin(f_k y), sin(f_k zn), sin(f_k x + pi/2), ... ] (code.py:30-42);
 // i == kPeDim is the constant 1 that multiplies the bias row.

@@ -104,6 +104,8 @@ int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, c
 // ---- bts_loss_reg.hip: the alpha / surfaceness / entropy / depth regularisers
 size_t loss_reg_bytes(long B, int n_patches, int ph, int pw, int K);
 int loss_reg_impl(const BtsLossRegArgs* a, void* workspace, hipStream_t s);
+// ---- bts_sample_fine.hip: importance / depth draws and their merge with the coarse depths; from-dist sampling
+int sample_fine_launch(const BtsSampleFineArgs* a, hipStream_t s);
 // ---- bts_automask.hip: the error map of use_automasking
 long automask_tiles(int n, int H, int W);
 int automask_errors_launch(const float* images, int n, int v, int H, int W, const int* ids_loss, int L, float scale, float* errors,

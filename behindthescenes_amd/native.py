@@ -432,6 +432,63 @@ def sample_coarse(rays: torch.Tensor, u: torch.Tensor, lindisp: bool) -> torch.T
     return out
 
 
+def sample_fine(rays, weights, z_coarse, depth, u, t, noise, depth_std: float, lindisp: bool, nan_count=None):
+    """NeRFRenderer.sample_fine / sample_fine_depth and their merge with the coarse depths in one launch (bts_sample_fine,
+    csrc/bts_sample_fine.hip).  rays (B, 8); weights (B, Kc), u, t (B, n_imp) or all None (no importance draws); depth (B), noise
+    (B, Kfd) or both None (no depth draws); nan_count: an int32 tensor of one element the NaNs among the produced samples are added to,
+    or None.  With z_coarse (B, Kc) -> the sorted union (B, Kc + n_imp + Kfd); with z_coarse None -> (importance | None, depth | None),
+    unsorted.  Asynchronous on the current stream."""
+    _req(rays, "rays")
+    B = rays.shape[0]
+    _req(rays, "rays", (B, 8))
+    n_imp = 0 if u is None else u.shape[-1]
+    Kfd = 0 if noise is None else noise.shape[-1]
+    if n_imp + Kfd == 0:
+        raise BtsNativeError("sample_fine: neither importance draws (u, t) nor depth draws (noise) were given")
+    for name, x in (("weights", weights if n_imp else None), ("z_coarse", z_coarse)):
+        if x is not None:
+            _req(x, name)
+    # the per-ray count of the weights / coarse depths (the depth draws alone have none of their own: the smallest the entry takes)
+    Kc = weights.shape[-1] if n_imp else (z_coarse.shape[-1] if z_coarse is not None else 2)
+    if n_imp:
+        _req(weights, "weights", (B, Kc)), _req(u, "u", (B, n_imp)), _req(t, "t", (B, n_imp))
+    if z_coarse is not None:
+        _req(z_coarse, "z_coarse", (B, Kc))
+    if Kfd:
+        _req(depth, "depth", (B,)), _req(noise, "noise", (B, Kfd))
+    if nan_count is not None:
+        _req_as(nan_count, "nan_count", torch.int32, (1,))
+    dev = rays.device
+    if z_coarse is not None:
+        out, out_d = torch.empty((B, Kc + n_imp + Kfd), device=dev, dtype=torch.float32), None
+    else:
+        out = torch.empty((B, n_imp), device=dev, dtype=torch.float32) if n_imp else None
+        out_d = torch.empty((B, Kfd), device=dev, dtype=torch.float32) if Kfd else None
+    a = _lib.BtsSampleFineArgs(rays=_addr(rays), weights=_addr(weights if n_imp else None), z_coarse=_addr(z_coarse), depth=_addr(depth if Kfd else None),
+                               u=_addr(u), t=_addr(t), noise=_addr(noise), z_out=_addr(out), z_depth_out=_addr(out_d), nan_count=_addr(nan_count),
+                               B=B, mode=_lib.BTS_SAMPLE_FINE, Kc=Kc, n_coarse=Kc, Kf=n_imp + Kfd, Kfd=Kfd, lindisp=int(bool(lindisp)), sorted=1,
+                               depth_std=float(depth_std))
+    _lib.check(_lib.load().bts_sample_fine(C.byref(a), _stream(rays)), "bts_sample_fine")
+    return out if z_coarse is not None else (out, out_d)
+
+
+def sample_coarse_from_dist(weights, z_samp, u, t, lindisp: bool, sort: bool = False, nan_count=None):
+    """NeRFRenderer.sample_coarse_from_dist (bts_sample_fine in from-dist mode): weights, z_samp (B, ns), u, t (B, n_coarse) in [0, 1)
+    -> (B, n_coarse), ascending with ``sort``.  n_coarse > ns is an error (the reference raises there)."""
+    _req(weights, "weights"), _req(u, "u")
+    if weights.dim() != 2 or u.dim() != 2:
+        raise BtsNativeError(f"sample_coarse_from_dist: expected weights (B, ns) and u (B, n_coarse), got {tuple(weights.shape)}, {tuple(u.shape)}")
+    (B, ns), n_coarse = weights.shape, u.shape[1]
+    _req(z_samp, "z_samp", (B, ns)), _req(u, "u", (B, n_coarse)), _req(t, "t", (B, n_coarse))
+    if nan_count is not None:
+        _req_as(nan_count, "nan_count", torch.int32, (1,))
+    out = torch.empty((B, n_coarse), device=weights.device, dtype=torch.float32)
+    a = _lib.BtsSampleFineArgs(weights=_addr(weights), z_coarse=_addr(z_samp), u=_addr(u), t=_addr(t), z_out=_addr(out), nan_count=_addr(nan_count), B=B,
+                               mode=_lib.BTS_SAMPLE_FROM_DIST, Kc=ns, n_coarse=n_coarse, lindisp=int(bool(lindisp)), sorted=int(bool(sort)))
+    _lib.check(_lib.load().bts_sample_fine(C.byref(a), _stream(out)), "bts_sample_fine")
+    return out
+
+
 def invert_small(m: torch.Tensor) -> torch.Tensor:
     """(..., d, d) with d in {3, 4} -> inverses (bts_invert_small); the stand-in for torch.inverse on poses / intrinsics."""
     d = m.shape[-1]

@@ -32,7 +32,8 @@ class _RenderWrapper(torch.nn.Module):
 
 class NeRFRenderer(torch.nn.Module):
     def __init__(self, n_coarse=128, n_fine=0, n_fine_depth=0, noise_std=0.0, depth_std=0.01, eval_batch_size=100000,
-                 white_bkgd=False, lindisp=False, sched=None, hard_alpha_cap=False, lean_training_outputs=False):
+                 white_bkgd=False, lindisp=False, sched=None, hard_alpha_cap=False, lean_training_outputs=False,
+                 native_fine_sampling=False):
         super().__init__()
         self.n_coarse, self.n_fine, self.n_fine_depth = n_coarse, n_fine, n_fine_depth
         self.noise_std, self.depth_std = noise_std, depth_std
@@ -49,6 +50,14 @@ class NeRFRenderer(torch.nn.Module):
         # the lean training render also projects only the tiles of the feature map its samples read (BTSNet.native_field(sampled=...));
         # an attribute, not a config key: switch it off for an A/B
         self.sparse_projection = True
+        # (not a reference key) what sits between the two renders -- sample_fine, sample_fine_depth, the cat and the sort -- and
+        # sample_coarse_from_dist as ONE library call (native.sample_fine, csrc/bts_sample_fine.hip) instead of the torch composition
+        # below; the reference's NaN asserts become a device counter nothing waits for: see check_fine_samples()
+        self.native_fine_sampling = bool(native_fine_sampling)
+        self.register_buffer("fine_nan_count", torch.zeros(1, dtype=torch.int32), persistent=False)
+        # the draw seam of forward() under native_fine_sampling, like sample_coarse(rays, u): a dict with any of u, t (B, n_fine - n_fine_depth),
+        # noise (B, n_fine_depth), dist_u, dist_t (B, n_coarse) replaces the torch draw of that name; None: every draw is torch's
+        self.fine_draws = None
 
     # ---- sampling (nerf.py:103-208) ---------------------------------------------------------------------------------
     def sample_coarse(self, rays, u=None):
@@ -59,15 +68,45 @@ class NeRFRenderer(torch.nn.Module):
             u = torch.rand((B, self.n_coarse), device=rays.device, dtype=torch.float32)
         return native.sample_coarse(rays.float().contiguous(), u.contiguous(), self.lindisp)
 
-    def sample_coarse_from_dist(self, rays, weights, z_samp):
+    def _nan_counter(self, device):
+        """the persistent int32 the native sampling adds its NaN count to, on the rays' device"""
+        if self.fine_nan_count.device != device:
+            self.fine_nan_count = torch.zeros(1, dtype=torch.int32, device=device)
+        return self.fine_nan_count
+
+    def check_fine_samples(self):
+        """The reference's `assert not torch.any(torch.isnan(z))` for every native_fine_sampling call since the last check: one 4-byte
+        read (a synchronisation -- call it where the step synchronises anyway).  Raises once, then the counter is clean."""
+        n = int(self.fine_nan_count.item())
+        if n:
+            self.fine_nan_count.zero_()
+            raise AssertionError(f"{n} NaN sample depths since the last check (nerf.py:157, 190, 206)")
+
+    def _draws_from_dist(self, rays, u, t):
+        """the reference's two draws of sample_coarse_from_dist, in its order and shapes (nerf.py:137, 140)"""
+        if u is None:
+            u = torch.rand(rays.shape[0], self.n_coarse, dtype=torch.float32, device=rays.device)
+        if t is None:
+            t = torch.rand_like(u, dtype=torch.float32)
+        return u, t
+
+    def sample_coarse_from_dist(self, rays, weights, z_samp, u=None, t=None):
         B = rays.shape[0]
         num_samples = self.n_coarse
+        if self.native_fine_sampling:
+            u, t = self._draws_from_dist(rays, u, t)
+            count = torch.zeros(1, dtype=torch.int32, device=rays.device)
+            z_new = native.sample_coarse_from_dist(weights.detach().float().contiguous(), z_samp.float().contiguous(), u.contiguous(), t.contiguous(),
+                                                   self.lindisp, nan_count=count)
+            assert int(count.item()) == 0
+            return z_new
         weights = weights.detach() + 1e-5
         pdf = weights / torch.sum(weights, -1, keepdim=True)
         cdf = torch.cat([torch.zeros_like(pdf[:, :1]), torch.cumsum(pdf, -1)], -1)
-        u = torch.rand(B, num_samples, dtype=torch.float32, device=rays.device)
+        if u is None:
+            u = torch.rand(B, num_samples, dtype=torch.float32, device=rays.device)
         ids = torch.clamp(torch.searchsorted(cdf, u, right=True) - 1, 0, num_samples - 1)
-        interp = torch.rand_like(ids, dtype=torch.float32)
+        interp = torch.rand_like(ids, dtype=torch.float32) if t is None else t
         if self.lindisp:
             z_samp = 1 / z_samp
         centers = .5 * (z_samp[:, 1:] + z_samp[:, :-1])
@@ -79,14 +118,43 @@ class NeRFRenderer(torch.nn.Module):
         assert not torch.any(torch.isnan(z_new))
         return z_new
 
-    def sample_fine(self, rays, weights):
+    def _draws_fine(self, rays, u, t):
+        """the reference's two draws of sample_fine, in its order and shapes (nerf.py:176-182)"""
+        if u is None:
+            u = torch.rand(rays.shape[0], self.n_fine - self.n_fine_depth, dtype=torch.float32, device=rays.device)
+        if t is None:
+            t = torch.rand_like(u)
+        return u, t
+
+    def _draw_fine_depth(self, rays, noise):
+        """the reference's draw of sample_fine_depth (nerf.py:202)"""
+        if noise is None:
+            noise = torch.randn((rays.shape[0], self.n_fine_depth), dtype=torch.float32, device=rays.device)
+        return noise
+
+    def _native_weights(self, weights):
+        weights = weights.detach().float().contiguous()
+        if weights.shape[-1] != self.n_coarse:
+            raise native.BtsNativeError(f"native_fine_sampling: {weights.shape[-1]} weights per ray but n_coarse = {self.n_coarse} (the kernel "
+                                        "divides the bin index by the number of weights)")
+        return weights
+
+    def sample_fine(self, rays, weights, u=None, t=None):
         B = rays.shape[0]
+        if self.native_fine_sampling:
+            u, t = self._draws_fine(rays, u, t)
+            count = torch.zeros(1, dtype=torch.int32, device=rays.device)
+            z, _ = native.sample_fine(rays.float().contiguous(), self._native_weights(weights), None, None, u.contiguous(), t.contiguous(), None,
+                                      self.depth_std, self.lindisp, nan_count=count)
+            assert int(count.item()) == 0
+            return z
         weights = weights.detach() + 1e-5
         pdf = weights / torch.sum(weights, -1, keepdim=True)
         cdf = torch.cat([torch.zeros_like(pdf[:, :1]), torch.cumsum(pdf, -1)], -1)
-        u = torch.rand(B, self.n_fine - self.n_fine_depth, dtype=torch.float32, device=rays.device)
+        if u is None:
+            u = torch.rand(B, self.n_fine - self.n_fine_depth, dtype=torch.float32, device=rays.device)
         inds = torch.clamp_min(torch.searchsorted(cdf, u, right=True).float() - 1.0, 0.0)
-        z_steps = (inds + torch.rand_like(inds)) / self.n_coarse
+        z_steps = (inds + (torch.rand_like(inds) if t is None else t)) / self.n_coarse
         near, far = rays[:, -2:-1], rays[:, -1:]
         if not self.lindisp:
             z = near * (1 - z_steps) + far * z_steps
@@ -95,9 +163,16 @@ class NeRFRenderer(torch.nn.Module):
         assert not torch.any(torch.isnan(z))
         return z
 
-    def sample_fine_depth(self, rays, depth):
+    def sample_fine_depth(self, rays, depth, noise=None):
+        if self.native_fine_sampling:
+            noise = self._draw_fine_depth(rays, noise)
+            count = torch.zeros(1, dtype=torch.int32, device=rays.device)
+            _, z = native.sample_fine(rays.float().contiguous(), None, None, depth.detach().float().contiguous(), None, None, noise.contiguous(),
+                                      self.depth_std, self.lindisp, nan_count=count)
+            assert int(count.item()) == 0
+            return z
         z = depth.unsqueeze(1).repeat((1, self.n_fine_depth))
-        z = z + torch.randn_like(z) * self.depth_std
+        z = z + (torch.randn_like(z) if noise is None else noise) * self.depth_std
         z = torch.max(torch.min(z, rays[:, -1:]), rays[:, -2:-1])
         assert not torch.any(torch.isnan(z))
         return z
@@ -172,6 +247,7 @@ class NeRFRenderer(torch.nn.Module):
         sb = rays.shape[0]
         rays = rays.reshape(-1, 8)
         jitter = None
+        draws = self.fine_draws or {}
         if sample_from_dist is None:
             if isinstance(model, BTSNet) and getattr(self.sample_coarse, "__func__", None) is NeRFRenderer.sample_coarse:
                 # nerf.py:103-123 inside the render kernel: only the jitter is drawn here (the reference's torch.rand_like, :112).
@@ -183,8 +259,15 @@ class NeRFRenderer(torch.nn.Module):
         else:
             prop_weights, prop_z = sample_from_dist
             ns = prop_weights.shape[-1]
-            z_coarse = self.sample_coarse_from_dist(rays, prop_weights.reshape(-1, ns), prop_z.reshape(-1, ns))
-            z_coarse, _ = torch.sort(z_coarse, dim=-1)
+            if self.native_fine_sampling:
+                # nerf.py:125-159 and the sort of :340 in one launch; the NaN assert is the device counter (check_fine_samples)
+                u, t = self._draws_from_dist(rays, draws.get("dist_u"), draws.get("dist_t"))
+                z_coarse = native.sample_coarse_from_dist(prop_weights.detach().reshape(-1, ns).float().contiguous(),
+                                                          prop_z.detach().reshape(-1, ns).float().contiguous(), u.contiguous(), t.contiguous(),
+                                                          self.lindisp, sort=True, nan_count=self._nan_counter(rays.device))
+            else:
+                z_coarse = self.sample_coarse_from_dist(rays, prop_weights.reshape(-1, ns), prop_z.reshape(-1, ns))
+                z_coarse, _ = torch.sort(z_coarse, dim=-1)
         if (self.lean_training_outputs and self.training and not self.using_fine and torch.is_grad_enabled() and not getattr(model, "torch_mode", False)
                 and not getattr(getattr(model, "spec", None), "mlp_color", False)):   # (MLP-predicted colour: no per-ray invalid sums)
             # in a training step nothing downstream of the renderer reads the per-sample tensors except the loss'
@@ -203,13 +286,24 @@ class NeRFRenderer(torch.nn.Module):
             comp = self._composite(model, rays, z_coarse, True, sb, need_w, want_alphas, want_rgb_samps, True, False, jitter=jitter,
                                    want_z=want_z_samps or self.using_fine)
         outputs = dict(coarse=self._format_outputs(comp, sb, want_weights, want_alphas, want_z_samps, want_rgb_samps))
-        if self.using_fine:
+        if self.using_fine and self.native_fine_sampling:
+            # nerf.py:356-367 as ONE library call between the two renders: the draws (torch's, in the composition's order and shapes), then
+            # coarse weights, depths and depth -> the sorted union.  Nothing is synchronised: NaNs are counted on the device.
+            n_imp, n_fd = self.n_fine - self.n_fine_depth, self.n_fine_depth
+            u, t = self._draws_fine(rays, draws.get("u"), draws.get("t")) if n_imp > 0 else (None, None)
+            noise = self._draw_fine_depth(rays, draws.get("noise")) if n_fd > 0 else None
+            z_comb = native.sample_fine(rays.float().contiguous(), self._native_weights(comp[0]) if n_imp > 0 else None, comp[5].detach().contiguous(),
+                                        comp[2].detach().contiguous() if n_fd > 0 else None, None if u is None else u.contiguous(),
+                                        None if t is None else t.contiguous(), None if noise is None else noise.contiguous(), self.depth_std,
+                                        self.lindisp, nan_count=self._nan_counter(rays.device))
+        elif self.using_fine:
             all_samps = [comp[5]]
             if self.n_fine - self.n_fine_depth > 0:
                 all_samps.append(self.sample_fine(rays, comp[0].detach()))
             if self.n_fine_depth > 0:
                 all_samps.append(self.sample_fine_depth(rays, comp[2]))
             z_comb, _ = torch.sort(torch.cat(all_samps, dim=-1), dim=-1)
+        if self.using_fine:
             fine = self.composite(model, rays, z_comb, coarse=False, sb=sb, want_weights=want_weights, want_alphas=want_alphas,
                                   want_rgb_samps=want_rgb_samps)
             outputs["fine"] = self._format_outputs(fine, sb, want_weights, want_alphas, want_z_samps, want_rgb_samps)
@@ -248,7 +342,8 @@ class NeRFRenderer(torch.nn.Module):
                    noise_std=conf.get("noise_std", 0.0), depth_std=conf.get("depth_std", 0.01),
                    white_bkgd=conf.get("white_bkgd", white_bkgd), lindisp=conf.get("lindisp", True),
                    eval_batch_size=conf.get("eval_batch_size", eval_batch_size), sched=conf.get("sched", None),
-                   hard_alpha_cap=conf.get("hard_alpha_cap", False), lean_training_outputs=conf.get("lean_training_outputs", False))
+                   hard_alpha_cap=conf.get("hard_alpha_cap", False), lean_training_outputs=conf.get("lean_training_outputs", False),
+                   native_fine_sampling=conf.get("native_fine_sampling", False))
 
     def bind_parallel(self, net, gpus=None, simple_output=False):
         """Same contract as nerf.py:440-457.  Multi-GPU is one process per GPU (DDP over RCCL); the reference's dead

@@ -504,6 +504,58 @@ int bts_patch_rays(const float* poses_c2w, const float* projs, const float* imag
 int bts_sample_coarse(const float* rays, const float* u, int64_t B, int32_t K, int32_t lindisp, float* z_samp,
                       void* stream);
 
+/* What sits between the coarse and the fine render of NeRFRenderer.forward (models/common/render/nerf.py:161-208, 356-367), and
+ * sample_coarse_from_dist (:125-159), in ONE launch (csrc/bts_sample_fine.hip).  The caller draws the random numbers.
+ * mode BTS_SAMPLE_FINE: rays (B, 8), weights (B, Kc), z_coarse (B, Kc), depth (B), u and t (B, Kf - Kfd) in [0, 1), noise (B, Kfd)
+ * standard normal -> z_out (B, Kc + Kf) = the ascending sort of [z_coarse | sample_fine | sample_fine_depth].  With z_coarse == NULL
+ * ("pieces") nothing is merged: z_out (B, Kf - Kfd) = sample_fine and z_depth_out (B, Kfd) = sample_fine_depth as drawn, unsorted (a
+ * part with no draws is neither read nor written: its pointers may be NULL).
+ * mode BTS_SAMPLE_FROM_DIST: weights and z_coarse (= z_samp) (B, Kc = ns), u and t (B, n_coarse) -> z_out (B, n_coarse), ascending when
+ * `sorted`; rays, depth, noise, Kf and Kfd are not read.
+ * Per ray, in plain fp32 with IEEE divisions and no contraction:
+ *   S = sum_k (w_k + 1e-5), pdf_k = (w_k + 1e-5) / S, cdf = [0, inclusive scan of pdf] (a fixed order of summation, not the sequential one)
+ *   importance draw: ind = max(upper_bound(cdf, u) - 1, 0), sv = (ind + t) / Kc, z = bts_sample_coarse's near / far map of sv
+ *   depth draw:      z = max(min(depth + noise * depth_std, far), near), product and sum rounded separately
+ *   from-dist:       id = clamp(upper_bound(cdf, u) - 1, 0, n_coarse - 1), borders = [z_0, (z_i + z_{i+1}) / 2, z_{ns-1}] over 1 / z under
+ *                    lindisp, z = left (1 - t) + right t, 1 / z under lindisp
+ * The reference's quirks, kept on purpose:
+ *   - the last cdf entry is whatever fp32 gives, not 1, and ind has NO upper clamp: u at or above it gives ind = Kc and a depth beyond far;
+ *   - upper_bound is searchsorted(right=True), the first entry > u, with ATen's comparison (a NaN weight makes every entry "not above u":
+ *     finite samples, NOT counted below);
+ *   - sv divides by the number of weights per ray Kc (the reference's self.n_coarse), also when Kf differs;
+ *   - from-dist clamps the interval by n_coarse - 1, not by ns - 1: with n_coarse < ns the far intervals are never drawn;
+ *   - min / max are torch's: a NaN operand gives NaN (fminf / fmaxf would drop it);
+ *   - the merge orders like torch.sort: ascending, NaNs last; only the values are produced (the reference discards the permutation);
+ *     z_coarse need not be sorted.
+ * nan_count (int32, may be NULL): the number of NaNs among the PRODUCED samples (not the coarse ones) is ADDED to it with at most one
+ * integer atomic per wave -- what the reference's `assert not torch.any(torch.isnan(...))` look at, without a synchronisation.
+ * No float atomics; reruns are bit-identical.  BTS_E_INVALID with a bts_last_error text, nothing launched, for: a NULL required pointer, a
+ * non-positive size, Kfd > Kf, n_coarse > ns (the reference raises there), an unknown mode.  BTS_E_UNSUPPORTED outside 2 <= Kc,
+ * 1 <= Kf, Kc + Kf <= 256 (the render kernels' own limit; from-dist: 2 <= ns <= 256) or with more than 2^29 rays. */
+#define BTS_SAMPLE_FINE 0
+#define BTS_SAMPLE_FROM_DIST 1
+typedef struct {
+  const float* rays;       /* (B, 8): near = [6], far = [7] */
+  const float* weights;    /* (B, Kc) */
+  const float* z_coarse;   /* (B, Kc); fine mode: NULL = pieces; from-dist: z_samp */
+  const float* depth;      /* (B) */
+  const float* u;          /* (B, Kf - Kfd) | (B, n_coarse) */
+  const float* t;          /* like u */
+  const float* noise;      /* (B, Kfd) */
+  float* z_out;
+  float* z_depth_out;      /* pieces only: (B, Kfd) */
+  int32_t* nan_count;      /* (1) or NULL */
+  int64_t B;
+  int32_t mode;            /* BTS_SAMPLE_FINE | BTS_SAMPLE_FROM_DIST */
+  int32_t Kc;              /* weights per ray (from-dist: ns) */
+  int32_t n_coarse;        /* from-dist: samples to draw */
+  int32_t Kf, Kfd;         /* fine: n_fine, n_fine_depth */
+  int32_t lindisp;
+  int32_t sorted;          /* from-dist: sort z_out */
+  float depth_std;
+} BtsSampleFineArgs;
+int bts_sample_fine(const BtsSampleFineArgs* args, void* stream);
+
 /* distance_to_z (utils/projection_operations.py:4-16): depths (N, H, W), inv_K (N, 3, 3) = inverse(projs) -> z (N, H, W) */
 int bts_distance_to_z(const float* depths, const float* inv_K, int32_t N, int32_t H, int32_t W, float* out, void* stream);
 

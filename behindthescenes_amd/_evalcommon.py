@@ -49,6 +49,8 @@ class FusedOccupancy:
 
     def _field(self):
         who, ft = type(self).__name__, self.net.native_field()
+        if isinstance(ft, native.MultiViewField):
+            raise BtsNativeError(f"{who}: not available for a field with more than one encoder view")
         if ft.mlp_color:
             raise BtsNativeError(f"{who}: not available for MLP-predicted colour (sample_color=False)")
         if ft.n != 1:

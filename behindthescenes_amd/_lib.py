@@ -48,6 +48,18 @@ class BtsRenderGrads(C.Structure):
                                           "d_empty_proj", "d_proj_tiles")]
 
 
+BTS_MV_MAX_VIEWS = 8
+
+
+class BtsMultiViewField(C.Structure):
+    """Merged encoder views (include/bts_render.h): view v is the single-view field (cfg[v], view[v]), then the encoder / render group tables."""
+    _fields_ = [(k, C.c_int32) for k in ("V", "n_enc_groups", "n_ren_groups", "reserved_")] + \
+               [("cfg", BtsFieldCfg * BTS_MV_MAX_VIEWS), ("view", BtsFieldTensors * BTS_MV_MAX_VIEWS),
+                ("enc_group_start", C.c_int32 * (BTS_MV_MAX_VIEWS + 1)), ("enc_member", C.c_int32 * BTS_MV_MAX_VIEWS),
+                ("enc_mult", C.c_int32 * BTS_MV_MAX_VIEWS), ("ren_group_start", C.c_int32 * (BTS_MV_MAX_VIEWS + 1)),
+                ("ren_member", C.c_int32 * BTS_MV_MAX_VIEWS)]
+
+
 class BtsLossArgs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("rgb", "depth", "weights", "invalid", "rgb_gt", "parts", "g_rgb", "g_depth")] + \
                [(k, C.c_int32) for k in ("n_patches", "patch_h", "patch_w", "nv", "K", "invalid_policy", "edge_aware_smoothness")] + \
@@ -249,6 +261,12 @@ SYMBOLS = {
     "bts_render_bwd_mlp_color": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsRenderArgs),
                                            C.POINTER(BtsRenderGrads), _P, C.c_size_t, _P]),
     "bts_field_query_mlp_color": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), _P, _I, _I, _P, _P, _P, _P]),
+    # merged encoder views (combine_ids / several ids_encoder)
+    "bts_render_fwd_multi_view": (C.c_int, [C.POINTER(BtsMultiViewField), C.POINTER(BtsRenderArgs), _P]),
+    "bts_render_bwd_multi_view_workspace": (C.c_size_t, [C.POINTER(BtsMultiViewField), C.POINTER(BtsRenderArgs)]),
+    "bts_render_bwd_multi_view": (C.c_int, [C.POINTER(BtsMultiViewField), C.POINTER(BtsRenderArgs), C.POINTER(BtsRenderGrads), C.POINTER(_P),
+                                            C.POINTER(_P), _P, C.c_size_t, _P]),
+    "bts_field_query_multi_view": (C.c_int, [C.POINTER(BtsMultiViewField), _P, _I, _P, _P, _P, _P]),
     # LiDAR occupancy evaluation (evaluator_lidar.py)
     "bts_lidar_slices_workspace": (C.c_size_t, [_I, _I]),
     "bts_lidar_slices": (C.c_int, [_P, C.POINTER(C.c_int32), _I, _P, _P, C.c_float, C.c_float, _I, C.c_float, _P, _P, _P]),

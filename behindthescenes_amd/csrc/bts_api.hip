@@ -637,6 +637,131 @@ int bts_field_query_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, 
   return mlp_color_field_query_impl(cfg, t, xyz, P, only_density, rgb, invalid, sigma, (hipStream_t)stream);
 }
 
+// ---- merged encoder views: everything bts_multi_view.hip's kernels index with is checked here; a bad table never reaches a launch
+static int check_group_table(const int32_t* start, const int32_t* member, int n_groups, int n_views, const char* who) {
+  if (n_groups < 1 || n_groups > BTS_MV_MAX_VIEWS) {
+    set_error("%s: %ld groups; 1 .. 8 are supported", who, (long)n_groups);
+    return BTS_E_INVALID;
+  }
+  if (start[0] != 0) {
+    set_error("%s: a group table must start at member 0 (got %ld)", who, (long)start[0]);
+    return BTS_E_INVALID;
+  }
+  unsigned seen = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    if (start[g + 1] <= start[g]) {
+      set_error("%s: group %ld is empty (or the table runs backwards)", who, (long)g);
+      return BTS_E_INVALID;
+    }
+    if (start[g + 1] > BTS_MV_MAX_VIEWS) {
+      set_error("%s: group %ld runs past the table's 8 members", who, (long)g);
+      return BTS_E_INVALID;
+    }
+    for (int m = start[g]; m < start[g + 1]; ++m) {
+      if (member[m] < 0 || member[m] >= n_views) {
+        set_error("%s: member %ld of group %ld is not one of the %ld views", who, (long)member[m], (long)g, (long)n_views);
+        return BTS_E_INVALID;
+      }
+      if (seen & (1u << member[m])) {
+        set_error("%s: view %ld is a member of two groups", who, (long)member[m]);
+        return BTS_E_INVALID;
+      }
+      seen |= 1u << member[m];
+    }
+  }
+  return BTS_OK;
+}
+
+static int check_multi_view(const BtsMultiViewField* mv, const char* who) {
+  if (!mv) {
+    set_error("%s: NULL field", who);
+    return BTS_E_INVALID;
+  }
+  if (mv->V < 1 || mv->V > BTS_MV_MAX_VIEWS) {
+    set_error("%s: V=%ld encoder views; 1 .. 8 are supported", who, (long)mv->V);
+    return BTS_E_INVALID;
+  }
+  const BtsFieldCfg* c0 = &mv->cfg[0];
+  if (c0->nv < 1 || c0->nv > BTS_MAX_VIEWS) {
+    set_error("%s: nv=%ld render views; 1 .. 8 are supported", who, (long)c0->nv);
+    return BTS_E_INVALID;
+  }
+  if (int rc = check_group_table(mv->enc_group_start, mv->enc_member, mv->n_enc_groups, mv->V, who)) return rc;
+  if (int rc = check_group_table(mv->ren_group_start, mv->ren_member, mv->n_ren_groups, c0->nv, who)) return rc;
+  for (int g = 0; g < mv->n_enc_groups; ++g)
+    if (mv->enc_mult[g] != 1 && mv->enc_mult[g] != 2) {
+      set_error("%s: encoder group %ld has multiplicity %ld; 1 or 2 expected", who, (long)g, (long)mv->enc_mult[g]);
+      return BTS_E_INVALID;
+    }
+  for (int v = 1; v < mv->V; ++v) {
+    const BtsFieldCfg* c = &mv->cfg[v];
+    if (c->n != c0->n || c->C != c0->C || c->d_hidden != c0->d_hidden || c->n_blocks != c0->n_blocks || c->H != c0->H || c->W != c0->W ||
+        c->feat_shift != c0->feat_shift || c->tile_blocks != c0->tile_blocks) {
+      set_error("%s: encoder view %ld differs from view 0 in n / C / d_hidden / n_blocks / H / W / feat_shift / tile_blocks", who, (long)v);
+      return BTS_E_UNSUPPORTED;
+    }
+  }
+  if (int rc = check_cfg(c0, &mv->view[0], true)) return rc;
+  for (int v = 0; v < mv->V; ++v)
+    if (!mv->view[v].proj_nhwc || !mv->view[v].K_enc || !mv->view[v].w2c_enc) {
+      set_error("%s: encoder view %ld: proj_nhwc, K_enc and w2c_enc are required", who, (long)v);
+      return BTS_E_INVALID;
+    }
+  return BTS_OK;
+}
+
+static int check_multi_view_args(const BtsRenderArgs* a, const char* who, bool bwd) {
+  if (int rc = check_render_args(a, who, bwd, true, bwd ? "%s: NULL argument (rays, z_samp and the forward's sigma_raw + trans are required)" : kFwdArgsNull))
+    return rc;
+  if (a->K > 256) {
+    set_error("%s: K=%ld samples per ray; the merged-view kernels take whole rays of at most 256 samples per work-group", who, (long)a->K);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (!bwd && (a->invalid_wsum || a->invalid_any)) {
+    set_error("%s: invalid_wsum / invalid_any are not produced for merged encoder views (request weights and invalid)", who);
+    return BTS_E_UNSUPPORTED;
+  }
+  return BTS_OK;
+}
+
+int bts_render_fwd_multi_view(const BtsMultiViewField* mv, const BtsRenderArgs* a, void* stream) {
+  if (int rc = check_multi_view(mv, "bts_render_fwd_multi_view")) return rc;
+  if (int rc = check_multi_view_args(a, "bts_render_fwd_multi_view", false)) return rc;
+  return multi_view_render_fwd_impl(mv, a, (hipStream_t)stream);
+}
+
+size_t bts_render_bwd_multi_view_workspace(const BtsMultiViewField* mv, const BtsRenderArgs* a) {
+  if (!mv || !a || mv->V < 1 || mv->V > BTS_MV_MAX_VIEWS || mv->cfg[0].n <= 0 || a->rays_per_sample <= 0 || a->K <= 0 || mv->cfg[0].d_hidden <= 0)
+    return 0;
+  return multi_view_bwd_workspace_impl(mv, a);
+}
+
+int bts_render_bwd_multi_view(const BtsMultiViewField* mv, const BtsRenderArgs* a, const BtsRenderGrads* g, float* const* d_proj_views,
+                              unsigned char* const* d_proj_tiles_views, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_multi_view(mv, "bts_render_bwd_multi_view")) return rc;
+  if (int rc = check_multi_view_args(a, "bts_render_bwd_multi_view", true)) return rc;
+  if (!g) {
+    set_error("%s: NULL gradient struct", "bts_render_bwd_multi_view");
+    return BTS_E_INVALID;
+  }
+  const size_t need = multi_view_bwd_workspace_impl(mv, a);
+  if (workspace_bytes < need || !workspace) {
+    set_error("%s: workspace too small (%ld bytes needed)", "bts_render_bwd_multi_view", (long)need);
+    return BTS_E_WORKSPACE;
+  }
+  return multi_view_render_bwd_impl(mv, a, g, d_proj_views, d_proj_tiles_views, workspace, (hipStream_t)stream);
+}
+
+int bts_field_query_multi_view(const BtsMultiViewField* mv, const float* xyz, int32_t P, float* rgb, float* invalid, float* sigma,
+                               void* stream) {
+  if (int rc = check_multi_view(mv, "bts_field_query_multi_view")) return rc;
+  if (!xyz || !sigma || P <= 0) {
+    set_error("%s: NULL/empty query argument (P=%ld)", "bts_field_query_multi_view", (long)P);
+    return BTS_E_INVALID;
+  }
+  return multi_view_field_query_impl(mv, xyz, P, rgb, invalid, sigma, (hipStream_t)stream);
+}
+
 // ---- LiDAR occupancy evaluation (evaluator_lidar.py): limits and host-side checks shared by the three entry points
 static int check_lidar_limits(int T, int y_res, const char* who) {
   if (T <= 0 || y_res <= 0) {

@@ -120,6 +120,13 @@ size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs*
 int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
                               hipStream_t s);
 
+// ---- bts_multi_view.hip: merged encoder views (the field is checked by bts_api.hip before any of these runs)
+int multi_view_render_fwd_impl(const BtsMultiViewField* mv, const BtsRenderArgs* a, hipStream_t s);
+int multi_view_field_query_impl(const BtsMultiViewField* mv, const float* xyz, int P, float* rgb, float* invalid, float* sigma, hipStream_t s);
+size_t multi_view_bwd_workspace_impl(const BtsMultiViewField* mv, const BtsRenderArgs* a);
+int multi_view_render_bwd_impl(const BtsMultiViewField* mv, const BtsRenderArgs* a, const BtsRenderGrads* g, float* const* d_proj_views,
+                               unsigned char* const* d_proj_tiles_views, void* workspace, hipStream_t s);
+
 // ---- bts_occ.hip: LiDAR occupancy evaluation.  *_layout: the ONE statement of a workspace's layout, run over a Carver (below) once to
 // count the bytes and once to hand out the pointers
 class Carver;

@@ -12,12 +12,11 @@
 //                      and the blocks' weight gradients are contracted per work-group through LDS, once per 256 samples.
 // Passes B (scatter_kernel<HD, true>: dG += w_tap u0) and C (dwpe_rows_kernel: dW_pe, db_in) of bts_bwd_rows.hip run unchanged on
 // what pass A leaves.  Replaces nerf.py:210-313 + models_bts.py:266-338 (sample_color=False) + resnetfc.py:132-184 of the reference.
-#include "bts_bwd.h"
+#include "bts_mc_field.h"
 #include "bts_host.h"
 
 namespace bts {
 
-constexpr int kMcThreads = 256;   // samples of one work-group iteration (whole rays: K <= 256)
 constexpr int kMcOut = 4;         // lin_out rows: density + three colour channels
 
 struct McParams {
@@ -34,122 +33,30 @@ struct McParams {
   float* d_mlp;            // packed, four-output layout, or null
 };
 
-// everything between a world point and the four MLP outputs; h0 = lin_in's output, nn = fc_0's output, h1 = the last hidden layer (before
-// lin_out's relu), in hidden order
-template <int C, int HD, int NB>
-struct McAct {
-  float h0[HD];
-  float nn[NB > 0 ? HD : 1];
-  float h1[NB > 0 ? HD : 1];
-  __device__ __forceinline__ float& last(int j) {
-    if constexpr (NB > 0) return h1[j];
-    else return h0[j];
-  }
-};
-
 template <int C, int HD, int NB>
 __device__ __forceinline__ void mc_field(const FwdParams& p, const Cam& enc, int sample, float px, float py, float pz, const float* empty_proj,
                                          McAct<C, HD, NB>& a, float (&o)[kMcOut], bool& invalid) {
-  constexpr int D_IN = C + kPeDim;
-  const MlpLayout ml{D_IN, HD, NB};
   const cfp w = as_const(p.mlp);
   const Proj pe = p.code_mode == 1 ? project<true>(enc, px, py, pz) : project<false>(enc, px, py, pz);
   invalid = pe.invalid;
   float v3[3];
   v3[0] = pe.x, v3[1] = pe.y;
   v3[2] = depth_code(pe, p.code_mode == 1, p.inv_z != 0, p.inv_dmax, p.inv_range, p.d_min, p.range);
-  // bilinear(G) (models_bts.py:173-182 after lin_in's feature columns; ATen's nw, ne, sw, se order), or the projected empty feature
+  // bilinear(G), or the projected empty feature
   if (p.learn_empty && pe.invalid) {
 #pragma unroll
     for (int j = 0; j < HD; ++j) a.h0[j] = empty_proj[j];
   } else {
     const Taps tp = make_taps(pe.x, pe.y, p.H, p.W, p.fs);
     const long plane = (long)(p.H >> p.fs) * (p.W >> p.fs);
-    const float4* G = reinterpret_cast<const float4*>(p.proj + (long)sample * plane * HD);
-#pragma unroll
-    for (int s4 = 0; s4 < HD / 4; ++s4) {
-      const float4 t00 = G[(long)tp.o00 * (HD / 4) + s4], t01 = G[(long)tp.o01 * (HD / 4) + s4];
-      const float4 t10 = G[(long)tp.o10 * (HD / 4) + s4], t11 = G[(long)tp.o11 * (HD / 4) + s4];
-      const float g00[4] = {t00.x, t00.y, t00.z, t00.w}, g01[4] = {t01.x, t01.y, t01.z, t01.w};
-      const float g10[4] = {t10.x, t10.y, t10.z, t10.w}, g11[4] = {t11.x, t11.y, t11.z, t11.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = g00[e] * tp.w00;
-        v = v + g01[e] * tp.w01;
-        v = v + g10[e] * tp.w10;
-        v = v + g11[e] * tp.w11;
-        a.h0[proj_hidden_of_storage(4 * s4 + e)] = v;
-      }
-    }
+    mc_bilinear<HD, true>(a.h0, p.proj + (long)sample * plane * HD, tp, 1.0f);
   }
-  // positional encoding (code.py:30-42): [x, y, code, per octave sin(3), "cos"(3)]
   float enc_in[kPeDim];
-  enc_in[0] = v3[0], enc_in[1] = v3[1], enc_in[2] = v3[2];
-  float ff = p.freq_factor;
-#pragma unroll
-  for (int oct = 0; oct < kNumFreqs; ++oct) {
-    float t[6];
-    pe_octave(t, v3, ff);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) enc_in[3 + 6 * oct + i] = t[i];
-    ff = ff * 2.0f;
-  }
-  // lin_in's encoding columns and bias (resnetfc.py:147)
-#pragma unroll
-  for (int j = 0; j < HD; ++j) {
-    float acc = w[ml.b_in() + j];
-#pragma unroll
-    for (int k = 0; k < kPeDim; ++k) acc = __builtin_fmaf(w[ml.w_in() + j * D_IN + C + k], enc_in[k], acc);
-    a.h0[j] = a.h0[j] + acc;
-  }
-  // ResnetBlockFC (resnetfc.py:53-62): h1 = h0 + fc_1(relu(fc_0(relu(h0))))
-  if constexpr (NB > 0) {
-    static_assert(NB == 1, "the envelope has at most one block");
-#pragma unroll
-    for (int j = 0; j < HD; ++j) {
-      float acc = w[ml.blk_b0(0) + j];
-#pragma unroll
-      for (int i = 0; i < HD; ++i) acc = __builtin_fmaf(w[ml.blk_w0(0) + j * HD + i], fmaxf(a.h0[i], 0.0f), acc);
-      a.nn[j] = acc;
-    }
-#pragma unroll
-    for (int j = 0; j < HD; ++j) {
-      float acc = w[ml.blk_b1(0) + j];
-#pragma unroll
-      for (int i = 0; i < HD; ++i) acc = __builtin_fmaf(w[ml.blk_w1(0) + j * HD + i], fmaxf(a.nn[i], 0.0f), acc);
-      a.h1[j] = a.h0[j] + acc;
-    }
-  }
-  // lin_out, four rows (resnetfc.py:183): w_out (4, HD) row-major, b_out (4)
-#pragma unroll
-  for (int r = 0; r < kMcOut; ++r) {
-    float acc = w[ml.w_out() + kMcOut * HD + r];
-#pragma unroll
-    for (int j = 0; j < HD; ++j) acc = __builtin_fmaf(w[ml.w_out() + r * HD + j], fmaxf(a.last(j), 0.0f), acc);
-    o[r] = acc;
-  }
+  mc_encode(enc_in, v3, p.freq_factor);
+  mc_mlp<C, HD, NB, kMcOut>(w, enc_in, a, o);
 }
 
 __device__ __forceinline__ float mc_sigmoid(float s) { return sigmoidf(s); }
-
-// w_in[:, :C] . empty_feature (the projected empty feature, hidden order) into LDS
-template <int C, int HD>
-__device__ __forceinline__ void mc_stage_empty(float* empty_proj, const FwdParams& p) {
-  const MlpLayout ml{C + kPeDim, HD, 0};
-  for (int j = threadIdx.x; j < HD; j += blockDim.x) {
-    float a = 0.0f;
-    if (p.learn_empty && p.empty_feature)
-      for (int c = 0; c < C; ++c) a = __builtin_fmaf(p.mlp[ml.w_in() + j * (C + kPeDim) + c], p.empty_feature[c], a);
-    empty_proj[j] = a;
-  }
-}
-
-// the sample depth of (ray, k): the caller's z_samp, or NeRFRenderer.sample_coarse from the jitter (nerf.py:103-123, as bts_sample_coarse)
-__device__ __forceinline__ float mc_depth(const FwdParams& p, long ray, int k) {
-  if (p.z_samp) return p.z_samp[ray * p.K + k];
-  const float near = p.rays[ray * 8 + 6], far = p.rays[ray * 8 + 7];
-  return coarse_depth(p.jitter[ray * p.K + k], coarse_base(p.K, k), 1.0f / (float)p.K, near, far, p.lindisp != 0);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // forward
@@ -260,42 +167,6 @@ __global__ __launch_bounds__(kMcThreads) void mc_query_kernel(const FwdParams p)
 // ---------------------------------------------------------------------------------------------------------------
 // backward, pass A
 // ---------------------------------------------------------------------------------------------------------------
-// per-work-group contraction of one outer-product sum over the iteration's samples: D[r][c] += sum_s A[s][r] B[s][c], c = COLS is the
-// constant-1 column (the bias).  Lane t owns entries t, t + 256, ...: they stay in registers for the work-group's whole life.
-template <int ROWS, int COLS>
-struct McTile {
-  static constexpr int N = ROWS * (COLS + 1);
-  static constexpr int PER = (N + kMcThreads - 1) / kMcThreads;
-  float acc[PER];
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) acc[q] = 0.0f;
-  }
-  __device__ __forceinline__ void add(const float* A, int astr, const float* Bm, int bstr, int S) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = threadIdx.x + q * kMcThreads;
-      if (e < N) {
-        const int r = e / (COLS + 1), c = e - r * (COLS + 1);
-        float a = acc[q];
-        for (int s = 0; s < S; ++s) a = __builtin_fmaf(A[s * astr + r], c < COLS ? Bm[s * bstr + c] : 1.0f, a);
-        acc[q] = a;
-      }
-    }
-  }
-  // weights at w_off ([ROWS][COLS] row-major), bias at b_off ([ROWS])
-  __device__ __forceinline__ void flush(float* d_mlp, int w_off, int b_off) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int e = threadIdx.x + q * kMcThreads;
-      if (e < N && acc[q] != 0.0f) {
-        const int r = e / (COLS + 1), c = e - r * (COLS + 1);
-        flush_add_f32(d_mlp + (c < COLS ? w_off + r * COLS + c : b_off + r), acc[q]);
-      }
-    }
-  }
-};
-
 template <int C, int HD, int NB>
 __global__ __launch_bounds__(kMcThreads) void mc_rows_kernel(const McParams mp) {
   const FwdParams& p = mp.f;

@@ -56,6 +56,10 @@ class BTSNet(nn.Module):
         # sample_color=False on the HIP kernels (bts_*_mlp_color) instead of the PyTorch composition of torch_modes.py; opt-in, the
         # composition stays the default
         self.native_mlp_color = bool(conf.get("native_mlp_color", False))
+        # merged encoder views (combine_ids / several ids_encoder) on the HIP kernels (bts_*_multi_view) instead of the composition; opt-in
+        # as well (measured on one MI355X, README "Merged encoder views": 9.7 x the composition forward + backward at 8 x 2 048 rays, 17.6 x
+        # forward on a 192 x 640 frame; the encoder then sees its batch view-major)
+        self.native_multi_view = bool(conf.get("native_multi_view", False))
         if self.return_sample_depth:
             raise NotImplementedError("return_sample_depth is not used by any shipped config")
 
@@ -68,6 +72,7 @@ class BTSNet(nn.Module):
         # coarse MLP serves both.  Here it is one more packed parameter vector (and its own projected map G) through the same kernels.
         self.mlp_fine = make_mlp(conf["mlp_fine"], d_in, d_out=self._d_out, allow_empty=True)
         self._combined = False        # set by encode(): several encoder views merged per point (combine_ids, the waymo mode)
+        self._latents_mv = None       # set by encode() with native_multi_view: per scale, per encoder view (n, C, h, w)
         if self.learn_empty:
             self.empty_feature = nn.Parameter(torch.randn((self.encoder.latent_size,), requires_grad=True))
         self._scale = 0
@@ -96,8 +101,14 @@ class BTSNet(nn.Module):
         """True when the field is served by the PyTorch compositions of torch_modes.py instead of the fused HIP kernels: the two modes
         no shipped config uses -- MLP-predicted colours (`sample_color: false`) and merged encoder views
         (`encode(..., combine_ids=...)` or more than one encoder view).  `native_mlp_color: true` puts the first of them on the kernels
-        (bts_*_mlp_color)."""
-        return (not self.sample_color and not self.native_mlp_color) or self._combined
+        (bts_*_mlp_color), `native_multi_view: true` the second (bts_*_multi_view).  Both at once -- `sample_color: false` on several encoder
+        views -- stays on the composition whatever the keys say."""
+        return (not self.sample_color and not self.native_mlp_color) or (self._combined and not self.multi_view)
+
+    @property
+    def multi_view(self):
+        """True when the last ``encode`` left several encoder views to the HIP kernels (`native_multi_view: true`, sampled colours)."""
+        return self._combined and self.native_multi_view and self.sample_color
 
     def mlp(self, coarse=True):
         """models_bts.py:293-307: the MLP of the coarse pass, or of the fine pass when a separate one was configured."""
@@ -120,6 +131,10 @@ class BTSNet(nn.Module):
         not need them (see native_scale_maps); built on first access for callers that do."""
         if not getattr(self, "_has_latents", False):
             return None
+        if self._grid_f_features is None and self._latents_mv is not None:
+            h_, w_ = self._grid_size
+            self._grid_f_features = [torch.stack([v if v.shape[-2:] == (h_, w_) else F.interpolate(v, (h_, w_)) for v in views], dim=1)
+                                     for views in self._latents_mv]
         if self._grid_f_features is None:
             h_, w_ = self._grid_size
             self._grid_f_features = [il if il.shape[-2:] == (h_, w_) else
@@ -175,27 +190,35 @@ class BTSNet(nn.Module):
         do_flip = bool(self.flip_augmentation and self.training and (torch.rand(1) > .5).item())
         if do_flip:
             images_encoder = torch.flip(images_encoder, dims=(-1,))
-        enc_in = images_encoder.reshape(n * nv_enc, c, h, w)
+        # several encoder views (native_multi_view): the encoder's batch is VIEW-major, so that view v's maps are the contiguous slice
+        # [v n, (v + 1) n) -- an ordinary single-view field each (the batch is the same set of images: BatchNorm sees no difference)
+        enc_in = (images_encoder.transpose(0, 1) if self.multi_view else images_encoder).reshape(n * nv_enc, c, h, w)
         image_latents_ms = self.encoder(enc_in)
         if do_flip:
             image_latents_ms = [torch.flip(il, dims=(-1,)) for il in image_latents_ms]
         _, _, h_, w_ = image_latents_ms[0].shape
         self._shift_ms = [self._scale_shift(il.shape[-2:], (h_, w_)) for il in image_latents_ms]
-        self._latents_ms = [(il if sh is not None else F.interpolate(il, (h_, w_))).unsqueeze(1)
-                            for il, sh in zip(image_latents_ms, self._shift_ms)]
+        image_latents_ms = [il if sh is not None else F.interpolate(il, (h_, w_)) for il, sh in zip(image_latents_ms, self._shift_ms)]
+        if self.multi_view:
+            self._latents_mv = [[il[v * n:(v + 1) * n] for v in range(nv_enc)] for il in image_latents_ms]
+            self._latents_ms = [views[0].unsqueeze(1) for views in self._latents_mv]
+        else:
+            self._latents_mv = None
+            self._latents_ms = [il.unsqueeze(1) for il in image_latents_ms]
         self._shift_ms = [sh or 0 for sh in self._shift_ms]
         self._grid_size = (h_, w_)
         self._has_latents = True
         self._grid_f_features = None
         self.grid_f_Ks = Ks_encoder
         self.grid_f_poses_w2c = poses_w2c_encoder
-        self.grid_f_combine = None
+        enc_groups, ren_groups = self._view_groups(images.shape[1], ids_encoder, ids_render, combine_ids)
+        self.grid_f_combine = enc_groups
         # colours: (x*.5+.5) fused into the rgb0 packing kernel unless the caller supplies processed frames
         src = _take(colours if colours is not None else images, ids_render)
         self._grid_c_src, self._grid_c_raw = src, colours is None     # grid_c_imgs (models_bts.py:82) is materialised on first access
         self.grid_c_Ks = _take(Ks, ids_render)
         self.grid_c_poses_w2c = _take(poses_w2c, ids_render)
-        self.grid_c_combine = None
+        self.grid_c_combine = ren_groups
 
         # ---- hand-over into the renderer's HBM layouts
         self._native = {}
@@ -213,25 +236,35 @@ class BTSNet(nn.Module):
             self._imgs_nhwc4 = self._K_r = self._w2c_r = None
         self._K_enc = Ks_encoder[:, 0].detach().float().contiguous()
         self._w2c_enc = poses_w2c_encoder[:, 0].detach().float().contiguous()
+        if self.multi_view:
+            self._K_enc_mv = [Ks_encoder[:, v].detach().float().contiguous() for v in range(nv_enc)]
+            self._w2c_enc_mv = [poses_w2c_encoder[:, v].detach().float().contiguous() for v in range(nv_enc)]
         # a render view that IS the encoder frame (eval_depth: ids_render = [0]) shares its camera bit for bit: the kernels skip its
         # second projection (BtsFieldCfg.enc_render_view)
         ids_r, id_e = [int(i) for i in ids_render], int(ids_encoder[0])
-        self._enc_view = ids_r.index(id_e) if id_e in ids_r else -1
+        self._enc_view = ids_r.index(id_e) if (id_e in ids_r and not self.multi_view) else -1
+
+    @staticmethod
+    def _view_groups(n_frames, ids_encoder, ids_render, combine_ids):
+        """models_bts.py:93-113: ``combine_ids`` restricted to the encoder / render views (as positions in ids_encoder / ids_render), then
+        every ungrouped frame on its own, empty groups dropped -> (encoder groups, render groups); (None, None) without combine_ids."""
+        if combine_ids is None:
+            return None, None
+        groups = [list(g) for g in combine_ids]
+        grouped = set(sum(groups, []))
+        groups += [[i] for i in range(n_frames) if i not in grouped]
+        pos_e = {int(f): i for i, f in enumerate(ids_encoder)}
+        pos_r = {int(f): i for i, f in enumerate(ids_render)}
+        enc_groups = [g for g in ([pos_e[i] for i in grp if i in pos_e] for grp in groups) if g]
+        ren_groups = [g for g in ([pos_r[i] for i in grp if i in pos_r] for grp in groups) if g]
+        return enc_groups, ren_groups
 
     def _encode_torch_mode(self, images, Ks, poses_w2c, images_encoder, Ks_encoder, poses_w2c_encoder, ids_encoder, ids_render, colours, combine_ids):
         """encode() for the PyTorch-composed modes (models_bts.py:93-136): every encoder view's maps at scale 0's size, the view groups."""
         from . import torch_modes
         torch_modes.warn_once("combine_ids / several encoder views" if self._combined else "sample_color=False")
         n, nv_enc, c, h, w = images_encoder.shape
-        enc_groups = ren_groups = None
-        if combine_ids is not None:
-            groups = [list(g) for g in combine_ids]
-            grouped = set(sum(groups, []))
-            groups += [[i] for i in range(images.shape[1]) if i not in grouped]
-            pos_e = {int(f): i for i, f in enumerate(ids_encoder)}
-            pos_r = {int(f): i for i, f in enumerate(ids_render)}
-            enc_groups = [g for g in ([pos_e[i] for i in grp if i in pos_e] for grp in groups) if g]
-            ren_groups = [g for g in ([pos_r[i] for i in grp if i in pos_r] for grp in groups) if g]
+        enc_groups, ren_groups = self._view_groups(images.shape[1], ids_encoder, ids_render, combine_ids)
         do_flip = bool(self.flip_augmentation and self.training and (torch.rand(1) > .5).item())
         enc_in = torch.flip(images_encoder, dims=(-1,)) if do_flip else images_encoder
         latents = self.encoder(enc_in.reshape(n * nv_enc, c, h, w))
@@ -240,7 +273,7 @@ class BTSNet(nn.Module):
         h_, w_ = latents[0].shape[-2:]
         self._grid_f_features = [F.interpolate(il, (h_, w_)).view(n, nv_enc, -1, h_, w_) for il in latents]
         self._has_latents, self._grid_size = True, (h_, w_)
-        self._latents_ms, self._shift_ms = None, None
+        self._latents_ms, self._shift_ms, self._latents_mv = None, None, None
         self.grid_f_Ks, self.grid_f_poses_w2c, self.grid_f_combine = Ks_encoder, poses_w2c_encoder, enc_groups
         src = _take(colours if colours is not None else images, ids_render)
         self._grid_c_src, self._grid_c_raw = src, colours is None
@@ -253,7 +286,7 @@ class BTSNet(nn.Module):
         not silently run on the PREVIOUS encode's maps -- it raises until ``encode`` is called again."""
         self._has_latents = False
         self._native = {}
-        self._latents_ms = self._shift_ms = self._grid_f_features = None
+        self._latents_ms = self._shift_ms = self._grid_f_features = self._latents_mv = None
         self._grid_c_src = None
 
     def native_field(self, coarse=True, sampled=None) -> "native.FieldTensors":
@@ -272,6 +305,8 @@ class BTSNet(nn.Module):
         s = self._scale
         fine = not coarse and self.mlp_fine is not None
         mlp, spec = (self.mlp_fine, self.spec_fine) if fine else (self.mlp_coarse, self.spec)
+        if self.multi_view:
+            return self._native_multi_view(s, fine, mlp, spec)
         if sampled is not None:
             rays, z_samp, jitter, lindisp = sampled
             f = self._latents_ms[s]
@@ -303,6 +338,22 @@ class BTSNet(nn.Module):
             self._native[(s, fine)] = (ft, version)
         return self._native[(s, fine)][0]
 
+    def _native_multi_view(self, s, fine, mlp, spec) -> "native.MultiViewField":
+        """native_field() for several encoder views: one ordinary single-view field per view (its own ProjectFunction forms G_v and takes
+        its gradient), cached like the single-view one.  Always the full maps (no sparse projection)."""
+        version = (mlp.lin_in.weight._version, torch.is_grad_enabled())
+        hit = self._native.get((s, fine))
+        if hit is None or hit[1] != version:
+            views = []
+            for v, f in enumerate(self._latents_mv[s]):
+                f = f.float()
+                spec_v = dataclasses.replace(spec, tile_blocks=native.is_channels_last(f))
+                proj = native.ProjectFunction.apply(f, mlp.packed(), spec_v, None)
+                views.append(native.FieldTensors(spec_v, proj, self._K_enc_mv[v], self._w2c_enc_mv[v], self._imgs_nhwc4, self._K_r, self._w2c_r,
+                                                 self.empty_feature if self.learn_empty else None, feat_shift=self._shift_ms[s]))
+            self._native[(s, fine)] = (native.MultiViewField(views, self.grid_f_combine, self.grid_c_combine), version)
+        return self._native[(s, fine)][0]
+
     def forward(self, xyz, coarse=True, viewdirs=None, far=False, only_density=False):
         """xyz (n, P, 3) world points -> rgb (n,P,nv*3), invalid (n,P,nv) float, sigma (n,P,1)  (models_bts.py:266-338).
         Forward-only (the reference's callers of this entry point -- occupancy profiles, LiDAR / 3D-bbox evaluators -- run it
@@ -311,11 +362,14 @@ class BTSNet(nn.Module):
             from . import torch_modes
             with profiler.record_function("model_inference"):
                 return torch_modes.field_forward(self, xyz, coarse=coarse, only_density=only_density)
+        if self.multi_view and only_density:
+            raise NotImplementedError("only_density with several encoder views: the reference itself fails here (models_bts.py:281-284 flattens "
+                                      "the view axis into the feature axis)")
         ft = self.native_field(coarse)
         with torch.no_grad(), profiler.record_function("model_inference"):   # models_bts.py:275
             rgb, invalid, sigma = native.field_query(ft, self.mlp(coarse).packed().detach(), xyz.detach().float().contiguous(),
                                                      only_density=only_density)
-        nv = 1 if self.spec.mlp_color else self._grid_c_src.shape[1]
+        nv = 1 if self.spec.mlp_color else ft.nv
         if only_density:
             rgb = torch.zeros((xyz.shape[0], xyz.shape[1], nv * 3), device=sigma.device)
             invalid = invalid.unsqueeze(1)   # the reference returns (n, nv_enc=1, P, 1) here (models_bts.py:337)
@@ -326,6 +380,8 @@ class BTSNet(nn.Module):
         vertical level slowest (get_pts' order) -> (n, columns) fraction of levels whose running density sum stays <= threshold, points
         flagged invalid by any view counting as density 1 (only_density: by the encoder view only).  The reference chunks the 4.19 M
         points of its grid into 50 000-point field queries and post-processes in torch; here no per-point tensor reaches HBM."""
+        if self.multi_view:
+            raise native.BtsNativeError("occupancy_profile: not available for a field with more than one encoder view; use forward()")
         ft = self.native_field()
         with torch.no_grad(), profiler.record_function("model_inference"):
             return native.occupancy_profile(ft, self.mlp_coarse.packed().detach(), q_pts.detach().float().contiguous(), int(levels),

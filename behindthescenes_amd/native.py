@@ -698,6 +698,70 @@ class FieldTensors:
                                empty_feature=_addr(self.empty_feature), mlp_params=mlp_params.data_ptr())
 
 
+def group_tables(groups, n_views: int, singles_twice: bool):
+    """View groups as BtsMultiViewField takes them: ``groups`` = lists of view positions (torch_modes._merge_groups' argument), or None
+    for no merge (every view its own group, counted once: the plain mean) -> (start, member, mult).  ``singles_twice``: a one-member
+    group of a merged field is counted twice (the reference's feature merge, models_bts.py:196-209)."""
+    merged = groups is not None
+    groups = [[int(v) for v in g] for g in groups] if merged else [[v] for v in range(n_views)]
+    start, member, mult = [0], [], []
+    for g in groups:
+        member += g
+        start.append(len(member))
+        mult.append(2 if (merged and singles_twice and len(g) == 1) else 1)
+    return start, member, mult
+
+
+class MultiViewField:
+    """Several encoder views merged per point (BtsMultiViewField): ``views`` = one ordinary ``FieldTensors`` per encoder view, all of
+    one spec and size (view 0 carries the render views' frames and cameras); ``enc_groups`` / ``ren_groups`` = lists of view positions
+    as ``torch_modes._merge_groups`` takes them, or None (no merge).  ``nv`` is nv', the number of render groups."""
+
+    mlp_color = False
+    partial = None
+    proj_link = None
+
+    def __init__(self, views, enc_groups=None, ren_groups=None):
+        views = list(views)
+        if not 1 <= len(views) <= _lib.BTS_MV_MAX_VIEWS:
+            raise BtsNativeError(f"{len(views)} encoder views; 1 .. {_lib.BTS_MV_MAX_VIEWS} are supported")
+        v0 = views[0]
+        for i, v in enumerate(views):
+            if v.proj_nhwc is None:
+                raise BtsNativeError(f"encoder view {i}: merged encoder views need the projected feature map")
+            if v.spec.mlp_color:
+                raise BtsNativeError("merged encoder views with MLP-predicted colour are served by the PyTorch composition only")
+        if v0.nv < 1:
+            raise BtsNativeError("merged encoder views need at least one render view")
+        self.views, self.spec, self.n, self.H, self.W, self.feat_shift = views, v0.spec, v0.n, v0.H, v0.W, v0.feat_shift
+        self.enc_tables = group_tables(enc_groups, len(views), True)
+        self.ren_tables = group_tables(ren_groups, v0.nv, False)
+        self.nv = len(self.ren_tables[2])
+        self.empty_feature = v0.empty_feature
+
+    @property
+    def proj_maps(self):
+        return [v.proj_nhwc for v in self.views]
+
+    @property
+    def proj_nhwc(self):
+        return self.views[0].proj_nhwc
+
+    def struct(self, mlp_params: torch.Tensor) -> "_lib.BtsMultiViewField":
+        mv = _lib.BtsMultiViewField()
+        mv.V = len(self.views)
+        for i, v in enumerate(self.views):
+            mv.cfg[i], mv.view[i] = v.cfg(), v.tensors(mlp_params)
+        (es, em, ek), (rs, rm, _) = self.enc_tables, self.ren_tables
+        mv.n_enc_groups, mv.n_ren_groups = len(ek), len(rs) - 1
+        for name, vals in (("enc_group_start", es), ("enc_member", em), ("enc_mult", ek), ("ren_group_start", rs), ("ren_member", rm)):
+            if len(vals) > len(getattr(mv, name)):
+                raise BtsNativeError(f"{name}: {len(vals)} entries exceed the table ({len(getattr(mv, name))})")
+            for i, x in enumerate(vals):
+                getattr(mv, name)[i] = x
+        return mv
+
+
 def check_supported(spec: FieldSpec, nv: int = 1):
     cfg = _spec_cfg(spec, nv=nv)
     if not _lib.load().bts_supported(C.byref(cfg)):
@@ -751,16 +815,23 @@ def render_fwd(ft: FieldTensors, mlp_params: torch.Tensor, rays: torch.Tensor, z
 
     if ft.mlp_color and want_invalid_sums:
         raise BtsNativeError("render_fwd: MLP-predicted colour produces no invalid_wsum / invalid_any (request weights and invalid instead)")
+    multi = isinstance(ft, MultiViewField)
+    if multi and want_invalid_sums:
+        raise BtsNativeError("render_fwd: merged encoder views produce no invalid_wsum / invalid_any (request weights and invalid instead)")
     outs = dict(rgb=new(B, nv * 3), depth=new(B), weights=new(B, K) if want_weights else None,
                 alphas=new(B, K) if want_alphas else None, invalid=new(B, K, nv) if want_invalid else None,
                 rgb_samps=new(B, K, nv * 3) if want_rgb_samps else None, sigma_raw=new(B, K) if want_saved else None,
                 trans=new(B, K) if want_saved else None, invalid_wsum=new(B, nv) if want_invalid_sums else None,
                 invalid_any=new(B, nv) if want_invalid_sums else None,
                 z_samp=new(B, K) if (z_samp is None and want_z) else None)
-    cfg, tens = ft.cfg(), ft.tensors(mlp_params)
     args = _render_args(ft, rays, z_samp, hard_alpha_cap, white_bkgd, outs, sigma_noise, jitter, lindisp)
-    fn = "bts_render_fwd_mlp_color" if ft.mlp_color else "bts_render_fwd"
-    _lib.check(getattr(_lib.load(), fn)(C.byref(cfg), C.byref(tens), C.byref(args), _stream(rays)), fn)
+    if multi:
+        mv = ft.struct(mlp_params)
+        _lib.check(_lib.load().bts_render_fwd_multi_view(C.byref(mv), C.byref(args), _stream(rays)), "bts_render_fwd_multi_view")
+    else:
+        cfg, tens = ft.cfg(), ft.tensors(mlp_params)
+        fn = "bts_render_fwd_mlp_color" if ft.mlp_color else "bts_render_fwd"
+        _lib.check(getattr(_lib.load(), fn)(C.byref(cfg), C.byref(tens), C.byref(args), _stream(rays)), fn)
     if z_samp is not None:
         outs["z_samp"] = z_samp
     return outs
@@ -817,6 +888,35 @@ def render_bwd(ft: FieldTensors, mlp_params, rays, z_samp, sigma_raw, trans, *, 
     return d_proj, d_mlp, d_empty
 
 
+def render_bwd_multi_view(ft: MultiViewField, mlp_params, rays, z_samp, sigma_raw, trans, *, hard_alpha_cap, g_rgb=None, g_depth=None,
+                          g_weights=None, g_alphas=None, need_proj=None, need_mlp=True, need_empty=False, white_bkgd=False, rgb_samps=None,
+                          sigma_noise=None):
+    """Returns ([d_proj_nhwc | None per encoder view], d_mlp_params | None, d_empty_proj | None) (bts_render_bwd_multi_view); ``need_proj``:
+    one flag per view (None: every view)."""
+    B, K = z_samp.shape
+    for name, g in (("g_rgb", g_rgb), ("g_depth", g_depth), ("g_weights", g_weights), ("g_alphas", g_alphas)):
+        if g is not None:
+            _req(g, name)
+    _req(sigma_raw, "sigma_raw", (B, K)), _req(trans, "trans", (B, K))
+    dev, V = rays.device, len(ft.views)
+    need_proj = [True] * V if need_proj is None else list(need_proj)
+    d_projs = [torch.zeros(v.proj_nhwc.shape, device=dev, dtype=torch.float32) if need else None for v, need in zip(ft.views, need_proj)]
+    d_mlp = torch.zeros(ft.spec.mlp_param_count(), device=dev, dtype=torch.float32) if need_mlp else None
+    d_empty = torch.zeros(ft.spec.d_hidden, device=dev, dtype=torch.float32) if need_empty else None
+    if rgb_samps is not None:
+        _req(rgb_samps, "rgb_samps", (B, K, ft.nv * 3))
+    args = _render_args(ft, rays, z_samp, hard_alpha_cap, white_bkgd, dict(sigma_raw=sigma_raw, trans=trans, rgb_samps=rgb_samps), sigma_noise)
+    grads = BtsRenderGrads(g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), g_weights=_addr(g_weights), g_alphas=_addr(g_alphas),
+                           d_mlp_params=_addr(d_mlp), d_empty_proj=_addr(d_empty))
+    maps = (C.c_void_p * V)(*[_addr(d) for d in d_projs])
+    mv, lib = ft.struct(mlp_params), _lib.load()
+    ws_bytes = lib.bts_render_bwd_multi_view_workspace(C.byref(mv), C.byref(args))
+    ws = _workspace(dev, int(ws_bytes))
+    _lib.check(lib.bts_render_bwd_multi_view(C.byref(mv), C.byref(args), C.byref(grads), maps, None, _ptr(ws), ws_bytes, _stream(rays)),
+               "bts_render_bwd_multi_view")
+    return d_projs, d_mlp, d_empty
+
+
 _WS = {}
 WORKSPACE_CACHE_LIMIT = 256 << 20   # bytes: larger scratch is allocated per call and goes back to torch's caching allocator
 
@@ -847,6 +947,16 @@ def field_query(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Tensor, o
     _req(xyz, "xyz", (ft.n, P, 3))
     _check_partial(ft, None, None, "field_query")
     dev = xyz.device
+    if isinstance(ft, MultiViewField):
+        if only_density:
+            raise NotImplementedError("only_density with several encoder views: the reference itself fails here (models_bts.py:281-284)")
+        rgb = torch.empty((n, P, ft.nv * 3), device=dev, dtype=torch.float32)
+        invalid = torch.empty((n, P, ft.nv), device=dev, dtype=torch.float32)
+        sigma = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
+        mv = ft.struct(mlp_params)
+        _lib.check(_lib.load().bts_field_query_multi_view(C.byref(mv), _ptr(xyz), P, _ptr(rgb), _ptr(invalid), _ptr(sigma), _stream(xyz)),
+                   "bts_field_query_multi_view")
+        return rgb, invalid, sigma
     if ft.mlp_color:
         # sample_color=False (models_bts.py:315-338): rgb (n, P, 3) from the MLP, zeros with only_density (:336); invalid (n, P, 1)
         rgb = torch.empty((n, P, 3), device=dev, dtype=torch.float32)
@@ -874,6 +984,8 @@ def occupancy_profile(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Ten
     [, sigma (n, levels * columns)]  (bts_occupancy_profile: render_profile of scripts/inference_setup.py in one pass)."""
     n, P, _ = xyz.shape
     _req(xyz, "xyz", (ft.n, P, 3))
+    if isinstance(ft, MultiViewField):
+        raise BtsNativeError("occupancy_profile: not available for a field with more than one encoder view; use field_query")
     if ft.mlp_color:
         raise BtsNativeError("occupancy_profile: not available for MLP-predicted colour (sample_color=False); use field_query")
     if levels <= 0 or P % levels:
@@ -1318,3 +1430,53 @@ class RenderFunction(torch.autograd.Function):
             if need_mlp:
                 d_mlp[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C] += torch.outer(d_eproj, ft.empty_feature.detach())
         return (d_proj, d_mlp, d_empty) + (None,) * 15
+
+
+class MultiViewRenderFunction(torch.autograd.Function):
+    """composite() over merged encoder views (MultiViewField) as one differentiable op.  Differentiable inputs: mlp_params, empty_feature
+    and every view's projected map (the trailing arguments); differentiable outputs: rgb, depth, weights, alphas."""
+
+    @staticmethod
+    def forward(ctx, mlp_params, empty_feature, ft: MultiViewField, rays, z_samp, hard_alpha_cap, white_bkgd, want_weights, want_alphas,
+                want_rgb_samps, grad_mode, want_invalid, sigma_noise, jitter, lindisp, want_z, *projs):
+        ctx.set_materialize_grads(False)
+        needs_grad = any(ctx.needs_input_grad[:2] + ctx.needs_input_grad[16:]) and grad_mode
+        # rgb_samps is kept for the backward as well (it then skips the colour taps)
+        out = render_fwd(ft, mlp_params, rays, z_samp, hard_alpha_cap=hard_alpha_cap, white_bkgd=white_bkgd, want_weights=want_weights,
+                         want_alphas=want_alphas, want_invalid=want_invalid, want_rgb_samps=want_rgb_samps or needs_grad, want_saved=needs_grad,
+                         sigma_noise=sigma_noise, jitter=jitter, lindisp=lindisp, want_z=want_z or needs_grad)
+        ctx.ft, ctx.hard_alpha_cap, ctx.white_bkgd = ft, hard_alpha_cap, white_bkgd
+        ctx.sigma_noise = sigma_noise if needs_grad else None
+        if needs_grad:
+            ctx.save_for_backward(mlp_params, rays, out["z_samp"], out["sigma_raw"], out["trans"], out["rgb_samps"])
+        empty = rays.new_empty(0)
+        z_out = out["z_samp"] if (z_samp is None and out["z_samp"] is not None) else empty
+        res = (out["rgb"], out["depth"], out["weights"] if want_weights else empty, out["alphas"] if want_alphas else empty,
+               out["invalid"] if want_invalid else empty, out["rgb_samps"] if want_rgb_samps else empty, z_out)
+        ctx.mark_non_differentiable(*res[4:])
+        ctx.has = (want_weights, want_alphas)
+        return res
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_weights, g_alphas, _g_inv, _g_rs, _g_z):
+        mlp_params, rays, z_samp, sigma_raw, trans, rgb_samps = ctx.saved_tensors
+
+        def prep(g, present=True):
+            return g.contiguous() if (g is not None and present and g.numel() > 0) else None
+
+        ft = ctx.ft
+        need_mlp, need_empty = ctx.needs_input_grad[:2]
+        d_projs, d_mlp, d_eproj = render_bwd_multi_view(
+            ft, mlp_params, rays, z_samp, sigma_raw, trans, hard_alpha_cap=ctx.hard_alpha_cap, g_rgb=prep(g_rgb), g_depth=prep(g_depth),
+            g_weights=prep(g_weights, ctx.has[0]), g_alphas=prep(g_alphas, ctx.has[1]), need_proj=ctx.needs_input_grad[16:], need_mlp=need_mlp,
+            need_empty=need_empty or (need_mlp and ft.spec.learn_empty), white_bkgd=ctx.white_bkgd, rgb_samps=rgb_samps, sigma_noise=ctx.sigma_noise)
+        d_empty = None
+        if d_eproj is not None:
+            # the projected empty feature is w_in[:, :C] @ empty_feature: chain rule on parameter-sized tensors (as RenderFunction)
+            spec = ft.spec
+            w_f = mlp_params[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C]
+            if need_empty:
+                d_empty = w_f.t() @ d_eproj
+            if need_mlp:
+                d_mlp[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C] += torch.outer(d_eproj, ft.empty_feature.detach())
+        return (d_mlp, d_empty) + (None,) * 14 + tuple(d_projs)

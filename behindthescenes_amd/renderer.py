@@ -223,6 +223,18 @@ class NeRFRenderer(torch.nn.Module):
             # nerf.py:279-280: sigmas + randn_like(sigmas) * noise_std in training mode (no shipped config turns it on); drawn here with
             # torch's generator, added inside the kernels (BtsRenderArgs.sigma_noise).  `sigma_noise` lets a caller inject the draw.
             sigma_noise = torch.randn(shape, device=rays.device, dtype=torch.float32) * self.noise_std
+        if isinstance(ft, native.MultiViewField):
+            # several encoder views on the kernels (native_multi_view): one projected map per view, no per-ray invalid sums
+            if want_invalid_sums:
+                raise native.BtsNativeError("lean_training_outputs is not available for merged encoder views; switch it off")
+            rgb, depth, weights, alphas, invalid, rgb_samps, z_out = native.MultiViewRenderFunction.apply(
+                mlp_params, empty, ft, rays, z_samp, bool(self.hard_alpha_cap), bool(self.white_bkgd), bool(want_weights), bool(want_alphas),
+                bool(want_rgb_samps), torch.is_grad_enabled(), bool(want_invalid), None if sigma_noise is None else sigma_noise.float().contiguous(),
+                jitter, bool(self.lindisp), bool(want_z), *ft.proj_maps)
+            if z_samp is None:
+                z_samp = z_out if z_out.numel() else None
+            return (weights if want_weights else None, rgb, depth, alphas if want_alphas else None, invalid if want_invalid else None, z_samp,
+                    rgb_samps if want_rgb_samps else None)
         rgb, depth, weights, alphas, invalid, rgb_samps, inv_wsum, inv_any, z_out = native.RenderFunction.apply(
             ft.proj_nhwc, mlp_params, empty, ft, rays, z_samp, bool(self.hard_alpha_cap), bool(self.white_bkgd),
             bool(want_weights), bool(want_alphas), bool(want_rgb_samps), torch.is_grad_enabled(), bool(want_invalid), bool(want_invalid_sums),
@@ -269,7 +281,8 @@ class NeRFRenderer(torch.nn.Module):
                 z_coarse = self.sample_coarse_from_dist(rays, prop_weights.reshape(-1, ns), prop_z.reshape(-1, ns))
                 z_coarse, _ = torch.sort(z_coarse, dim=-1)
         if (self.lean_training_outputs and self.training and not self.using_fine and torch.is_grad_enabled() and not getattr(model, "torch_mode", False)
-                and not getattr(getattr(model, "spec", None), "mlp_color", False)):   # (MLP-predicted colour: no per-ray invalid sums)
+                and not getattr(getattr(model, "spec", None), "mlp_color", False)   # (MLP-predicted colour: no per-ray invalid sums)
+                and not getattr(model, "multi_view", False)):                       # (nor merged encoder views)
             # in a training step nothing downstream of the renderer reads the per-sample tensors except the loss'
             # invalid-ray mask, and that only through sum_k weights * invalid / any_k invalid per view -- the render kernel's
             # epilogue emits exactly those (8 B per ray and view), and weights / alphas / invalid are neither written nor returned

@@ -4,7 +4,8 @@ HIP"): several ENCODER views whose samples are merged per point (``combine_ids``
 
 These run as ordinary PyTorch-ROCm ops on whatever device the tensors live on -- they are NOT the fused HIP path and make no claim
 on its speed; ``BTSNet`` switches to them only for those two modes (and says so once), every shipped configuration stays on the
-kernels of libbts_render.so.  Pinned to the real reference by tests/golden/modes.npz (tests/golden/gen_golden_modes.py)."""
+kernels of libbts_render.so.  Pinned to the real reference by tests/golden/modes.npz (tests/golden/gen_golden_modes.py).  They are the
+DEFAULT for the two modes, not the only path: ``native_mlp_color: true`` / ``native_multi_view: true`` put either on HIP kernels."""
 import warnings
 
 import torch

@@ -858,6 +858,69 @@ int bts_field_query_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, 
 
 
 /* ---------------------------------------------------------------------------------------------------------------------------------
+ * Merged encoder views: BTSNet.encode(..., combine_ids=...) or more than one ids_encoder (models_bts.py:93-136, 190-210, 237-258; the
+ * reference trainer's `frame_sample_mode: waymo-N`).  Additive to ABI 9: every struct and entry point above is unchanged.
+ *
+ * For a point and the encoder views v = 0 .. V-1, view v gives the projection with its frustum flag o_v, the bilinear features F_v
+ * (learn_empty: empty_feature where o_v is set), the positional code PE_v of ITS (x, y, depth code) and the entry e_v = [F_v, PE_v].
+ * What the reference computes, quirks included:
+ *   - every encoder GROUP yields one entry: its first member with o = 0, else its first member (torch.min's tie rule on the CPU); the
+ *     entry's flag is the picked member's;
+ *   - a one-member group of a field WITH combine_ids enters the mean and its divisor TWICE (models_bts.py:196-209 lacks the `continue`
+ *     its colour twin has): enc_mult[g] = 2;
+ *   - no combine_ids and V > 1: the plain mean over the views, flag = any -- V one-member groups with enc_mult = 1;
+ *   - MLP input = sum_g enc_mult[g] entry_g / T, T = sum_g enc_mult[g]; invalid_features = any of the entries' flags; empty_empty zeroes
+ *     sigma on that merged flag;
+ *   - colours: the same pick per RENDER group over the cfg's nv render views, one-member groups once; nv' = n_ren_groups;
+ *     invalid (.., nv') = the picked render view's flag | invalid_features;
+ *   - only_density with V > 1 fails in the reference: there is no such entry here.
+ * lin_in is linear, so the kernels read view v's PROJECTED map G_v = F_v . w_in[:, :C]^T (bts_project_features*).
+ *
+ * BtsMultiViewField: view v is the ordinary single-view field (cfg[v], view[v]); of view[v] proj_nhwc, K_enc and w2c_enc are read, the
+ * render views (imgs_nhwc4, K_r, w2c_r: cfg[0].nv of them), empty_feature and mlp_params come from view[0].  enc_render_view is ignored.
+ * Checked before any launch, with a message (bts_last_error):
+ *   BTS_E_INVALID      V < 1, V or a group count above BTS_MV_MAX_VIEWS, a group table that does not start at 0 or runs past
+ *                      BTS_MV_MAX_VIEWS members, an empty group, a member index out of range, a view in two groups, a multiplicity other
+ *                      than 1 or 2, a required NULL pointer
+ *   BTS_E_UNSUPPORTED  views whose n / C / d_hidden / n_blocks / H / W / feat_shift / tile_blocks differ or lie outside bts_supported
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_MV_MAX_VIEWS 8
+typedef struct BtsMultiViewField {
+  int32_t V;                 /* encoder views */
+  int32_t n_enc_groups;      /* encoder groups, 1 .. BTS_MV_MAX_VIEWS */
+  int32_t n_ren_groups;      /* render groups = nv', 1 .. BTS_MV_MAX_VIEWS */
+  int32_t reserved_;
+  BtsFieldCfg cfg[BTS_MV_MAX_VIEWS];
+  BtsFieldTensors view[BTS_MV_MAX_VIEWS];
+  int32_t enc_group_start[BTS_MV_MAX_VIEWS + 1];   /* members of encoder group g: enc_member[enc_group_start[g] .. enc_group_start[g + 1]) */
+  int32_t enc_member[BTS_MV_MAX_VIEWS];            /* encoder view indices 0 .. V-1, in the group's order */
+  int32_t enc_mult[BTS_MV_MAX_VIEWS];              /* per encoder group: 1, or 2 for the one-member group counted twice */
+  int32_t ren_group_start[BTS_MV_MAX_VIEWS + 1];
+  int32_t ren_member[BTS_MV_MAX_VIEWS];            /* render view indices 0 .. cfg[0].nv - 1 */
+} BtsMultiViewField;
+
+/* NeRFRenderer.composite (nerf.py:210-313) over this field: sigma = softplus(o0); sigma_noise, hard_alpha_cap, white_bkgd, in-kernel
+ * sample_coarse (jitter, z_samp_out, lindisp) and feat_shift as in bts_render_fwd.  Outputs: rgb (n*Bp, nv' * 3), depth, weights, alphas,
+ * invalid (n*Bp, K, nv'), rgb_samps (n*Bp, K, nv' * 3), sigma_raw, trans, z_samp_out.  invalid_wsum / invalid_any are NOT produced
+ * (BTS_E_UNSUPPORTED when given).  K <= 256 (BTS_E_UNSUPPORTED above). */
+int bts_render_fwd_multi_view(const BtsMultiViewField* mv, const BtsRenderArgs* a, void* stream);
+
+/* Backward of bts_render_fwd_multi_view, the sigma path (sampled colours carry no parameter gradient).  Inputs: g_rgb (n*Bp, nv' * 3),
+ * g_depth, g_weights, g_alphas (any may be NULL); `a` carries z_samp and the forward's sigma_raw and trans; a->rgb_samps, when given, is
+ * READ.  Outputs, ACCUMULATED: d_proj_views[v] (view v's projected-map gradient, NULL entries and a NULL array are skipped) with
+ * d_proj_tiles_views[v] (its tile flags in ABI 9's geometry, or NULL), g->d_mlp_params, g->d_empty_proj; g->d_proj_nhwc and
+ * g->d_proj_tiles are not read.  workspace: bts_render_bwd_multi_view_workspace(mv, a) bytes (0 for a NULL argument); contents need no
+ * initialisation. */
+size_t bts_render_bwd_multi_view_workspace(const BtsMultiViewField* mv, const BtsRenderArgs* a);
+int bts_render_bwd_multi_view(const BtsMultiViewField* mv, const BtsRenderArgs* a, const BtsRenderGrads* g, float* const* d_proj_views,
+                              unsigned char* const* d_proj_tiles_views, void* workspace, size_t workspace_bytes, void* stream);
+
+/* BTSNet.forward on raw points: xyz (n, P, 3) -> rgb (n, P, nv' * 3) or NULL, invalid (n, P, nv') or NULL, sigma (n, P). */
+int bts_field_query_multi_view(const BtsMultiViewField* mv, const float* xyz, int32_t P, float* rgb, float* invalid, float* sigma,
+                               void* stream);
+
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
  * LiDAR occupancy evaluation: the ground-truth half of models/bts/evaluator_lidar.py (BTSWrapper.forward :266-340), next to the density
  * query (bts_field_query) it is compared with.  Additive to ABI 9: every struct and entry point above is unchanged.
  *

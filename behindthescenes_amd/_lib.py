@@ -177,6 +177,18 @@ class BtsNovelViews(C.Structure):
                [(k, C.c_int32) for k in ("Hc", "Wc", "img_row0", "img_col0", "depth_row0", "depth_col0")]
 
 
+BTS_TRAIN_VIS_MAX_FRAMES = 6
+
+
+class BtsTrainVis(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("T", "v", "h", "w", "K", "nv", "S", "lut_N")] + [("z_near", C.c_float), ("z_far", C.c_float)] + \
+               [("imgs", C.c_void_p * BTS_TRAIN_VIS_MAX_FRAMES), ("rgb", C.c_void_p), ("depth", C.c_void_p * BTS_MAX_SCALES)] + \
+               [(k, C.c_void_p) for k in ("alphas", "invalid", "lut", "z_near_far", "input_im", "recon_im", "recon_depth", "depth_profile", "ray_entropy",
+                                          "alpha_sum", "recon_mse", "invalids", "f_depth", "f_profile", "f_entropy", "f_alpha_sum", "f_mse",
+                                          "f_invalid", "workspace")] + \
+               [("workspace_bytes", C.c_size_t)]
+
+
 BTS_LIDAR_MAX_CLOUDS = 32
 BTS_BBOX_MAX_BOXES = 4096
 BTS_BBOX_MAX_VERTS = 64
@@ -288,6 +300,9 @@ SYMBOLS = {
     "bts_colorize": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "bts_pack_u8": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _I, _I, _I, C.c_float, C.c_float, _P, _I, _I, _I, _I, _P]),
     "bts_novel_views": (C.c_int, [C.POINTER(BtsFieldCfg), C.POINTER(BtsFieldTensors), C.POINTER(BtsNovelViews), _P]),
+    # the trainer's visualisation panels (models/bts/trainer.py:430-506)
+    "bts_train_vis_workspace": (C.c_size_t, [_I, _I, _I, _I]),
+    "bts_train_vis": (C.c_int, [C.POINTER(BtsTrainVis), _P]),
 }
 
 _lock = threading.Lock()

@@ -1131,4 +1131,68 @@ int bts_novel_views(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsN
   return launched(novel_view_finish_launch(a, s), who);
 }
 
+// ---- training visualisation panels (models/bts/trainer.py:430-506)
+static bool train_vis_counts_ok(long T, long K) { return T >= 1 && T <= BTS_TRAIN_VIS_MAX_FRAMES && K >= 2 && K <= 256; }
+
+size_t bts_train_vis_workspace(int32_t T, int32_t h, int32_t w, int32_t K) {
+  if (!train_vis_counts_ok(T, K) || !train_vis_sizes_ok(h, w)) return 0;
+  return train_vis_bytes(T, w);
+}
+
+int bts_train_vis(const BtsTrainVis* a, void* stream) {
+  const char* who = "bts_train_vis";
+  if (!a) {
+    set_error("%s: NULL argument struct", who);
+    return BTS_E_INVALID;
+  }
+  if (a->T < 1 || a->T > BTS_TRAIN_VIS_MAX_FRAMES || a->T > a->v) {
+    set_error("%s: T=%ld frames are outside [1, min(v = %ld, 6)]", who, (long)a->T, (long)a->v);
+    return BTS_E_INVALID;
+  }
+  if (a->K < 2 || a->K > 256) {
+    set_error("%s: K=%ld samples are outside [2, 256]", who, (long)a->K);
+    return BTS_E_INVALID;
+  }
+  if (a->nv < 1 || a->nv > BTS_MAX_VIEWS) {
+    set_error("%s: nv=%ld render views are outside [1, BTS_MAX_VIEWS = %ld]", who, (long)a->nv, (long)BTS_MAX_VIEWS);
+    return BTS_E_INVALID;
+  }
+  if (a->S < 1 || a->S > BTS_MAX_SCALES) {
+    set_error("%s: S=%ld depth scales are outside [1, BTS_MAX_SCALES = %ld]", who, (long)a->S, (long)BTS_MAX_SCALES);
+    return BTS_E_INVALID;
+  }
+  if (!train_vis_sizes_ok(a->h, a->w)) {
+    set_error("%s: the frame size h=%ld, w=%ld is outside [1, 8192]", who, (long)a->h, (long)a->w);
+    return BTS_E_INVALID;
+  }
+  if (!a->lut || a->lut_N < 1 || a->lut_N > BTS_CMAP_MAX_N) {
+    set_error("%s: an empty colour table: lut is NULL or lut_N=%ld is outside [1, 65536]", who, (long)a->lut_N);
+    return BTS_E_INVALID;
+  }
+  for (int i = 0; i < a->T; ++i)
+    if (!a->imgs[i]) {
+      set_error("%s: NULL pointer: imgs[%ld]", who, (long)i);
+      return BTS_E_INVALID;
+    }
+  for (int i = 0; i < a->S; ++i)
+    if (!a->depth[i]) {
+      set_error("%s: NULL pointer: depth[%ld]", who, (long)i);
+      return BTS_E_INVALID;
+    }
+  if (!a->rgb || !a->alphas || !a->invalid) {
+    set_error("%s: NULL pointer among the inputs rgb, alphas, invalid", who);
+    return BTS_E_INVALID;
+  }
+  if (!a->input_im || !a->recon_im || !a->recon_depth || !a->depth_profile || !a->ray_entropy || !a->alpha_sum || !a->recon_mse || !a->invalids) {
+    set_error("%s: NULL pointer among the eight output panels", who);
+    return BTS_E_INVALID;
+  }
+  const size_t need = train_vis_bytes(a->T, a->w);
+  if (!a->workspace || a->workspace_bytes < need || ((uintptr_t)a->workspace & 15) != 0) {
+    set_error("%s: workspace too small or not 16-byte aligned (%ld bytes needed)", who, (long)need);
+    return BTS_E_WORKSPACE;
+  }
+  return launched(train_vis_launch(a, (hipStream_t)stream), who);
+}
+
 }  // extern "C"

@@ -180,6 +180,11 @@ int pack_u8_launch(const float* x, long sb, long sy, long sx, long sc, int B, in
                    int Hc, int Wc, int row0, int col0, hipStream_t s);
 int novel_view_finish_launch(const BtsNovelViews* a, hipStream_t s);
 
+// ---- bts_train_vis.hip: the trainer's visualisation panels
+bool train_vis_sizes_ok(int h, int w);
+size_t train_vis_bytes(int T, int w);
+int train_vis_launch(const BtsTrainVis* a, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------------------------
 // small helpers of the host layer
 // ---------------------------------------------------------------------------------------------------------------

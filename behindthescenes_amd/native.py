@@ -1134,6 +1134,63 @@ def novel_views(ft: Optional["FieldTensors"], mlp_params, a: "_lib.BtsNovelViews
     _lib.check(_lib.load().bts_novel_views(C.byref(cfg), C.byref(tens), C.byref(a), stream), "bts_novel_views")
 
 
+def train_vis(imgs, rgb, depths, alphas, invalid, z_near, z_far, N: int, lut_f64, fields: bool = False):
+    """The trainer's visualisation panels (bts_train_vis, csrc/bts_train_vis.hip) for batch element 0: ``imgs`` a list of >= T tensors
+    ``(3, h, w)``, ``rgb (v, h, w, nv, 3)``, ``depths`` a list of S ``(v, h, w)``, ``alphas (v, h, w, K)``, ``invalid (v, h, w, K, nv)``,
+    all contiguous float32 on one GPU and read where they lie; ``lut_f64 (N + 3, 3)``; ``z_near`` / ``z_far`` two numbers, or two
+    tensors on that GPU (the trainer's: read by the kernel, no ``.item()``).  T = min(v, 6).  -> dict of the eight panels
+    (``recon_depth`` as ``(S, T, 3, h, w)``), plus the six ``f_*`` fields with ``fields``.  Nothing synchronises, the inputs are not
+    written."""
+    _req(alphas, "alphas")
+    if alphas.dim() != 4:
+        raise BtsNativeError(f"alphas: (v, h, w, K) expected, got {tuple(alphas.shape)}")
+    v, h, w, K = (int(s) for s in alphas.shape)
+    T = min(v, _lib.BTS_TRAIN_VIS_MAX_FRAMES)
+    _req(invalid, "invalid")
+    if invalid.dim() != 5 or tuple(invalid.shape[:4]) != (v, h, w, K):
+        raise BtsNativeError(f"invalid: ({v}, {h}, {w}, {K}, nv) expected, got {tuple(invalid.shape)}")
+    nv = int(invalid.shape[4])
+    _req(rgb, "rgb", (v, h, w, nv, 3))
+    if len(imgs) < T:
+        raise BtsNativeError(f"imgs: {T} frames expected, got {len(imgs)}")
+    if not 1 <= len(depths) <= _lib.BTS_MAX_SCALES:
+        raise BtsNativeError(f"depths: 1 .. {_lib.BTS_MAX_SCALES} scales expected, got {len(depths)}")
+    S, dev = len(depths), alphas.device
+    _req_as(lut_f64, "lut_f64", torch.float64, (N + 3, 3))
+    a = _lib.BtsTrainVis(T=T, v=v, h=h, w=w, K=K, nv=nv, S=S, lut_N=int(N), rgb=_addr(rgb), alphas=_addr(alphas), invalid=_addr(invalid),
+                         lut=_addr(lut_f64))
+    z_pair = None
+    if isinstance(z_near, torch.Tensor) or isinstance(z_far, torch.Tensor):
+        z_pair = torch.stack([torch.as_tensor(z, device=dev).detach().reshape(()).float() for z in (z_near, z_far)])
+        a.z_near_far = z_pair.data_ptr()
+    else:
+        a.z_near, a.z_far = float(z_near), float(z_far)
+    for i in range(T):
+        a.imgs[i] = _addr(_req(imgs[i], f"imgs[{i}]", (3, h, w)))
+    for i, d in enumerate(depths):
+        a.depth[i] = _addr(_req(d, f"depth[{i}]", (v, h, w)))
+    for t in list(imgs[:T]) + list(depths) + [rgb, invalid, lut_f64]:
+        if t.device != dev:
+            raise BtsNativeError(f"every input must live on {dev} (got {t.device})")
+    need = int(_lib.load().bts_train_vis_workspace(T, h, w, K))
+    if need == 0:
+        raise BtsNativeError(f"train_vis: T={T}, h={h}, w={w}, K={K} is outside the envelope (K in [2, 256], h and w at most 8192)")
+    f32 = dict(device=dev, dtype=torch.float32)
+    out = dict(input_im=torch.empty((T, 3, h, w), **f32), recon_im=torch.empty((T, 3, h, w), **f32),
+               recon_depth=torch.empty((S, T, 3, h, w), **f32), depth_profile=torch.empty((3 * T, 3, K, w), **f32),
+               ray_entropy=torch.empty((T, 3, h, w), **f32), alpha_sum=torch.empty((T, 3, h, w), **f32),
+               recon_mse=torch.empty((T, 3, h, w), **f32), invalids=torch.empty((T, 3, h, w), **f32))
+    if fields:
+        out.update(f_depth=torch.empty((S, T, h, w), **f32), f_profile=torch.empty((3 * T, K, w), **f32), f_entropy=torch.empty((T, h, w), **f32),
+                   f_alpha_sum=torch.empty((T, h, w), **f32), f_mse=torch.empty((T, h, w), **f32), f_invalid=torch.empty((T, h, w), **f32))
+    for k, t in out.items():
+        setattr(a, k, t.data_ptr())
+    ws = _workspace(dev, need + 16)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _lib.check(_lib.load().bts_train_vis(C.byref(a), _stream(alphas)), "bts_train_vis")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------------------
 # the Monodepth2 decoder's tail (SURVEY 8 row f4): reflect-pad 3x3 convolution [+ nearest x2 in front] [+ ELU], channels-last
 # --------------------------------------------------------------------------------------------------------------

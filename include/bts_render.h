@@ -1232,6 +1232,61 @@ typedef struct {
 } BtsNovelViews;
 int bts_novel_views(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsNovelViews* a, void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Training visualisation panels: the trainer's `visualize` (models/bts/trainer.py:430-506) up to, not including, make_grid -- for the
+ * first T = min(v, 6) rendered frames of batch element 0 the eight float32, channel-planar panels it logs.  Additive to ABI 9: every
+ * struct and entry point above is unchanged.  Two launches, nothing synchronises, nothing is allocated, no atomics: a rerun is
+ * bit-identical.  Inputs are float32, contiguous, read where they lie; only frames [0, T) of them are touched.
+ *   input_im      (T, 3, h, w)     img * .5 + .5 (multiply, then add)
+ *   recon_im      (T, 3, h, w)     mean over the nv render views of rgb
+ *   recon_depth   (S, T, 3, h, w)  cmap(((1 / d - 1 / z_far) / (1 / z_near - 1 / z_far)).clamp(0, 1)) per scale
+ *   depth_profile (3 T, 3, K, w)   cmap(alphas[rows].clamp_min(0) / max), transposed to K x w; row 3 f + j = frame f, image row rows[j]
+ *   ray_entropy   (T, 3, h, w)     cmap(-sum_k p ln p / log2(K)), p = (alphas + 1e-5) / sum_k (alphas + 1e-5)
+ *   alpha_sum     (T, 3, h, w)     cmap(sum_k (alphas + 1e-5) / K)
+ *   recon_mse     (T, 3, h, w)     cmap((((input_im - recon_im)^2) / 2).mean over the channels.clamp(0, 1))
+ *   invalids      (T, 3, h, w)     cmap(invalid.mean over K, then over nv)
+ * cmap: the caller's float64 table (lut_N + 3, 3) as for bts_colorize, the index rule stated there; a panel value is the row's double
+ * rounded once to fp32.  The f_* pointers, when not NULL, receive the scalar fields the colour map is applied to.
+ * Quirks of the reference that are reproduced ON PURPOSE:
+ *   - the entropy is a NATURAL logarithm above and log2(K) below;
+ *   - 1e-5 is added to alphas before the entropy and before the alpha sum, but not before the profile (which is taken first);
+ *   - the profile is divided by ONE maximum over all 3 T rows, taken unclamped (all rows zero: 0 / 0 = NaN, the bad colour; a NaN in
+ *     them makes the maximum NaN, as torch's max());
+ *   - the profile rows are h / 4, h / 2 and 3 h / 4 (integer divisions; they may coincide on tiny frames);
+ *   - the depth is clamped AFTER the normalisation, every step in fp32 with IEEE division (z_near, z_far are float32 tensors there):
+ *     a depth of 0 is +inf -> 1 -> the last colour, a NaN stays a NaN and takes the bad colour;
+ *   - a value of exactly 1 folds to the last colour (matplotlib's xa == N), a NaN takes the bad colour;
+ *   - the squared error is halved before its channel mean;
+ *   - recon_im is a MEAN over the render views;
+ *   - alpha_sum's .clamp(-1) is a lower bound of -1, a no-op, and is not there.
+ * The one divergence: the reference's in-place `alphas += 1e-5` edits the caller's render dict; here alphas and invalid are const and
+ * the inputs are bit-identical after the call.  Every use of the sum includes the 1e-5, so no output differs.
+ * BTS_E_INVALID with a message naming the argument: NULL pointers, T outside [1, 6] or above v, K outside [2, 256], nv outside
+ * [1, BTS_MAX_VIEWS], S outside [1, BTS_MAX_SCALES], h or w outside [1, 8192], lut_N outside [1, BTS_CMAP_MAX_N]; BTS_E_WORKSPACE.
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_TRAIN_VIS_MAX_FRAMES 6
+typedef struct {
+  int32_t T, v, h, w;              /* frames shown, frames rendered (T = min(v, 6)), frame size */
+  int32_t K, nv, S, lut_N;         /* samples per ray, render views, depth scales, colours of the table */
+  float z_near, z_far;
+  const float* imgs[BTS_TRAIN_VIS_MAX_FRAMES];   /* the first T: (3, h, w) each in [-1, 1], batch element 0 of the loader's list */
+  const float* rgb;                /* (v, h, w, nv, 3) */
+  const float* depth[BTS_MAX_SCALES];            /* the first S: (v, h, w) */
+  const float* alphas;             /* (v, h, w, K) */
+  const float* invalid;            /* (v, h, w, K, nv) */
+  const double* lut;               /* (lut_N + 3, 3) */
+  const float* z_near_far;         /* (2) on the device: read instead of z_near / z_far (the trainer holds them as tensors); or NULL */
+  float *input_im, *recon_im, *recon_depth, *depth_profile, *ray_entropy, *alpha_sum, *recon_mse, *invalids;   /* out, see above */
+  /* out or NULL: the fields before the colour map -- (S, T, h, w), (3 T, K, w), and (T, h, w) for the last four */
+  float *f_depth, *f_profile, *f_entropy, *f_alpha_sum, *f_mse, *f_invalid;
+  void* workspace;                 /* bts_train_vis_workspace bytes, 16-byte aligned; contents need no initialisation */
+  size_t workspace_bytes;
+} BtsTrainVis;
+/* 0 outside the limits above */
+size_t bts_train_vis_workspace(int32_t T, int32_t h, int32_t w, int32_t K);
+int bts_train_vis(const BtsTrainVis* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

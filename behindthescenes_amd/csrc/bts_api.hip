@@ -578,16 +578,39 @@ static int check_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, con
   return BTS_OK;
 }
 
-static int check_mlp_color_args(const BtsRenderArgs* a, const char* who, bool bwd) {
+// The render arguments of the two lane = sample families (bts_mc_field.h).  kernels, family: how the texts name the caller's ("this head's" /
+// "MLP-predicted colour", "the merged-view" / "merged encoder views")
+static int check_lane_sample_args(const BtsRenderArgs* a, const char* who, bool bwd, const char* kernels, const char* family) {
   if (int rc = check_render_args(a, who, bwd, true, bwd ? "%s: NULL argument (rays, z_samp and the forward's sigma_raw + trans are required)" : kFwdArgsNull))
     return rc;
+  // set_error takes one string and up to three longs, so the family's words go into the format itself (they are literals of this file,
+  // without a '%', and the longest format stays well inside the buffer); the compiler does not check these two formats
+  char fmt[192];
   if (a->K > 256) {
-    set_error("%s: K=%ld samples per ray; this head's kernels take whole rays of at most 256 samples per work-group", who, (long)a->K);
+    snprintf(fmt, sizeof(fmt), "%%s: K=%%ld samples per ray; %s kernels take whole rays of at most 256 samples per work-group", kernels);
+    set_error(fmt, who, (long)a->K);
     return BTS_E_UNSUPPORTED;
   }
   if (!bwd && (a->invalid_wsum || a->invalid_any)) {
-    set_error("%s: invalid_wsum / invalid_any are not produced for MLP-predicted colour (request weights and invalid)", who);
+    snprintf(fmt, sizeof(fmt), "%%s: invalid_wsum / invalid_any are not produced for %s (request weights and invalid)", family);
+    set_error(fmt, who);
     return BTS_E_UNSUPPORTED;
+  }
+  return BTS_OK;
+}
+static int check_mlp_color_args(const BtsRenderArgs* a, const char* who, bool bwd) {
+  return check_lane_sample_args(a, who, bwd, "this head's", "MLP-predicted colour");
+}
+
+// what a backward entry of the two families checks behind its field and arguments: the gradient struct and the workspace (need bytes)
+static int check_bwd_call(const BtsRenderGrads* g, const void* workspace, size_t workspace_bytes, size_t need, const char* who) {
+  if (!g) {
+    set_error("%s: NULL gradient struct", who);
+    return BTS_E_INVALID;
+  }
+  if (workspace_bytes < need || !workspace) {
+    set_error("%s: workspace too small (%ld bytes needed)", who, (long)need);
+    return BTS_E_WORKSPACE;
   }
   return BTS_OK;
 }
@@ -615,15 +638,7 @@ int bts_render_bwd_mlp_color(const BtsFieldCfg* cfg, const BtsFieldTensors* t, c
                              void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_mlp_color(cfg, t, "bts_render_bwd_mlp_color")) return rc;
   if (int rc = check_mlp_color_args(a, "bts_render_bwd_mlp_color", true)) return rc;
-  if (!g) {
-    set_error("%s: NULL gradient struct", "bts_render_bwd_mlp_color");
-    return BTS_E_INVALID;
-  }
-  const size_t need = mlp_color_bwd_workspace_impl(cfg, a);
-  if (workspace_bytes < need || !workspace) {
-    set_error("%s: workspace too small (%ld bytes needed)", "bts_render_bwd_mlp_color", (long)need);
-    return BTS_E_WORKSPACE;
-  }
+  if (int rc = check_bwd_call(g, workspace, workspace_bytes, mlp_color_bwd_workspace_impl(cfg, a), "bts_render_bwd_mlp_color")) return rc;
   return mlp_color_render_bwd_impl(cfg, t, a, g, workspace, (hipStream_t)stream);
 }
 
@@ -711,17 +726,7 @@ static int check_multi_view(const BtsMultiViewField* mv, const char* who) {
 }
 
 static int check_multi_view_args(const BtsRenderArgs* a, const char* who, bool bwd) {
-  if (int rc = check_render_args(a, who, bwd, true, bwd ? "%s: NULL argument (rays, z_samp and the forward's sigma_raw + trans are required)" : kFwdArgsNull))
-    return rc;
-  if (a->K > 256) {
-    set_error("%s: K=%ld samples per ray; the merged-view kernels take whole rays of at most 256 samples per work-group", who, (long)a->K);
-    return BTS_E_UNSUPPORTED;
-  }
-  if (!bwd && (a->invalid_wsum || a->invalid_any)) {
-    set_error("%s: invalid_wsum / invalid_any are not produced for merged encoder views (request weights and invalid)", who);
-    return BTS_E_UNSUPPORTED;
-  }
-  return BTS_OK;
+  return check_lane_sample_args(a, who, bwd, "the merged-view", "merged encoder views");
 }
 
 int bts_render_fwd_multi_view(const BtsMultiViewField* mv, const BtsRenderArgs* a, void* stream) {
@@ -740,15 +745,7 @@ int bts_render_bwd_multi_view(const BtsMultiViewField* mv, const BtsRenderArgs* 
                               unsigned char* const* d_proj_tiles_views, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_multi_view(mv, "bts_render_bwd_multi_view")) return rc;
   if (int rc = check_multi_view_args(a, "bts_render_bwd_multi_view", true)) return rc;
-  if (!g) {
-    set_error("%s: NULL gradient struct", "bts_render_bwd_multi_view");
-    return BTS_E_INVALID;
-  }
-  const size_t need = multi_view_bwd_workspace_impl(mv, a);
-  if (workspace_bytes < need || !workspace) {
-    set_error("%s: workspace too small (%ld bytes needed)", "bts_render_bwd_multi_view", (long)need);
-    return BTS_E_WORKSPACE;
-  }
+  if (int rc = check_bwd_call(g, workspace, workspace_bytes, multi_view_bwd_workspace_impl(mv, a), "bts_render_bwd_multi_view")) return rc;
   return multi_view_render_bwd_impl(mv, a, g, d_proj_views, d_proj_tiles_views, workspace, (hipStream_t)stream);
 }
 

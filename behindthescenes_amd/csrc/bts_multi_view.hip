@@ -5,7 +5,9 @@
 // picked views.  lin_in is linear, so  lin_in(mean) = sum_g c_g (G_v[taps] | empty_proj) + W_pe . (sum_g c_g PE_v) + b  with v = the
 // group's pick, c_g = multiplicity / T and G_v the projected map of view v (the projected-feature shortcut).
 //
-// Kernels, lane = SAMPLE (or point), fp32 throughout, the structure of bts_mlp_color.hip (bts_mc_field.h holds what the two share):
+// Kernels, lane = SAMPLE (or point), fp32 throughout.  The MLP and its backward, a sample's alpha, the sums along a ray, the kernels'
+// parameters and passes B and C's launches are bts_mc_field.h's, shared with bts_mlp_color.hip; this file holds the merged views' own: the
+// picks (mv_field), the render groups' colours (mv_color), the per-view rows (mv_scale_kernel) and the workspace.
 //   mv_render_kernel   one work-group = R = 256 / K whole rays: projection into the views, the picks, lin_in, blocks, lin_out, softplus,
 //                      the render groups' colour taps; one lane per ray composites front to back from LDS.
 //   mv_query_kernel    one lane = one query point (bts_field_query_multi_view).
@@ -15,7 +17,6 @@
 // Passes B (scatter_kernel<HD, true>) and C (dwpe_rows_kernel) of bts_bwd_rows.hip then run unchanged once per view, with that view's
 // camera, map and rows: both are linear in the rows and sum_v c_v = 1, so db_in, dW_pe, dG_v and d_empty_proj come out right.
 #include "bts_mc_field.h"
-#include "bts_host.h"
 
 namespace bts {
 
@@ -32,20 +33,11 @@ struct MvTables {
   int ren_start[kMvMax + 1], ren_member[kMvMax];   // render groups over the cfg's nv render views
 };
 
-struct MvParams {
-  FwdParams f;        // view 0's field: sizes, switches, MLP, empty feature, the render views' frames and cameras (proj, K_enc, w2c_enc: `t`)
+// f = view 0's field: sizes, switches, MLP, empty feature, the render views' frames and cameras (proj, K_enc, w2c_enc: `t`); g_rgb is
+// (B, nv' * 3), gs_ws = |dL/d(lin_out's output)|.  One flat kernel argument: the tables are read through kernarg_view
+struct MvParams : McParams {
   MvTables t;
-  int R;              // rays per work-group iteration (kMcThreads / K)
-  long n_groups;      // ceil(n * Bp / R)
-  // backward
-  const float* g_rgb;      // (B, nv' * 3)
-  const float* g_depth;    // (B)
-  const float* g_weights;  // (B, K)
-  const float* g_alphas;   // (B, K)
-  float* u0_ws;            // (B, K, HD) storage order
-  float* gs_ws;            // (B, K) |dL/d(lin_out's output)|
-  float* cw_ws;            // (V, B, K) c_v per sample
-  float* d_mlp;            // packed, or null
+  float* cw_ws;            // backward: (V, B, K) c_v per sample
 };
 typedef const MvParams __attribute__((address_space(4)))* MvArgs;   // the tables are read from the kernarg segment: wave-uniform s_loads
 
@@ -132,37 +124,23 @@ __global__ __launch_bounds__(kMcThreads) void mv_render_kernel(const MvParams mp
   __shared__ float s_z[kMcThreads], s_a[kMcThreads], s_w[kMcThreads], s_T[kMcThreads], s_ws[kMcThreads];
   __shared__ float s_c[kMcThreads * kMvColStride];
   mc_stage_empty<C, HD>(s_empty, p);
-  const int K = p.K, R = mp.R, nvp = mp.t.n_ren, nv3 = 3 * nvp;
-  const long B = (long)p.n * p.Bp;
-  const long ray0 = (long)blockIdx.x * R;
+  const int K = p.K, nvp = mp.t.n_ren, nv3 = 3 * nvp;
+  const long ray0 = (long)blockIdx.x * mp.R;
   const int tid = threadIdx.x;
-  const int r_loc = tid / K, k = tid - r_loc * K;
-  const long ray = ray0 + r_loc;
-  const bool live = r_loc < R && ray < B;
-  float z = 0.0f;
-  if (live) {
-    z = mc_depth(p, ray, k);
-    s_z[tid] = z;
-    if (p.z_out) p.z_out[ray * K + k] = z;
-  }
+  const McLane ln = mc_lane(mp, ray0, s_z, [&](long ray, int k) { return mc_depth(p, ray, k); });
+  const long i = ln.ray * K + ln.k;
   __syncthreads();
   float o0 = 0.0f;
-  if (live) {
-    const int sample = (int)(ray / p.Bp);
-    const float* rr = p.rays + ray * 8;
+  if (ln.live) {
+    const int sample = (int)(ln.ray / p.Bp);
+    const float* rr = p.rays + ln.ray * 8;
+    const float z = ln.z;
     const float px = rr[0] + z * rr[3], py = rr[1] + z * rr[4], pz = rr[2] + z * rr[5];
     McAct<C, HD, NB> act;
     bool inv_f;
     mv_field<C, HD, NB>(q, p, sample, px, py, pz, s_empty, act, o0, inv_f, nullptr, 0);
-    float sg = softplus(o0);                                   // models_bts.py:313
-    if (p.empty_empty && inv_f) sg = 0.0f;                     // models_bts.py:323-324, on the merged flag
-    if (p.sigma_noise) sg = sg + p.sigma_noise[ray * K + k];   // nerf.py:279-280
-    const float delta = k < K - 1 ? s_z[tid + 1] - z : 1e10f;  // nerf.py:276-277
-    const float t = transmittance(delta, sg);                  // exp(-|delta| relu(sigma)), nerf.py:283
-    float alpha = 1.0f - t;
-    if (p.hard_cap && k == K - 1) alpha = 1.0f;                // nerf.py:285-286
-    s_a[tid] = alpha;
-    const long i = ray * K + k;
+    // softplus: models_bts.py:313; the empty_empty select on the merged flag
+    s_a[tid] = mc_alpha(p, s_z, ln.k, i, z, softplus(o0), p.empty_empty && inv_f).alpha;
 #pragma unroll 1
     for (int g = 0; g < nvp; ++g) {
       float col[3];
@@ -178,25 +156,16 @@ __global__ __launch_bounds__(kMcThreads) void mv_render_kernel(const MvParams mp
     }
   }
   __syncthreads();
-  // one lane per ray: the transmittance product, depth and the weight sum, front to back (nerf.py:288-304)
-  if (tid < R && ray0 + tid < B) {
-    const long rw = ray0 + tid;
+  // one lane per ray: the transmittance product, the weights, depth and the weight sum
+  if (mc_ray_lane(mp, ray0)) {
     const int base = tid * K;
-    float T = 1.0f, wsum = 0.0f, dep = 0.0f;
-    for (int kk = 0; kk < K; ++kk) {
-      const float al = s_a[base + kk];
-      const float wk = al * T;
-      s_T[base + kk] = T, s_w[base + kk] = wk;
-      dep = dep + wk * s_z[base + kk];
-      wsum = wsum + wk;
-      T = T * ((1.0f - al) + 1e-10f);
-    }
-    s_ws[tid] = wsum;
-    p.depth[rw] = dep;
+    const McRaySums sums = mc_scan(s_a, s_z, s_T, base, K, [&](int kk, float wk) { s_w[base + kk] = wk; });
+    s_ws[tid] = sums.wsum;
+    p.depth[ray0 + tid] = sums.depth;
   }
   __syncthreads();
   // one lane per (ray, view, channel): rgb = sum_k w_k c_k
-  const int rays_here = (int)min((long)R, B - ray0);
+  const int rays_here = mc_rays_here(mp, ray0);
   for (int idx = tid; idx < rays_here * nv3; idx += kMcThreads) {
     const int r = idx / nv3, j = idx - r * nv3;
     const int base = r * K;
@@ -204,8 +173,7 @@ __global__ __launch_bounds__(kMcThreads) void mv_render_kernel(const MvParams mp
     for (int kk = 0; kk < K; ++kk) acc = acc + s_w[base + kk] * s_c[(base + kk) * kMvColStride + j];
     p.rgb[(ray0 + r) * nv3 + j] = p.white_bkgd ? acc + (1.0f - s_ws[r]) : acc;
   }
-  if (live) {
-    const long i = ray * K + k;
+  if (ln.live) {
     if (p.weights) p.weights[i] = s_w[tid];
     if (p.alphas) p.alphas[i] = s_a[tid];
     if (p.trans) p.trans[i] = s_T[tid];
@@ -257,64 +225,49 @@ template <int C, int HD, int NB>
 __global__ __launch_bounds__(kMcThreads) void mv_rows_kernel(const MvParams mp) {
   const FwdParams& p = mp.f;
   const MvArgs q = kernarg_view<MvParams>();
-  constexpr int D_IN = C + kPeDim;
-  constexpr int ASTR = HD + 1, BSTR = HD + 1;
+  constexpr int ASTR = HD + 1, BSTR = HD + 1;   // mc_mlp_bwd's rows
   __shared__ float s_empty[HD];
   __shared__ float s_z[kMcThreads], s_a[kMcThreads], s_t[kMcThreads], s_cd[kMcThreads], s_go[kMcThreads];
   __shared__ float s_A[kMcThreads * ASTR], s_B[kMcThreads * BSTR];
   mc_stage_empty<C, HD>(s_empty, p);
-  const MlpLayout ml{D_IN, HD, NB};
+  const MlpLayout ml{C + kPeDim, HD, NB};
   const cfp w = as_const(p.mlp);
-  const int K = p.K, R = mp.R, nvp = mp.t.n_ren, nv3 = 3 * nvp, V = mp.t.V;
-  const long B = (long)p.n * p.Bp;
-  const long samples = B * K;
+  const int K = p.K, nvp = mp.t.n_ren, nv3 = 3 * nvp, V = mp.t.V;
+  const long samples = (long)p.n * p.Bp * K;
   const int tid = threadIdx.x;
-  const int r_loc = tid / K, k = tid - r_loc * K;
   const bool want_w = mp.d_mlp != nullptr;
   McTile<1, HD> t_out;
   McTile<HD, HD> t_w1, t_w0;
   t_out.zero(), t_w1.zero(), t_w0.zero();
   for (long grp = blockIdx.x; grp < mp.n_groups; grp += gridDim.x) {
-    const long ray0 = grp * R;
-    const long ray = ray0 + r_loc;
-    const bool live = r_loc < R && ray < B;
+    const long ray0 = grp * mp.R;
     __syncthreads();   // the previous iteration's LDS readers are done
-    float z = 0.0f;
-    if (live) {
-      z = p.z_samp[ray * K + k];
-      s_z[tid] = z;
-    }
+    const McLane ln = mc_lane(mp, ray0, s_z, [&](long ray, int k) { return p.z_samp[ray * K + k]; });
+    const long i = ln.ray * K + ln.k;
     __syncthreads();
     // ---- the sample's field, activations kept in registers
     McAct<C, HD, NB> act;
-#pragma unroll
-    for (int j = 0; j < HD; ++j) act.h0[j] = 0.0f, act.nn[NB > 0 ? j : 0] = 0.0f, act.h1[NB > 0 ? j : 0] = 0.0f;
+    act.zero();
     float dsig = 0.0f;   // d sigma / d o0
-    if (live) {
-      const long i = ray * K + k;
-      const int sample = (int)(ray / p.Bp);
-      const float* rr = p.rays + ray * 8;
+    if (ln.live) {
+      const int sample = (int)(ln.ray / p.Bp);
+      const float* rr = p.rays + ln.ray * 8;
+      const float z = ln.z;
       const float px = rr[0] + z * rr[3], py = rr[1] + z * rr[4], pz = rr[2] + z * rr[5];
       for (int v = 0; v < V; ++v) mp.cw_ws[v * samples + i] = 0.0f;
       float o_now;
       bool inv_f;
       mv_field<C, HD, NB>(q, p, sample, px, py, pz, s_empty, act, o_now, inv_f, mp.cw_ws + i, samples);
       const float o0 = p.sigma_raw[i];   // the forward's (the same value: same routine)
-      float sg = softplus(o0);
-      dsig = sigmoidf(o0);
-      if (p.empty_empty && inv_f) sg = 0.0f, dsig = 0.0f;
-      if (p.sigma_noise) sg = sg + p.sigma_noise[i];
-      const bool sg_pos = sg > 0.0f;
-      const float delta = k < K - 1 ? s_z[tid + 1] - z : 1e10f;
-      const float t = transmittance(delta, sg);
-      float alpha = 1.0f - t;
-      if (p.hard_cap && k == K - 1) alpha = 1.0f;
-      s_a[tid] = alpha;
-      s_t[tid] = (p.hard_cap && k == K - 1) || !sg_pos ? 0.0f : fabsf(delta) * t;   // d alpha / d sigma (relu'(0) = 0)
+      const bool empty = p.empty_empty && inv_f;
+      dsig = empty ? 0.0f : sigmoidf(o0);
+      const McAlpha al = mc_alpha(p, s_z, ln.k, i, z, softplus(o0), empty);
+      s_a[tid] = al.alpha;
+      s_t[tid] = mc_dalpha_dsigma(p, ln.k, al);
       // g_rgb . colours of this sample (the forward's colours when the caller kept them, else the taps again)
       float cd = 0.0f;
       if (mp.g_rgb) {
-        const float* gr = mp.g_rgb + ray * nv3;
+        const float* gr = mp.g_rgb + ln.ray * nv3;
         if (p.rgb_samps) {
           for (int j = 0; j < nv3; ++j) cd = __builtin_fmaf(gr[j], p.rgb_samps[i * nv3 + j], cd);
         } else {
@@ -331,9 +284,8 @@ __global__ __launch_bounds__(kMcThreads) void mv_rows_kernel(const MvParams mp) 
       s_cd[tid] = cd;
     }
     __syncthreads();
-    // ---- one lane per ray: back to front.  P = sum_{j>k} g_w_j alpha_j prod_{k<i<j} (1 - alpha_i + 1e-10), so that dL/dalpha_k =
-    // g_w_k T_k - T_k P + g_alpha_k without a division (the reference's cumprod gradient, nerf.py:288-289)
-    if (tid < R && ray0 + tid < B) {
+    // ---- one lane per ray: back to front
+    if (mc_ray_lane(mp, ray0)) {
       const long rw = ray0 + tid;
       const int base = tid * K;
       float g_bk = 0.0f;
@@ -342,25 +294,20 @@ __global__ __launch_bounds__(kMcThreads) void mv_rows_kernel(const MvParams mp) 
       const float g_dep = mp.g_depth ? mp.g_depth[rw] : 0.0f;
       float P = 0.0f;
       for (int kk = K - 1; kk >= 0; --kk) {
-        const long i = rw * K + kk;
-        const float al = s_a[base + kk], T = p.trans[i];
+        const long ik = rw * K + kk;
         float gw = g_dep * s_z[base + kk] + g_bk;
-        if (mp.g_weights) gw = gw + mp.g_weights[i];
+        if (mp.g_weights) gw = gw + mp.g_weights[ik];
         gw = gw + s_cd[base + kk];
-        float ga = gw * T - T * P;
-        if (mp.g_alphas) ga = ga + mp.g_alphas[i];
-        P = gw * al + ((1.0f - al) + 1e-10f) * P;
-        s_go[base + kk] = ga * s_t[base + kk];
+        s_go[base + kk] = mc_suffix_step(mp, ik, gw, s_a[base + kk], p.trans[ik], P) * s_t[base + kk];
       }
     }
     __syncthreads();
     // ---- the MLP backward of this lane's sample
     float go[1] = {0.0f};
-    if (live) go[0] = s_go[tid] * dsig;   // softplus' = sigmoid, and the empty_empty select
+    if (ln.live) go[0] = s_go[tid] * dsig;   // softplus' = sigmoid, and the empty_empty select
     float u0[HD];
-    mc_mlp_bwd<C, HD, NB, 1>(w, act, go, live, want_w, (int)min((long)R, B - ray0) * K, s_A, s_B, t_out, t_w1, t_w0, u0);
-    if (live) {
-      const long i = ray * K + k;
+    mc_mlp_bwd<C, HD, NB, 1>(w, act, go, ln.live, want_w, mc_rays_here(mp, ray0) * K, s_A, s_B, t_out, t_w1, t_w0, u0);
+    if (ln.live) {
       mc_store_row<HD>(mp.u0_ws + i * HD, u0);
       mp.gs_ws[i] = fabsf(go[0]);
     }
@@ -390,8 +337,6 @@ __global__ __launch_bounds__(256) void mv_scale_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int mv_status(const char* who) { return launch_check("%s: kernel launch failed (HIP error %ld)", who); }
-
 // the kernels' parameters of a CHECKED field (bts_api.hip: check_multi_view)
 static MvParams mv_params(const BtsMultiViewField* mv) {
   MvParams mp;
@@ -411,30 +356,14 @@ static MvParams mv_params(const BtsMultiViewField* mv) {
   return mp;
 }
 
-static void mv_render_args(MvParams& mp, const BtsFieldCfg* cfg, const BtsRenderArgs* a) {
-  FwdParams& p = mp.f;
-  p.rays = a->rays, p.z_samp = a->z_samp;
-  p.Bp = a->rays_per_sample, p.K = a->K, p.hard_cap = a->hard_alpha_cap, p.white_bkgd = a->white_bkgd;
-  p.rgb_samps = a->rgb_samps, p.sigma_raw = a->sigma_raw, p.trans = a->trans, p.sigma_noise = a->sigma_noise;
-  mp.R = kMcThreads / p.K;
-  mp.n_groups = ((long)cfg->n * p.Bp + mp.R - 1) / mp.R;
-}
-
 int multi_view_render_fwd_impl(const BtsMultiViewField* mv, const BtsRenderArgs* a, hipStream_t s) {
   const BtsFieldCfg* cfg = &mv->cfg[0];
   MvParams mp = mv_params(mv);
-  mv_render_args(mp, cfg, a);
-  FwdParams& p = mp.f;
-  p.jitter = a->z_samp ? nullptr : a->jitter, p.z_out = a->z_samp ? nullptr : a->z_samp_out, p.lindisp = a->lindisp;
-  p.rgb = a->rgb, p.depth = a->depth, p.weights = a->weights, p.alphas = a->alphas, p.invalid = a->invalid;
-  if (mp.n_groups > 0x7FFFFFFFL) {
-    set_error("%s: too many rays in one call (%ld)", "bts_render_fwd_multi_view", (long)cfg->n * p.Bp);
-    return BTS_E_UNSUPPORTED;
-  }
+  if (int rc = mc_render_params(mp, cfg, a, false, "bts_render_fwd_multi_view")) return rc;
   return with_shape(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto sh) {
     using S = decltype(sh);
     mv_render_kernel<S::C, S::HD, S::NB><<<(int)mp.n_groups, kMcThreads, 0, s>>>(mp);
-    return mv_status("bts_render_fwd_multi_view");
+    return mc_status("bts_render_fwd_multi_view");
   });
 }
 
@@ -453,7 +382,7 @@ int multi_view_field_query_impl(const BtsMultiViewField* mv, const float* xyz, i
   return with_shape(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto sh) {
     using S = decltype(sh);
     mv_query_kernel<S::C, S::HD, S::NB><<<(int)blocks, kMcThreads, 0, s>>>(mp);
-    return mv_status("bts_field_query_multi_view");
+    return mc_status("bts_field_query_multi_view");
   });
 }
 
@@ -484,30 +413,20 @@ int multi_view_render_bwd_impl(const BtsMultiViewField* mv, const BtsRenderArgs*
                                unsigned char* const* d_proj_tiles_views, void* workspace, hipStream_t s) {
   const BtsFieldCfg* cfg = &mv->cfg[0];
   MvParams mp = mv_params(mv);
-  mv_render_args(mp, cfg, a);
-  FwdParams& p = mp.f;
-  p.tiles_per_sample = (a->rays_per_sample + 255) / 256;
-  p.lpr = 64, p.groups = (long)cfg->n * p.Bp;
-  if (p.groups > 0x7FF00000L) {
-    set_error("%s: too many rays in one call (%ld)", "bts_render_bwd_multi_view", p.groups);
-    return BTS_E_UNSUPPORTED;
-  }
-  const bool want_c = g->d_mlp_params != nullptr;
-  bool want_b = g->d_empty_proj != nullptr;
-  for (int v = 0; v < mv->V; ++v) want_b = want_b || (d_proj_views && d_proj_views[v]);
-  if (!want_b && !want_c) return BTS_OK;
+  if (int rc = mc_render_params(mp, cfg, a, true, "bts_render_bwd_multi_view")) return rc;
+  bool want = g->d_mlp_params || g->d_empty_proj;
+  for (int v = 0; v < mv->V; ++v) want = want || (d_proj_views && d_proj_views[v]);
+  if (!want) return BTS_OK;
   Carver carve(workspace);
   const MvWs ws = mv_ws_layout(carve, mv, a);
   const long samples = (long)cfg->n * a->rays_per_sample * a->K;
   mp.g_rgb = g->g_rgb, mp.g_depth = g->g_depth, mp.g_weights = g->g_weights, mp.g_alphas = g->g_alphas;
   mp.u0_ws = ws.u0, mp.gs_ws = ws.gs, mp.cw_ws = ws.cw, mp.d_mlp = g->d_mlp_params;
-  // persistent grid of at most render_grid's size (the weight-gradient partials are flushed once per work-group)
-  const int grid = render_grid(p);
+  const int grid = render_grid(mp.f);
   int rc = with_shape(cfg->C, cfg->d_hidden, cfg->n_blocks, [&](auto sh) {
     using S = decltype(sh);
-    const long g_ = mp.n_groups < grid ? mp.n_groups : grid;
-    mv_rows_kernel<S::C, S::HD, S::NB><<<(int)g_, kMcThreads, 0, s>>>(mp);
-    return mv_status("bts_render_bwd_multi_view");
+    mv_rows_kernel<S::C, S::HD, S::NB><<<mc_rows_grid(mp, grid), kMcThreads, 0, s>>>(mp);
+    return mc_status("bts_render_bwd_multi_view");
   });
   const int hd4 = cfg->d_hidden / 4;
   const long scale_blocks = (samples * hd4 + 255) / 256;
@@ -516,20 +435,12 @@ int multi_view_render_bwd_impl(const BtsMultiViewField* mv, const BtsRenderArgs*
     for (int m = 0; m < mv->enc_group_start[mv->n_enc_groups]; ++m) grouped = grouped || mv->enc_member[m] == v;
     if (!grouped) continue;   // c_v = 0 everywhere
     mv_scale_kernel<<<(int)(scale_blocks < 4096 ? scale_blocks : 4096), 256, 0, s>>>(ws.u0, ws.gs, ws.cw + (long)v * samples, ws.rows, ws.gs_v, samples, hd4);
-    rc = mv_status("bts_render_bwd_multi_view");
+    rc = mc_status("bts_render_bwd_multi_view");
     if (rc) break;
-    BwdParams bp;
-    memset(&bp, 0, sizeof(bp));
-    bp.f = p;
+    BwdParams bp = mc_pass_params(mp.f, cfg, g, d_proj_views ? d_proj_views[v] : nullptr, d_proj_tiles_views ? d_proj_tiles_views[v] : nullptr,
+                                  ws.gs_v, ws.flush);
     bp.f.proj = mv->view[v].proj_nhwc, bp.f.K_enc = mv->view[v].K_enc, bp.f.w2c_enc = mv->view[v].w2c_enc;
-    bp.g_rgb = g->g_rgb, bp.g_depth = g->g_depth;
-    bp.d_proj = d_proj_views ? d_proj_views[v] : nullptr, bp.d_mlp = g->d_mlp_params, bp.d_empty_proj = g->d_empty_proj;
-    bp.gs_ws = ws.gs_v, bp.flush_ws = ws.flush;
-    bp.tiles = (bp.d_proj && d_proj_tiles_views) ? d_proj_tiles_views[v] : nullptr;
-    bp.tiles_per_img = (int)map_tiles(cfg->H, cfg->W, cfg->feat_shift);
-    bp.tile_tw = tile_cols(cfg->H >> cfg->feat_shift, cfg->W >> cfg->feat_shift, cfg->tile_blocks);
-    if (want_c) rc = launch_dwpe_rows(bp.f, ws.rows, bp.d_mlp, bp.flush_ws, cfg->C, cfg->d_hidden, cfg->n_blocks, cfg->n, grid, s, false);
-    if (rc == BTS_OK && (bp.d_proj || bp.d_empty_proj)) rc = launch_scatter_rows(bp, ws.rows, cfg->d_hidden, cfg->n, s);
+    rc = mc_launch_passes_bc(bp, ws.rows, cfg, grid, s);
   }
   return rc;
 }

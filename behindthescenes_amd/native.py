@@ -848,17 +848,38 @@ def _check_partial(ft: "FieldTensors", rays, samples, what="render"):
         raise BtsNativeError(f"{what}: the projected map of this field was built for another ray set (sparse projection, native_field(sampled=...))")
 
 
+def _render_bwd_checks(z_samp, sigma_raw, trans, g_rgb, g_depth, g_weights, g_alphas):
+    """What every render backward checks first: the upstream gradients and the forward's saved state."""
+    B, K = z_samp.shape
+    for name, g in (("g_rgb", g_rgb), ("g_depth", g_depth), ("g_weights", g_weights), ("g_alphas", g_alphas)):
+        if g is not None:
+            _req(g, name)
+    _req(sigma_raw, "sigma_raw", (B, K)), _req(trans, "trans", (B, K))
+
+
+def _render_bwd_structs(ft, rays, z_samp, sigma_raw, trans, hard_alpha_cap, white_bkgd, g_rgb, g_depth, g_weights, g_alphas, need_mlp, need_empty,
+                        rgb_samps, sigma_noise, d_proj=None, tiles=None):
+    """Behind the caller's map gradients: zeroed d_mlp_params and d_empty_proj, the rgb_samps check, BtsRenderArgs and BtsRenderGrads
+    (d_proj, tiles: the single map of bts_render_bwd).  Returns (args, grads, d_mlp, d_empty)."""
+    B, K = z_samp.shape
+    dev = rays.device
+    d_mlp = torch.zeros(ft.spec.mlp_param_count(), device=dev, dtype=torch.float32) if need_mlp else None
+    d_empty = torch.zeros(ft.spec.d_hidden, device=dev, dtype=torch.float32) if need_empty else None
+    if rgb_samps is not None:
+        _req(rgb_samps, "rgb_samps", (B, K, ft.nv * 3))
+    args = _render_args(ft, rays, z_samp, hard_alpha_cap, white_bkgd, dict(sigma_raw=sigma_raw, trans=trans, rgb_samps=rgb_samps), sigma_noise)
+    grads = BtsRenderGrads(g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), g_weights=_addr(g_weights), g_alphas=_addr(g_alphas),
+                           d_proj_nhwc=_addr(d_proj), d_mlp_params=_addr(d_mlp), d_empty_proj=_addr(d_empty), d_proj_tiles=_addr(tiles))
+    return args, grads, d_mlp, d_empty
+
+
 def render_bwd(ft: FieldTensors, mlp_params, rays, z_samp, sigma_raw, trans, *, hard_alpha_cap, g_rgb=None, g_depth=None,
                g_weights=None, g_alphas=None, need_proj=True, need_mlp=True, need_empty=False, white_bkgd=False, rgb_samps=None,
                sigma_noise=None, proj_grad=None):
     """Returns (d_proj_nhwc | None, d_mlp_params | None, d_empty_proj | None) (bts_render_bwd).  ``proj_grad`` = (d_proj, tiles): add
     into THIS d_proj (the caller vouches that it is zero wherever ``tiles`` is) and flag the 64-texel tiles that received something
     (BtsRenderGrads.d_proj_tiles) -- no fill of a map-sized tensor."""
-    B, K = z_samp.shape
-    for name, g in (("g_rgb", g_rgb), ("g_depth", g_depth), ("g_weights", g_weights), ("g_alphas", g_alphas)):
-        if g is not None:
-            _req(g, name)
-    _req(sigma_raw, "sigma_raw", (B, K)), _req(trans, "trans", (B, K))
+    _render_bwd_checks(z_samp, sigma_raw, trans, g_rgb, g_depth, g_weights, g_alphas)
     dev = rays.device
     tiles = None
     if need_proj and proj_grad is not None:
@@ -866,14 +887,9 @@ def render_bwd(ft: FieldTensors, mlp_params, rays, z_samp, sigma_raw, trans, *, 
         _req(d_proj, "proj_grad[0]", tuple(ft.proj_nhwc.shape))
     else:
         d_proj = torch.zeros(ft.proj_nhwc.shape, device=dev, dtype=torch.float32) if need_proj else None
-    d_mlp = torch.zeros(ft.spec.mlp_param_count(), device=dev, dtype=torch.float32) if need_mlp else None
-    d_empty = torch.zeros(ft.spec.d_hidden, device=dev, dtype=torch.float32) if need_empty else None
+    args, grads, d_mlp, d_empty = _render_bwd_structs(ft, rays, z_samp, sigma_raw, trans, hard_alpha_cap, white_bkgd, g_rgb, g_depth, g_weights,
+                                                      g_alphas, need_mlp, need_empty, rgb_samps, sigma_noise, d_proj, tiles)
     cfg, tens = ft.cfg(), ft.tensors(mlp_params)
-    if rgb_samps is not None:
-        _req(rgb_samps, "rgb_samps", (B, K, ft.nv * 3))
-    args = _render_args(ft, rays, z_samp, hard_alpha_cap, white_bkgd, dict(sigma_raw=sigma_raw, trans=trans, rgb_samps=rgb_samps), sigma_noise)
-    grads = BtsRenderGrads(g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), g_weights=_addr(g_weights), g_alphas=_addr(g_alphas),
-                           d_proj_nhwc=_addr(d_proj), d_mlp_params=_addr(d_mlp), d_empty_proj=_addr(d_empty), d_proj_tiles=_addr(tiles))
     lib = _lib.load()
     if ft.mlp_color:
         ws_bytes = lib.bts_render_bwd_mlp_color_workspace(C.byref(cfg), C.byref(args))
@@ -893,21 +909,12 @@ def render_bwd_multi_view(ft: MultiViewField, mlp_params, rays, z_samp, sigma_ra
                           sigma_noise=None):
     """Returns ([d_proj_nhwc | None per encoder view], d_mlp_params | None, d_empty_proj | None) (bts_render_bwd_multi_view); ``need_proj``:
     one flag per view (None: every view)."""
-    B, K = z_samp.shape
-    for name, g in (("g_rgb", g_rgb), ("g_depth", g_depth), ("g_weights", g_weights), ("g_alphas", g_alphas)):
-        if g is not None:
-            _req(g, name)
-    _req(sigma_raw, "sigma_raw", (B, K)), _req(trans, "trans", (B, K))
+    _render_bwd_checks(z_samp, sigma_raw, trans, g_rgb, g_depth, g_weights, g_alphas)
     dev, V = rays.device, len(ft.views)
     need_proj = [True] * V if need_proj is None else list(need_proj)
     d_projs = [torch.zeros(v.proj_nhwc.shape, device=dev, dtype=torch.float32) if need else None for v, need in zip(ft.views, need_proj)]
-    d_mlp = torch.zeros(ft.spec.mlp_param_count(), device=dev, dtype=torch.float32) if need_mlp else None
-    d_empty = torch.zeros(ft.spec.d_hidden, device=dev, dtype=torch.float32) if need_empty else None
-    if rgb_samps is not None:
-        _req(rgb_samps, "rgb_samps", (B, K, ft.nv * 3))
-    args = _render_args(ft, rays, z_samp, hard_alpha_cap, white_bkgd, dict(sigma_raw=sigma_raw, trans=trans, rgb_samps=rgb_samps), sigma_noise)
-    grads = BtsRenderGrads(g_rgb=_addr(g_rgb), g_depth=_addr(g_depth), g_weights=_addr(g_weights), g_alphas=_addr(g_alphas),
-                           d_mlp_params=_addr(d_mlp), d_empty_proj=_addr(d_empty))
+    args, grads, d_mlp, d_empty = _render_bwd_structs(ft, rays, z_samp, sigma_raw, trans, hard_alpha_cap, white_bkgd, g_rgb, g_depth, g_weights,
+                                                      g_alphas, need_mlp, need_empty, rgb_samps, sigma_noise)
     maps = (C.c_void_p * V)(*[_addr(d) for d in d_projs])
     mv, lib = ft.struct(mlp_params), _lib.load()
     ws_bytes = lib.bts_render_bwd_multi_view_workspace(C.byref(mv), C.byref(args))
@@ -947,12 +954,12 @@ def field_query(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Tensor, o
     _req(xyz, "xyz", (ft.n, P, 3))
     _check_partial(ft, None, None, "field_query")
     dev = xyz.device
+    if isinstance(ft, MultiViewField) and only_density:
+        raise NotImplementedError("only_density with several encoder views: the reference itself fails here (models_bts.py:281-284)")
+    sigma = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
     if isinstance(ft, MultiViewField):
-        if only_density:
-            raise NotImplementedError("only_density with several encoder views: the reference itself fails here (models_bts.py:281-284)")
         rgb = torch.empty((n, P, ft.nv * 3), device=dev, dtype=torch.float32)
         invalid = torch.empty((n, P, ft.nv), device=dev, dtype=torch.float32)
-        sigma = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
         mv = ft.struct(mlp_params)
         _lib.check(_lib.load().bts_field_query_multi_view(C.byref(mv), _ptr(xyz), P, _ptr(rgb), _ptr(invalid), _ptr(sigma), _stream(xyz)),
                    "bts_field_query_multi_view")
@@ -961,7 +968,6 @@ def field_query(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Tensor, o
         # sample_color=False (models_bts.py:315-338): rgb (n, P, 3) from the MLP, zeros with only_density (:336); invalid (n, P, 1)
         rgb = torch.empty((n, P, 3), device=dev, dtype=torch.float32)
         invalid = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
-        sigma = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
         cfg, tens = ft.cfg(), ft.tensors(mlp_params)
         _lib.check(_lib.load().bts_field_query_mlp_color(C.byref(cfg), C.byref(tens), _ptr(xyz), P, int(only_density), _ptr(rgb), _ptr(invalid),
                                                          _ptr(sigma), _stream(xyz)), "bts_field_query_mlp_color")
@@ -969,7 +975,6 @@ def field_query(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Tensor, o
     nv = 0 if only_density else ft.nv
     rgb = torch.empty((n, P, nv * 3), device=dev, dtype=torch.float32) if nv else None
     invalid = torch.empty((n, P, max(nv, 1)), device=dev, dtype=torch.float32)
-    sigma = torch.empty((n, P, 1), device=dev, dtype=torch.float32)
     if nv == 0 and not only_density:  # no colour views: invalid is the feature-frustum test only
         only_density = True
     cfg, tens = ft.cfg(), ft.tensors(mlp_params)
@@ -1409,6 +1414,22 @@ class ProjectFunction(torch.autograd.Function):
         return d_feat, d_mlp, None, None, None
 
 
+def _prep_grad(g, present=True):
+    """An upstream gradient as the backward takes it: contiguous, or None where there is none (or its output was not requested)."""
+    return g.contiguous() if (g is not None and present and g.numel() > 0) else None
+
+
+def _empty_feature_chain(spec, mlp_params, empty_feature, d_eproj, d_mlp, need_empty, need_mlp):
+    """The projected empty feature is w_in[:, :C] @ empty_feature (a 64x64 GEMV): the chain rule on parameter-sized tensors.  Adds the
+    weights' part into d_mlp and returns d_empty_feature (or None)."""
+    if d_eproj is None:
+        return None
+    w_f = mlp_params[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C]
+    if need_mlp:
+        d_mlp[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C] += torch.outer(d_eproj, empty_feature.detach())
+    return w_f.t() @ d_eproj if need_empty else None
+
+
 class RenderFunction(torch.autograd.Function):
     """composite() as one differentiable op.  Differentiable inputs: proj_nhwc (G), mlp_params, empty_feature.
     Differentiable outputs: rgb, depth, weights, alphas (invalid / rgb_samps carry no gradient, as in the reference where
@@ -1450,11 +1471,7 @@ class RenderFunction(torch.autograd.Function):
     def backward(ctx, g_rgb, g_depth, g_weights, g_alphas, _g_inv, _g_rs, _g_iw, _g_ia, _g_z):
         mlp_params, rays, z_samp, sigma_raw, trans, *rest = ctx.saved_tensors
         rgb_samps = rest[0] if rest else None
-
-        def prep(g, present=True):
-            return g.contiguous() if (g is not None and present and g.numel() > 0) else None
-
-        ft = ctx.ft
+        prep, ft = _prep_grad, ctx.ft
         need_proj, need_mlp, need_empty = ctx.needs_input_grad[:3]
         pg, link, G, entry = None, ctx.link, ft.proj_nhwc, None
         if (need_proj and SPARSE_PROJ_GRAD and link is not None and link.renders == 1 and link.entry is None and not G.retains_grad
@@ -1477,15 +1494,7 @@ class RenderFunction(torch.autograd.Function):
                 entry.buf.zero_(), entry.tiles.zero_()
                 entry.busy, link.entry = False, None
             raise
-        d_empty = None
-        if d_eproj is not None:
-            # the projected empty feature is w_in[:, :C] @ empty_feature (a 64x64 GEMV): chain rule on parameter-sized tensors
-            spec = ft.spec
-            w_f = mlp_params[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C]
-            if need_empty:
-                d_empty = w_f.t() @ d_eproj
-            if need_mlp:
-                d_mlp[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C] += torch.outer(d_eproj, ft.empty_feature.detach())
+        d_empty = _empty_feature_chain(ft.spec, mlp_params, ft.empty_feature, d_eproj, d_mlp, need_empty, need_mlp)
         return (d_proj, d_mlp, d_empty) + (None,) * 15
 
 
@@ -1517,23 +1526,11 @@ class MultiViewRenderFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb, g_depth, g_weights, g_alphas, _g_inv, _g_rs, _g_z):
         mlp_params, rays, z_samp, sigma_raw, trans, rgb_samps = ctx.saved_tensors
-
-        def prep(g, present=True):
-            return g.contiguous() if (g is not None and present and g.numel() > 0) else None
-
-        ft = ctx.ft
+        prep, ft = _prep_grad, ctx.ft
         need_mlp, need_empty = ctx.needs_input_grad[:2]
         d_projs, d_mlp, d_eproj = render_bwd_multi_view(
             ft, mlp_params, rays, z_samp, sigma_raw, trans, hard_alpha_cap=ctx.hard_alpha_cap, g_rgb=prep(g_rgb), g_depth=prep(g_depth),
             g_weights=prep(g_weights, ctx.has[0]), g_alphas=prep(g_alphas, ctx.has[1]), need_proj=ctx.needs_input_grad[16:], need_mlp=need_mlp,
             need_empty=need_empty or (need_mlp and ft.spec.learn_empty), white_bkgd=ctx.white_bkgd, rgb_samps=rgb_samps, sigma_noise=ctx.sigma_noise)
-        d_empty = None
-        if d_eproj is not None:
-            # the projected empty feature is w_in[:, :C] @ empty_feature: chain rule on parameter-sized tensors (as RenderFunction)
-            spec = ft.spec
-            w_f = mlp_params[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C]
-            if need_empty:
-                d_empty = w_f.t() @ d_eproj
-            if need_mlp:
-                d_mlp[:spec.d_hidden * spec.d_in].view(spec.d_hidden, spec.d_in)[:, :spec.C] += torch.outer(d_eproj, ft.empty_feature.detach())
+        d_empty = _empty_feature_chain(ft.spec, mlp_params, ft.empty_feature, d_eproj, d_mlp, need_empty, need_mlp)
         return (d_mlp, d_empty) + (None,) * 14 + tuple(d_projs)

@@ -115,16 +115,23 @@ NOISE_STD = 0.5
 # K = 48 leaves 16 lanes of every work-group idle (5 rays of 48 samples), the re10k shape
 OPTIONS = [(16, True, False, False, 0, False), (48, True, False, False, 0, False), (16, False, False, False, 0, False),
            (16, True, True, False, 0, False), (16, True, False, True, 0, False), (16, True, False, False, 1, False),
-           (16, True, False, False, 0, True)]
+           (16, True, False, False, 0, True),
+           # K = 96: R = 2 rays per work-group iteration (64 lanes idle) and more iterations than the backward's persistent grid has
+           # work-groups (824 rays: 412 iterations on a grid of 208), so that pass A's loop runs twice in nearly every one
+           (96, True, False, False, 0, False)]
 
 
-@pytest.mark.parametrize("opt", OPTIONS, ids=["plain", "K48", "nocap", "white", "noise", "feat_shift1", "jitter"])
+@pytest.mark.parametrize("opt", OPTIONS, ids=["plain", "K48", "nocap", "white", "noise", "feat_shift1", "jitter", "K96"])
 @pytest.mark.parametrize("shape", SHAPES, ids=["64_64_0", "32_32_1"])
 def test_render_and_gradients_vs_composition(shape, opt):
     K, hard_cap, white, noisy, fs, jit = opt
     ref, nat, rays, cfg, g = _nets(*shape, fs=fs)
     n = rays.shape[0]
     rays = rays.reshape(-1, 8)
+    if K > 64:   # the second iteration this case is for: render_grid has a work-group per 4 rays, rounded up to 8
+        B = rays.shape[0]
+        groups, grid = -(-B // (256 // K)), -(-(-(-B // 4)) // 8) * 8
+        assert groups > max(8, -(-B // 4)) and groups > grid, (B, groups, grid)
     u = torch.rand(rays.shape[0], K, generator=g)
     noise = torch.randn(rays.shape[0], K, generator=g) * NOISE_STD if noisy else None
     kw = dict(hard_cap=hard_cap, white=white, noise=noise)

@@ -265,6 +265,19 @@ def test_whole_rays_of_256_samples_vs_composition():
     _render_both(comp, nat, r, rays, z, 1, 3, few_rays=True)
 
 
+def test_second_group_per_work_group_vs_composition():
+    """K = 96: work-group iterations of R = 2 rays, 23 of them for 45 rays (the last of one ray) on a grid of 16 work-groups, so that pass A's
+    persistent loop runs twice in some: its tiles accumulate, its activations are zeroed again.  The block path (32, 32, 1)."""
+    comp, nat, scene = _pair((32, 32, 1), (16, 32), 1, 6, ENC3, seed=26)
+    rays = _interior_rays(scene, [0, 3], 16, 32, 45, 9)
+    B, K = rays.shape[0], 96
+    groups, grid = -(-B // (256 // K)), -(-(-(-B // 4)) // 8) * 8     # render_grid: a work-group per 4 rays, rounded up to 8
+    assert B == 45 and groups > max(8, -(-B // 4)) and groups > grid, (B, groups, grid)
+    z = bts.native.sample_coarse(rays, torch.rand((B, K), generator=torch.Generator().manual_seed(10)).cuda(), True)
+    r = bts.NeRFRenderer(n_coarse=K, lindisp=True, hard_alpha_cap=True).cuda().eval()
+    _render_both(comp, nat, r, rays, z, 1, 3)
+
+
 def test_white_background_and_density_noise_vs_composition():
     comp, nat, scene = _pair((64, 64, 0), (16, 32), 2, 6, ENC3, seed=24, train=True)
     rays = _interior_rays(scene, [0, 3], 16, 32, 45, 7)

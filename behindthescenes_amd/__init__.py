@@ -24,7 +24,9 @@ from .novel_views import FusedNovelViews, color_tensor, colorize_u8, pack_u8, re
 from . import automask  # noqa: F401
 from .automask import automask_errors, automask_images  # noqa: F401
 from . import train_vis  # noqa: F401
+from . import image_processor  # noqa: F401
+from .image_processor import PatchProcessor, RGBProcessor, make_image_processor  # noqa: F401
 from .train_vis import vis_panels, visualize  # noqa: F401
 
 __all__ = ["BTSNet", "NeRFRenderer", "PositionalEncoding", "ResnetFC", "ResnetBlockFC", "make_mlp", "make_backbone",
-           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "FusedDepthEval", "compute_depth_metrics", "depth_metrics", "FusedNVSEval", "compute_nvs_metrics", "nvs_metrics", "FusedBBoxOccupancyEval", "bbox_occupancy", "FusedNovelViews", "color_tensor", "colorize_u8", "pack_u8", "render_poses", "novel_views", "automask", "automask_errors", "automask_images", "train_vis", "vis_panels", "visualize", "BtsNativeError"]
+           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "FusedDepthEval", "compute_depth_metrics", "depth_metrics", "FusedNVSEval", "compute_nvs_metrics", "nvs_metrics", "FusedBBoxOccupancyEval", "bbox_occupancy", "FusedNovelViews", "color_tensor", "colorize_u8", "pack_u8", "render_poses", "novel_views", "automask", "automask_errors", "automask_images", "train_vis", "vis_panels", "visualize", "image_processor", "make_image_processor", "RGBProcessor", "PatchProcessor", "BtsNativeError"]

@@ -189,6 +189,15 @@ class BtsTrainVis(C.Structure):
                [("workspace_bytes", C.c_size_t)]
 
 
+BTS_PATCH_COLOR_SIZE = 3
+BTS_PATCH_COLOR_CHANNELS = 27
+
+
+class BtsPatchColor(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n", "nv", "H", "W", "K", "patch", "white_bkgd", "reserved_")] + [("rays_per_sample", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("rays", "z_samp", "weights", "imgs_nhwc4", "K_r", "w2c_r", "rgb", "rgb_samps")]
+
+
 BTS_LIDAR_MAX_CLOUDS = 32
 BTS_BBOX_MAX_BOXES = 4096
 BTS_BBOX_MAX_VERTS = 64
@@ -235,6 +244,9 @@ SYMBOLS = {
     # the per-pixel criteria l1 / l2, median thresholding, the diverse flags (csrc/bts_loss_pixel.hip)
     "bts_pixel_loss_workspace": (C.c_size_t, [C.c_int64, _I, _I, _I]),
     "bts_pixel_loss": (C.c_int, [C.POINTER(BtsPixelLossArgs), _P, C.c_size_t, _P]),
+    # the criteria l1 / l2 for a run-time channel count (csrc/bts_loss_pixel_c.hip)
+    "bts_pixel_loss_channels_workspace": (C.c_size_t, [C.c_int64]),
+    "bts_pixel_loss_channels": (C.c_int, [C.POINTER(BtsPixelLossArgs), _I, _P, C.c_size_t, _P]),
     "bts_loss_diverse_flags": (C.c_int, [_P, _P, _P, C.c_int64, _I, _I, _P, _P]),
     # auto-masking: the error map (csrc/bts_automask.hip) and the three loss entry points with the per-ray bound `thresh`
     "bts_automask_errors": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, C.c_float, _P, _P, _P]),
@@ -303,6 +315,10 @@ SYMBOLS = {
     # the trainer's visualisation panels (models/bts/trainer.py:430-506)
     "bts_train_vis_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "bts_train_vis": (C.c_int, [C.POINTER(BtsTrainVis), _P]),
+    # patch colours (image_processor {type: patch}): the 27-channel rgb from the render's weights, its backward, the point query
+    "bts_patch_color_fwd": (C.c_int, [C.POINTER(BtsPatchColor), _P]),
+    "bts_patch_color_bwd": (C.c_int, [C.POINTER(BtsPatchColor), _P, _P, _P]),
+    "bts_patch_color_query": (C.c_int, [C.POINTER(BtsPatchColor), _P, _I, _P, _P]),
 }
 
 _lock = threading.Lock()

@@ -413,6 +413,45 @@ int bts_pixel_loss_automask(const BtsPixelLossArgs* a, const float* thresh, void
   if (int rc = check_thresh(thresh, who)) return rc;
   return pixel_loss_entry(a, thresh, workspace, workspace_bytes, stream, who);
 }
+size_t bts_pixel_loss_channels_workspace(int64_t B) { return B > 0 && B <= (1L << 29) ? pixel_loss_channels_bytes((long)B) : 0; }
+int bts_pixel_loss_channels(const BtsPixelLossArgs* a, int32_t channels, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char who[] = "bts_pixel_loss_channels";
+  if (!a || !a->rgb || !a->rgb_gt || !a->out) {
+    set_error("%s: NULL required pointer (args, rgb, rgb_gt, out)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->B <= 0 || a->nv <= 0) {
+    set_error("%s: non-positive size (B, nv)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->B > (1L << 29)) {
+    set_error("%s: %ld rays are more than 2^29", who, (long)a->B);
+    return BTS_E_INVALID;
+  }
+  if (channels < 1 || channels > BTS_PIXEL_LOSS_MAX_CHANNELS) {
+    set_error("%s: %ld channels are outside [1, %ld]", who, (long)channels, (long)BTS_PIXEL_LOSS_MAX_CHANNELS);
+    return BTS_E_INVALID;
+  }
+  if (a->criterion != 1 && a->criterion != 2) {
+    set_error("%s: unknown criterion %ld (1 = l1, 2 = l2)", who, (long)a->criterion);
+    return BTS_E_INVALID;
+  }
+  if (a->invalid_policy < 0 || a->invalid_policy > 3) {
+    set_error("%s: unknown invalid_policy %ld", who, (long)a->invalid_policy);
+    return BTS_E_INVALID;
+  }
+  if (a->median_thresholding || a->invalid_policy == 3 || a->edge_aware_smoothness) {
+    set_error("%s: median_thresholding, weight_guided_diverse and edge_aware_smoothness are served for 3 channels only (bts_pixel_loss)", who);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (int rc = check_policy_inputs(a->invalid_policy, a->invalid_any, a->invalid_wsum, a->invalid, a->weights, a->K, who)) return rc;
+  const size_t need = pixel_loss_channels_bytes((long)a->B);
+  if (!workspace || workspace_bytes < need) {
+    set_error("%s: workspace too small (%ld bytes needed, see bts_pixel_loss_channels_workspace)", who, (long)need);
+    return BTS_E_INVALID;
+  }
+  return launched(pixel_loss_channels_impl(a, channels, workspace, (hipStream_t)stream), who);
+}
 size_t bts_loss_regularisers_workspace(int64_t B, int32_t n_patches, int32_t patch_h, int32_t patch_w, int32_t K) {
   if (K < 2 || K > 256 || B > (1L << 29)) return 0;
   return loss_reg_bytes((long)B, n_patches, patch_h, patch_w, K);
@@ -1190,6 +1229,84 @@ int bts_train_vis(const BtsTrainVis* a, void* stream) {
     return BTS_E_WORKSPACE;
   }
   return launched(train_vis_launch(a, (hipStream_t)stream), who);
+}
+
+// ---- patch colours (image_processor {type: patch}): what the three entries share -- the struct, the frames and cameras, the sizes, the
+// compiled patch size; rays: the entry reads rays, z_samp, K and rays_per_sample
+static bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+static int check_patch_color(const BtsPatchColor* a, bool rays, const char* who) {
+  if (!a) {
+    set_error("%s: NULL argument struct", who);
+    return BTS_E_INVALID;
+  }
+  if (!a->imgs_nhwc4 || !a->K_r || !a->w2c_r || (rays && (!a->rays || !a->z_samp))) {
+    set_error("%s: NULL pointer among imgs_nhwc4, K_r, w2c_r (and rays, z_samp where the entry reads them)", who);
+    return BTS_E_INVALID;
+  }
+  if (misaligned(a->imgs_nhwc4, 16) || misaligned(a->K_r, 4) || misaligned(a->w2c_r, 4) || (rays && (misaligned(a->rays, 4) || misaligned(a->z_samp, 4)))) {
+    set_error("%s: misaligned pointer (imgs_nhwc4 needs 16 bytes, every other tensor 4)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->n <= 0 || a->nv <= 0 || a->H <= 0 || a->W <= 0 || (rays && (a->K <= 0 || a->rays_per_sample <= 0))) {
+    set_error("%s: non-positive size (n, nv, H, W; K and rays_per_sample where the entry reads them)", who);
+    return BTS_E_INVALID;
+  }
+  if (a->nv > BTS_MAX_VIEWS) {
+    set_error("%s: nv=%ld render views exceed BTS_MAX_VIEWS = %ld", who, (long)a->nv, (long)BTS_MAX_VIEWS);
+    return BTS_E_INVALID;
+  }
+  if ((long)a->H * a->W > (1L << 30)) {
+    set_error("%s: a frame of H=%ld x W=%ld texels is more than 2^30", who, (long)a->H, (long)a->W);
+    return BTS_E_INVALID;
+  }
+  if (!patch_color_size_ok(a->patch)) {
+    set_error("%s: patch=%ld, but the compiled patch size is %ld (27 channels)", who, (long)a->patch, (long)BTS_PATCH_COLOR_SIZE);
+    return BTS_E_UNSUPPORTED;
+  }
+  return BTS_OK;
+}
+static int check_patch_color_io(const void* in, const void* out, const char* names, const char* who) {
+  char fmt[128];
+  if (!in || !out) {
+    snprintf(fmt, sizeof(fmt), "%%s: NULL pointer among %s", names);
+    set_error(fmt, who);
+    return BTS_E_INVALID;
+  }
+  if (misaligned(in, 4) || misaligned(out, 4)) {
+    snprintf(fmt, sizeof(fmt), "%%s: misaligned pointer among %s (4 bytes)", names);
+    set_error(fmt, who);
+    return BTS_E_INVALID;
+  }
+  return BTS_OK;
+}
+
+int bts_patch_color_fwd(const BtsPatchColor* a, void* stream) {
+  const char* who = "bts_patch_color_fwd";
+  if (int rc = check_patch_color(a, true, who)) return rc;
+  if (int rc = check_patch_color_io(a->weights, a->rgb, "weights, rgb", who)) return rc;
+  if (misaligned(a->rgb_samps, 4)) {
+    set_error("%s: misaligned pointer rgb_samps (4 bytes)", who);
+    return BTS_E_INVALID;
+  }
+  return patch_color_fwd_impl(a, (hipStream_t)stream);
+}
+
+int bts_patch_color_bwd(const BtsPatchColor* a, const float* g_rgb, float* g_weights, void* stream) {
+  const char* who = "bts_patch_color_bwd";
+  if (int rc = check_patch_color(a, true, who)) return rc;
+  if (int rc = check_patch_color_io(g_rgb, g_weights, "g_rgb, g_weights", who)) return rc;
+  return patch_color_bwd_impl(a, g_rgb, g_weights, (hipStream_t)stream);
+}
+
+int bts_patch_color_query(const BtsPatchColor* a, const float* xyz, int32_t P, float* rgb, void* stream) {
+  const char* who = "bts_patch_color_query";
+  if (int rc = check_patch_color(a, false, who)) return rc;
+  if (int rc = check_patch_color_io(xyz, rgb, "xyz, rgb", who)) return rc;
+  if (P <= 0) {
+    set_error("%s: non-positive point count P=%ld", who, (long)P);
+    return BTS_E_INVALID;
+  }
+  return patch_color_query_impl(a, xyz, P, rgb, (hipStream_t)stream);
 }
 
 }  // extern "C"

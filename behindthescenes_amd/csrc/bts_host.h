@@ -101,6 +101,9 @@ int photometric_loss_median_impl(const BtsLossArgs* a, int n, const float* thres
 // ---- bts_loss_pixel.hip: criteria l1 / l2, median thresholding, the diverse flags
 size_t pixel_loss_bytes(long B, int n, int ph, int pw);
 int pixel_loss_impl(const BtsPixelLossArgs* a, void* workspace, hipStream_t s, const float* thresh = nullptr);
+// ---- bts_loss_pixel_c.hip: criteria l1 / l2 for a run-time channel count
+size_t pixel_loss_channels_bytes(long B);
+int pixel_loss_channels_impl(const BtsPixelLossArgs* a, int channels, void* workspace, hipStream_t s);
 // ---- bts_loss_reg.hip: the alpha / surfaceness / entropy / depth regularisers
 size_t loss_reg_bytes(long B, int n_patches, int ph, int pw, int K);
 int loss_reg_impl(const BtsLossRegArgs* a, void* workspace, hipStream_t s);
@@ -119,6 +122,12 @@ int mlp_color_field_query_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t,
 size_t mlp_color_bwd_workspace_impl(const BtsFieldCfg* cfg, const BtsRenderArgs* a);
 int mlp_color_render_bwd_impl(const BtsFieldCfg* cfg, const BtsFieldTensors* t, const BtsRenderArgs* a, const BtsRenderGrads* g, void* workspace,
                               hipStream_t s);
+
+// ---- bts_patch_color.hip: 27-channel patch colours from the render's weights
+bool patch_color_size_ok(int patch);
+int patch_color_fwd_impl(const BtsPatchColor* a, hipStream_t s);
+int patch_color_bwd_impl(const BtsPatchColor* a, const float* g_rgb, float* g_weights, hipStream_t s);
+int patch_color_query_impl(const BtsPatchColor* a, const float* xyz, int P, float* rgb, hipStream_t s);
 
 // ---- bts_multi_view.hip: merged encoder views (the field is checked by bts_api.hip before any of these runs)
 int multi_view_render_fwd_impl(const BtsMultiViewField* mv, const BtsRenderArgs* a, hipStream_t s);

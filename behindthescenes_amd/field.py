@@ -60,6 +60,10 @@ class BTSNet(nn.Module):
         # as well (measured on one MI355X, README "Merged encoder views": 9.7 x the composition forward + backward at 8 x 2 048 rays, 17.6 x
         # forward on a 192 x 640 frame; the encoder then sees its batch view-major)
         self.native_multi_view = bool(conf.get("native_multi_view", False))
+        # image_processor {type: patch}: a 27-channel images_alt is DECLARED to be image_processor.PatchProcessor(3)'s output of `images`
+        # (nothing checks it) and is rendered by the bts_patch_color_* kernels from the packed RGB frames; opt-in
+        self.native_patch_color = bool(conf.get("native_patch_color", False))
+        self._patch = 0               # set by encode(): 3 when the colour grid is PatchProcessor(3)'s, else 0
         if self.return_sample_depth:
             raise NotImplementedError("return_sample_depth is not used by any shipped config")
 
@@ -172,6 +176,7 @@ class BTSNet(nn.Module):
         if ids_encoder is None:
             ids_encoder = list(range(images.shape[1]))
         self._combined = combine_ids is not None or len(ids_encoder) != 1
+        self._patch = self._patch_of(images_alt)       # (raises where 27 channels cannot be served, before anything is computed)
         # (the PyTorch-composed modes also run where torch runs; everything else is HIP and says so loudly on a CPU tensor)
         poses_w2c = torch.inverse(poses_c2w) if (self.torch_mode and not poses_c2w.is_cuda) else native.invert_small(poses_c2w)
         images_encoder, Ks_encoder, poses_w2c_encoder = _take(images, ids_encoder), _take(Ks, ids_encoder), _take(poses_w2c, ids_encoder)
@@ -229,6 +234,10 @@ class BTSNet(nn.Module):
             # automasking: images_alt carries the error map as a fourth channel (automask.automask_images); the renderer samples the three
             # colours -- grid_c_imgs keeps all four, as the reference's does
             rgb_src = src[:, :, :3] if (colours is not None and src.shape[2] == 4) else src
+            if self._patch:
+                # patch colours: the centre triple (channels 12..14) IS the processed frame, already in [0, 1]; the kernels form the other
+                # 24 channels from it by the double clamp -- grid_c_imgs keeps all 27, as the reference's does
+                rgb_src = src[:, :, 12:15]
             self._imgs_nhwc4 = native.pack_rgb(rgb_src.detach().float().contiguous(), scale, shift)
             self._K_r = self.grid_c_Ks.detach().float().contiguous()
             self._w2c_r = self.grid_c_poses_w2c.detach().float().contiguous()
@@ -243,6 +252,21 @@ class BTSNet(nn.Module):
         # second projection (BtsFieldCfg.enc_render_view)
         ids_r, id_e = [int(i) for i in ids_render], int(ids_encoder[0])
         self._enc_view = ids_r.index(id_e) if (id_e in ids_r and not self.multi_view) else -1
+
+    def _patch_of(self, colours):
+        """3 when ``images_alt`` carries PatchProcessor(3)'s 27 channels and this field serves them, 0 for three (or automasking's four)
+        channels; raises where 27 channels cannot be served."""
+        if colours is None or colours.shape[2] != 27:
+            return 0
+        if not self.native_patch_color:
+            raise NotImplementedError("a 27-channel images_alt (image_processor {type: patch}) needs the model-config key native_patch_color: true; "
+                                      "the frames are then taken to be PatchProcessor(3)'s output and rendered by the bts_patch_color_* kernels")
+        if not self.sample_color:
+            raise NotImplementedError("patch colours with sample_color: false: the MLP predicts the colour and no colour frames are sampled")
+        if self._combined:
+            raise NotImplementedError("patch colours with merged encoder views (combine_ids / several ids_encoder: native_multi_view picks colours "
+                                      "per view group, the torch-composed mode samples every channel of grid_c_imgs) are not served")
+        return 3
 
     @staticmethod
     def _view_groups(n_frames, ids_encoder, ids_render, combine_ids):
@@ -288,6 +312,7 @@ class BTSNet(nn.Module):
         self._native = {}
         self._latents_ms = self._shift_ms = self._grid_f_features = self._latents_mv = None
         self._grid_c_src = None
+        self._patch = 0
 
     def native_field(self, coarse=True, sampled=None) -> "native.FieldTensors":
         """Field state of the current scale in the C-ABI layouts.  The projected feature map G = F . w_in[:, :C]^T is built lazily
@@ -308,6 +333,9 @@ class BTSNet(nn.Module):
         if self.multi_view:
             return self._native_multi_view(s, fine, mlp, spec)
         if sampled is not None:
+            if self._patch:
+                raise native.BtsNativeError("the sparse one-shot projection serves the lean training render, which has no weights to hand on: "
+                                            + native.PATCH_COLOR_MESSAGE)
             rays, z_samp, jitter, lindisp = sampled
             f = self._latents_ms[s]
             f = f.reshape(f.shape[0], *f.shape[2:]).float()
@@ -321,7 +349,7 @@ class BTSNet(nn.Module):
             proj = native.ProjectFunction.apply(f, mlp.packed(), spec, link, tiles)
             ft = native.FieldTensors(spec, proj, self._K_enc, self._w2c_enc, self._imgs_nhwc4, self._K_r, self._w2c_r,
                                      self.empty_feature if self.learn_empty else None, feat_shift=self._shift_ms[s], enc_view=self._enc_view)
-            ft.proj_link = link
+            ft.proj_link, ft.patch = link, self._patch
             ft.partial = (rays.data_ptr(), rays.shape[0])     # valid for THIS sample set only (native.FieldTensors.partial)
             return ft
         version = (mlp.lin_in.weight._version, torch.is_grad_enabled())
@@ -334,7 +362,7 @@ class BTSNet(nn.Module):
             proj = native.ProjectFunction.apply(f, mlp.packed(), spec, link)
             ft = native.FieldTensors(spec, proj, self._K_enc, self._w2c_enc, self._imgs_nhwc4, self._K_r, self._w2c_r,
                                      self.empty_feature if self.learn_empty else None, feat_shift=self._shift_ms[s], enc_view=self._enc_view)
-            ft.proj_link = link
+            ft.proj_link, ft.patch = link, self._patch
             self._native[(s, fine)] = (ft, version)
         return self._native[(s, fine)][0]
 
@@ -355,7 +383,7 @@ class BTSNet(nn.Module):
         return self._native[(s, fine)][0]
 
     def forward(self, xyz, coarse=True, viewdirs=None, far=False, only_density=False):
-        """xyz (n, P, 3) world points -> rgb (n,P,nv*3), invalid (n,P,nv) float, sigma (n,P,1)  (models_bts.py:266-338).
+        """xyz (n, P, 3) world points -> rgb (n,P,nv*3) (nv*27 with patch colours), invalid (n,P,nv) float, sigma (n,P,1)  (models_bts.py:266-338).
         Forward-only (the reference's callers of this entry point -- occupancy profiles, LiDAR / 3D-bbox evaluators -- run it
         under no_grad); training goes through the renderer's composite, which is differentiable."""
         if self.torch_mode:
@@ -370,6 +398,10 @@ class BTSNet(nn.Module):
             rgb, invalid, sigma = native.field_query(ft, self.mlp(coarse).packed().detach(), xyz.detach().float().contiguous(),
                                                      only_density=only_density)
         nv = 1 if self.spec.mlp_color else ft.nv
+        if self._patch and not only_density:
+            # the points' 27 colours per view (bts_patch_color_query); density and flags are bts_field_query's above
+            with torch.no_grad():
+                rgb = native.patch_color_query(ft, xyz.detach().float().contiguous(), self._patch)
         if only_density:
             rgb = torch.zeros((xyz.shape[0], xyz.shape[1], nv * 3), device=sigma.device)
             invalid = invalid.unsqueeze(1)   # the reference returns (n, nv_enc=1, P, 1) here (models_bts.py:337)

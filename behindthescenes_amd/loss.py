@@ -74,6 +74,12 @@ def _pixel_terms(rgb, depth, need_grad, kw):
     return out[:3], g_rgb, g_depth
 
 
+def _pixel_c_terms(rgb, depth, need_grad, kw):
+    """l1 / l2 on other than 3 colour channels: the rgb term arrives normalised by C B; no smoothness term"""
+    out, g_rgb = native.pixel_loss_channels(rgb, need_grad=need_grad, **kw)
+    return out[:3], g_rgb, None
+
+
 def _reg_terms(alphas, depth, need_grad, kw):
     """one scale's regularisers as one (6,) tensor: [alpha_reg, surfaceness, entropy, depth term, invalid rays, reg = sum_t coef_t term_t]"""
     _, _, g_alphas, g_depth, out = native.loss_regularisers_packed(alphas, depth, need_grad=need_grad, **kw)
@@ -202,7 +208,7 @@ class ReconstructionLoss:
     def _split_gt(self, rgb_gt):
         """-> (colours (B, 3), threshold (B) | None): with automasking the fourth channel of rgb_gt is the per-ray bound (loss.py:139-143)"""
         if not self.use_automasking:
-            return _flat(rgb_gt, (3,)).detach(), None
+            return _flat(rgb_gt, (rgb_gt.shape[-1],)).detach(), None      # (3; C of a processed target, image_processor.PatchProcessor's 27)
         if rgb_gt.shape[-1] != 4:
             raise ValueError(f"use_automasking=True reads the error map as rgb_gt's fourth channel (automask.automask_images, a sampler "
                              f"with channels=4); got rgb_gt with {rgb_gt.shape[-1]} channels")
@@ -259,10 +265,33 @@ class ReconstructionLoss:
         rgb = level["rgb"]                                   # (n, pc, h, w, nv, 3)
         n, pc, h, w, nv, c = rgb.shape
         if c != 3:
-            raise NotImplementedError("the HIP loss takes 3 colour channels")
+            return self._terms_channels(level, level0, gt, eas)
         policy, masks = self._mask_inputs(level0, per_sample)
         kw.update(masks, rgb_gt=rgb_gt, patch_h=h, patch_w=w, invalid_policy=policy, eas=eas, thresh=thresh)
         terms = _NativeTerms.apply(fn, (0, 1), _flat(rgb, (nv * 3,)), _flat(level["depth"], ()) if eas else None, kw)
+        return terms, n * pc * h * w
+
+    def _terms_channels(self, level, level0, gt, eas):
+        """_terms for other than 3 colour channels (the 27 of image_processor {type: patch}): criterion l1 / l2 on bts_pixel_loss_channels
+        under none / strict / weight_guided; every other option names itself"""
+        rgb_gt, thresh = gt
+        rgb = level["rgb"]
+        n, pc, h, w, nv, c = rgb.shape
+        what = f"on {c} colour channels is not served (the HIP loss takes it on 3; on C channels: criterion l1 / l2, invalid_policy none / strict / weight_guided)"
+        if not self.pixel_criterion:
+            raise NotImplementedError(f"criterion 'l1+ssim' {what}")
+        if self.median_thresholding:
+            raise NotImplementedError(f"median_thresholding {what}")
+        if self.diverse:
+            raise NotImplementedError(f"invalid_policy 'weight_guided_diverse' {what}")
+        if self.use_automasking or thresh is not None:
+            raise NotImplementedError(f"use_automasking {what}")
+        if eas:
+            raise NotImplementedError(f"lambda_edge_aware_smoothness > 0 {what}; the reference itself raises there: its edge_aware_smoothness "
+                                      "reshapes the target to 3 channels")
+        policy, masks = self._mask_inputs(level0)
+        kw = dict(masks, rgb_gt=rgb_gt, criterion=self.criterion_str, invalid_policy=policy)
+        terms = _NativeTerms.apply(_pixel_c_terms, (0, 1), _flat(rgb, (nv * c,)), None, kw)
         return terms, n * pc * h * w
 
     def _sums(self, level, level0, gt, eas):

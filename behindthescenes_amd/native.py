@@ -307,6 +307,37 @@ def pixel_loss(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch
     return out, thresholds, kept, g_rgb, g_depth
 
 
+PIXEL_LOSS_MAX_CHANNELS = 27
+
+
+def pixel_loss_channels(rgb, rgb_gt, weights, invalid, criterion: str, invalid_policy, scale_rgb: float = 1.0, need_grad: bool = True,
+                        invalid_wsum=None, invalid_any=None):
+    """Criterion "l1" / "l2" for C colour channels, 1 <= C <= 27 (bts_pixel_loss_channels, csrc/bts_loss_pixel_c.hip): rgb (B, nv*C),
+    rgb_gt (B, C), weights (B, K) | None, invalid (B, K, nv) | None (or the renderer's per-ray reductions), invalid_policy none / strict /
+    weight_guided -> out (4) = [rgb term = sum e / (B C), 0, invalid rays, B C], g_rgb (B, nv*C) | None = scale_rgb * d out[0] / d rgb."""
+    if criterion not in PIXEL_CRITERIA:
+        raise BtsNativeError(f"pixel_loss_channels: criterion {criterion!r} is not one of {sorted(PIXEL_CRITERIA)}")
+    if invalid_policy not in PIXEL_POLICIES or PIXEL_POLICIES[invalid_policy] == 3:
+        raise BtsNativeError(f"pixel_loss_channels: invalid_policy {invalid_policy!r} is not one of none / strict / weight_guided")
+    _req(rgb_gt, "rgb_gt")
+    B, ch = rgb_gt.shape
+    if not 1 <= ch <= PIXEL_LOSS_MAX_CHANNELS or rgb.shape[-1] % ch:
+        raise BtsNativeError(f"pixel_loss_channels: rgb_gt has {ch} channels (1 .. {PIXEL_LOSS_MAX_CHANNELS}), rgb {rgb.shape[-1]} per ray")
+    nv = rgb.shape[-1] // ch
+    _req(rgb, "rgb", (B, nv * ch))
+    policy, K, nv, masks = _invalid_inputs(invalid_policy, PIXEL_POLICIES, B, weights, invalid, invalid_wsum, invalid_any, None, nv)
+    dev = rgb.device
+    out = torch.empty((4,), device=dev, dtype=torch.float32)
+    g_rgb = torch.empty_like(rgb) if need_grad else None
+    a = _lib.BtsPixelLossArgs(rgb=rgb.data_ptr(), rgb_gt=rgb_gt.data_ptr(), **{name: _addr(t) for name, t in masks.items()}, out=out.data_ptr(),
+                              g_rgb=_addr(g_rgb), B=B, n=1, patch_h=1, patch_w=1, nv=nv, K=K, criterion=PIXEL_CRITERIA[criterion],
+                              invalid_policy=policy, scale_rgb=scale_rgb, scale_eas=0.0)
+    lib = _lib.load()
+    ws = _scratch(dev, lib.bts_pixel_loss_channels_workspace(B))
+    _lib.check(lib.bts_pixel_loss_channels(C.byref(a), ch, ws.data_ptr(), ws.numel(), _stream(rgb)), "bts_pixel_loss_channels")
+    return out, g_rgb
+
+
 def photometric_loss_median(rgb, depth, weights, invalid, rgb_gt, n: int, patch_h: int, patch_w: int, invalid_policy, eas: bool,
                             scale_rgb: float = 1.0, scale_eas: float = 1.0, need_grad: bool = True, invalid_wsum=None, invalid_any=None,
                             thresh=None, parts=None):
@@ -682,6 +713,9 @@ class FieldTensors:
         # sampled=...): only the tiles those samples read were projected, the rest of proj_nhwc is uninitialised memory), else None.
         # field_query / occupancy_profile reject a partial map, render_fwd / render_bwd check the sample set.
         self.partial = None
+        # 3 when the frames stand for PatchProcessor(3)'s 27-channel output (BTSNet native_patch_color): the colours then come from the
+        # bts_patch_color_* entries behind the render (PatchColorFunction); 0 = the frames' own three channels
+        self.patch = 0
 
     @property
     def mlp_color(self) -> bool:
@@ -981,6 +1015,87 @@ def field_query(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Tensor, o
     _lib.check(_lib.load().bts_field_query(C.byref(cfg), C.byref(tens), _ptr(xyz), P, int(only_density), _ptr(rgb), _ptr(invalid),
                                            _ptr(sigma), _stream(xyz)), "bts_field_query")
     return rgb, invalid, sigma
+
+
+# --------------------------------------------------------------------------------------------------------------
+# patch colours (image_processor {type: patch}): 27 channels per render view from the render's weights
+# --------------------------------------------------------------------------------------------------------------
+PATCH_COLOR_MESSAGE = ("patch colours (native_patch_color: a 27-channel images_alt) are rendered by the entry-by-entry path only: the render "
+                       "kernels, then bts_patch_color_fwd / _bwd on their weights")
+
+
+def _patch_color_struct(ft, patch, rays=None, z_samp=None, weights=None, white_bkgd=False, rgb=None, rgb_samps=None):
+    if ft.imgs_nhwc4 is None or ft.nv < 1:
+        raise BtsNativeError("patch colours need the packed colour frames and the render cameras (nv >= 1)")
+    B, K = z_samp.shape if z_samp is not None else (0, 0)
+    return _lib.BtsPatchColor(n=ft.n, nv=ft.nv, H=ft.H, W=ft.W, K=K, patch=int(patch), white_bkgd=int(bool(white_bkgd)), reserved_=0,
+                              rays_per_sample=B // ft.n, rays=_addr(rays), z_samp=_addr(z_samp), weights=_addr(weights),
+                              imgs_nhwc4=_addr(ft.imgs_nhwc4), K_r=_addr(ft.K_r), w2c_r=_addr(ft.w2c_r), rgb=_addr(rgb), rgb_samps=_addr(rgb_samps))
+
+
+def _patch_color_rays(ft, rays, z_samp):
+    B, K = z_samp.shape
+    _req(rays, "rays", (B, 8)), _req(z_samp, "z_samp")
+    if B % ft.n != 0:
+        raise BtsNativeError(f"{B} rays do not split evenly over n={ft.n} samples")
+    return B, K
+
+
+def patch_color_fwd(ft: FieldTensors, rays, z_samp, weights, *, white_bkgd=False, want_rgb_samps=False, patch=3):
+    """rays (B, 8), z_samp / weights (B, K) of a render of ``ft`` -> rgb (B, nv * 27), rgb_samps (B, K, nv * 27) | None
+    (bts_patch_color_fwd): rgb = sum_k weights * the double-clamp colours (+ 1 - sum weights with white_bkgd)."""
+    B, K = _patch_color_rays(ft, rays, z_samp)
+    _req(weights, "weights", (B, K))
+    ch = ft.nv * _lib.BTS_PATCH_COLOR_CHANNELS
+    rgb = torch.empty((B, ch), device=rays.device, dtype=torch.float32)
+    rgb_samps = torch.empty((B, K, ch), device=rays.device, dtype=torch.float32) if want_rgb_samps else None
+    a = _patch_color_struct(ft, patch, rays, z_samp, weights, white_bkgd, rgb, rgb_samps)
+    _lib.check(_lib.load().bts_patch_color_fwd(C.byref(a), _stream(rays)), "bts_patch_color_fwd")
+    return rgb, rgb_samps
+
+
+def patch_color_bwd(ft: FieldTensors, rays, z_samp, g_rgb, *, white_bkgd=False, patch=3):
+    """g_rgb (B, nv * 27) -> g_weights (B, K) = sum_{v, ch} g_rgb * colour (- sum g_rgb with white_bkgd)  (bts_patch_color_bwd)."""
+    B, K = _patch_color_rays(ft, rays, z_samp)
+    _req(g_rgb, "g_rgb", (B, ft.nv * _lib.BTS_PATCH_COLOR_CHANNELS))
+    g_weights = torch.empty((B, K), device=rays.device, dtype=torch.float32)
+    a = _patch_color_struct(ft, patch, rays, z_samp, None, white_bkgd)
+    _lib.check(_lib.load().bts_patch_color_bwd(C.byref(a), _ptr(g_rgb), _ptr(g_weights), _stream(rays)), "bts_patch_color_bwd")
+    return g_weights
+
+
+def patch_color_query(ft: FieldTensors, xyz, patch=3):
+    """xyz (n, P, 3) -> the points' colours in every render view, (n, P, nv * 27)  (bts_patch_color_query)."""
+    n, P, _ = xyz.shape
+    _req(xyz, "xyz", (ft.n, P, 3))
+    rgb = torch.empty((n, P, ft.nv * _lib.BTS_PATCH_COLOR_CHANNELS), device=xyz.device, dtype=torch.float32)
+    a = _patch_color_struct(ft, patch)
+    _lib.check(_lib.load().bts_patch_color_query(C.byref(a), _ptr(xyz), P, _ptr(rgb), _stream(xyz)), "bts_patch_color_query")
+    return rgb
+
+
+class PatchColorFunction(torch.autograd.Function):
+    """The 27-channel colours behind a render, chained after RenderFunction.  Differentiable input: ``weights`` (the render's);
+    differentiable output: rgb (B, nv * 27).  rgb_samps (B, K, nv * 27, or empty) carries no gradient.  Nothing per sample is saved: the
+    backward forms the taps again from rays and z_samp."""
+
+    @staticmethod
+    def forward(ctx, weights, ft: FieldTensors, rays, z_samp, white_bkgd, want_rgb_samps):
+        ctx.set_materialize_grads(False)
+        rgb, rgb_samps = patch_color_fwd(ft, rays, z_samp, weights.detach().contiguous(), white_bkgd=white_bkgd, want_rgb_samps=want_rgb_samps,
+                                         patch=ft.patch)
+        ctx.ft, ctx.white_bkgd = ft, white_bkgd
+        ctx.save_for_backward(rays, z_samp)
+        rs = rgb_samps if want_rgb_samps else rays.new_empty(0)
+        ctx.mark_non_differentiable(rs)
+        return rgb, rs
+
+    @staticmethod
+    def backward(ctx, g_rgb, _g_rs):
+        if g_rgb is None:
+            return (None,) * 6
+        rays, z_samp = ctx.saved_tensors
+        return (patch_color_bwd(ctx.ft, rays, z_samp, g_rgb.contiguous(), white_bkgd=ctx.white_bkgd, patch=ctx.ft.patch),) + (None,) * 5
 
 
 def occupancy_profile(ft: FieldTensors, mlp_params: torch.Tensor, xyz: torch.Tensor, levels: int, threshold: float = 8.0,

@@ -129,6 +129,8 @@ def _why_not(wrapped, sampler):
         return "a PyTorch-composed field mode (merged encoder views)"
     if getattr(net, "multi_view", False):
         return "more than one encoder view (native_multi_view renders entry by entry)"
+    if getattr(net, "_patch", 0) or sampler.channels == 27:
+        return native.PATCH_COLOR_MESSAGE
     if sampler.channels != 3 or sampler.height is None or sampler.width is None:
         return "the sampler needs height, width and three channels"
     src = getattr(net, "_grid_c_src", None)

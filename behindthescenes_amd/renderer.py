@@ -235,12 +235,21 @@ class NeRFRenderer(torch.nn.Module):
                 z_samp = z_out if z_out.numel() else None
             return (weights if want_weights else None, rgb, depth, alphas if want_alphas else None, invalid if want_invalid else None, z_samp,
                     rgb_samps if want_rgb_samps else None)
+        patch = getattr(ft, "patch", 0)
+        if patch and want_invalid_sums:
+            raise native.BtsNativeError("lean_training_outputs returns no weights: " + native.PATCH_COLOR_MESSAGE)
+        # patch colours: colours are linear in the weights, so the render runs as ever -- asked for its weights, and for its depths where it
+        # samples in-kernel -- and PatchColorFunction forms the 27-channel rgb (and rgb_samps) from them; the render's own 3-channel rgb is
+        # dropped, everything else goes through untouched
         rgb, depth, weights, alphas, invalid, rgb_samps, inv_wsum, inv_any, z_out = native.RenderFunction.apply(
             ft.proj_nhwc, mlp_params, empty, ft, rays, z_samp, bool(self.hard_alpha_cap), bool(self.white_bkgd),
-            bool(want_weights), bool(want_alphas), bool(want_rgb_samps), torch.is_grad_enabled(), bool(want_invalid), bool(want_invalid_sums),
-            None if sigma_noise is None else sigma_noise.float().contiguous(), jitter, bool(self.lindisp), bool(want_z))
+            bool(want_weights or patch), bool(want_alphas), bool(want_rgb_samps and not patch), torch.is_grad_enabled(), bool(want_invalid),
+            bool(want_invalid_sums), None if sigma_noise is None else sigma_noise.float().contiguous(), jitter, bool(self.lindisp),
+            bool(want_z or patch))
         if z_samp is None:
             z_samp = z_out if z_out.numel() else None
+        if patch:
+            rgb, rgb_samps = native.PatchColorFunction.apply(weights, ft, rays, z_samp.detach(), bool(self.white_bkgd), bool(want_rgb_samps))
         ret = (weights if want_weights else None, rgb, depth, alphas if want_alphas else None, invalid if want_invalid else None, z_samp,
                rgb_samps if want_rgb_samps else None)
         return ret + (inv_wsum, inv_any) if want_invalid_sums else ret
@@ -283,6 +292,8 @@ class NeRFRenderer(torch.nn.Module):
         if (self.lean_training_outputs and self.training and not self.using_fine and torch.is_grad_enabled() and not getattr(model, "torch_mode", False)
                 and not getattr(getattr(model, "spec", None), "mlp_color", False)   # (MLP-predicted colour: no per-ray invalid sums)
                 and not getattr(model, "multi_view", False)):                       # (nor merged encoder views)
+            if getattr(model, "_patch", 0):
+                raise native.BtsNativeError("lean_training_outputs returns no weights: " + native.PATCH_COLOR_MESSAGE)
             # in a training step nothing downstream of the renderer reads the per-sample tensors except the loss'
             # invalid-ray mask, and that only through sum_k weights * invalid / any_k invalid per view -- the render kernel's
             # epilogue emits exactly those (8 B per ray and view), and weights / alphas / invalid are neither written nor returned

@@ -228,6 +228,8 @@ class FusedTrainStep(torch.nn.Module):
             return "use_automasking (the one-call training step's loss pass has no per-pixel bound; the entries compute the error map)"
         if crit.invalid_policy not in native.INVALID_POLICIES:
             return f"invalid_policy {crit.invalid_policy}"
+        if getattr(net, "_patch", 0) or smp.channels == 27:
+            return native.PATCH_COLOR_MESSAGE
         if smp.channels != 3 or smp.patch_size_x * smp.patch_size_y > 64:
             return "patches of more than 64 pixels / other than 3 colour channels"
         if net.mlp_fine is not None or not net.native_scale_maps:
@@ -463,6 +465,8 @@ class FusedEvalFrame(torch.nn.Module):
         if not net.sample_color:
             # bts_eval_frame knows the sampled-colour field only; native_mlp_color renders entry by entry (bts_render_fwd_mlp_color)
             return "sample_color=False (MLP-predicted colours: the one-call eval frame serves sampled colours only)"
+        if getattr(net, "_patch", 0) or self.sampler.channels == 27:
+            return native.PATCH_COLOR_MESSAGE
         if net.torch_mode or net.mlp_fine is not None or net.get_scale() != 0 or (net.flip_augmentation and net.training):
             return "a PyTorch-composed field mode / a separate fine MLP / a scale other than 0 / flip augmentation"
         if len(ids_encoder) != 1 or len(ids_render) > _lib.BTS_MAX_VIEWS or self.sampler.channels != 3:

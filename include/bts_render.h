@@ -353,6 +353,19 @@ typedef struct {
 size_t bts_pixel_loss_workspace(int64_t B, int32_t n, int32_t patch_h, int32_t patch_w);
 int bts_pixel_loss(const BtsPixelLossArgs* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same criteria l1 / l2 for `channels` = C colour channels, 1 <= C <= 27 (csrc/bts_loss_pixel_c.hip; the colour targets of
+ * image_processor {type: patch} have 27): rgb (B, nv, C), rgb_gt (B, C), g_rgb (B, nv, C) of the same BtsPixelLossArgs,
+ *   e[ray, ch] = min_v crit(rgb[ray, v, ch] - gt[ray, ch]) * keep[ray],   out[0] = sum e / (B C),
+ * out = [rgb term, 0, number of invalid rays, B C as a float].  The keep flag, the per-channel minimum over the views, amin's equally
+ * shared ties, sign(0) = 0 and the fixed-order sums are bts_pixel_loss's; invalid_policy none / strict / weight_guided.  g_depth, when
+ * given, receives zeros (no term reads the depth).  n, patch_h, patch_w are not read.  NOT served, BTS_E_UNSUPPORTED with a message
+ * naming the option: median_thresholding, weight_guided_diverse, edge_aware_smoothness (the reference itself fails there on other than
+ * 3 channels: its edge_aware_smoothness reshapes the target to 3).  `workspace`: bts_pixel_loss_channels_workspace(B) bytes (8 bytes per
+ * 256 rays; any alignment; contents need not be initialised).  BTS_E_INVALID as bts_pixel_loss, and for C outside [1, 27]. */
+#define BTS_PIXEL_LOSS_MAX_CHANNELS 27
+size_t bts_pixel_loss_channels_workspace(int64_t B);
+int bts_pixel_loss_channels(const BtsPixelLossArgs* args, int32_t channels, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The per-(ray, view) flag of weight_guided_diverse (above) as 0 / 1 floats: rgb_samps (B, K, nv, 3), weights (B, K), invalid (B, K, nv)
  * -> flags (B, nv).  Criterion "l1+ssim" with weight_guided_diverse needs no kernel of its own: these flags, handed to
  * bts_photometric_loss / _tiled as invalid_any under the strict policy, give its all_v(flag > .5) -- the diverse rule.  BTS_E_INVALID for
@@ -1286,6 +1299,53 @@ typedef struct {
 /* 0 outside the limits above */
 size_t bts_train_vis_workspace(int32_t T, int32_t h, int32_t w, int32_t K);
 int bts_train_vis(const BtsTrainVis* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Patch colours: the trainer's `image_processor: {type: patch}` (models/bts/trainer.py:54-69, models/bts/model/image_processor.py:
+ * 69-93) on the render side.  PatchProcessor(3) turns every colour frame into 27 channels; encode(images_alt=...) makes them the colour
+ * grid, and the renderer's rgb becomes (..., nv * 27).  Additive to ABI 9: every struct and entry point above is unchanged.
+ *   channel order      channel (y * 3 + x) * 3 + c of the processed frame at pixel (i, j) is rgb[c] at row clamp(i + y - 1, 0, H - 1),
+ *                      column clamp(j + x - 1, 0, W - 1), y, x in 0..2 (y slowest, then x, then the colour c).
+ *   double clamp       the 27-channel frames are never formed.  A grid_sample(bilinear, border, align_corners=False) tap of them at a
+ *                      point whose four bilinear texels are rows y_0, y_1 and columns x_0, x_1 (already clamped into the frame) with weights
+ *                      w_ab is   colour[(y, x, c)] = sum_{a, b} w_ab * rgb0[clamp(y_a + y - 1), clamp(x_b + x - 1)].c   -- the texel is
+ *                      shifted and clamped AGAIN, not the coordinate.  imgs_nhwc4 are the renderer's packed frames (n, nv, H, W, 4) in [0, 1].
+ *   border behaviour   a sample outside a render view (or behind it) reads the clamped border colours, as padding_mode="border" does; the
+ *                      flags are the render's `invalid`, these entries write none.
+ * Colours are linear in the compositing weights: bts_render_fwd runs unchanged and hands its `weights` to bts_patch_color_fwd,
+ *   rgb[ray, v * 27 + ch] = sum_k weights[ray, k] * colour[ray, k, v, ch]  (+ 1 - sum_k weights[ray, k] with white_bkgd),
+ * and bts_patch_color_bwd returns g_weights[ray, k] = sum_{v, ch} g_rgb[ray, v * 27 + ch] * colour[ray, k, v, ch] (- sum g_rgb with
+ * white_bkgd) for bts_render_bwd's g_weights: WRITTEN, not accumulated; the taps are formed again, nothing per sample is saved.  A
+ * sample's position is the render kernels' (rays[0:3] + z * rays[3:6], the same projection routine).  fp32, fixed-order sums along the
+ * ray, no atomics: a rerun is bit-identical.  K is any positive sample count.
+ * bts_patch_color_query: the colours of n x P world points xyz (n, P, 3) -> rgb (n, P, nv * 27), BTSNet.forward(xyz)'s rgb; rays, z_samp,
+ * weights, K, rays_per_sample and white_bkgd are not read.
+ * Quirks of the reference that are kept ON PURPOSE:
+ *   - PatchProcessor pads by REPLICATION (F.pad mode="replicate"), hence the clamps;
+ *   - the centre triple, channels 12..14, is the ordinary processed frame: the 3-channel render's colours;
+ *   - colours are sampled for points outside the frustum as well (they are only flagged).
+ * BTS_E_INVALID with a message: NULL struct or required pointer, imgs_nhwc4 not 16-byte aligned or another pointer not 4-byte aligned,
+ * non-positive n, nv, H, W (K, rays_per_sample, P where read), nv above BTS_MAX_VIEWS.  BTS_E_UNSUPPORTED: patch != 3 (the one size
+ * that is compiled; an even size fails in the reference too), or more than 2^31 - 2^20 rays / points in one call.
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_PATCH_COLOR_SIZE 3
+#define BTS_PATCH_COLOR_CHANNELS 27
+typedef struct {
+  int32_t n, nv, H, W;             /* batch elements, render views, frame size */
+  int32_t K, patch, white_bkgd, reserved_;   /* samples per ray, patch size (3), rgb += 1 - sum(weights) */
+  int64_t rays_per_sample;         /* rays of one batch element: B = n * rays_per_sample */
+  const float* rays;               /* (B, 8) */
+  const float* z_samp;             /* (B, K) the render's depths */
+  const float* weights;            /* (B, K) the render's weights */
+  const float* imgs_nhwc4;         /* (n, nv, H, W, 4) rgb0 */
+  const float* K_r;                /* (n, nv, 3, 3) */
+  const float* w2c_r;              /* (n, nv, 4, 4) */
+  float* rgb;                      /* out (B, nv * 27); not read by _bwd / _query */
+  float* rgb_samps;                /* out (B, K, nv * 27) or NULL: the per-sample colours */
+} BtsPatchColor;
+int bts_patch_color_fwd(const BtsPatchColor* a, void* stream);
+int bts_patch_color_bwd(const BtsPatchColor* a, const float* g_rgb, float* g_weights, void* stream);
+int bts_patch_color_query(const BtsPatchColor* a, const float* xyz, int32_t P, float* rgb, void* stream);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,65 @@ def test_fused_step_equals_the_entry_by_entry_step(shape):
         assert err <= 2e-5, (shape, k, err)
 
 
+def test_hand_over_past_one_pack_trip_against_torch():
+    """n * nv * H * W = 18 * 4 * 96 * 320 = 2 211 840 packed pixels > 2048 x 1024: pack_rgb_body makes a second trip with the frame table
+    inside handover_kernel, as on every step of exp_kitti_360.yaml's batch.  Both routes of the step run that body, so the step's arena
+    is held against torch and against the single entry points instead: the packed frames, the cameras, the patch rays and colours --
+    bit for bit.  (kitti_mono's frame ids; the stand-in encoder's map is unsmoothed noise, 256 rays per sample: the step itself is small)"""
+    import behindthescenes_amd as bts
+    from behindthescenes_amd import native, synthetic as S, train_step as TS
+    cfg = dict(SHAPES["kitti_mono"], n=18, H=96, W=320)
+    n, V, H, W, nv = cfg["n"], cfg["V"], cfg["H"], cfg["W"], len(cfg["ids_render"])
+    assert n * nv * H * W > 2048 * 1024
+    dev = torch.device("cuda")
+    scene = S.synthetic_scene(n, V, H, W, 1, seed=5, baseline=0.4)                 # (its one-channel map is not used)
+    torch.manual_seed(11)
+    net = bts.BTSNet(S.field_conf(cfg["C"], cfg["HD"], cfg["NB"], H, W, z_near=cfg["z"][0], z_far=cfg["z"][1], code_mode=cfg["code_mode"]))
+    net.encoder = bts.FeatureMapEncoder((H, W), cfg["C"], num_views=n)
+    S.init_mlp_(net.mlp_coarse, seed=7)
+    net = net.to(dev).train()
+    renderer = bts.NeRFRenderer.from_conf(dict(n_coarse=cfg["K"], lindisp=True, hard_alpha_cap=True, lean_training_outputs=True)).to(dev).train()
+    sampler = bts.PatchRaySampler(ray_batch_size=cfg["rays"], z_near=cfg["z"][0], z_far=cfg["z"][1], patch_size=8)
+    crit = bts.ReconstructionLoss({"criterion": "l1+ssim", "invalid_policy": cfg["policy"], "lambda_edge_aware_smoothness": 0.001})
+    step = TS.FusedTrainStep(renderer.bind_parallel(net).train(), sampler, crit)
+    images, projs, poses = (scene[k].to(dev) for k in ("images", "projs", "poses"))
+    torch.manual_seed(3)
+    pv, py, px = sampler.draw_patches(n, len(cfg["ids_loss"]), H, W)
+    py[0, 0], px[0, 0], py[n - 1, -1], px[n - 1, -1] = H - 8, W - 8, H - 8, W - 8          # the last legal row / column, first and last sample
+    assert int(pv.max()) < len(cfg["ids_loss"]) and int(py.max()) + 8 <= H and int(px.max()) + 8 <= W and min(int(pv.min()), int(py.min()), int(px.min())) >= 0
+    TS.release_arenas()
+    with torch.no_grad():
+        loss, _, data = step(images, projs, poses, ids_encoder=[0], ids_render=cfg["ids_render"], ids_loss=cfg["ids_loss"], patches=(pv, py, px))
+    assert step.last_path == "fused" and bool(torch.isfinite(loss))
+    (arena,) = [a for pool in TS._ARENAS.values() for a in pool]
+    # the packed render frames: torch's two element-wise kernels, rgb0 layout
+    ip = images * .5 + .5
+    want = torch.zeros((n, nv, H, W, 4), device=dev)
+    want[..., :3] = ip[:, cfg["ids_render"]].permute(0, 1, 3, 4, 2)
+    assert arena.imgs.shape == want.shape and torch.equal(arena.imgs, want)
+    # the cameras: [K_enc (n, 9) | w2c_enc (n, 16) | K_r (n, nv, 9) | w2c_r (n, nv, 16)]
+    cams = arena.cams
+    o = [0]
+
+    def take(*shape):
+        count = 1
+        for s in shape:
+            count *= s
+        t = cams[o[0]:o[0] + count].view(*shape)
+        o[0] += count
+        return t
+    K_enc, w2c_enc, K_r, w2c_r = take(n, 3, 3), take(n, 4, 4), take(n, nv, 3, 3), take(n, nv, 4, 4)
+    assert o[0] == cams.numel()
+    assert torch.equal(K_enc, projs[:, 0]) and torch.equal(K_r, projs[:, cfg["ids_render"]])
+    assert torch.equal(w2c_enc, native.invert_small(poses[:, 0])) and torch.equal(w2c_r, native.invert_small(poses[:, cfg["ids_render"]]))
+    # the patch rays and colours: the single entry point on the same draws, over the loss frames of images * .5 + .5
+    ids_loss = cfg["ids_loss"]
+    rays, gt = native.patch_rays(poses[:, ids_loss].contiguous(), projs[:, ids_loss].contiguous(), ip[:, ids_loss].contiguous(),
+                                 pv.int().to(dev), py.int().to(dev), px.int().to(dev), 8, 8, cfg["z"][0], cfg["z"][1])
+    assert torch.equal(data["rays"], rays) and torch.equal(data["rgb_gt"].reshape(n, -1, 3), gt)
+    TS.release_arenas()
+
+
 def test_concurrent_scales_equal_serial_scales():
     """BtsTrainStep.concurrent_scales: the four scales' chains of an exp_re10k.yaml step on side queues of the library against the same
     chains one after the other -- identical forward bits, gradients to the order of the float atomics."""

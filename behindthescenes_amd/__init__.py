@@ -15,6 +15,8 @@ from . import lidar_occupancy  # noqa: F401
 from .lidar_occupancy import FusedOccupancyEval  # noqa: F401
 from . import depth_metrics  # noqa: F401
 from .depth_metrics import FusedDepthEval, compute_depth_metrics  # noqa: F401
+from . import lidar_depth  # noqa: F401
+from .lidar_depth import load_depth, load_depth_batch  # noqa: F401
 from . import nvs_metrics  # noqa: F401
 from .nvs_metrics import FusedNVSEval, compute_nvs_metrics  # noqa: F401
 from . import bbox_occupancy  # noqa: F401
@@ -29,4 +31,4 @@ from .image_processor import PatchProcessor, RGBProcessor, make_image_processor 
 from .train_vis import vis_panels, visualize  # noqa: F401
 
 __all__ = ["BTSNet", "NeRFRenderer", "PositionalEncoding", "ResnetFC", "ResnetBlockFC", "make_mlp", "make_backbone",
-           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "FusedDepthEval", "compute_depth_metrics", "depth_metrics", "FusedNVSEval", "compute_nvs_metrics", "nvs_metrics", "FusedBBoxOccupancyEval", "bbox_occupancy", "FusedNovelViews", "color_tensor", "colorize_u8", "pack_u8", "render_poses", "novel_views", "automask", "automask_errors", "automask_images", "train_vis", "vis_panels", "visualize", "image_processor", "make_image_processor", "RGBProcessor", "PatchProcessor", "BtsNativeError"]
+           "ImageRaySampler", "PatchRaySampler", "RandomRaySampler", "gen_rays", "distance_to_z", "ReconstructionLoss", "FusedTrainStep", "FusedEvalFrame", "FusedOccupancyEval", "lidar_occupancy", "FusedDepthEval", "compute_depth_metrics", "depth_metrics", "lidar_depth", "load_depth", "load_depth_batch", "FusedNVSEval", "compute_nvs_metrics", "nvs_metrics", "FusedBBoxOccupancyEval", "bbox_occupancy", "FusedNovelViews", "color_tensor", "colorize_u8", "pack_u8", "render_poses", "novel_views", "automask", "automask_errors", "automask_images", "train_vis", "vis_panels", "visualize", "image_processor", "make_image_processor", "RGBProcessor", "PatchProcessor", "BtsNativeError"]

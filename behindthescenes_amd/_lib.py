@@ -155,6 +155,12 @@ class BtsDepthMetrics(C.Structure):
                 ("counts", C.c_void_p)]
 
 
+class BtsLidarDepth(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("offsets", C.POINTER(C.c_int64)), ("P", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("B", "H", "W", "convention", "eigen_depth", "p_fp64", "max_blocks", "reserved_")] + \
+               [("depth", C.c_void_p)]
+
+
 class BtsNvsMetrics(C.Structure):
     _fields_ = [("pred", C.c_void_p)] + [(k, C.c_int64) for k in ("pred_sb", "pred_sy", "pred_sx", "pred_sc")] + \
                [("gt", C.c_void_p)] + [(k, C.c_int64) for k in ("gt_sb", "gt_sy", "gt_sx", "gt_sc")] + \
@@ -207,6 +213,8 @@ BTS_DEPTH_METRICS_ROW = 12
 BTS_NVS_METRICS_MAX_FRAMES = 64
 BTS_NVS_METRICS_ROW = 8
 BTS_LIDAR_MAX_SLICES = 16
+BTS_LIDAR_DEPTH_MAX_FRAMES = 32
+BTS_LIDAR_DEPTH_CONVENTIONS = {"kitti_raw": 0, "kitti_360": 1}
 BTS_FRAMES_PARTIALS = 64
 BTS_CMAP_MAX_N = 65536
 
@@ -300,6 +308,9 @@ SYMBOLS = {
     # depth evaluation metrics (evaluator.py:96-151)
     "bts_depth_metrics_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "bts_depth_metrics": (C.c_int, [C.POINTER(BtsDepthMetrics), _P, C.c_size_t, _P]),
+    # LiDAR ground-truth depth maps (kitti_raw_dataset.py:256-302, kitti_360_dataset.py:505-539)
+    "bts_lidar_depth_workspace": (C.c_size_t, [_I, _I, _I, _I]),
+    "bts_lidar_depth": (C.c_int, [C.POINTER(BtsLidarDepth), _P, C.c_size_t, _P]),
     # NVS evaluation metrics (evaluator_nvs.py:141-178 without LPIPS)
     "bts_nvs_metrics_workspace": (C.c_size_t, [_I, _I, _I]),
     "bts_nvs_metrics": (C.c_int, [C.POINTER(BtsNvsMetrics), _P, C.c_size_t, _P]),

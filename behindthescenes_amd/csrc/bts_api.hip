@@ -1309,4 +1309,67 @@ int bts_patch_color_query(const BtsPatchColor* a, const float* xyz, int32_t P, f
   return patch_color_query_impl(a, xyz, P, rgb, (hipStream_t)stream);
 }
 
+// ---- LiDAR ground-truth depth maps (kitti_raw_dataset.py:256-302, kitti_360_dataset.py:505-539)
+// 0: served; BTS_E_INVALID / BTS_E_UNSUPPORTED: which of the two the sizes are (no message)
+static int lidar_depth_sizes(long B, long H, long W) {
+  if (B <= 0 || B > BTS_LIDAR_DEPTH_MAX_FRAMES || H <= 0 || W <= 0) return BTS_E_INVALID;
+  if (W < 2 || H * W >= (1L << 24)) return BTS_E_UNSUPPORTED;
+  return BTS_OK;
+}
+
+size_t bts_lidar_depth_workspace(int32_t B, int32_t H, int32_t W, int32_t p_fp64) {
+  if (lidar_depth_sizes(B, H, W) != BTS_OK) return 0;
+  return lidar_depth_bytes(B, H, W, p_fp64 != 0);
+}
+
+int bts_lidar_depth(const BtsLidarDepth* a, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "bts_lidar_depth";
+  BTS_CHECK_LAYOUT(a && a->offsets && a->P && a->depth && a->H > 0 && a->W > 0, who);
+  if (a->B <= 0 || a->B > BTS_LIDAR_DEPTH_MAX_FRAMES) {
+    set_error("%s: B=%ld frames; between 1 and 32 per call", who, (long)a->B);
+    return BTS_E_INVALID;
+  }
+  if (a->convention != BTS_LIDAR_DEPTH_KITTI_RAW && a->convention != BTS_LIDAR_DEPTH_KITTI_360) {
+    set_error("%s: unknown convention %ld (0 kitti_raw, 1 kitti_360)", who, (long)a->convention);
+    return BTS_E_INVALID;
+  }
+  if (a->eigen_depth && a->convention != BTS_LIDAR_DEPTH_KITTI_RAW) {
+    set_error("%s: eigen_depth is kitti_raw's; kitti_360's load_depth has no crop", who);
+    return BTS_E_INVALID;
+  }
+  if (a->offsets[0] != 0) {
+    set_error("%s: offsets[0] = %ld, expected 0", who, (long)a->offsets[0]);
+    return BTS_E_INVALID;
+  }
+  for (int f = 0; f < a->B; ++f) {
+    if (a->offsets[f + 1] < a->offsets[f]) {
+      set_error("%s: offsets decrease at frame %ld (%ld after %ld)", who, (long)f, (long)a->offsets[f + 1], (long)a->offsets[f]);
+      return BTS_E_INVALID;
+    }
+  }
+  const int64_t N = a->offsets[a->B];
+  if (N > 0 && (!a->points || ((uintptr_t)a->points & 15) != 0)) {
+    set_error("%s: points NULL or not 16-byte aligned", who);
+    return BTS_E_INVALID;
+  }
+  if (a->W < 2) {
+    set_error("%s: W=%ld; with one column every pixel shares one key of the reference's duplicate search", who, (long)a->W);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (lidar_depth_sizes(a->B, a->H, a->W) != BTS_OK) {
+    set_error("%s: H * W = %ld pixels; from 2^24 the reference's float32 key stops being exact", who, (long)a->H * a->W);
+    return BTS_E_UNSUPPORTED;
+  }
+  if (N >= (1LL << 31)) {
+    set_error("%s: N=%ld points; fewer than 2^31 per call", who, (long)N);
+    return BTS_E_UNSUPPORTED;
+  }
+  const size_t need = lidar_depth_bytes(a->B, a->H, a->W, a->p_fp64 != 0);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) {
+    set_error("%s: workspace NULL, too small or not 16-byte aligned (%ld bytes needed, see bts_lidar_depth_workspace)", who, (long)need);
+    return BTS_E_INVALID;
+  }
+  return launched(lidar_depth_launch(a, workspace, (hipStream_t)stream), who);
+}
+
 }  // extern "C"

@@ -166,6 +166,10 @@ int depth_metrics_launch(const BtsDepthMetrics* a, void* workspace, hipStream_t 
 size_t nvs_metrics_bytes(int B, int He, int We);
 int nvs_metrics_launch(const BtsNvsMetrics* a, void* workspace, hipStream_t s);
 
+// ---- bts_lidar_depth.hip: LiDAR ground-truth depth maps (both KITTI load_depth)
+size_t lidar_depth_bytes(int B, int H, int W, bool p_fp64);
+int lidar_depth_launch(const BtsLidarDepth* a, void* workspace, hipStream_t s);
+
 // ---- bts_bbox_occ.hip: 3D-bounding-box occupancy evaluation
 struct BBoxEvalWs {
   float *to_key, *tables;

@@ -11,7 +11,7 @@ one row per frame in a device buffer; ``compute()`` is the ONE device-to-host co
 There is no torch fallback: CPU tensors are rejected, as everywhere else in this package."""
 import torch
 
-from . import _lib, native
+from . import _lib, lidar_depth, native
 from ._evalcommon import MetricRows
 from ._lib import BtsNativeError
 from .train_step import FusedEvalFrame
@@ -82,6 +82,23 @@ class FusedDepthEval(MetricRows):
         row = self.update(depth[:, :1], depth_gt)
         data.update(_as_dict(row))
         data["depth_metrics_row"] = row
+        return data
+
+    def frame_lidar(self, images, projs, poses, points, P, convention, eigen_depth=False, size=None, **kwargs):
+        """``frame`` with the ground truth formed here: ``points (N, 4)`` the frame's raw Velodyne cloud and ``P (3, 4)`` on the device,
+        ``convention`` / ``eigen_depth`` as ``lidar_depth.load_depth`` takes them.  The map has the frame's size (the shipped configs
+        evaluate at it) or ``size = (H, W)``; it is formed on the same stream, nothing synchronises, and it is returned as
+        ``data["depth_gt"]`` (1, H, W) float32."""
+        if size is None:
+            if not isinstance(images, torch.Tensor) or images.dim() < 2:
+                raise BtsNativeError("images: expected a tensor (n, v, 3, H, W)")
+            size = tuple(images.shape[-2:])
+        self.full()      # before any launch
+        depth_gt = lidar_depth.load_depth(points, P, size, convention, eigen_depth)
+        if depth_gt.dtype != torch.float32:
+            depth_gt = depth_gt.float()      # the metrics are fp32, as the reference's after its data loader
+        data = self.frame(images, projs, poses, depth_gt, **kwargs)
+        data["depth_gt"] = depth_gt
         return data
 
     def compute(self):

@@ -1153,6 +1153,51 @@ def depth_metrics(pred: torch.Tensor, gt: torch.Tensor, depth_scaling=None, clam
     return out
 
 
+def lidar_depth(points: torch.Tensor, offsets, P: torch.Tensor, size, convention, eigen_depth=False, out=None, max_blocks=0):
+    """points (N, 4) float32, the B Velodyne clouds concatenated; ``offsets``: B + 1 host integers (cloud f is
+    ``points[offsets[f]:offsets[f + 1]]``); P (3, 4) float32 or float64 -> the ground-truth depth maps (B, H, W) in P's dtype --
+    load_depth of datasets/kitti_raw/kitti_raw_dataset.py:256-302 (``convention="kitti_raw"``, with its ``eigen_depth``) or of
+    datasets/kitti_360/kitti_360_dataset.py:505-539 (``"kitti_360"``) per cloud (bts_lidar_depth).  ``out``: the caller's (B, H, W)
+    buffer.  ``max_blocks``: a cap on the points pass's grid (tests).  The workspace is the cached per-stream scratch of this module;
+    nothing synchronises."""
+    if not isinstance(convention, str) or convention not in _lib.BTS_LIDAR_DEPTH_CONVENTIONS:
+        raise ValueError(f"convention: expected 'kitti_raw' or 'kitti_360', got {convention!r}")
+    if eigen_depth and convention != "kitti_raw":
+        raise ValueError("eigen_depth: the Eigen crop is kitti_raw's; kitti_360's load_depth has none")
+    try:
+        H, W = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size: expected (H, W), got {size!r}") from None
+    if not isinstance(P, torch.Tensor) or P.dtype not in (torch.float32, torch.float64):
+        raise BtsNativeError(f"P: expected a float32 or float64 tensor, got {getattr(P, 'dtype', type(P).__name__)}")
+    _req_as(P, "P", P.dtype, (3, 4))
+    _req(points, "points")
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise BtsNativeError(f"points: expected shape (N, 4), got {tuple(points.shape)}")
+    if points.device != P.device:
+        raise BtsNativeError(f"points on {points.device}, P on {P.device}")
+    offs = [int(o) for o in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    B = len(offs) - 1
+    if B < 1 or offs[0] != 0 or offs[-1] != points.shape[0] or any(b < a for a, b in zip(offs, offs[1:])):
+        raise ValueError(f"offsets: expected B + 1 non-decreasing integers from 0 to N={points.shape[0]}, got {offs}")
+    if H <= 0 or W <= 0:
+        raise ValueError(f"size: expected a positive (H, W), got {(H, W)}")
+    if out is None:
+        out = torch.empty((B, H, W), device=points.device, dtype=P.dtype)
+    else:
+        _req_as(out, "out", P.dtype, (B, H, W))
+    lib = _lib.load()
+    p64 = int(P.dtype == torch.float64)
+    ws_bytes = int(lib.bts_lidar_depth_workspace(B, H, W, p64))
+    ws = _workspace(points.device, max(ws_bytes, 16))
+    c_offs = (C.c_int64 * (B + 1))(*offs)
+    args = _lib.BtsLidarDepth(points=_addr(points) if points.shape[0] else None, offsets=c_offs, P=P.data_ptr(), B=B, H=H, W=W,
+                              convention=_lib.BTS_LIDAR_DEPTH_CONVENTIONS[convention], eigen_depth=int(bool(eigen_depth)), p_fp64=p64,
+                              max_blocks=int(max_blocks), depth=out.data_ptr())
+    _lib.check(lib.bts_lidar_depth(C.byref(args), _ptr(ws), ws_bytes, _stream(points)), "bts_lidar_depth")
+    return out
+
+
 def nvs_crop_box(eval_resolution):
     """The 5 % crop of evaluator_nvs.py:158-161 at ``eval_resolution = (h, w)``: (y0, y1, x0, x1), the reference's own expressions on
     Python floats; bts_nvs_metrics takes the box from here and derives none of its own."""

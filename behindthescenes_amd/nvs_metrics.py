@@ -13,7 +13,7 @@ in device buffers; ``compute()`` is the ONE device-to-host copy of an evaluation
 There is no torch fallback: CPU tensors are rejected, as everywhere else in this package."""
 import torch
 
-from . import _lib, native
+from . import _lib, lidar_depth, native
 from ._evalcommon import MetricRows, nan_skipping_means
 from ._lib import BtsNativeError
 from .depth_metrics import METRIC_KEYS as DEPTH_METRIC_KEYS, FusedDepthEval
@@ -113,6 +113,18 @@ class FusedNVSEval(MetricRows):
             drow = self.depth.update(data["fine"][0]["depth"][:, :1], depth_gt)      # :98-99
             data.update({k: drow[i] for i, k in enumerate(DEPTH_METRIC_KEYS)})
             data["depth_metrics_row"] = drow
+        return data
+
+    def frame_lidar(self, images, projs, poses, points, P, convention, eigen_depth=False, size=None, **kwargs):
+        """``frame`` with ``depth_gt`` formed on the same stream from the frame's raw Velodyne cloud (``lidar_depth.load_depth``: ``points
+        (N, 4)`` and ``P (3, 4)`` on the device) at ``eval_resolution`` or ``size = (H, W)``; nothing synchronises.  The map is returned as
+        ``data["depth_gt"]`` (1, H, W) float32."""
+        self.full(), self.depth.full()           # before any launch
+        depth_gt = lidar_depth.load_depth(points, P, self.eval_resolution if size is None else size, convention, eigen_depth)
+        if depth_gt.dtype != torch.float32:
+            depth_gt = depth_gt.float()
+        data = self.frame(images, projs, poses, depth_gt, **kwargs)
+        data["depth_gt"] = depth_gt
         return data
 
     def compute(self):

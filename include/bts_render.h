@@ -1347,6 +1347,63 @@ int bts_patch_color_fwd(const BtsPatchColor* a, void* stream);
 int bts_patch_color_bwd(const BtsPatchColor* a, const float* g_rgb, float* g_weights, void* stream);
 int bts_patch_color_query(const BtsPatchColor* a, const float* xyz, int32_t P, float* rgb, void* stream);
 
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * LiDAR ground-truth depth maps: load_depth of datasets/kitti_raw/kitti_raw_dataset.py:256-302 and of datasets/kitti_360/
+ * kitti_360_dataset.py:505-539 -- the producer of bts_depth_metrics' `gt` from a raw Velodyne cloud.  The .bin read, the calibration
+ * and the split files stay with the caller.  Additive to ABI 9: every struct and entry point above is unchanged.
+ *
+ * Per frame, from points (N, 4) fp32 whose fourth column is taken as 1, P (3, 4) and the target size (H, W); all arithmetic in P's
+ * dtype (fp32 or fp64) with IEEE division and no contraction, every row of P . p accumulated left to right with one rounding per term.
+ * The rules of the reference, reproduced ON PURPOSE (the plain z-buffer, the nearest point per pixel, is a DIFFERENT function):
+ *   1. front filter, kitti_raw only: points with x < 0 (or NaN) are dropped first; kitti_360 drops nothing, so a point behind the
+ *      camera can land in frame there with a negative depth (rule 7 removes it);
+ *   2. u = P . p, px = u0 / u2, py = u1 / u2, z = u2;
+ *   3. the pixel: kitti_raw x = rint(px) - 1, y = rint(py) - 1; kitti_360 x = rint((px * .5 + .5) * W), y = rint((py * .5 + .5) * H);
+ *      np.round rounds half to even, which is rint;
+ *   4. valid: 0 <= x < W and 0 <= y < H, compared as floating-point values (NaN and u2 == 0 fall out here, as in numpy);
+ *   5. scatter depth[y, x] = z: among the valid points of one pixel the one with the HIGHEST index wins (numpy's fancy assignment);
+ *   6. the "duplicates": key = y * (W - 1) + x - 1, the off-by-one of the Monodepth loaders.  Two pixels share a key exactly when
+ *      they are (y, W - 1) and (y + 1, 0).  For every key held by two or more valid points, the pixel of the key's FIRST point (lowest
+ *      index) receives the minimum z over ALL the key's points, the other pixel's included; the other pixel keeps rule 5.  So a pixel
+ *      that holds one point can receive the depth of a point of another row;
+ *   7. depth < 0 becomes 0;
+ *   8. eigen_depth (kitti_raw): only 1e-3 < depth < 80 inside rows [int(0.40810811 H), int(0.99189189 H)) and columns
+ *      [int(0.03594771 W), int(0.96405229 W)) survives, everything else becomes 0.
+ * Closed form per pixel q with key partner q': if q and q' together hold two or more points and the lowest index among them lies in
+ * q, depth[q] = min z over both pixels; otherwise depth[q] = the z of q's highest-indexed point; 0 where q holds no point.
+ * Integer atomics only (count, lowest index, highest index, the minimum of z's order-preserving integer image), so a rerun is
+ * bit-identical; nothing synchronises.  Outside the contract: an infinite coordinate or entry of P (nothing faults).
+ * --------------------------------------------------------------------------------------------------------------------------------- */
+#define BTS_LIDAR_DEPTH_MAX_FRAMES 32
+#define BTS_LIDAR_DEPTH_KITTI_RAW 0
+#define BTS_LIDAR_DEPTH_KITTI_360 1
+
+typedef struct {
+  const float* points;      /* (N, 4) fp32, the B clouds concatenated; 16-byte aligned */
+  const int64_t* offsets;   /* HOST array of B + 1: cloud f is points[offsets[f] : offsets[f + 1]]; offsets[0] = 0, non-decreasing */
+  const void* P;            /* (3, 4) fp32, or fp64 with p_fp64; one projection for all B clouds */
+  int32_t B, H, W;          /* frames, target size */
+  int32_t convention;       /* BTS_LIDAR_DEPTH_KITTI_RAW / _KITTI_360 */
+  int32_t eigen_depth;      /* rule 8; kitti_raw only */
+  int32_t p_fp64;           /* 0: P and depth are fp32; 1: fp64 */
+  int32_t max_blocks;       /* production callers pass 0.  > 0 caps the points pass's grid per frame: a test's way to more than one
+                             * grid trip at a small N; the map is the same, only slower */
+  int32_t reserved_;
+  void* depth;              /* out (B, H, W) in P's dtype */
+} BtsLidarDepth;
+
+/* bytes of bts_lidar_depth's workspace (four integers per pixel; contents need no initialisation: the call clears them); 0 for
+ * arguments the entry would reject */
+size_t bts_lidar_depth_workspace(int32_t B, int32_t H, int32_t W, int32_t p_fp64);
+
+/* Enqueues, on `stream`: the clear of the workspace, the points pass (thread = point, grid-stride), the pixels pass (thread = pixel).
+ * Everything is validated before anything is enqueued.  BTS_E_INVALID with a message: a NULL pointer, points not 16-byte aligned,
+ * B outside [1, 32], a non-positive H or W, offsets that do not start at 0 or decrease, an unknown convention, eigen_depth with
+ * kitti_360, a workspace that is NULL, too small or not 16-byte aligned.  BTS_E_UNSUPPORTED with a message: W < 2 (with W == 1 every
+ * pixel shares one key), H * W >= 2^24 (above it the reference's float32 key stops being exact), N >= 2^31. */
+int bts_lidar_depth(const BtsLidarDepth* a, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
